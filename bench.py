@@ -9,6 +9,7 @@ GPU (independent units, replicated keys, no data-path collective): weak scaling,
 LWEs of all ranks / max-over-ranks time.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR    (also writes the last timed step's outputs, *.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...      (no launcher: bench.py starts that torch.distributed.run itself, as a fresh child
@@ -48,7 +49,32 @@ def parse(argv=None):
     ap.add_argument("--no-p44", action="store_true", help="skip the PARAM_MESSAGE_4_CARRY_4 (config 5) section")
     ap.add_argument("--serial", action="store_true", help="headline without the keyswitch / blind-rotation pipelining")
     ap.add_argument("--print-launch", action="store_true", help="print the torch.distributed.run command --gpus N > 1 would start, and exit")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 48 << 20   # all ranks' dumped arrays together stay below 64 MB
+
+
+def dump_outputs(out_dir, big, dec, rank, world):
+    """The timed path's result as its caller receives it: the output LWE ciphertexts of the last timed step, as float64
+    torus values in [-1/2, 1/2) (u64 / 2^64, signed), and their decryptions.  A batch too large for the size budget is
+    cut to a fixed, seeded sample of rows (listed in ciphertexts_rows.npy).  With N > 1 ranks every rank writes its own
+    files, suffixed _rank<r>."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    rows = np.arange(big.shape[0])
+    max_rows = max(1, DUMP_BYTES // world // (big.shape[1] * 8))
+    if big.shape[0] > max_rows:
+        rows = np.sort(np.random.default_rng(SEED).choice(big.shape[0], size=max_rows, replace=False))
+        np.save(os.path.join(out_dir, f"ciphertexts_rows{suffix}.npy"), rows.astype(np.float64))
+    torus = big[rows].view(np.int64).astype(np.float64) * 2.0 ** -64
+    np.save(os.path.join(out_dir, f"ciphertexts{suffix}.npy"), torus)
+    np.save(os.path.join(out_dir, f"decrypted{suffix}.npy"), np.asarray(dec, dtype=np.float64))
 
 
 def launch_command(argv, gpus, port, script=None):
@@ -660,7 +686,6 @@ def main():
     # independent batches write to their own buffers (a ring of four): calls that write the same buffer are ordered by
     # the engine, which would serialise the overlapped mode
     d_outs = [torch.zeros_like(d_in) for _ in range(4)]
-    d_out = d_outs[0]
     torch.cuda.synchronize()
     step_no = [0]
 
@@ -696,8 +721,9 @@ def main():
     elapsed = time.perf_counter() - t0
     ks_ms, br_ms, calls = eng.kernel_times(reset=True)
     eng.set_pipeline(False)
-    got = d_out.cpu().numpy().view(np.uint64).copy()      # the TIMED loop's outputs, before anything else writes
-    got_others = [d.cpu().numpy().view(np.uint64).copy() for d in d_outs[1:]]
+    outs_all = [d.cpu().numpy().view(np.uint64).copy() for d in d_outs]    # the TIMED loop's outputs, before anything else writes
+    got, got_others = outs_all[0], outs_all[1:]
+    got_last = outs_all[(step_no[0] - 1) & 3]              # the buffer the last timed step wrote
     shadow = None
     if not args.serial:        # mode 1: only the keyswitch overlaps (bit-identical to serial calls)
         eng.set_pipeline(1)
@@ -753,6 +779,8 @@ def main():
         v = torch.tensor([1 if verified else 0], device=coll_dev)
         dist.all_reduce(v, op=dist.ReduceOp.MIN)
         verified = bool(v.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, got_last, ck.decrypt(got_last), rank, world)
 
     # ---- SURVEY 8(d) config 2, second variant: one shared identity table for the whole batch ----
     identity = None

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Reads the parameter CONSTANTS of the reference's shortint layer (numbers only) into JSON fixtures:
 
-    python3 tests/golden/make_param_table.py        (needs /root/reference; run in the authoring container)
+    python3 tests/golden/make_param_table.py <tfhe-rs checkout>        (the reference tree the fixtures were read from)
 
 Sources: tfhe/src/shortint/parameters/mod.rs (ClassicPBSParameters) and multi_bit.rs (MultiBitPBSParameters)
 -> tests/golden/reference_parameter_sets.json; parameters_compact_pk.rs (the "experimental" compact-public-key sets,
@@ -10,8 +10,9 @@ One record per `pub const`, with the line it starts on."""
 import json
 import os
 import re
+import sys
 
-ROOT = "/root/reference/tfhe/src/shortint/parameters"
+ROOT = os.path.join(sys.argv[1] if len(sys.argv) > 1 else ".", "tfhe", "src", "shortint", "parameters")
 FIELDS = {"lwe_dimension": int, "glwe_dimension": int, "polynomial_size": int, "lwe_modular_std_dev": float,
           "glwe_modular_std_dev": float, "pbs_base_log": int, "pbs_level": int, "ks_base_log": int, "ks_level": int,
           "message_modulus": int, "carry_modulus": int, "grouping_factor": int}

@@ -476,14 +476,15 @@ def test_pipelined_calls_are_bit_identical_to_serial_ones(p22):
     def run(pipelined):
         eng.set_pipeline(pipelined)
         outs = [torch.zeros_like(b) for b in batches]
+        chain = [torch.zeros_like(batches[0]) for _ in range(4)]
+        same = torch.zeros_like(batches[0])
+        torch.cuda.synchronize()            # torch's stream is not ordered with the engine's: its fills land first
         for b, o in zip(batches, outs):                                    # independent
             eng.apply_lookup_table_dev(b.data_ptr(), idx.data_ptr(), o.data_ptr(), B)
-        chain = [torch.zeros_like(batches[0]) for _ in range(4)]
         src = batches[0]
         for c in chain:                                                    # chained: input = previous output
             eng.apply_lookup_table_dev(src.data_ptr(), idx.data_ptr(), c.data_ptr(), B)
             src = c
-        same = torch.zeros_like(batches[0])
         for b in batches:                                                  # every output into one buffer
             eng.apply_lookup_table_dev(b.data_ptr(), idx.data_ptr(), same.data_ptr(), B)
         eng.synchronize()
@@ -517,18 +518,20 @@ def test_overlapped_batches_mode_matches_the_large_batch_kernel(p22):
     def run(mode):
         eng.set_pipeline(mode)
         outs = [torch.zeros_like(b) for b in batches]
+        chain = [torch.zeros_like(batches[0]) for _ in range(5)]
+        same = torch.zeros_like(batches[0])
+        scratch = batches[1].clone()        # call k reads scratch, call k+1 overwrites it
+        war_out = torch.zeros_like(scratch)
+        # torch's stream is not ordered with the engine's: its fills and the clone must be done before the first call
+        torch.cuda.synchronize()
         for b, o in zip(batches, outs):
             eng.apply_lookup_table_dev(b.data_ptr(), idx.data_ptr(), o.data_ptr(), B)
-        chain = [torch.zeros_like(batches[0]) for _ in range(5)]
         src = batches[0]
         for c in chain:
             eng.apply_lookup_table_dev(src.data_ptr(), idx.data_ptr(), c.data_ptr(), B)
             src = c
-        same = torch.zeros_like(batches[0])
         for b in batches:
             eng.apply_lookup_table_dev(b.data_ptr(), idx.data_ptr(), same.data_ptr(), B)
-        scratch = batches[1].clone()        # call k reads scratch, call k+1 overwrites it
-        war_out = torch.zeros_like(scratch)
         eng.apply_lookup_table_dev(scratch.data_ptr(), idx.data_ptr(), war_out.data_ptr(), B)
         eng.apply_lookup_table_dev(batches[2].data_ptr(), idx.data_ptr(), scratch.data_ptr(), B)
         eng.synchronize()
@@ -542,7 +545,9 @@ def test_overlapped_batches_mode_matches_the_large_batch_kernel(p22):
         wide_serial = run(0)
     finally:
         eng.set_variant(0)
-    assert all(np.array_equal(a, b) for a, b in zip(wide_serial, overlapped))
+    names = [f"outs[{i}]" for i in range(6)] + [f"chain[{i}]" for i in range(5)] + ["same", "war_out", "scratch"]
+    differ = [(nm, int((a != b).any(axis=1).sum())) for nm, a, b in zip(names, wide_serial, overlapped) if not np.array_equal(a, b)]
+    assert not differ, f"(output, LWEs that differ): {differ}"
     dec = lambda arrs: [ks.ck.decrypt_many(a.view(np.uint64)) for a in arrs]
     assert all(np.array_equal(a, b) for a, b in zip(dec(default_serial), dec(overlapped)))
 
@@ -567,6 +572,7 @@ def test_overlapped_mode_three_interleaved_dependent_chains(p22):
     def run(mode):
         eng.set_pipeline(mode)
         bufs = [[torch.zeros_like(h) for _ in range(depth)] for h in heads]
+        torch.cuda.synchronize()            # torch's stream is not ordered with the engine's: its fills land first
         for d in range(depth):
             for c in range(3):
                 src = heads[c] if d == 0 else bufs[c][d - 1]
