@@ -1204,11 +1204,12 @@ __device__ __forceinline__ void fft_inverse_multi(cplx (*x)[PL::R], const C& c, 
 // [-1/2, 1/2) is the same element mod 2^64.  Against the reference's rounding on the 2^-64 grid
 // this adds an unbiased error of at most 2^-53 of the torus, 2^-27 of the f64 FFT's own error
 // (the reference tolerates 2^14 ulp, fft/tests.rs:40-46, and measures ~2^38); 2 f64 + 2 integer
-// instructions instead of 9 f64.
+// instructions instead of 9 f64.  The mantissa << 12 is the whole bit pattern of the sum << 12: sign and exponent
+// (0x3FF, or 0x400 for 2.0 whose mantissa is 0) leave the 64-bit word at the top, so `acc += from_torus(x)` is one
+// 64-bit shift and one 64-bit add (v_lshlrev_b64, v_lshl_add_u64) rather than alignbit, shift, move and two adds.
 __device__ __forceinline__ uint64_t from_torus(double x) {
     const double u = __builtin_amdgcn_fract(x) + 1.0;
-    const uint32_t lo = (uint32_t)__double2loint(u), hi = (uint32_t)__double2hiint(u);
-    return ((uint64_t)__builtin_amdgcn_alignbit(hi, lo, 20) << 32) | (uint64_t)(lo << 12);
+    return (uint64_t)__double_as_longlong(u) << 12;
 }
 #else
 // The reference's formula literally; rint() (ties-to-even) stands in for Rust's round() (ties away):

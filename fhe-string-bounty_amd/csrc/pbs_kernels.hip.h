@@ -209,7 +209,26 @@ struct Rotation {
         neg = (uint32_t)(q8 >> 31);
         address = ((uint32_t)q8 & (((1u << (LOGN - LW)) - 1) << 3)) | row_base;       // v_and_or_b32
     }
+    // the same, handing out q8 itself: its sign bit is the negation flag (biased_difference takes the mask from it)
+    __device__ __forceinline__ void source_bytes_q8(int m, int h, uint32_t row_base, uint32_t& address, int32_t& q8) const {
+        constexpr int LW = swap_wave_bits<PL>();
+        q8 = qb8 + ((PL::point(0, m) + h * PL::P) >> LW) * 8;
+        address = ((uint32_t)q8 & (((1u << (LOGN - LW)) - 1) << 3)) | row_base;
+    }
 };
+
+// Single-level digit of (+-gathered - own), biased as decomp_single_biased returns it, without the conditional
+// negation.  K = bias_constant << 32 has a zero low word, so decomp_single_biased(v - own) = bits of hi(v - own + K).
+// With sm = 0 / all-ones the negation mask and o = (own + ~K) ^ ~sm (`own_nk` = own + ~K = own - K - 1):
+//   not negated: o = K - own,       s = gathered + o = v - own + K;
+//   negated:     o = own - K - 1,   s = gathered + own - K - 1 = ~(-gathered - own + K) = ~(v - own + K),
+// so the digit is the field of hi(s) ^ sm: xor, xor, one 64-bit add, xor, bfe in place of xor, xor, 64-bit own + sm,
+// sub, subb, add, bfe.  Bit-identical to decomp_single_biased(v - own, b, bias_constant).
+__device__ __forceinline__ uint32_t biased_difference(uint64_t gathered, int32_t q8, uint64_t own_nk, uint32_t b) {
+    const uint32_t sm = (uint32_t)(q8 >> 31), nsm = ~sm;
+    const uint64_t s = gathered + (own_nk ^ (((uint64_t)nsm << 32) | nsm));
+    return __builtin_amdgcn_ubfe((uint32_t)(s >> 32) ^ sm, 32u - b, b);
+}
 
 // LDS access by byte address (32-bit, address space 3)
 typedef __attribute__((address_space(3))) const uint64_t lds_cu64_t;
@@ -794,14 +813,39 @@ blind_rotate_wide_kernel(BlindRotateArgs args) {
         }
 
         uint32_t st_lo[K1][R], st_hi[K1][R];
+        const uint64_t nk = ~((uint64_t)dbias << 32);      // biased_difference
         uint32_t row_base[K1];
 #pragma unroll
         for (int p = 0; p < K1; p++) {
             row_base[p] = (acc_address + (uint32_t)p * 8u * N) | rot.rbits8;
             if constexpr (PL::SWAP) asm volatile("" : "+s"(row_base[p]));
         }
+        constexpr bool GATHER_BATCH = PL::SWAP && L == 1 && !ACC_LDS;
+        if constexpr (GATHER_BATCH) {
+            // all 2 K1 R reads in flight before the first use: issued one by one, hipcc waited for each (lgkmcnt(0) after
+            // every ds_read_b64, 16 LDS round trips of ~130 cycles in a row per wave-step at P22)
+            uint64_t gv[K1][R][2];
+            int32_t q8v[R][2];
 #pragma unroll
-        for (int p = 0; p < K1; p++)
+            for (int m = 0; m < R; m++)
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    uint32_t address;
+                    rot.source_bytes_q8(m, h, row_base[0], address, q8v[m][h]);
+#pragma unroll
+                    for (int p = 0; p < K1; p++) gv[p][m][h] = lds_load_u64(address + (uint32_t)p * 8u * N);   // row_base[p] - row_base[0]: the copy is 8N-aligned, rbits8 < 8N
+                }
+            FHE_PIN_ORDER();
+#pragma unroll
+            for (int p = 0; p < K1; p++)
+#pragma unroll
+                for (int m = 0; m < R; m++) {
+                    st_lo[p][m] = biased_difference(gv[p][m][0], q8v[m][0], acc_lo[p][m] + nk, bL);
+                    st_hi[p][m] = biased_difference(gv[p][m][1], q8v[m][1], acc_hi[p][m] + nk, bL);
+                }
+        }
+#pragma unroll
+        for (int p = 0; p < (GATHER_BATCH ? 0 : K1); p++)
 #pragma unroll
             for (int m = 0; m < R; m++)
 #pragma unroll
