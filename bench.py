@@ -8,8 +8,14 @@ tables already resident in HBM.  With N GPUs every rank runs its own 256-LWE bat
 GPU (independent units, replicated keys, no data-path collective): weak scaling, value = all
 LWEs of all ranks / max-over-ranks time.
 
+A plain run does only what the headline needs: set up, warm up, time the steps, decrypt-check the timed outputs,
+write them if --dump-outputs is given, and print the line.  --full adds every other section (mode 1 and serial
+comparison steps, the shared identity LUT, the batch-size sweep, FheString ms/op, multi-bit, N = 1024 and P44
+parameter sets, the CPU baseline), each after the headline steps; the --no-* options skip single ones of them.
+
     python bench.py --gpus 1 --steps 20 --warmup 3
     python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR    (also writes the last timed step's outputs, *.npy)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full                (also every secondary section)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...      (no launcher: bench.py starts that torch.distributed.run itself, as a fresh child
@@ -43,10 +49,14 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=10, help="untimed steps before the timed ones (topped up to 40 untimed steps, see prewarm_steps)")
     ap.add_argument("--batch", type=int, default=256, help="LWEs per step per GPU")
     ap.add_argument("--log2-points", type=int, default=0, help="blind-rotate variant (0 = default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-strings", action="store_true", help="skip the FheString ms/op section")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the batch-size sweep")
-    ap.add_argument("--no-p44", action="store_true", help="skip the PARAM_MESSAGE_4_CARRY_4 (config 5) section")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every secondary section (comparison modes, sweep, strings, other "
+                         "parameter sets, CPU baseline); a plain run measures the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-strings", action="store_true",
+                    help="with --full: skip the FheString ms/op, multi-bit and N = 1024 sections")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: skip the batch-size sweep")
+    ap.add_argument("--no-p44", action="store_true", help="with --full: skip the PARAM_MESSAGE_4_CARRY_4 (config 5) section")
     ap.add_argument("--serial", action="store_true", help="headline without the keyswitch / blind-rotation pipelining")
     ap.add_argument("--print-launch", action="store_true", help="print the torch.distributed.run command --gpus N > 1 would start, and exit")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -674,7 +684,7 @@ def main():
     eng = fhestr.Engine(P, local_rank, args.log2_points)
     # server keys are generated on the device (bit-identical to fhe_client_gen_server_keys, see
     # tests/test_gpu_parity.py); the standard-domain copies are only exported where the CPU baseline runs
-    need_host_keys = rank == 0 and world == 1 and not args.no_cpu_baseline
+    need_host_keys = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     glwe_sk, small_sk = ck.secret_keys()
     exported = eng.generate_keys(glwe_sk, small_sk, SEED, export=need_host_keys)
     bsk, ksk = exported if need_host_keys else (None, None)
@@ -700,10 +710,10 @@ def main():
             dist.barrier()
 
     # throughput mode: consecutive steps are independent batches, so the keyswitch of step k+1 may run in the shadow
-    # of the blind rotation of step k (fhe_engine_set_pipeline); the serial figure is reported next to it
+    # of the blind rotation of step k (fhe_engine_set_pipeline); with --full the serial figure is reported next to it
     # Headline = overlapped batches (mode 2: consecutive steps alternate between two streams on the two-LWEs-per-CU
-    # kernel); mode 1 (keyswitch in the shadow of the previous blind rotation, the round-2 headline) and the serial
-    # figure are reported next to it.
+    # kernel); with --full, mode 1 (keyswitch in the shadow of the previous blind rotation, the round-2 headline) and the
+    # serial figure are reported next to it.
     eng.set_pipeline(0 if args.serial else 2)
     # Untimed, before the W warm-up steps the caller asked for: enough steps that the clock ramp that follows an idle GPU is over after
     # the idle seconds of key generation and encryption (profiles/r03_after_idle.txt: launches run 12-16 % slower for tens of ms) --
@@ -725,7 +735,7 @@ def main():
     got, got_others = outs_all[0], outs_all[1:]
     got_last = outs_all[(step_no[0] - 1) & 3]              # the buffer the last timed step wrote
     shadow = None
-    if not args.serial:        # mode 1: only the keyswitch overlaps (bit-identical to serial calls)
+    if args.full and not args.serial:        # mode 1: only the keyswitch overlaps (bit-identical to serial calls)
         eng.set_pipeline(1)
         n_sh = min(args.steps, 20)
         d_out_sh = torch.zeros_like(d_in)
@@ -744,7 +754,7 @@ def main():
                   "verified_decrypt": bool(np.array_equal(ck.decrypt(d_out_sh.cpu().numpy().view(np.uint64)), tables[sel, msgs])),
                   "kernel_ms": {"keyswitch": sh_ks / max(sh_calls, 1), "blind_rotate": sh_br / max(sh_calls, 1)}}
     serial = None
-    if not args.serial:        # the same steps one after the other (what a single dependent chain of calls gets)
+    if args.full and not args.serial:        # the same steps one after the other (what a single dependent chain of calls gets)
         n_serial = min(args.steps, 10)
         d_out_serial = torch.zeros_like(d_in)
 
@@ -784,7 +794,7 @@ def main():
 
     # ---- SURVEY 8(d) config 2, second variant: one shared identity table for the whole batch ----
     identity = None
-    if world == 1:
+    if args.full and world == 1:
         ident_id, _ = eng.generate_lookup_table(lambda x: x)
         d_same = torch.full((B,), int(ident_id), dtype=torch.int32, device="cuda")
         d_id_out = torch.zeros_like(d_in)
@@ -805,7 +815,7 @@ def main():
 
     # ---- batch-size sweep like the reference's throughput bench (benches/core_crypto/pbs_bench.rs:430-549) ----
     sweep = None
-    if world == 1 and not args.no_sweep:
+    if args.full and world == 1 and not args.no_sweep:
         sweep = {}
         for nb in (1, 16, 32, 64, 128, 256, 512, 1024, 4096):
             reps_in = (nb + B - 1) // B
@@ -830,7 +840,7 @@ def main():
         br_avg_ms = br_ms / max(calls, 1)
         rec = {
             "metric": "PBS/sec (whole node)", "value": value, "unit": "PBS/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "prewarm_steps": prewarm,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "prewarm_steps": prewarm, "full": args.full,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": "batched KS+PBS: 256 independent shortint LWE ciphertexts, "
@@ -868,7 +878,7 @@ def main():
     # ---- FheString ms/op (BASELINE.json configs 3 and 4): level batches sharded over the ranks, one
     #      RCCL all-gather per level; single GPU = same code with world 1.  A watchdog makes sure the
     #      headline line is printed even if a collective of this secondary section were to hang. ----
-    if not args.no_strings:
+    if args.full and not args.no_strings:
         import threading
 
         def bail():
@@ -895,26 +905,26 @@ def main():
                 if isinstance(string_ops.get(key), dict):
                     rec[field] = string_ops[key]["ms_per_op"]
 
-    if rank == 0 and world == 1 and not args.no_strings:
+    if args.full and rank == 0 and world == 1 and not args.no_strings:
         try:
             rec["multi_bit_pbs"] = bench_multi_bit(fhestr, local_rank, B, args.steps)
         except Exception as e:   # secondary section
             rec["multi_bit_pbs"] = {"error": f"{type(e).__name__}: {e}"}
 
-    if rank == 0 and world == 1 and not args.no_strings:
+    if args.full and rank == 0 and world == 1 and not args.no_strings:
         try:
             rec["n1024_k2"] = bench_n1024_k2(fhestr, local_rank)
         except Exception as e:   # secondary section
             rec["n1024_k2"] = {"error": f"{type(e).__name__}: {e}"}
 
-    if rank == 0 and world == 1 and not args.no_p44:
+    if args.full and rank == 0 and world == 1 and not args.no_p44:
         try:
             rec["p44"] = bench_p44(fhestr, local_rank)
         except Exception as e:   # secondary section
             rec["p44"] = {"error": f"{type(e).__name__}: {e}"}
 
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 cb, cpu_out = cpu_baseline(P, bsk, ksk, cts, tables, sel)
                 cb["decrypt_matches_gpu"] = bool(np.array_equal(ck.decrypt(cpu_out), dec))
@@ -924,7 +934,8 @@ def main():
                                        "sample": f"failed: {e}"}
         else:
             rec["cpu_baseline"] = None
-            rec["cpu_baseline_reason"] = ("--no-cpu-baseline" if args.no_cpu_baseline else
+            rec["cpu_baseline_reason"] = ("timed with --full only" if not args.full else
+                                          "--no-cpu-baseline" if args.no_cpu_baseline else
                                           "timed on rank 0 at N = 1 only (the contract); see the N = 1 line of the same tree")
         print(json.dumps(rec), flush=True)
     if world > 1:

@@ -21,8 +21,8 @@ for rnd in range(int(os.environ.get("AB_ROUNDS", "2"))):
         own = own.split() if own else []
         if lib != "default":
             env["FHESTR_LIB"] = os.path.join(ROOT, lib)
-        r = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-sweep",
-                            "--no-strings", "--no-p44"] + extra + own, cwd=ROOT, env=env, capture_output=True, text=True)
+        r = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--warmup", "3"] + extra + own,
+                           cwd=ROOT, env=env, capture_output=True, text=True)
         line = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
         if not line:
             print(lib, "FAILED", r.stdout[-500:], r.stderr[-1500:], flush=True)

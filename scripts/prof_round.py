@@ -65,7 +65,7 @@ def main():
         prog = ["python3", "scripts/p44_prof.py"]
         stats_prog = prog
     else:
-        common = ["--no-cpu-baseline", "--no-sweep", "--no-strings", "--no-p44"]
+        common = ["--full", "--no-cpu-baseline", "--no-sweep", "--no-strings", "--no-p44"]   # --full: blind_rotate_kernel runs in the serial steps
         prog = ["python3", "bench.py", "--steps", "3", "--warmup", "1"] + common
         stats_prog = ["python3", "bench.py", "--steps", "40", "--warmup", "5"] + common
     # 1. kernel-trace + stats

@@ -1,4 +1,4 @@
-"""Print the fields of a bench.py JSON line that the round's documents quote.   python3 scripts/show_bench.py FILE"""
+"""Print the fields of a `bench.py --full` JSON line that the round's documents quote.   python3 scripts/show_bench.py FILE"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print("value", round(d["value"]), "PBS/s; ms/step", round(d["ms_per_step"], 3), "; serial", round(d["serial"]["pbs_per_s_per_gpu"]),

@@ -50,3 +50,11 @@ def test_self_launch_relays_rank0_line():
 def test_self_launch_propagates_a_failing_rank():
     out = _self_launch({"FAKE_RANK_FAIL": "1"})
     assert out.returncode != 0
+
+
+def test_full_is_off_by_default_and_forwarded_to_the_ranks():
+    import bench
+    assert bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    assert bench.parse(["--steps", "3", "--full", "--no-p44"]).full is True
+    cmd = bench.launch_command(["--gpus", "2", "--steps", "5", "--full"], 2, 29555)
+    assert cmd[-5:] == ["--gpus", "2", "--steps", "5", "--full"]
