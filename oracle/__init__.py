@@ -450,6 +450,22 @@ class MultiBitServerKey:
         lib().orc_bsk_to_fourier(C.byref(self._pk.c()), self.bsk, self.fbsk)
         self._fft = lib().orc_fft_new(p.N)
 
+    @classmethod
+    def from_keys(cls, params: Params, grouping: int, bsk, threads: int | None = None):
+        """Oracle operators over a multi-bit key made elsewhere (standard domain, n / g * 2^g GGSWs); no keyswitching key."""
+        self = cls.__new__(cls)
+        self.params, self.grouping = params, grouping
+        self.threads = threads or min(8, os.cpu_count() or 1)
+        self.n_ggsw = params.n // grouping * (1 << grouping)
+        self.ksk = None
+        self._pk = dataclasses.replace(params, n=self.n_ggsw)
+        self.bsk = _a(bsk).reshape(-1)
+        assert self.bsk.size == self.n_ggsw * params.pbs_level * (params.k + 1) ** 2 * params.N
+        self.fbsk = np.zeros(self.bsk.size, dtype=np.float64)
+        lib().orc_bsk_to_fourier(C.byref(self._pk.c()), self.bsk, self.fbsk)
+        self._fft = lib().orc_fft_new(params.N)
+        return self
+
     generate_lookup_table = ServerKey.generate_lookup_table
 
     def keyswitch(self, ct):

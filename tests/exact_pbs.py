@@ -93,3 +93,192 @@ def pbs_exact(params, bsk, ct_small, lut):
             out[p * N + 1: (p + 1) * N] = U64(0) - acc[p][:0:-1]
     out[k * N] = acc[k][0]
     return out
+
+
+# ---- batched exact blind rotation over keys held as small integers ---------------------------------------------------
+#
+# A key word is a sum of terms  c << t  with c a small signed integer: the 8-bit limbs of a full-range u64 (t = 0, 8, ..
+# 56), or a single term for the structured keys below.  digits (x) c then stays below L (k+1) N 2^(bl-1) 2^8 <= 2^44 on
+# every shape of the engine, so ONE f64 negacyclic FFT product per term, rounded to the nearest integer, is exact (the
+# rounding assertion in _spectral_product keeps that honest), and the term's contribution is that integer << t in
+# wrapping 64-bit arithmetic.  Vectorised over a batch of LWEs: step i uses GGSW i of every LWE at once.
+
+C_BITS = 8                     # structured keys: c in (-2^7, 2^7)
+EXACT_BOUND_LOG2 = 56          # worst-case |f64 value| of a correct f64 external product, in units of 2^-64 (see structured_bsk)
+
+
+def limb_terms(bsk):
+    """A full-range u64 key as its eight 8-bit limbs: [(int64 array, shift)]."""
+    bsk = np.asarray(bsk, dtype=U64)
+    return [(((bsk >> U64(8 * j)) & U64(0xFF)).astype(np.int64), 8 * j) for j in range(8)]
+
+
+def structured_shift(params, grouping=0):
+    """Largest t <= 14 for which a correct f64 PBS of a key with words c << t (|c| < 2^7) is bit exact:
+        * every product sum(digit * c) * 2^t lies on the 2^12 grid of the engine's from_torus (t >= 12), and
+        * its worst case L (k+1) N 2^(bl-1) 2^7 2^t -- times (2^G - 1) 2 for a multi-bit key's combined GGSW -- stays
+          below 2^56, so an f64 transform's rounding (relative 2^-53 times a few log N) stays far below half a grid step."""
+    L, K1, N, bl = params.pbs_level, params.k + 1, params.N, params.pbs_base_log
+    worst = np.log2(L * K1 * N) + (bl - 1) + (C_BITS - 1)
+    if grouping:
+        worst += np.log2(((1 << grouping) - 1) * 2)
+    t = min(14, int(np.floor(EXACT_BOUND_LOG2 - worst)))
+    assert t >= 12 and worst + t <= EXACT_BOUND_LOG2, (params.name, worst, t)
+    return t
+
+
+def structured_bsk(params, rng, grouping=0):
+    """Bootstrapping key whose every word is c << t, c uniform in (-2^7, 2^7) stored as wrapping u64.  Returns
+    (bsk [n_ggsw, L, k+1, k+1, N] u64, key terms [(c, t)], t); multi-bit keys hold n / G * 2^G GGSWs."""
+    n_ggsw = params.n // grouping * (1 << grouping) if grouping else params.n
+    t = structured_shift(params, grouping)
+    lim = 1 << (C_BITS - 1)
+    c = rng.integers(-lim + 1, lim, size=(n_ggsw, params.pbs_level, params.k + 1, params.k + 1, params.N), dtype=np.int64)
+    return c.astype(U64) << U64(t), [(c, t)], t
+
+
+def edge_small_cts(params, rng, count):
+    """Small-key LWEs whose masks hold a_i = 0, values that modulus-switch to 0, 1, N, 2N - 1 and 2N, and random words;
+    bodies include 0 and 2^64 - 1."""
+    logN = params.N.bit_length() - 1
+    q = 1 << (63 - logN)                                   # one step of the switched modulus 2N
+    edges = [0, 1, q - 1, q, 2 * q, (params.N - 1) * q + q // 2, params.N * q, 2**63, 2**64 - q, 2**64 - 1]
+    cts = rng.integers(0, 2**64, size=(count, params.n + 1), dtype=np.uint64)
+    slots = [(b, i) for b in range(count) for i in range(params.n) if (i + b) % 3 == 0]      # a third of the mask: every edge in turn
+    for j, (b, i) in enumerate(slots):
+        cts[b, i] = edges[j % len(edges)]
+    cts[0, params.n] = 0
+    if count > 1:
+        cts[1, params.n] = 2**64 - 1
+    return cts
+
+
+def monomial_mul_rows(polys, d):
+    """polys[b] * X^d[b] for a batch: polys [B, ..., N] u64, d [B] in [0, 2N)."""
+    N = polys.shape[-1]
+    src = (np.arange(N)[None, :] - np.asarray(d, dtype=np.int64)[:, None]) % (2 * N)          # [B, N]
+    neg = src >= N
+    src = np.where(neg, src - N, src)
+    shape = (polys.shape[0],) + (1,) * (polys.ndim - 2) + (N,)
+    out = np.take_along_axis(polys, src.reshape(shape), axis=-1)
+    with np.errstate(over="ignore"):
+        return np.where(neg.reshape(shape), U64(0) - out, out)
+
+
+def _spectral_product(D, Kspec, tw):
+    """sum over (level, row) of digits (x) key, back to integers: D [B, L, K1, N] spectra of the digits, Kspec [(B,) L, K1, K1, N]
+    spectra of one key term -> [B, K1, N] int64, exact."""
+    S = np.einsum("blrn,blrcn->bcn" if Kspec.ndim == 5 else "blrn,lrcn->bcn", D, Kspec)
+    prod = np.fft.ifft(S, axis=-1) * np.conj(tw)
+    r = np.rint(prod.real)
+    assert np.abs(prod.real - r).max() < 0.05 and np.abs(prod.imag).max() < 0.05      # exactness margin
+    return r.astype(np.int64)
+
+
+def _external_product(acc_in, terms_spec, tw, bl, L):
+    """acc_in [B, K1, N] u64 decomposed and multiplied by the GGSW held as spectra of its terms: [(Kspec, t)] -> [B, K1, N] u64."""
+    digs = decompose(acc_in, bl, L)                                        # L arrays [B, K1, N], level L first
+    lvl_first = np.stack(digs[::-1], axis=1)                               # [B, L, K1, N], level 1 first (the key's order)
+    D = np.fft.fft(lvl_first.astype(np.float64) * tw, axis=-1)
+    out = np.zeros(acc_in.shape, dtype=U64)
+    with np.errstate(over="ignore"):
+        for Kspec, t in terms_spec:
+            out += _spectral_product(D, Kspec, tw).astype(U64) << U64(t)
+    return out
+
+
+def _sample_extract(acc, k, N):
+    B = acc.shape[0]
+    out = np.zeros((B, k * N + 1), dtype=U64)
+    with np.errstate(over="ignore"):
+        for p in range(k):
+            out[:, p * N] = acc[:, p, 0]
+            out[:, p * N + 1: (p + 1) * N] = U64(0) - acc[:, p, :0:-1]
+    out[:, k * N] = acc[:, k, 0]
+    return out
+
+
+def _start(params, cts, luts, lut_idx):
+    N, K1, n = params.N, params.k + 1, params.n
+    logN = N.bit_length() - 1
+    cts = np.asarray(cts, dtype=U64).reshape(-1, n + 1)
+    luts = np.asarray(luts, dtype=U64).reshape(-1, K1, N)
+    idx = np.zeros(len(cts), dtype=np.int64) if lut_idx is None else np.asarray(lut_idx, dtype=np.int64)
+    ms = np.vectorize(lambda x: modulus_switch(x, logN), otypes=[np.int64])
+    acc = monomial_mul_rows(luts[idx], (2 * N - ms(cts[:, n])) % (2 * N))  # X^{-ms(body)}
+    return cts, acc, ms
+
+
+def pbs_exact_batch(params, terms, cts, luts, lut_idx=None):
+    """Classic PBS of every row of cts (small-key LWEs) with LUT luts[lut_idx[b]], exact; the key as terms [(c, t)] of
+    shape [n, L, k+1, k+1, N] (limb_terms(bsk) for any key).  Same algorithm as pbs_exact."""
+    n, k, N, bl, L = params.n, params.k, params.N, params.pbs_base_log, params.pbs_level
+    cts = np.asarray(cts, dtype=U64).reshape(-1, n + 1)
+    if len(cts) > _chunk(params):
+        return _chunked(pbs_exact_batch, params, (terms,), cts, luts, lut_idx)
+    tw = _twist(N)
+    cts, acc, ms = _start(params, cts, luts, lut_idx)
+    with np.errstate(over="ignore"):
+        for i in range(n):
+            live = cts[:, i] != 0                                           # bootstrap.rs:281
+            if not live.any():
+                continue
+            d = ms(cts[:, i]) % (2 * N)
+            ct1 = monomial_mul_rows(acc, d) - acc
+            spec = [(np.fft.fft(c[i].astype(np.float64) * tw, axis=-1), t) for c, t in terms]
+            acc = np.where(live[:, None, None], acc + _external_product(ct1, spec, tw, bl, L), acc)
+    return _sample_extract(acc, k, N)
+
+
+def multi_bit_pbs_exact_batch(params, grouping, terms, cts, luts, lut_idx=None):
+    """Multi-bit PBS (oracle/tfhe_oracle.c multi_bit_blind_rotate, exact branch) of every row of cts.  Per group: the
+    combined GGSW  GGSW_0 + sum_{sel >= 1} X^{ms(sum of the selected mask elements)} GGSW_sel  (the selected sum taken
+    in wrapping u64, then switched; selector bit G-1-b <-> mask element b of the group), then acc <- combined (x) acc.
+    terms [(c, t)] of shape [n / G * 2^G, L, k+1, k+1, N]."""
+    n, k, N, bl, L = params.n, params.k, params.N, params.pbs_base_log, params.pbs_level
+    G = grouping
+    cts = np.asarray(cts, dtype=U64).reshape(-1, n + 1)
+    if len(cts) > _chunk(params):
+        return _chunked(multi_bit_pbs_exact_batch, params, (grouping, terms), cts, luts, lut_idx)
+    tw = _twist(N)
+    cts, acc, ms = _start(params, cts, luts, lut_idx)
+    B = len(cts)
+    with np.errstate(over="ignore"):
+        for grp in range(n // G):
+            mask = cts[:, grp * G:(grp + 1) * G]
+            spec = []
+            for c, t in terms:
+                comb = np.broadcast_to(c[grp << G], (B,) + c.shape[1:]).copy()
+                for sel in range(1, 1 << G):
+                    deg = np.zeros(B, dtype=U64)
+                    for b in range(G):
+                        if (sel >> (G - 1 - b)) & 1:
+                            deg += mask[:, b]
+                    sw = ms(deg) % (2 * N)
+                    term = np.broadcast_to(c[(grp << G) + sel], (B,) + c.shape[1:])
+                    comb += _monomial_mul_signed(term, sw)
+                spec.append((np.fft.fft(comb.astype(np.float64) * tw, axis=-1), t))
+            acc = _external_product(acc, spec, tw, bl, L)
+    return _sample_extract(acc, k, N)
+
+
+def _monomial_mul_signed(polys, d):
+    """Signed-integer twin of monomial_mul_rows: polys [B, ..., N] int64."""
+    N = polys.shape[-1]
+    src = (np.arange(N)[None, :] - np.asarray(d, dtype=np.int64)[:, None]) % (2 * N)
+    neg = src >= N
+    src = np.where(neg, src - N, src)
+    shape = (polys.shape[0],) + (1,) * (polys.ndim - 2) + (N,)
+    out = np.take_along_axis(polys, np.broadcast_to(src.reshape(shape), polys.shape), axis=-1)
+    return np.where(neg.reshape(shape), -out, out)
+
+
+def _chunk(params):
+    """LWEs per pass: the digit spectra of a pass stay near 32 MB."""
+    return max(1, (1 << 21) // (params.pbs_level * (params.k + 1) * params.N))
+
+
+def _chunked(fn, params, args, cts, luts, lut_idx):
+    idx = np.zeros(len(cts), dtype=np.int64) if lut_idx is None else np.asarray(lut_idx, dtype=np.int64)
+    step = _chunk(params)
+    return np.concatenate([fn(params, *args, cts[s:s + step], luts, idx[s:s + step]) for s in range(0, len(cts), step)])
