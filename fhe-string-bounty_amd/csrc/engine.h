@@ -142,6 +142,7 @@ struct Engine {
     ~Engine();
     int use();
     int set_variant(int logR);
+    int allow_rotate_lds();   // hipFuncAttributeMaxDynamicSharedMemorySize of the variants' rotation kernels
     int load_keys(const uint64_t* bsk_std, const uint64_t* ksk);
     int load_seeded_keys(const uint8_t ksk_seed[16], const uint64_t* ksk_bodies, const uint8_t bsk_seed[16], const uint64_t* bsk_bodies,
                          uint64_t* bsk_std_out, uint64_t* ksk_out);
@@ -161,7 +162,8 @@ struct Engine {
     int check_lut_idx(const uint32_t* lut_idx, uint32_t count) const;
 
     int launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t count, hipStream_t on = nullptr, bool shadow = false, int digits_slot = 0);
-    int launch_blind_rotate(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big, uint32_t count, hipStream_t on = nullptr, bool two_per_cu = false);
+    int launch_blind_rotate(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big, uint32_t count, hipStream_t on = nullptr, bool two_per_cu = false,
+                            bool one_workgroup_only = false);   // never a kernel that needs several workgroups resident at once (cluster_settle's re-run)
     bool shadow_keyswitch_fits();
     int ks_pbs_dev(const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint64_t* d_big_out, uint32_t count, bool allow_pipeline = false);
     int ks_pbs_host(const uint64_t* in, const uint32_t* lut_idx, uint64_t* out, uint32_t count);

@@ -199,42 +199,24 @@ BrVariant make_multibit_variant() {
     return v;
 }
 
-// Multi-bit PBS for a shape served by the classic split kernel / the large-N kernel: same Fourier key layout and
-// conversion, rotation = EXTPROD mode against GGSWs prepared by multibit_combine_generic_kernel.
+// Multi-bit PBS for a shape served by the classic split / N = 8192 / large-N kernel (`v` from make_variant, make_seq_variant or make_large_variant):
+// same Fourier key layout and conversion, rotation = that kernel's EXTPROD mode against GGSWs prepared by multibit_combine_generic_kernel.
+template <auto EXTPROD_KERNEL>
+BrVariant make_multibit_two_kernel_variant(BrVariant v, int G) {
+    v.grouping = G;
+    v.rotate_fn = v.extprod_fn = reinterpret_cast<const void*>(EXTPROD_KERNEL);
+    v.combine_generic_fn = G == 2 ? reinterpret_cast<const void*>(&multibit_combine_generic_kernel<2>)
+                                  : reinterpret_cast<const void*>(&multibit_combine_generic_kernel<3>);
+    v.combined_bytes = (size_t)v.L * v.k1 * v.k1 * ((size_t)1 << (v.logN - 1)) * 16;
+    return v;
+}
 template <int LOGN, int LOGR, int K1, int L>
 BrVariant make_multibit_generic_variant(int G) {
-    BrVariant v = make_variant<LOGN, LOGR, K1, L>();
-    v.grouping = G;
-    v.extprod_fn = reinterpret_cast<const void*>(&blind_rotate_kernel<LOGN, LOGR, K1, L, true>);
-    v.rotate_fn = v.extprod_fn;
-    v.combine_generic_fn = G == 2 ? reinterpret_cast<const void*>(&multibit_combine_generic_kernel<2>)
-                                  : reinterpret_cast<const void*>(&multibit_combine_generic_kernel<3>);
-    v.combined_bytes = (size_t)L * K1 * K1 * (size_t)(1 << (LOGN - 1)) * 16;
-    return v;
+    return make_multibit_two_kernel_variant<&blind_rotate_kernel<LOGN, LOGR, K1, L, true>>(make_variant<LOGN, LOGR, K1, L>(), G);
 }
-
 template <int LOGN, int K1, int L>
 BrVariant make_multibit_seq_variant(int G) {
-    BrVariant v = make_seq_variant<LOGN, K1, L>();
-    v.grouping = G;
-    v.extprod_fn = reinterpret_cast<const void*>(&blind_rotate_seq_kernel<LOGN, K1, L, true>);
-    v.rotate_fn = v.extprod_fn;
-    v.combine_generic_fn = G == 2 ? reinterpret_cast<const void*>(&multibit_combine_generic_kernel<2>)
-                                  : reinterpret_cast<const void*>(&multibit_combine_generic_kernel<3>);
-    v.combined_bytes = (size_t)L * K1 * K1 * (size_t)(1 << (LOGN - 1)) * 16;
-    return v;
-}
-
-template <int LOGN, int K1, int L>
-BrVariant make_multibit_large_variant(int G) {
-    BrVariant v = make_large_variant<LOGN, K1, L>();
-    v.grouping = G;
-    v.extprod_fn = reinterpret_cast<const void*>(&blind_rotate_large_kernel<LOGN, K1, L, true>);
-    v.rotate_fn = v.extprod_fn;
-    v.combine_generic_fn = G == 2 ? reinterpret_cast<const void*>(&multibit_combine_generic_kernel<2>)
-                                  : reinterpret_cast<const void*>(&multibit_combine_generic_kernel<3>);
-    v.combined_bytes = (size_t)L * K1 * K1 * (size_t)(1 << (LOGN - 1)) * 16;
-    return v;
+    return make_multibit_two_kernel_variant<&blind_rotate_seq_kernel<LOGN, K1, L, true>>(make_seq_variant<LOGN, K1, L>(), G);
 }
 
 static const std::vector<BrVariant>& variants() {
@@ -288,10 +270,22 @@ static const BrVariant* find_variant(const fhe_params_t& p, int selector) {
     return nullptr;
 }
 
+// The engine's two variants for a selector: `small` up to one LWE per CU, `large` above.  Selector 0 (automatic): the "wide"
+// twin of the default (same points per thread => same key layout) serves the big batches.
+struct BrVariantPair { const BrVariant *small, *large; };
+static BrVariantPair find_variant_pair(const fhe_params_t& p, int selector) {
+    const BrVariant* v = find_variant(p, selector);
+    const BrVariant* w = v && selector == 0 ? find_variant(p, v->logR | 16) : nullptr;
+    return {v, w ? w : v};
+}
+
+// dynamic LDS of a variant's rotation kernel: its fixed part + its table per small-LWE coefficient
+static size_t rotate_lds(const BrVariant* v, const fhe_params_t& p) { return v->lds_bytes + (size_t)p.n * v->lds_per_n; }
+
 // ---- Engine -----------------------------------------------------------------------------------
 // Everything Engine::create checks before it touches a device: shapes the kernels are instantiated for, decomposition
 // ranges of the keyswitch paths (any level count: more than 16 levels take the byte-plane kernel, ks_mfma_supported).
-int params_supported(const fhe_params_t& p, int selector, const BrVariant** out_v) {
+int params_supported(const fhe_params_t& p, int selector) {
     if ((p.N & (p.N - 1)) || p.N < 128) return fail("polynomial size must be a power of two >= 128");
     if (p.pbs_base_log < 1 || p.pbs_base_log > 31 || p.pbs_base_log * p.pbs_level > (p.pbs_level >= 3 ? 62u : 31u))
         return fail("unsupported PBS decomposition (base_log * level must be <= 31, or <= 62 with >= 3 levels)");
@@ -299,13 +293,11 @@ int params_supported(const fhe_params_t& p, int selector, const BrVariant** out_
         return fail("unsupported keyswitch decomposition (base_log 1..7, base_log * level <= 62)");
     if (p.msg_mod * p.carry_mod == 0 || (p.N % (p.msg_mod * p.carry_mod)) != 0)
         return fail("msg_mod * carry_mod must divide N");
-    const BrVariant* v = find_variant(p, selector);
     if (p.grouping_factor > 1 && (p.n % p.grouping_factor) != 0) return fail("grouping factor must divide n");
-    if (!v) return fail("no blind-rotation kernel instantiated for this (N, k, level, grouping factor)");
-    if (out_v) *out_v = v;
+    if (!find_variant(p, selector)) return fail("no blind-rotation kernel instantiated for this (N, k, level, grouping factor)");
     return 0;
 }
-int params_supported(const fhe_params_t& p) { return params_supported(p, 0, nullptr); }
+int params_supported(const fhe_params_t& p) { return params_supported(p, 0); }
 
 // Every environment switch of the library in one place, read when an engine is created.  They exist for diagnostics and A/B
 // measurements (scripts/); the product interface is the API: fhe_engine_set_variant / _set_pipeline / _set_keep_busy /
@@ -329,9 +321,8 @@ EngineEnv EngineEnv::read() {
 }
 
 int Engine::create(const fhe_params_t& p, int device, Engine** out) {
-    const int env_logr = EngineEnv::read().log2_points;
-    const BrVariant* v = nullptr;
-    if (params_supported(p, env_logr, &v)) return 1;
+    const EngineEnv env = EngineEnv::read();
+    if (params_supported(p, env.log2_points)) return 1;
     int count = 0;
     HIP_TRY(hipGetDeviceCount(&count));
     if (count <= 0) return fail("no HIP device: libfhestr has no CPU fallback");
@@ -340,9 +331,9 @@ int Engine::create(const fhe_params_t& p, int device, Engine** out) {
     Engine* e = new Engine();
     e->p = p;
     e->device = device;
-    e->variant = v;
-    e->variant_large = v;
-    const EngineEnv env = EngineEnv::read();
+    const BrVariantPair vp = find_variant_pair(p, env.log2_points);
+    e->variant = vp.small;
+    e->variant_large = vp.large;
     if (env.wide_fair >= 0) e->wide_fair_shift = (uint32_t)std::min(20, env.wide_fair);
     if (env.dense_per_cu >= 0) e->dense_per_cu = (uint32_t)env.dense_per_cu;
     if (env.cluster_fallback >= 0) e->cluster_fallback = env.cluster_fallback != 0;
@@ -356,10 +347,6 @@ int Engine::create(const fhe_params_t& p, int device, Engine** out) {
 #ifdef FHESTR_TEST_HOOKS      // fault injection exists only in the test build (make testhooks), never in the product library
     if (env.cluster_test_fault >= 0) e->cluster_test_fault = (uint32_t)env.cluster_test_fault;
 #endif
-    if (env_logr == 0) {   // automatic: "wide" twin (same points per thread => same key layout) for big batches
-        const BrVariant* w = find_variant(p, v->logR | 16);
-        if (w) e->variant_large = w;
-    }
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     e->cu_count = prop.multiProcessorCount;
@@ -412,26 +399,21 @@ static int ensure(void** ptr, size_t* cap, size_t bytes) {
 }
 
 int Engine::set_variant(int logR) {
-    const BrVariant* v = find_variant(p, logR);
-    if (!v) return fail("no such blind-rotation variant for these parameters");
-    if (d_fbsk && v->logR != variant->logR)
+    const BrVariantPair vp = find_variant_pair(p, logR);
+    if (!vp.small) return fail("no such blind-rotation variant for these parameters");
+    if (d_fbsk && vp.small->logR != variant->logR)
         return fail("variant must be chosen before fhe_engine_load_keys (Fourier key layout depends on it)");
-    variant = v;
-    variant_large = v;
+    variant = vp.small;
+    variant_large = vp.large;
     shadow_fit = -1;
-    if (logR == 0) {
-        const BrVariant* w = find_variant(p, v->logR | 16);
-        if (w) variant_large = w;
-    }
-    if (d_fbsk) {
-        HIP_TRY(hipFuncSetAttribute(variant->rotate_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(variant->lds_bytes + (size_t)p.n * variant->lds_per_n)));
-        HIP_TRY(hipFuncSetAttribute(variant_large->rotate_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(variant_large->lds_bytes + (size_t)p.n * variant_large->lds_per_n)));
-        if (variant->rotate_combined_fn)
-            HIP_TRY(hipFuncSetAttribute(variant->rotate_combined_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)(variant->lds_bytes + (size_t)p.n * variant->lds_per_n)));
-    }
+    return d_fbsk ? allow_rotate_lds() : 0;
+}
+
+int Engine::allow_rotate_lds() {
+    HIP_TRY(hipFuncSetAttribute(variant->rotate_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rotate_lds(variant, p)));
+    HIP_TRY(hipFuncSetAttribute(variant_large->rotate_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rotate_lds(variant_large, p)));
+    if (variant->rotate_combined_fn)
+        HIP_TRY(hipFuncSetAttribute(variant->rotate_combined_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rotate_lds(variant, p)));
     return 0;
 }
 
@@ -669,14 +651,7 @@ int Engine::install_keys(uint64_t* d_ksk_std, uint64_t* d_std) {
         HIP_TRY(hipStreamSynchronize(stream));
     }
     if (variant->combine_generic_fn && probe_slot_exponents()) return 1;
-    HIP_TRY(hipFuncSetAttribute(variant->rotate_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(variant->lds_bytes + (size_t)p.n * variant->lds_per_n)));
-    HIP_TRY(hipFuncSetAttribute(variant_large->rotate_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(variant_large->lds_bytes + (size_t)p.n * variant_large->lds_per_n)));
-    if (variant->rotate_combined_fn)
-        HIP_TRY(hipFuncSetAttribute(variant->rotate_combined_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(variant->lds_bytes + (size_t)p.n * variant->lds_per_n)));
-    return 0;
+    return allow_rotate_lds();
 }
 
 // fill_accumulator: shortint/engine/mod.rs:72-128.  box_values[i] = the torus value the table returns on box i
@@ -809,171 +784,199 @@ int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t cou
     return fail("keyswitch key not installed");
 }
 
-int Engine::launch_blind_rotate(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big,
-                                uint32_t count, hipStream_t on, bool two_per_cu) {
+// ---- blind-rotation dispatch: choose_rotate_path is the map, then one launch function per path ----------------------
+enum class BrPath { Overlapped, MultiBitCombined, MultiBitTwoKernel, WholeXcd, Cluster, Large, Dense, Plain };
+
+// Which path serves a batch, and (`v`) on which of the engine's two variants.  Reads cu_count and the dispatch settings
+// (cluster_mode, cluster_max_batch, xcd_auto_max, multibit_combine_max, dense_per_cu, whether d_fbsk_dense exists); calls no HIP
+// function.  The order of the tests matters.  one_workgroup_only: the re-run of Engine::cluster_settle, never a multi-CU kernel.
+static BrPath choose_rotate_path(const Engine& e, uint32_t count, bool two_per_cu, bool one_workgroup_only, const BrVariant*& v) {
+    const uint32_t cus = (uint32_t)e.cu_count;
+    // one LWE per CU or fewer: spread it over more threads; above that: the compact layout that lets two LWEs share a CU
+    v = two_per_cu || count > cus ? e.variant_large : e.variant;
+    if (two_per_cu) return BrPath::Overlapped;      // overlapped throughput mode: the compact layout whatever the batch size, on the given stream
+    // far fewer LWEs than CUs: the idle CUs prepare the groups' GGSWs (lwe_multi_bit_programmable_bootstrapping.rs
+    // splits the same way over CPU threads), the rotation then runs n/G plain external products
+    if (v->combine_fn && count <= e.multibit_combine_max) return BrPath::MultiBitCombined;
+    // multi-bit PBS on a shape without a fused kernel: prepare the (LWE, group) GGSWs, then n/G external products per LWE
+    if (v->extprod_fn) return BrPath::MultiBitTwoKernel;
+    // automatic mode: the whole-XCD kernel up to two LWEs per XCD (one LWE 12.3 ms, 16 LWEs 18.4 ms; the 8-CU clusters: 20.9 /
+    // 21.4 ms), the 8-CU clusters above (256 LWEs: 1.15 k PBS/s against 0.85 k -- four LWEs in flight per XCD amortise the
+    // hand-over latency better than two; profiles/r04_xcd_history.txt).  Mode 2: clusters, never the whole-XCD kernel.
+    // (a device with fewer than 8 * C compute units -- e.g. one XCD of a partitioned GPU -- cannot host a grid of either
+    // kernel: it takes the one-workgroup kernel below)
+    const int mode = one_workgroup_only ? 0 : e.cluster_mode;
+    if (v->xcd_fn && mode != 0 && mode != 2 && (mode == 1 || count <= std::min(e.cluster_max_batch, e.xcd_auto_max)) &&
+        cus >= 8u * (uint32_t)v->xcd_size)
+        return BrPath::WholeXcd;
+    if (v->cluster_fn && mode != 0 && (mode >= 1 || count <= e.cluster_max_batch) && cus >= 8u * (uint32_t)v->cluster_size)
+        return BrPath::Cluster;
+    if (v->large) return BrPath::Large;      // polynomial beyond the LDS: one workgroup per LWE with an HBM workspace
+    // more than two LWEs per CU: the variant that puts four on one
+    if (v->dense_fn && e.d_fbsk_dense && e.dense_per_cu && count > e.dense_per_cu * cus) return BrPath::Dense;
+    return BrPath::Plain;
+}
+
+// May a call take throughput mode 2 (whole calls overlapped on several streams)?  Own stream only (a caller's stream is ordered by the caller); the
+// rotation is the two-LWEs-per-CU twin of the primary variant, not multi-bit, at most one LWE per CU: two such launches then share every CU.
+static bool overlapped_mode_eligible(const Engine& e, uint32_t count) {
+    return e.stream == e.own_stream && e.variant_large != e.variant && e.variant_large->wide && !e.variant->extprod_fn &&
+           !e.variant->combine_fn && count <= (uint32_t)e.cu_count;
+}
+// May a call take throughput mode 1 (its keyswitch in the shadow of the previous call's blind rotation)?  Own stream only; the rotation is the plain
+// launch of a variant neither wide nor large nor two-kernel multi-bit, at most one LWE per CU.  Engine::shadow_keyswitch_fits is asked as well.
+static bool shadow_mode_eligible(const Engine& e, uint32_t count) {
+    return e.stream == e.own_stream && !e.variant->large && !e.variant->wide && !e.variant->extprod_fn && count <= (uint32_t)e.cu_count;
+}
+
+// The Fourier key `v` reads: a wide variant on a plan of its own that is not the engine's primary variant takes the dense kernel's copy (nullptr: missing).
+static const double* rotation_key(const Engine& e, const BrVariant* v) { return v->own_plan && v != e.variant ? e.d_fbsk_dense : e.d_fbsk; }
+
+static int rotate_overlapped(Engine& e, const BrVariant* w, BlindRotateArgs a, hipStream_t on) {
+    a.fair_shift = e.wide_fair_shift;      // the two launches that share the GPU progress at the same rate (110 k -> 122 k PBS/s)
+    if (!(a.fbsk = rotation_key(e, w))) return fail("wide kernel: the key copy in its plan's order is missing");
+    void* args[] = {(void*)&a};
+    HIP_TRY(hipLaunchKernel(w->rotate_fn, dim3(a.batch), dim3(w->threads), args, rotate_lds(w, e.p), on));
+    return 0;
+}
+
+static int rotate_multibit_combined(Engine& e, const BrVariant* v, const BlindRotateArgs& a) {
+    const size_t groups = e.p.n / e.p.grouping_factor;
+    if (ensure(&e.d_ws, &e.cap_ws, (size_t)a.batch * groups * v->combined_bytes)) return 1;
+    MultiBitCombineArgs ca{a, reinterpret_cast<double2*>(e.d_ws)};
+    void* cargs[] = {(void*)&ca};
+    HIP_TRY(hipLaunchKernel(v->combine_fn, dim3((unsigned)groups, (unsigned)v->combine_grid_y, (a.batch + v->combine_chunk - 1) / v->combine_chunk),
+                            dim3(v->threads), cargs, v->combine_lds, e.stream));
+    BlindRotateArgs b = a;
+    b.fbsk = reinterpret_cast<const double*>(e.d_ws);
+    void* bargs[] = {(void*)&b};
+    HIP_TRY(hipLaunchKernel(v->rotate_combined_fn, dim3(a.batch), dim3(v->threads), bargs, rotate_lds(v, e.p), e.stream));
+    return 0;
+}
+
+// Sub-batches keep the prepared GGSWs within a fixed workspace.
+static int rotate_multibit_two_kernel(Engine& e, const BrVariant* v, const BlindRotateArgs& a) {
+    const fhe_params_t& p = e.p;
+    const uint32_t count = a.batch;
+    const size_t groups = p.n / p.grouping_factor, per_lwe = groups * v->combined_bytes;
+    const size_t rot_ws = v->large ? v->ws_bytes : 0;
+    size_t cap = e.multibit_workspace_cap;
+    if (cap == 0) {       // automatic: half of what is free now (plus what the workspace already holds), at most 64 GB
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        cap = std::min<size_t>((size_t)64 << 30, (free_b + e.cap_ws) / 2);
+    }
+    const uint32_t sub_max = (uint32_t)std::max<size_t>(1, std::min<size_t>(count, cap / (per_lwe + rot_ws)));
+    if (ensure(&e.d_ws, &e.cap_ws, (size_t)sub_max * (per_lwe + rot_ws))) return 1;
+    unsigned char* rot_base = reinterpret_cast<unsigned char*>(e.d_ws) + (size_t)sub_max * per_lwe;
+    const uint32_t logN = (uint32_t)v->logN, ggsw_elems = (uint32_t)(v->combined_bytes / 16);
+    const size_t combine_lds = ((size_t)(1u << ((logN + 1) / 2)) + (size_t)(1u << (logN + 1 - (logN + 1) / 2))) * 16;
+    const size_t big = (size_t)p.k * p.N + 1;
+    for (uint32_t first = 0; first < count; first += sub_max) {
+        const uint32_t sub = std::min(sub_max, count - first);
+        MultiBitCombineGenericArgs ca{a.lwe_small + (size_t)first * (p.n + 1), reinterpret_cast<const double2*>(e.d_fbsk), e.d_slot_exp,
+                                      reinterpret_cast<double2*>(e.d_ws), p.n, logN, p.N / 2, ggsw_elems, sub};
+        void* cargs[] = {(void*)&ca};
+        HIP_TRY(hipLaunchKernel(v->combine_generic_fn, dim3((unsigned)groups, (ggsw_elems + 511) / 512, (sub + 7) / 8), dim3(256),
+                                cargs, combine_lds, e.stream));
+        BlindRotateLargeArgs la{{a.lwe_small + (size_t)first * (p.n + 1), a.lut_idx ? a.lut_idx + first : nullptr, a.luts,
+                                 reinterpret_cast<const double*>(e.d_ws), a.lwe_out + (size_t)first * big, p.n, p.pbs_base_log, sub,
+                                 p.grouping_factor}, rot_base};
+        void* largs[] = {v->large ? (void*)&la : (void*)&la.base};      // the HBM-workspace kernels take theirs behind the same arguments
+        HIP_TRY(hipLaunchKernel(v->extprod_fn, dim3(sub), dim3(v->threads), largs, rotate_lds(v, p), e.stream));
+    }
+    return 0;
+}
+
+// Several CUs per LWE (the whole-XCD kernel and the 8-CU clusters): the grid is a whole number of 8 * C workgroups (the
+// dispatcher deals workgroups round-robin over the 8 XCDs, the kernel forms its clusters from what each XCD actually
+// received) and every workgroup of it must be resident at once: `rounds` workgroups per CU, no more.
+static int rotate_multi_cu(Engine& e, const BlindRotateArgs& a, const void* fn, uint32_t C, int threads, size_t lds, size_t lds_one_per_cu,
+                           size_t ws_per_cluster, uint32_t rounds) {
+    const uint32_t quantum = 8 * C;
+    const uint32_t max_clusters = std::min<uint32_t>((uint32_t)CLUSTER_MAX, ((uint32_t)e.cu_count / quantum) * 8 * rounds);
+    const uint32_t grid = (std::min(a.batch, max_clusters) + 7) / 8 * quantum;
+    if (grid <= (uint32_t)e.cu_count) lds = std::max(lds, lds_one_per_cu);
+    if (ensure(&e.d_cluster_ws, &e.cap_cluster_ws, (size_t)max_clusters * ws_per_cluster)) return 1;
+    if (!e.d_cluster_ctl) {
+        HIP_TRY(hipMalloc((void**)&e.d_cluster_ctl, sizeof(ClusterCtl) + sizeof(ClusterStatus)));
+        HIP_TRY(hipMemsetAsync(e.d_cluster_ctl, 0, sizeof(ClusterCtl) + sizeof(ClusterStatus), e.stream));
+    }
+    // tickets and flags start from zero; the status words behind them are sticky (read by cluster_status())
+    HIP_TRY(hipMemsetAsync(e.d_cluster_ctl, 0, sizeof(ClusterCtl), e.stream));
+    ClusterCtl* ctl = reinterpret_cast<ClusterCtl*>(e.d_cluster_ctl);
+    BlindRotateClusterArgs ka{a, reinterpret_cast<unsigned char*>(e.d_cluster_ws), ctl, reinterpret_cast<ClusterStatus*>(ctl + 1),
+                              e.cluster_spin_limit, e.cluster_test_fault};
+    void* kargs[] = {(void*)&ka};
+    HIP_TRY(hipLaunchKernel(fn, dim3(grid), dim3(threads), kargs, lds, e.stream));
+    return e.cluster_settle(a.lwe_small, a.lut_idx, a.lwe_out, a.batch);
+}
+
+// All CUs of an XCD per LWE (pbs_xcd_kernels.hip.h).  Up to 8 LWEs: one cluster per XCD, one 256-thread workgroup
+// per CU (the dynamic LDS request is padded past half a CU's LDS so that no CU takes two).  More: two clusters per
+// XCD, i.e. two workgroups on every CU -- the grid is exactly what the device holds.
+static int rotate_whole_xcd(Engine& e, const BrVariant* v, const BlindRotateArgs& a) {
+    const size_t lds2 = v->xcd_lds + (size_t)e.p.n * 4;
+    if (e.xcd_per_cu < 0) {       // once per engine: do two of its workgroups fit a CU?  (registers, LDS: asked, not assumed)
+        int per_cu = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->xcd_fn, v->xcd_threads, lds2));
+        e.xcd_per_cu = per_cu;
+    }
+    const uint32_t rounds = (a.batch > 8 && e.xcd_per_cu >= 2) ? 2u : 1u;
+    return rotate_multi_cu(e, a, v->xcd_fn, (uint32_t)v->xcd_size, v->xcd_threads, lds2, v->xcd_lds_one_per_cu, v->xcd_ws, rounds);
+}
+
+static int rotate_large(Engine& e, const BrVariant* v, const BlindRotateArgs& a) {
+    if (ensure(&e.d_ws, &e.cap_ws, (size_t)a.batch * v->ws_bytes)) return 1;
+    BlindRotateLargeArgs la{a, reinterpret_cast<unsigned char*>(e.d_ws)};
+    void* largs[] = {(void*)&la};
+    HIP_TRY(hipLaunchKernel(v->rotate_fn, dim3(a.batch), dim3(v->threads), largs, rotate_lds(v, e.p), e.stream));
+    return 0;
+}
+
+static int rotate_dense(Engine& e, const BrVariant* v, BlindRotateArgs a) {
+    a.fair_shift = 0;
+    a.fbsk = e.d_fbsk_dense;
+    void* args[] = {(void*)&a};
+    HIP_TRY(hipLaunchKernel(v->dense_fn, dim3(a.batch), dim3(v->threads), args, v->dense_lds + (size_t)e.p.n * v->lds_per_n, e.stream));
+    return 0;
+}
+
+static int rotate_plain(Engine& e, const BrVariant* v, BlindRotateArgs a) {
+    uint32_t grid = a.batch;
+    // keep-busy mode (fhe_engine_set_keep_busy): a launch that would leave more than half of the CUs idle carries replicas of
+    // its workgroups on them (they recompute and store nothing) -- the part then keeps its clock for the large launch that
+    // follows (2.22 -> 2.39 GHz over 14 ms otherwise, profiles/r03_after_idle.txt), at the price of the energy
+    if (e.keep_busy && !v->wide && !v->large && a.batch * 2 <= (uint32_t)e.cu_count) grid = a.batch * ((uint32_t)e.cu_count / a.batch);
+    if (!(a.fbsk = rotation_key(e, v))) return fail("wide kernel: the key copy in its plan's order is missing");
+    void* args[] = {(void*)&a};
+    HIP_TRY(hipLaunchKernel(v->rotate_keypf_fn && v->wide ? v->rotate_keypf_fn : v->rotate_fn, dim3(grid), dim3(v->threads), args,
+                            rotate_lds(v, e.p), e.stream));
+    return 0;
+}
+
+int Engine::launch_blind_rotate(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big, uint32_t count, hipStream_t on,
+                                bool two_per_cu, bool one_workgroup_only) {
     if (!d_fbsk) return fail("keys not loaded");
     if (n_luts == 0) return fail("no lookup table uploaded");
     BlindRotateArgs a{d_sm, d_lut_idx, d_luts, d_fbsk, d_big, p.n, p.pbs_base_log, count};
     a.grouping = 0;
     // two-LWEs-per-CU kernel: fair time-sliced priorities when every CU gets an even number of workgroups (pbs_kernels.hip.h)
-    a.fair_shift = (!two_per_cu && wide_fair_shift && count > (uint32_t)cu_count && (((count + (uint32_t)cu_count - 1) / (uint32_t)cu_count) & 1u) == 0) ? wide_fair_shift : 0u;
-    void* args[] = {(void*)&a};
-    if (two_per_cu) {          // overlapped throughput mode: the compact layout whatever the batch size, on the given stream
-        const BrVariant* w = variant_large;
-        a.fair_shift = wide_fair_shift;      // the two launches that share the GPU progress at the same rate (110 k -> 122 k PBS/s)
-        if (w->own_plan && w != variant) {
-            if (!d_fbsk_dense) return fail("wide kernel: the key copy in its plan's order is missing");
-            a.fbsk = d_fbsk_dense;
-        }
-        HIP_TRY(hipLaunchKernel(w->rotate_fn, dim3(count), dim3(w->threads), args, w->lds_bytes + (size_t)p.n * w->lds_per_n, on ? on : stream));
-        return 0;
+    const uint32_t cus = (uint32_t)cu_count;
+    a.fair_shift = (count > cus && (((count + cus - 1) / cus) & 1u) == 0) ? wide_fair_shift : 0u;
+    const BrVariant* v = nullptr;
+    switch (choose_rotate_path(*this, count, two_per_cu, one_workgroup_only, v)) {
+        case BrPath::Overlapped: return rotate_overlapped(*this, v, a, on ? on : stream);
+        case BrPath::MultiBitCombined: return rotate_multibit_combined(*this, v, a);
+        case BrPath::MultiBitTwoKernel: return rotate_multibit_two_kernel(*this, v, a);
+        case BrPath::WholeXcd: return rotate_whole_xcd(*this, v, a);
+        case BrPath::Cluster:       // 8-CU clusters (pbs_cluster_kernels.hip.h): never more than one workgroup per CU
+            return rotate_multi_cu(*this, a, v->cluster_fn, (uint32_t)v->cluster_size, v->threads, v->cluster_lds + (size_t)p.n * 4, 0, v->cluster_ws, 1);
+        case BrPath::Large: return rotate_large(*this, v, a);
+        case BrPath::Dense: return rotate_dense(*this, v, a);
+        case BrPath::Plain: break;
     }
-    // one LWE per CU or fewer: spread it over more threads; above that: the compact layout that
-    // lets two LWEs share a CU
-    const BrVariant* v = count > (uint32_t)cu_count ? variant_large : variant;
-    if (v->combine_fn && count <= multibit_combine_max) {
-        // far fewer LWEs than CUs: the idle CUs prepare the groups' GGSWs (lwe_multi_bit_programmable_bootstrapping.rs
-        // splits the same way over CPU threads), the rotation then runs n/G plain external products
-        const size_t groups = p.n / p.grouping_factor;
-        if (ensure(&d_ws, &cap_ws, (size_t)count * groups * v->combined_bytes)) return 1;
-        MultiBitCombineArgs ca{a, reinterpret_cast<double2*>(d_ws)};
-        void* cargs[] = {(void*)&ca};
-        HIP_TRY(hipLaunchKernel(v->combine_fn, dim3((unsigned)groups, (unsigned)v->combine_grid_y, (count + v->combine_chunk - 1) / v->combine_chunk),
-                                dim3(v->threads), cargs,
-                                v->combine_lds, stream));
-        BlindRotateArgs b = a;
-        b.fbsk = reinterpret_cast<const double*>(d_ws);
-        void* bargs[] = {(void*)&b};
-        HIP_TRY(hipLaunchKernel(v->rotate_combined_fn, dim3(count), dim3(v->threads), bargs,
-                                v->lds_bytes + (size_t)p.n * v->lds_per_n, stream));
-        return 0;
-    }
-    if (v->extprod_fn) {
-        // multi-bit PBS on a shape without a fused kernel: prepare the (LWE, group) GGSWs, then n/G external
-        // products per LWE; sub-batches keep the prepared GGSWs within a fixed workspace
-        const size_t groups = p.n / p.grouping_factor, per_lwe = groups * v->combined_bytes;
-        const size_t rot_ws = v->large ? v->ws_bytes : 0;
-        size_t cap = multibit_workspace_cap;
-        if (cap == 0) {       // automatic: half of what is free now (plus what the workspace already holds), at most 64 GB
-            size_t free_b = 0, total_b = 0;
-            HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-            cap = std::min<size_t>((size_t)64 << 30, (free_b + cap_ws) / 2);
-        }
-        const uint32_t sub_max = (uint32_t)std::max<size_t>(1, std::min<size_t>(count, cap / (per_lwe + rot_ws)));
-        if (ensure(&d_ws, &cap_ws, (size_t)sub_max * (per_lwe + rot_ws))) return 1;
-        unsigned char* rot_base = reinterpret_cast<unsigned char*>(d_ws) + (size_t)sub_max * per_lwe;
-        uint32_t logN = 0;
-        while ((1u << logN) < p.N) logN++;
-        const uint32_t ggsw_elems = (uint32_t)(v->combined_bytes / 16);
-        const size_t combine_lds = ((size_t)(1u << ((logN + 1) / 2)) + (size_t)(1u << (logN + 1 - (logN + 1) / 2))) * 16;
-        const size_t big = (size_t)p.k * p.N + 1;
-        for (uint32_t first = 0; first < count; first += sub_max) {
-            const uint32_t sub = std::min(sub_max, count - first);
-            MultiBitCombineGenericArgs ca{d_sm + (size_t)first * (p.n + 1), reinterpret_cast<const double2*>(d_fbsk), d_slot_exp,
-                                          reinterpret_cast<double2*>(d_ws), p.n, logN, p.N / 2, ggsw_elems, sub};
-            void* cargs[] = {(void*)&ca};
-            HIP_TRY(hipLaunchKernel(v->combine_generic_fn, dim3((unsigned)groups, (ggsw_elems + 511) / 512, (sub + 7) / 8), dim3(256),
-                                    cargs, combine_lds, stream));
-            BlindRotateArgs b{d_sm + (size_t)first * (p.n + 1), d_lut_idx ? d_lut_idx + first : nullptr, d_luts,
-                              reinterpret_cast<const double*>(d_ws), d_big + (size_t)first * big, p.n, p.pbs_base_log, sub,
-                              p.grouping_factor};
-            if (v->large) {
-                BlindRotateLargeArgs la{b, rot_base};
-                void* largs[] = {(void*)&la};
-                HIP_TRY(hipLaunchKernel(v->extprod_fn, dim3(sub), dim3(v->threads), largs,
-                                        v->lds_bytes + (size_t)p.n * v->lds_per_n, stream));
-            } else {
-                void* bargs[] = {(void*)&b};
-                HIP_TRY(hipLaunchKernel(v->extprod_fn, dim3(sub), dim3(v->threads), bargs,
-                                        v->lds_bytes + (size_t)p.n * v->lds_per_n, stream));
-            }
-        }
-        return 0;
-    }
-    // (a device with fewer than 8 * C compute units -- e.g. one XCD of a partitioned GPU -- cannot host a grid of the
-    // cluster kernel: it takes the one-workgroup kernel below)
-    // automatic mode: the whole-XCD kernel up to two LWEs per XCD (one LWE 12.3 ms, 16 LWEs 18.4 ms; the 8-CU clusters: 20.9 /
-    // 21.4 ms), the 8-CU clusters above (256 LWEs: 1.15 k PBS/s against 0.85 k -- four LWEs in flight per XCD amortise the
-    // hand-over latency better than two; profiles/r04_xcd_history.txt)
-    if (v->xcd_fn && cluster_mode != 0 && cluster_mode != 2 && (cluster_mode == 1 || count <= std::min(cluster_max_batch, xcd_auto_max)) &&
-        (uint32_t)cu_count >= 8u * (uint32_t)v->xcd_size) {
-        // All CUs of an XCD per LWE (pbs_xcd_kernels.hip.h).  Up to 8 LWEs: one cluster per XCD, one 256-thread workgroup
-        // per CU (the dynamic LDS request is padded past half a CU's LDS so that no CU takes two).  More: two clusters per
-        // XCD, i.e. two workgroups on every CU -- the grid is exactly what the device holds, every workgroup must be resident.
-        const uint32_t C = (uint32_t)v->xcd_size, quantum = 8 * C;
-        const size_t lds2 = v->xcd_lds + (size_t)p.n * 4;
-        if (xcd_per_cu < 0) {       // once per engine: do two of its workgroups fit a CU?  (registers, LDS: asked, not assumed)
-            int per_cu = 0;
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->xcd_fn, v->xcd_threads, lds2));
-            xcd_per_cu = per_cu;
-        }
-        const uint32_t rounds = (count > 8 && xcd_per_cu >= 2) ? 2u : 1u;
-        const uint32_t max_clusters = std::min<uint32_t>((uint32_t)CLUSTER_MAX, ((uint32_t)cu_count / quantum) * 8 * rounds);
-        const uint32_t want = std::min(count, max_clusters);
-        const uint32_t grid = (want + 7) / 8 * quantum;
-        const size_t lds = grid <= (uint32_t)cu_count ? std::max(lds2, v->xcd_lds_one_per_cu) : lds2;
-        if (ensure(&d_cluster_ws, &cap_cluster_ws, (size_t)max_clusters * v->xcd_ws)) return 1;
-        if (!d_cluster_ctl) {
-            HIP_TRY(hipMalloc((void**)&d_cluster_ctl, sizeof(ClusterCtl) + sizeof(ClusterStatus)));
-            HIP_TRY(hipMemsetAsync(d_cluster_ctl, 0, sizeof(ClusterCtl) + sizeof(ClusterStatus), stream));
-        }
-        HIP_TRY(hipMemsetAsync(d_cluster_ctl, 0, sizeof(ClusterCtl), stream));
-        ClusterCtl* ctl = reinterpret_cast<ClusterCtl*>(d_cluster_ctl);
-        BlindRotateClusterArgs ka{a, reinterpret_cast<unsigned char*>(d_cluster_ws), ctl, reinterpret_cast<ClusterStatus*>(ctl + 1),
-                                  cluster_spin_limit, cluster_test_fault};
-        void* kargs[] = {(void*)&ka};
-        HIP_TRY(hipLaunchKernel(v->xcd_fn, dim3(grid), dim3(v->xcd_threads), kargs, lds, stream));
-        return cluster_settle(d_sm, d_lut_idx, d_big, count);
-    }
-    if (v->cluster_fn && cluster_mode != 0 && (cluster_mode >= 1 || count <= cluster_max_batch) &&
-        (uint32_t)cu_count >= 8u * (uint32_t)v->cluster_size) {
-        // Several CUs per LWE: the grid is a whole number of 8 * C workgroups (the dispatcher deals workgroups
-        // round-robin over the 8 XCDs, the kernel forms its clusters from what each XCD actually received),
-        // never more than one workgroup per CU -- every workgroup of the grid must be resident at once.
-        const uint32_t C = (uint32_t)v->cluster_size, quantum = 8 * C;
-        const uint32_t max_clusters = std::min<uint32_t>((uint32_t)CLUSTER_MAX, ((uint32_t)cu_count / quantum) * 8);
-        const uint32_t want = std::min(count, max_clusters);
-        const uint32_t grid = (want + 7) / 8 * quantum;
-        if (ensure(&d_cluster_ws, &cap_cluster_ws, (size_t)max_clusters * v->cluster_ws)) return 1;
-        if (!d_cluster_ctl) {
-            HIP_TRY(hipMalloc((void**)&d_cluster_ctl, sizeof(ClusterCtl) + sizeof(ClusterStatus)));
-            HIP_TRY(hipMemsetAsync(d_cluster_ctl, 0, sizeof(ClusterCtl) + sizeof(ClusterStatus), stream));
-        }
-        // tickets and flags start from zero; the status words behind them are sticky (read by cluster_status())
-        HIP_TRY(hipMemsetAsync(d_cluster_ctl, 0, sizeof(ClusterCtl), stream));
-        ClusterCtl* ctl = reinterpret_cast<ClusterCtl*>(d_cluster_ctl);
-        BlindRotateClusterArgs ka{a, reinterpret_cast<unsigned char*>(d_cluster_ws), ctl, reinterpret_cast<ClusterStatus*>(ctl + 1),
-                                  cluster_spin_limit, cluster_test_fault};
-        void* kargs[] = {(void*)&ka};
-        HIP_TRY(hipLaunchKernel(v->cluster_fn, dim3(grid), dim3(v->threads), kargs, v->cluster_lds + (size_t)p.n * 4, stream));
-        return cluster_settle(d_sm, d_lut_idx, d_big, count);
-    }
-    if (v->large) {
-        if (ensure(&d_ws, &cap_ws, (size_t)count * v->ws_bytes)) return 1;
-        BlindRotateLargeArgs la{a, reinterpret_cast<unsigned char*>(d_ws)};
-        void* largs[] = {(void*)&la};
-        HIP_TRY(hipLaunchKernel(v->rotate_fn, dim3(count), dim3(v->threads), largs,
-                                v->lds_bytes + (size_t)p.n * v->lds_per_n, stream));
-        return 0;
-    }
-    // keep-busy mode (fhe_engine_set_keep_busy): a launch that would leave more than half of the CUs idle carries replicas of
-    // its workgroups on them (they recompute and store nothing) -- the part then keeps its clock for the large launch that
-    // follows (2.22 -> 2.39 GHz over 14 ms otherwise, profiles/r03_after_idle.txt), at the price of the energy
-    if (v->dense_fn && d_fbsk_dense && dense_per_cu && count > dense_per_cu * (uint32_t)cu_count) {       // more than two LWEs per CU: the variant that puts four on one
-        a.fair_shift = 0;
-        a.fbsk = d_fbsk_dense;
-        HIP_TRY(hipLaunchKernel(v->dense_fn, dim3(count), dim3(v->threads), args, v->dense_lds + (size_t)p.n * v->lds_per_n, stream));
-        return 0;
-    }
-    uint32_t grid = count;
-    if (keep_busy && !v->wide && !v->large && count * 2 <= (uint32_t)cu_count) grid = count * ((uint32_t)cu_count / count);
-    if (v->own_plan && v != variant) {
-        if (!d_fbsk_dense) return fail("wide kernel: the key copy in its plan's order is missing");
-        a.fbsk = d_fbsk_dense;
-    }
-    HIP_TRY(hipLaunchKernel(v->rotate_keypf_fn && v->wide ? v->rotate_keypf_fn : v->rotate_fn, dim3(grid), dim3(v->threads), args,
-                            v->lds_bytes + (size_t)p.n * v->lds_per_n, stream));
-    return 0;
+    return rotate_plain(*this, v, a);
 }
 
 // Can a 64-register keyswitch wave sit on a SIMD next to the blind rotation's waves?  (one workgroup per CU, its waves
@@ -1005,8 +1008,7 @@ int Engine::ks_pbs_dev(const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint
     }
     hipEvent_t* e4 = &ring[(ring_used % RING) * 4];     // keyswitch start / end, blind rotation start / end
     ring_used++;
-    if (allow_pipeline && pipeline == 2 && stream == own_stream && variant_large != variant && variant_large->wide &&
-        !variant->extprod_fn && !variant->combine_fn && count <= (uint32_t)cu_count) {
+    if (allow_pipeline && pipeline == 2 && overlapped_mode_eligible(*this, count)) {
         // Overlapped batches (fhe_engine_set_pipeline(2)): consecutive calls alternate between ovl_streams (2) streams and
         // run on the two-LWEs-per-CU kernel with time-sliced priorities (BlindRotateArgs::fair_shift), so two 256-LWE
         // launches share every CU and progress at the same rate -- the pace of a 512-LWE launch (2.09 ms per call,
@@ -1068,8 +1070,7 @@ int Engine::ks_pbs_dev(const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint
         pipe_calls++;
         return 0;
     }
-    if (allow_pipeline && pipeline == 1 && stream == own_stream && !variant->large && !variant->wide && !variant->extprod_fn &&
-        count <= (uint32_t)cu_count && shadow_keyswitch_fits()) {
+    if (allow_pipeline && pipeline == 1 && shadow_mode_eligible(*this, count) && shadow_keyswitch_fits()) {
         // Pipelined mode (fhe_engine_set_pipeline): the keyswitch of this call runs on a second stream, in a 64-VGPR
         // variant whose waves fit next to the two 220-VGPR waves per SIMD of the blind rotation still running for the
         // previous call, into the other of two small-ciphertext buffers.  Calls are independent unless this call's
@@ -1331,11 +1332,7 @@ int Engine::cluster_settle(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint
     HIP_TRY(hipMemsetAsync(d_st, 0, sizeof(st), stream));
     cluster_fallbacks++;
     cluster_last_error = st.error;
-    const int saved = cluster_mode;
-    cluster_mode = 0;
-    const int rc = launch_blind_rotate(d_sm, d_lut_idx, d_big, count);
-    cluster_mode = saved;
-    return rc;
+    return launch_blind_rotate(d_sm, d_lut_idx, d_big, count, nullptr, false, /*one_workgroup_only=*/true);
 }
 
 int Engine::cluster_check() {

@@ -4,7 +4,7 @@ Tier 1, bit exact: under a structured bootstrapping key (every word c << t, |c| 
 every value of a correct f64 PBS lies on the engine's from_torus grid with a wide margin (tests/test_exact_pbs.py pins
 that premise on the CPU oracle), so the whole output ciphertext -- mask and body -- must equal the exact integer PBS bit
 for bit.  A transform that lost precision, a wrong twiddle, a swapped GGSW block, level or sign shows as a mismatch.
-Each path is reached through the public setters and batch sizes only (Engine::launch_blind_rotate in csrc/engine.hip is
+Each path is reached through the public setters and batch sizes only (choose_rotate_path in csrc/engine.hip is
 the map; an MI355X has 256 CUs).
 
 Tier 2, full scale: uniformly random keys and LWEs with exactly one non-zero mask element (one CMUX, no decomposition
