@@ -112,6 +112,23 @@ int fhe_engine_expand_seeded_lwe(fhe_engine* eng, const uint8_t* seeds, const ui
     API_END
 }
 
+int fhe_engine_expand_compact_list(fhe_engine* eng, const uint64_t* list, uint32_t count, uint64_t* d_out, uint64_t* host_out) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    if (count) CHECK_PTR(list);
+    if (!d_out && !host_out) return fhe::fail("expand_compact_list: no destination");
+    return eng->impl->expand_compact_list(list, count, d_out, host_out);
+    API_END
+}
+
+int fhe_engine_expand_compact_list_dev(fhe_engine* eng, const uint64_t* d_list, uint32_t count, uint64_t* d_out) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    if (count) { CHECK_PTR(d_list); CHECK_PTR(d_out); }
+    return eng->impl->expand_compact_list_dev(d_list, count, d_out);
+    API_END
+}
+
 int fhe_engine_set_pipeline(fhe_engine* eng, int on) {
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng);

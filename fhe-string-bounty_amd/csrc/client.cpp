@@ -10,6 +10,7 @@
 #include <errno.h>
 #include <sys/random.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <thread>
@@ -217,6 +218,17 @@ int fhe_client_gen_server_keys(fhe_client_key* ck, uint64_t* bsk_std, uint64_t* 
         return fhe::fail(e.what());
     }
     return 0;
+}
+
+int fhe_client_gen_compact_public_key(fhe_client_key* ck, const uint8_t seed[32], uint64_t* pk_out) {
+    if (!ck || !seed || !pk_out) return fhe::fail("null pointer");
+    try {
+        auto& c = *ck->impl;
+        const int threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+        return fhe::compact_pk_generate(c.p, c.glwe_sk.data(), fhe::seed_from_bytes(seed), pk_out, threads);
+    } catch (const std::exception& e) {
+        return fhe::fail(e.what());
+    }
 }
 
 int fhe_client_secret_keys(fhe_client_key* ck, uint64_t* glwe_sk, uint64_t* small_sk) {

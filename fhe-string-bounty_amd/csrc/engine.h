@@ -118,6 +118,8 @@ struct Engine {
     uint32_t* d_slot_exp = nullptr;   // multi-bit two-kernel path: exponent of w = e^{i pi / N} each Fourier slot evaluates at
     size_t multibit_workspace_cap = 0;   // bytes of prepared GGSWs kept at once, larger batches run in sub-batches (0 = from free memory)
     void* d_meta = nullptr;
+    uint64_t* d_compact = nullptr;   // a compact ciphertext list on its way to compact_expand_kernel
+    size_t cap_compact = 0;
     void* d_ws = nullptr;      // per-LWE HBM workspace of the large-N blind rotation
     size_t cap_ws = 0;
     void* d_cluster_ws = nullptr;   // cluster kernel: 1.5 MB of exchange matrices per cluster (L2-resident by design)
@@ -147,6 +149,8 @@ struct Engine {
     int load_seeded_keys(const uint8_t ksk_seed[16], const uint64_t* ksk_bodies, const uint8_t bsk_seed[16], const uint64_t* bsk_bodies,
                          uint64_t* bsk_std_out, uint64_t* ksk_out);
     int expand_seeded_lwe(const uint8_t* seeds, const uint64_t* bodies, uint32_t count, uint64_t* d_out, uint64_t* host_out);
+    int expand_compact_list(const uint64_t* list, uint32_t count, uint64_t* d_out, uint64_t* host_out);
+    int expand_compact_list_dev(const uint64_t* d_list, uint32_t count, uint64_t* d_out);
     int generate_keys(const uint64_t* glwe_sk, const uint64_t* small_sk, const uint8_t seed[32],
                       uint64_t* bsk_std_out, uint64_t* ksk_out);
     int install_keys(uint64_t* d_ksk_std, uint64_t* d_bsk_std);
@@ -184,6 +188,11 @@ struct Engine {
     int kernel_times(double total_ms[2], uint32_t* calls, bool reset);
     int synchronize();
 };
+
+// compact_pk.cpp: k*N if it is a power of two (the dimension a compact public key works in), else 0; key generation
+struct Seed256;
+size_t compact_dim(const fhe_params_t& p);
+int compact_pk_generate(const fhe_params_t& p, const uint64_t* big_sk, const Seed256& seed, uint64_t* pk, int threads);
 
 int params_supported(const fhe_params_t& p);   // 0, or 1 with the reason in fhe_last_error (no device needed)
 

@@ -26,6 +26,7 @@
 #include "pbs_multibit_kernels.hip.h"
 #include "pbs_seq_kernels.hip.h"
 #include "seeded_kernels.hip.h"
+#include "compact_kernels.hip.h"
 
 namespace fhe {
 
@@ -362,7 +363,7 @@ Engine::~Engine() {
     if (stream) (void)sync_all_streams();
     auto rel = [](void* ptr) { if (ptr) (void)hipFree(ptr); };
     rel(d_ksk_packed); rel(d_ksk_rowsum); rel(d_fbsk); rel(d_fbsk_dense); rel(d_luts); rel(d_in); rel(d_small); rel(d_small2); rel(d_out); rel(d_idx);
-    rel(d_pool); rel(d_meta); rel(d_ws); rel(d_slot_exp); rel(d_cluster_ws); rel(d_cluster_ctl); rel(d_ksk_mfma); rel(d_ks_digits);
+    rel(d_pool); rel(d_meta); rel(d_ws); rel(d_slot_exp); rel(d_cluster_ws); rel(d_cluster_ctl); rel(d_ksk_mfma); rel(d_ks_digits); rel(d_compact);
     for (int q = 0; q < OVL_MAX; q++) { rel(ovl_digits[q]); rel(ovl_small[q]); if (ovl_done[q]) (void)hipEventDestroy(ovl_done[q]); if (q >= 2 && ovl_stream[q]) (void)hipStreamDestroy(ovl_stream[q]); }
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : ring) if (e) (void)hipEventDestroy(e);
@@ -501,6 +502,43 @@ int Engine::expand_seeded_lwe(const uint8_t* seeds, const uint64_t* bodies, uint
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     cleanup();
     if (e != hipSuccess) return fail(std::string("expand_seeded_lwe: ") + hipGetErrorString(e));
+    return 0;
+}
+
+// A public-key client's compact ciphertext list (shortint CompactCiphertextList, compact_kernels.hip.h) -> count big-key
+// ciphertexts at d_out.  d_list is ordered on the engine's stream like everything else; nothing synchronises.
+int Engine::expand_compact_list_dev(const uint64_t* d_list, uint32_t count, uint64_t* d_out) {
+    if (use()) return 1;
+    if (count == 0) return 0;
+    const uint32_t dim = p.k * p.N;
+    if (dim < 2 || (dim & (dim - 1))) return fail("compact lists need a power-of-two encryption key dimension, k*N = " + std::to_string(dim));
+    const uint32_t chunks = (dim / 2 + COMPACT_PAIRS_PER_WG - 1) / COMPACT_PAIRS_PER_WG;
+    if ((uint64_t)count * chunks > 0x7FFFFFFFull) return fail("expand_compact_list: too many ciphertexts for one launch");
+    hipLaunchKernelGGL(compact_expand_kernel, dim3(count * chunks), dim3(256), 0, stream, d_list, d_out, dim, count, chunks);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The same from a host list: 8 (ceil(count / kN) kN + count) bytes go over PCIe instead of 8 count (kN + 1).
+// Output on the device (d_out) and / or the host; synchronises, like expand_seeded_lwe.
+int Engine::expand_compact_list(const uint64_t* list, uint32_t count, uint64_t* d_out, uint64_t* host_out) {
+    if (use()) return 1;
+    if (count == 0) return 0;
+    const uint32_t dim = p.k * p.N;
+    if (dim < 2 || (dim & (dim - 1))) return fail("compact lists need a power-of-two encryption key dimension, k*N = " + std::to_string(dim));
+    const size_t list_words = (size_t)((count + dim - 1) / dim) * dim + count, words = (size_t)count * (dim + 1);
+    if (ensure((void**)&d_compact, &cap_compact, list_words * 8)) return 1;
+    uint64_t* d_tmp = nullptr;
+    if (!d_out) HIP_TRY(hipMalloc((void**)&d_tmp, words * 8));
+    uint64_t* target = d_out ? d_out : d_tmp;
+    hipError_t e = hipMemcpyAsync(d_compact, list, list_words * 8, hipMemcpyHostToDevice, stream);
+    int rc = 0;
+    if (e == hipSuccess) rc = expand_compact_list_dev(d_compact, count, target);
+    if (e == hipSuccess && rc == 0 && host_out) e = hipMemcpyAsync(host_out, target, words * 8, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && rc == 0) e = hipStreamSynchronize(stream);
+    (void)hipFree(d_tmp);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(std::string("expand_compact_list: ") + hipGetErrorString(e));
     return 0;
 }
 

@@ -236,4 +236,129 @@ int fhe_wire_read_shortint_ciphertext(const uint8_t* in, size_t in_len, int safe
     return 0;
 }
 
+// ---- public-key objects: compact ciphertext lists and the compact public key (csrc/compact_pk.cpp) -------------------
+//   LweCompactCiphertextList<Vec<u64>>  { data, lwe_size, lwe_ciphertext_count, ciphertext_modulus }
+//                                                     entities/lwe_compact_ciphertext_list.rs:18-27
+//   shortint::CompactCiphertextList     { ct_list, degree, message_modulus, carry_modulus, pbs_order, noise_level }
+//                                                     shortint/ciphertext/mod.rs:521-529 (pbs_order BEFORE noise_level)
+//   integer::CompactCiphertextList      { ct_list: the shortint list, num_blocks_per_integer: usize }
+//                                                     integer/ciphertext/mod.rs:71-78
+//   LweCompactPublicKey<Vec<u64>>       { glwe_ciphertext: GlweCiphertext { data, polynomial_size, ciphertext_modulus } }
+//                                                     entities/lwe_compact_public_key.rs:12-17, glwe_ciphertext.rs:286-293
+static int compact_list_body_write(Writer& w, const fhe_params_t* p, const uint64_t* list, uint32_t count) {
+    const size_t words = fhe_compact_list_len(p, count);
+    if (!fhe_compact_pk_len(p)) return fail("compact lists need a power-of-two encryption key dimension (k*N)");
+    w.vec_u64(list, words);
+    w.u64((uint64_t)p->k * p->N + 1);
+    w.u64(count);
+    w.native_modulus_u64();
+    return 0;
+}
+
+// the LweCompactCiphertextList at the reader's position; *count on success
+static int compact_list_body_read(Reader& r, const char* what, const fhe_params_t* p, uint64_t* list, uint32_t max_count, uint32_t* count) {
+    if (!fhe_compact_pk_len(p)) return fail("compact lists need a power-of-two encryption key dimension (k*N)");
+    const size_t n = r.vec_u64(list, fhe_compact_list_len(p, max_count));
+    const uint64_t lwe_size = r.u64(), cnt = r.u64();
+    r.native_modulus_u64();
+    if (!r.err.empty()) return fail(std::string(what) + ": " + r.err);
+    if (lwe_size != (uint64_t)p->k * p->N + 1)
+        return fail(std::string(what) + " does not match the parameter set (lwe_size " + std::to_string(lwe_size) + ")");
+    if (cnt > max_count) return fail(std::string(what) + ": " + std::to_string(cnt) + " ciphertexts, more than the destination holds");
+    // lwe_compact_ciphertext_list_size(lwe_dimension, count), entities/lwe_compact_ciphertext_list.rs:55-63
+    if (n != fhe_compact_list_len(p, (uint32_t)cnt))
+        return fail(std::string(what) + ": container of " + std::to_string(n) + " words does not hold " + std::to_string(cnt) + " ciphertexts");
+    *count = (uint32_t)cnt;
+    return 0;
+}
+
+int fhe_wire_write_compact_list(const fhe_params_t* p, const uint64_t* list, uint32_t count, uint8_t* out, size_t out_cap,
+                                size_t* written) {
+    if (!p || !list) return fail("null pointer");
+    Writer w{out, out_cap};
+    if (compact_list_body_write(w, p, list, count)) return 1;
+    return finish(w, written);
+}
+
+int fhe_wire_read_compact_list(const fhe_params_t* p, const uint8_t* in, size_t in_len, uint64_t* list, uint32_t max_count,
+                               uint32_t* count, size_t* consumed) {
+    if (!p || !in || !list || !count) return fail("null pointer");
+    Reader r{in, in_len};
+    if (compact_list_body_read(r, "LweCompactCiphertextList", p, list, max_count, count)) return 1;
+    if (consumed) *consumed = r.pos;
+    return 0;
+}
+
+int fhe_wire_write_shortint_compact_list(const fhe_params_t* p, const uint64_t* list, uint32_t count, const fhe_shortint_meta* meta,
+                                         uint64_t num_blocks_per_integer, uint8_t* out, size_t out_cap, size_t* written) {
+    if (!p || !list || !meta) return fail("null pointer");
+    if (meta->pbs_order > 1) return fail("pbs_order must be 0 (KeyswitchBootstrap) or 1 (BootstrapKeyswitch)");
+    if (meta->message_modulus != p->msg_mod || meta->carry_modulus != p->carry_mod)
+        return fail("CompactCiphertextList: message / carry modulus differ from the parameter set's");
+    if (num_blocks_per_integer && count % num_blocks_per_integer)
+        return fail("integer CompactCiphertextList: the ciphertext count is not a multiple of num_blocks_per_integer");
+    Writer w{out, out_cap};
+    if (compact_list_body_write(w, p, list, count)) return 1;
+    w.u64(meta->degree);
+    w.u64(meta->message_modulus);
+    w.u64(meta->carry_modulus);
+    w.u32(meta->pbs_order);
+    w.u64(meta->noise_level);
+    if (num_blocks_per_integer) w.u64(num_blocks_per_integer);
+    return finish(w, written);
+}
+
+int fhe_wire_read_shortint_compact_list(const fhe_params_t* p, const uint8_t* in, size_t in_len, int integer_form, uint64_t* list,
+                                        uint32_t max_count, uint32_t* count, fhe_shortint_meta* meta, uint64_t* num_blocks_per_integer,
+                                        size_t* consumed) {
+    if (!p || !in || !list || !count || !meta || (integer_form && !num_blocks_per_integer)) return fail("null pointer");
+    const char* what = integer_form ? "integer CompactCiphertextList" : "shortint CompactCiphertextList";
+    Reader r{in, in_len};
+    if (compact_list_body_read(r, what, p, list, max_count, count)) return 1;
+    meta->degree = r.u64();
+    meta->message_modulus = r.u64();
+    meta->carry_modulus = r.u64();
+    meta->pbs_order = r.u32();
+    meta->noise_level = r.u64();
+    const uint64_t blocks = integer_form ? r.u64() : 0;
+    if (!r.err.empty()) return fail(std::string(what) + ": " + r.err);
+    if (meta->pbs_order > 1) return fail(std::string(what) + ": unknown PBSOrder variant " + std::to_string(meta->pbs_order));
+    if (meta->message_modulus != p->msg_mod || meta->carry_modulus != p->carry_mod)
+        return fail(std::string(what) + " does not match the parameter set (message modulus " + std::to_string(meta->message_modulus) +
+                    ", carry modulus " + std::to_string(meta->carry_modulus) + ")");
+    if (integer_form && (blocks == 0 || *count % blocks))
+        return fail(std::string(what) + ": " + std::to_string(*count) + " ciphertexts are not a multiple of num_blocks_per_integer " +
+                    std::to_string(blocks));
+    if (num_blocks_per_integer) *num_blocks_per_integer = blocks;
+    if (consumed) *consumed = r.pos;
+    return 0;
+}
+
+int fhe_wire_write_compact_public_key(const fhe_params_t* p, const uint64_t* pk, uint8_t* out, size_t out_cap, size_t* written) {
+    if (!p || !pk) return fail("null pointer");
+    const size_t words = fhe_compact_pk_len(p);
+    if (!words) return fail("a compact public key needs a power-of-two encryption key dimension (k*N)");
+    Writer w{out, out_cap};
+    w.vec_u64(pk, words);
+    w.u64(words / 2);
+    w.native_modulus_u64();
+    return finish(w, written);
+}
+
+int fhe_wire_read_compact_public_key(const fhe_params_t* p, const uint8_t* in, size_t in_len, uint64_t* pk, size_t* consumed) {
+    if (!p || !in || !pk) return fail("null pointer");
+    const size_t want = fhe_compact_pk_len(p);
+    if (!want) return fail("a compact public key needs a power-of-two encryption key dimension (k*N)");
+    Reader r{in, in_len};
+    const size_t n = r.vec_u64(pk, want);
+    const uint64_t poly = r.u64();
+    r.native_modulus_u64();
+    if (!r.err.empty()) return fail("LweCompactPublicKey: " + r.err);
+    if (poly != want / 2 || n != want)   // GLWE size 2: mask and body polynomial
+        return fail("LweCompactPublicKey does not match the parameter set (polynomial size " + std::to_string(poly) + ", " +
+                    std::to_string(n) + " words)");
+    if (consumed) *consumed = r.pos;
+    return 0;
+}
+
 }  // extern "C"

@@ -140,6 +140,10 @@ EXPORTS = [
     "fhe_wire_write_seeded_keyswitch_key", "fhe_wire_read_seeded_keyswitch_key", "fhe_wire_write_seeded_bootstrap_key",
     "fhe_wire_read_seeded_bootstrap_key", "fhe_wire_write_multi_bit_bootstrap_key", "fhe_wire_read_multi_bit_bootstrap_key",
     "fhe_wire_write_compressed_server_key", "fhe_wire_read_compressed_server_key",
+    "fhe_compact_pk_len", "fhe_compact_list_len", "fhe_client_gen_compact_public_key", "fhe_compact_pk_encrypt",
+    "fhe_compact_expand_host", "fhe_compact_conv", "fhe_engine_expand_compact_list", "fhe_engine_expand_compact_list_dev",
+    "fhe_wire_write_compact_list", "fhe_wire_read_compact_list", "fhe_wire_write_shortint_compact_list",
+    "fhe_wire_read_shortint_compact_list", "fhe_wire_write_compact_public_key", "fhe_wire_read_compact_public_key",
     "fhe_engine_expand_seeded_lwe", "fhe_seeded_decompress_lwe_batch", "fhe_wire_write_compressed_ciphertext",
     "fhe_wire_read_compressed_ciphertext", "fhe_wire_write_radix_ciphertext", "fhe_wire_read_radix_ciphertext",
     "fhe_wire_write_compressed_radix_ciphertext", "fhe_wire_read_compressed_radix_ciphertext",
@@ -207,6 +211,16 @@ def lib() -> C.CDLL:
     sig("fhe_engine_cluster_fallbacks", vp, C.POINTER(u32))
     sig("fhe_engine_load_seeded_keys", vp, vp, vp, vp, vp, vp, vp)
     sig("fhe_engine_expand_seeded_lwe", vp, vp, vp, u32, vp, vp)
+    sig("fhe_engine_expand_compact_list", vp, vp, u32, vp, vp)
+    sig("fhe_engine_expand_compact_list_dev", vp, vp, u32, vp)
+    sig("fhe_client_gen_compact_public_key", vp, vp, vp)
+    sig("fhe_compact_pk_encrypt", PP, vp, vp, vp, u32, vp, i32)
+    sig("fhe_compact_expand_host", u32, vp, u32, vp)
+    sig("fhe_compact_conv", vp, vp, u32, vp, i32)
+    L.fhe_compact_pk_len.restype = C.c_size_t
+    L.fhe_compact_pk_len.argtypes = [PP]
+    L.fhe_compact_list_len.restype = C.c_size_t
+    L.fhe_compact_list_len.argtypes = [PP, u32]
     sig("fhe_lut_generate", vp, vp, C.POINTER(u32), C.POINTER(C.c_uint64))
     sig("fhe_lut_upload", vp, vp, C.POINTER(u32))
     sig("fhe_lut_download", vp, u32, vp)
@@ -399,6 +413,25 @@ class Engine:
         out = None if d_out else np.zeros((bodies.size, self.params.big_size), dtype=np.uint64)
         _check(lib().fhe_engine_expand_seeded_lwe(self._h, seeds.ctypes.data_as(C.c_void_p), _ptr(bodies), bodies.size,
                                                   C.c_void_p(d_out) if d_out else None, _ptr(out) if out is not None else None))
+        return out
+
+    def expand_compact_list(self, clist, count: int, d_out: int | None = None, d_list: int | None = None):
+        """A public-key client's compact ciphertext list (CompactPublicKey.encrypt; shortint CompactCiphertextList) ->
+        `count` big-key ciphertexts, written by the GPU (csrc/compact_kernels.hip.h).  d_out: device pointer to write
+        them to (count x big_size words: what apply_lookup_table_dev and Plan.run_batch_dev read) instead of returning
+        a host array.  d_list: the list is already on the device at this pointer (clist is ignored); then d_out is
+        required and the call only enqueues on the engine's stream."""
+        if d_list:
+            if not d_out:
+                raise FheError("expand_compact_list: a device-resident list needs a device destination (d_out)")
+            _check(lib().fhe_engine_expand_compact_list_dev(self._h, C.c_void_p(d_list), count, C.c_void_p(d_out)))
+            return None
+        clist = _u64(clist).reshape(-1)
+        if clist.size != compact_list_len(self.params, count):
+            raise FheError(f"compact list: {clist.size} words do not hold {count} ciphertexts of this parameter set")
+        out = None if d_out else np.zeros((count, self.params.big_size), dtype=np.uint64)
+        _check(lib().fhe_engine_expand_compact_list(self._h, _ptr(clist), count, C.c_void_p(d_out) if d_out else None,
+                                                    _ptr(out) if out is not None else None))
         return out
 
     def set_variant(self, selector: int):
@@ -643,12 +676,82 @@ class ClientKey:
                                                 threads or min(16, os.cpu_count() or 1)))
         return bsk, ksk
 
+    def compact_public_key(self, seed) -> "CompactPublicKey":
+        """The compact public key of this client's big key (shortint CompactPublicKey::new); `seed` (32 bytes or an
+        int) drives its mask and noise.  Refused when k*N is not a power of two."""
+        p = self.params
+        n = compact_pk_len(p)
+        if not n:
+            raise FheError(f"a compact public key needs a power-of-two encryption key dimension, k*N = {p.k * p.N}")
+        pk = np.zeros(n, dtype=np.uint64)
+        sb = (C.c_uint8 * 32)(*seed_bytes(seed))
+        _check(lib().fhe_client_gen_compact_public_key(self._h, sb, _ptr(pk)))
+        return CompactPublicKey(p, pk)
+
     def secret_keys(self):
         p = self.params
         g = np.zeros(p.k * p.N, dtype=np.uint64)
         s = np.zeros(p.n, dtype=np.uint64)
         _check(lib().fhe_client_secret_keys(self._h, _ptr(g), _ptr(s)))
         return g, s
+
+
+def compact_pk_len(params: Params) -> int:
+    """Words of a compact public key (2 k N), 0 when k*N is not a power of two (no compact form)."""
+    return int(lib().fhe_compact_pk_len(C.byref(params.c())))
+
+
+def compact_list_len(params: Params, count: int) -> int:
+    """Words of a compact list of `count` ciphertexts: ceil(count / kN) * kN + count (0: no compact form)."""
+    return int(lib().fhe_compact_list_len(C.byref(params.c()), count))
+
+
+def compact_conv(lhs, rhs, threads: int = 1) -> np.ndarray:
+    """lhs * reverse(rhs) in Z[X]/(X^n + 1), wrapping u64 (slice_semi_reverse_negacyclic_convolution)."""
+    lhs, rhs = _u64(lhs).reshape(-1), _u64(rhs).reshape(-1)
+    if lhs.size != rhs.size:
+        raise FheError("compact_conv: operands of different lengths")
+    out = np.zeros(lhs.size, dtype=np.uint64)
+    _check(lib().fhe_compact_conv(_ptr(lhs), _ptr(rhs), lhs.size, _ptr(out), threads))
+    return out
+
+
+def expand_compact_host(params: "Params | int", clist, count: int) -> np.ndarray:
+    """Host-side expansion of a compact list (fhe_compact_expand_host): (count, kN + 1).  `params` may also be a bare
+    power-of-two LWE dimension."""
+    dim = params if isinstance(params, int) else params.k * params.N
+    clist = _u64(clist).reshape(-1)
+    if dim < 2 or dim & (dim - 1):
+        raise FheError(f"compact lists need a power-of-two LWE dimension, got {dim}")
+    if clist.size != (count + dim - 1) // dim * dim + count:
+        raise FheError(f"compact list: {clist.size} words do not hold {count} ciphertexts of dimension {dim}")
+    out = np.zeros((count, dim + 1), dtype=np.uint64)
+    _check(lib().fhe_compact_expand_host(dim, _ptr(clist), count, _ptr(out)))
+    return out
+
+
+class CompactPublicKey:
+    """What a client publishes so that others can encrypt for it (shortint CompactPublicKey, public_key/compact.rs):
+    2 k N words, mask then body.  Holds no secret: encrypting takes this key and a seed of the encryptor's own."""
+
+    def __init__(self, params: Params, words):
+        self.params = params
+        self.words = _u64(words).reshape(-1)
+        if self.words.size == 0 or self.words.size != compact_pk_len(params):
+            raise FheError("compact public key: size does not match the parameter set")
+
+    def encrypt(self, msgs, seed, threads: int | None = None) -> np.ndarray:
+        """Compact list of the messages (each reduced mod msg_mod): compact_list_len(params, len(msgs)) words."""
+        msgs = _u64(np.atleast_1d(msgs)).reshape(-1)
+        out = np.zeros(compact_list_len(self.params, msgs.size), dtype=np.uint64)
+        sb = (C.c_uint8 * 32)(*seed_bytes(seed))
+        _check(lib().fhe_compact_pk_encrypt(C.byref(self.params.c()), _ptr(self.words), sb, _ptr(msgs), msgs.size, _ptr(out),
+                                            threads or min(16, os.cpu_count() or 1)))
+        return out
+
+    def encrypt_string(self, s: bytes, cap: int, seed, threads: int | None = None) -> np.ndarray:
+        """Compact list of the cap * blocks_per_char blocks of a zero padded string (string_to_blocks)."""
+        return self.encrypt(string_to_blocks(self.params, s, cap), seed, threads)
 
 
 class Plan:
@@ -820,6 +923,11 @@ class Plan:
     def run_batch_dev(self, d_inputs: int, d_outputs: int, instances: int):
         """The same on device arrays (raw pointers), ordered on the engine's stream; no host synchronisation."""
         _check(lib().fhe_plan_run_batch_dev(self._h, instances, C.c_void_p(d_inputs), C.c_void_p(d_outputs)))
+
+    def run_dev(self, d_inputs: int, d_outputs: int):
+        """One instance on device arrays: inputs n_inputs x (kN+1) words as Engine.expand_compact_list(..., d_out=)
+        leaves them, outputs n_outputs x (kN+1); ordered on the engine's stream, no host synchronisation."""
+        self.run_batch_dev(d_inputs, d_outputs, 1)
 
     def run_level_rank_dev(self, d_pool: int, level: int, rank: int):
         _check(lib().fhe_plan_run_level_rank_dev(self._h, C.c_void_p(d_pool), level, rank))

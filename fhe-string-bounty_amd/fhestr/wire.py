@@ -7,7 +7,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import FheError, Params, _check, _ptr, _u64, lib
+from . import CompactPublicKey, FheError, Params, _check, _ptr, _u64, compact_list_len, compact_pk_len, lib
 
 
 class _Meta(C.Structure):
@@ -60,6 +60,13 @@ def _sigs():
             ("fhe_wire_read_compressed_radix_ciphertext", [vp, sz, vp, vp, szp, sz, vp, szp, szp]),
             ("fhe_wire_write_multi_bit_bootstrap_key", [PP, vp, vp, sz, szp]),
             ("fhe_wire_read_multi_bit_bootstrap_key", [PP, vp, sz, vp, szp]),
+            ("fhe_wire_write_compact_list", [PP, vp, C.c_uint32, vp, sz, szp]),
+            ("fhe_wire_read_compact_list", [PP, vp, sz, vp, C.c_uint32, C.POINTER(C.c_uint32), szp]),
+            ("fhe_wire_write_shortint_compact_list", [PP, vp, C.c_uint32, C.POINTER(_Meta), C.c_uint64, vp, sz, szp]),
+            ("fhe_wire_read_shortint_compact_list", [PP, vp, sz, C.c_int, vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(_Meta),
+                                                     C.POINTER(C.c_uint64), szp]),
+            ("fhe_wire_write_compact_public_key", [PP, vp, vp, sz, szp]),
+            ("fhe_wire_read_compact_public_key", [PP, vp, sz, vp, szp]),
             ("fhe_wire_write_shortint_ciphertext", [vp, sz, C.POINTER(_Meta), C.c_int, vp, sz, szp]),
             ("fhe_wire_read_shortint_ciphertext", [vp, sz, C.c_int, C.c_uint64, vp, sz, szp, C.POINTER(_Meta), szp])):
         fn = getattr(L, name)
@@ -327,3 +334,67 @@ def read_compressed_radix_ciphertext(data: bytes, max_blocks: int = 4096):
     _check(_sigs().fhe_wire_read_compressed_radix_ciphertext(_in(data), len(data), _ptr(bodies), seeds.ctypes.data_as(C.c_void_p),
                                                              C.byref(size), max_blocks, m, C.byref(n), C.byref(used)))
     return bodies[:n.value].copy(), seeds[:n.value].copy(), size.value, _metas_out(m, n.value), used.value
+
+
+# ---- public-key objects: compact ciphertext lists and the compact public key (csrc/compact_pk.cpp) -------------------
+
+def compact_meta(params: Params) -> ShortintMeta:
+    """What CompactPublicKey::encrypt_slice declares (shortint/public_key/compact.rs:181-189): degree msg_mod - 1, nominal noise."""
+    return ShortintMeta(params.msg_mod - 1, 1, params.msg_mod, params.carry_mod, 0)
+
+
+def write_compact_list(params: Params, clist, count: int) -> bytes:
+    """core_crypto LweCompactCiphertextList<Vec<u64>>."""
+    clist = _u64(clist).reshape(-1)
+    if clist.size != compact_list_len(params, count) or not clist.size:
+        raise FheError("compact list: size does not match the count")
+    return _write(lambda out, cap, n: _sigs().fhe_wire_write_compact_list(C.byref(params.c()), _ptr(clist), count, out, cap, n))
+
+
+def read_compact_list(params: Params, data: bytes, max_count: int = 1 << 16):
+    """-> (list words, count, bytes consumed)"""
+    clist = np.zeros(max(1, compact_list_len(params, max_count)), dtype=np.uint64)
+    count, used = C.c_uint32(), C.c_size_t()
+    _check(_sigs().fhe_wire_read_compact_list(C.byref(params.c()), _in(data), len(data), _ptr(clist), max_count, C.byref(count),
+                                              C.byref(used)))
+    return clist[:compact_list_len(params, count.value)].copy(), count.value, used.value
+
+
+def write_shortint_compact_list(params: Params, clist, count: int, meta: ShortintMeta | None = None,
+                                num_blocks_per_integer: int = 0) -> bytes:
+    """shortint CompactCiphertextList, or integer CompactCiphertextList when num_blocks_per_integer > 0."""
+    clist = _u64(clist).reshape(-1)
+    if clist.size != compact_list_len(params, count) or not clist.size:
+        raise FheError("compact list: size does not match the count")
+    meta = meta or compact_meta(params)
+    m = _Meta(meta.degree, meta.noise_level, meta.message_modulus, meta.carry_modulus, meta.pbs_order)
+    return _write(lambda out, cap, n: _sigs().fhe_wire_write_shortint_compact_list(
+        C.byref(params.c()), _ptr(clist), count, C.byref(m), num_blocks_per_integer, out, cap, n))
+
+
+def read_shortint_compact_list(params: Params, data: bytes, integer: bool = False, max_count: int = 1 << 16):
+    """-> (list words, count, ShortintMeta, num_blocks_per_integer (0 for the shortint object), bytes consumed): feed the
+    first two to Engine.expand_compact_list"""
+    clist = np.zeros(max(1, compact_list_len(params, max_count)), dtype=np.uint64)
+    count, used, m, blocks = C.c_uint32(), C.c_size_t(), _Meta(), C.c_uint64()
+    _check(_sigs().fhe_wire_read_shortint_compact_list(C.byref(params.c()), _in(data), len(data), int(integer), _ptr(clist), max_count,
+                                                       C.byref(count), C.byref(m), C.byref(blocks), C.byref(used)))
+    return (clist[:compact_list_len(params, count.value)].copy(), count.value,
+            ShortintMeta(m.degree, m.noise_level, m.message_modulus, m.carry_modulus, m.pbs_order), blocks.value, used.value)
+
+
+def write_compact_public_key(params: Params, pk) -> bytes:
+    """core_crypto LweCompactPublicKey<Vec<u64>>; pk: a CompactPublicKey or its 2 k N words."""
+    words = _u64(getattr(pk, "words", pk)).reshape(-1)
+    if words.size != compact_pk_len(params) or not words.size:
+        raise FheError("compact public key: size does not match the parameter set")
+    return _write(lambda out, cap, n: _sigs().fhe_wire_write_compact_public_key(C.byref(params.c()), _ptr(words), out, cap, n))
+
+
+def read_compact_public_key(params: Params, data: bytes) -> CompactPublicKey:
+    n = compact_pk_len(params)
+    if not n:
+        raise FheError(f"a compact public key needs a power-of-two encryption key dimension, k*N = {params.k * params.N}")
+    pk, used = np.zeros(n, dtype=np.uint64), C.c_size_t()
+    _check(_sigs().fhe_wire_read_compact_public_key(C.byref(params.c()), _in(data), len(data), _ptr(pk), C.byref(used)))
+    return CompactPublicKey(params, pk)

@@ -401,6 +401,40 @@ int fhe_client_gen_server_keys(fhe_client_key *ck, uint64_t *bsk_std, uint64_t *
 /* Copy out the secret keys (either pointer may be NULL): glwe_sk k*N u64, small_sk n u64. */
 int fhe_client_secret_keys(fhe_client_key *ck, uint64_t *glwe_sk, uint64_t *small_sk);
 
+/* ---- public-key clients: compact public keys and compact ciphertext lists ------------------------
+ * shortint CompactPublicKey / CompactCiphertextList of the reference (M. Joye, eprint 2023/603;
+ * shortint/public_key/compact.rs, core_crypto/algorithms/lwe_compact_public_key_generation.rs:15-50,
+ * lwe_encryption.rs:1837-1958, lwe_compact_ciphertext_list_expansion.rs:12-58).  n = k*N, the big key's dimension,
+ * must be a power of two (compact.rs:65): every k = 1 set and k = 2, N = 1024; the other shapes are refused with a
+ * message, where the reference returns None.
+ *   public key: 2n words, mask a then body b = conv(a, s) + e          (conv: slice_algorithms.rs:610-659)
+ *   list:       one mask of n words per bin of up to n ciphertexts, then one body word per ciphertext:
+ *               ceil(count / n) * n + count words (entities/lwe_compact_ciphertext_list.rs:41-63) -- a 256-char
+ *               string under PARAM_MESSAGE_2_CARRY_2 is 24.6 KB instead of 16.8 MB of ciphertexts
+ *   expansion:  ciphertext i = (mask of bin i / n times X^(n - (i mod n + 1)) in Z[X]/(X^n + 1), body i), a big LWE
+ * Messages are reduced mod msg_mod and encoded like fhe_client_encrypt's (compact.rs:25-42); an expanded ciphertext
+ * has degree msg_mod - 1 and at most one nominal noise level (compact.rs:181-189): all three noise terms are drawn
+ * with glwe_std, the phase error has variance glwe_std^2 (1 + |r|^2 + |s|^2).
+ * Randomness as for the client key: ChaCha20 under `seed`, one stream per purpose and bin; one (key, seed, messages)
+ * gives one list bit for bit, whatever `threads` is.  Encrypting needs the public key and a seed, no client key.
+ * 0 words = the parameter set has no compact form. */
+size_t fhe_compact_pk_len(const fhe_params_t *params);
+size_t fhe_compact_list_len(const fhe_params_t *params, uint32_t count);
+int fhe_client_gen_compact_public_key(fhe_client_key *ck, const uint8_t seed[32], uint64_t *pk_out);
+int fhe_compact_pk_encrypt(const fhe_params_t *params, const uint64_t *pk, const uint8_t seed[32], const uint64_t *msgs,
+                           uint32_t count, uint64_t *list_out, int threads);
+/* Expansion on the host (any power-of-two lwe_dim): out = count x (lwe_dim + 1) words. */
+int fhe_compact_expand_host(uint32_t lwe_dim, const uint64_t *list, uint32_t count, uint64_t *out);
+/* Expansion on the GPU (csrc/compact_kernels.hip.h): the list goes over PCIe, the ciphertexts are written in HBM, into
+ * d_out (device, count x (kN+1) words; may be NULL) and / or host_out -- bit-identical to fhe_compact_expand_host.
+ * _dev: the list is already on the device; asynchronous on the engine's stream, no host synchronisation.  d_out is what
+ * fhe_ks_pbs_batch_dev and fhe_plan_run_batch_dev read: an expanded ciphertext never has to cross PCIe. */
+int fhe_engine_expand_compact_list(fhe_engine *eng, const uint64_t *list, uint32_t count, uint64_t *d_out, uint64_t *host_out);
+int fhe_engine_expand_compact_list_dev(fhe_engine *eng, const uint64_t *d_list, uint32_t count, uint64_t *d_out);
+/* out = lhs * reverse(rhs) in Z[X]/(X^n + 1), any n >= 1 and any rhs: the convolution behind the three functions above
+ * (slice_semi_reverse_negacyclic_convolution; known answer (1, 2, 3), (4, 5, 6) -> (-17, 5, 32)). */
+int fhe_compact_conv(const uint64_t *lhs, const uint64_t *rhs, uint32_t n, uint64_t *out, int threads);
+
 /* ---- tfhe-rs wire format (serde + bincode 1.x, fixed-width little endian) ---------------------- */
 /* Byte forms of core_crypto's LweCiphertext<Vec<u64>>, LweKeyswitchKey<Vec<u64>>, standard-domain
  * LweBootstrapKey<Vec<u64>> and shortint::Ciphertext as tfhe-rs 0.5 writes them with bincode::serialize /
@@ -504,6 +538,32 @@ int fhe_wire_write_multi_bit_bootstrap_key(const fhe_params_t *p, const uint64_t
                                            size_t *written);
 int fhe_wire_read_multi_bit_bootstrap_key(const fhe_params_t *p, const uint8_t *in, size_t in_len, uint64_t *bsk_std,
                                           size_t *consumed);
+
+/* Public-key objects (bincode as above): LweCompactCiphertextList<Vec<u64>> { data, lwe_size, lwe_ciphertext_count,
+ * ciphertext_modulus } (entities/lwe_compact_ciphertext_list.rs:18-27); shortint CompactCiphertextList { ct_list,
+ * degree, message_modulus, carry_modulus, pbs_order, noise_level } (shortint/ciphertext/mod.rs:521-529); integer
+ * CompactCiphertextList { ct_list, num_blocks_per_integer } (integer/ciphertext/mod.rs:71-78); LweCompactPublicKey
+ * { glwe_ciphertext: GlweCiphertext { data, polynomial_size, ciphertext_modulus } }, GLWE size 2, polynomial size kN
+ * (entities/lwe_compact_public_key.rs:12-17, glwe_ciphertext.rs:286-293).  Readers check lwe_size / polynomial size
+ * and the moduli against the parameter set, the container length against the count
+ * (lwe_compact_ciphertext_list_size), refuse more than max_count ciphertexts (list: room for
+ * fhe_compact_list_len(params, max_count) words) and never read past in_len.  Parity unpinned, as above.  The
+ * shortint CompactPublicKey wrapper (it embeds a ShortintParameterSet) is not covered. */
+int fhe_wire_write_compact_list(const fhe_params_t *p, const uint64_t *list, uint32_t count, uint8_t *out, size_t out_cap,
+                                size_t *written);
+int fhe_wire_read_compact_list(const fhe_params_t *p, const uint8_t *in, size_t in_len, uint64_t *list, uint32_t max_count,
+                               uint32_t *count, size_t *consumed);
+/* meta->message_modulus / carry_modulus must be the parameter set's; num_blocks_per_integer == 0 writes / expects the
+ * shortint object, > 0 the integer one (count must then be a multiple of it; the reader returns it through
+ * *num_blocks_per_integer, which may be NULL for the shortint object only). */
+int fhe_wire_write_shortint_compact_list(const fhe_params_t *p, const uint64_t *list, uint32_t count,
+                                         const fhe_shortint_meta *meta, uint64_t num_blocks_per_integer, uint8_t *out,
+                                         size_t out_cap, size_t *written);
+int fhe_wire_read_shortint_compact_list(const fhe_params_t *p, const uint8_t *in, size_t in_len, int integer_form,
+                                        uint64_t *list, uint32_t max_count, uint32_t *count, fhe_shortint_meta *meta,
+                                        uint64_t *num_blocks_per_integer, size_t *consumed);
+int fhe_wire_write_compact_public_key(const fhe_params_t *p, const uint64_t *pk, uint8_t *out, size_t out_cap, size_t *written);
+int fhe_wire_read_compact_public_key(const fhe_params_t *p, const uint8_t *in, size_t in_len, uint64_t *pk, size_t *consumed);
 
 #ifdef __cplusplus
 }
