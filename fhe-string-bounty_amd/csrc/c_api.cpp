@@ -183,6 +183,15 @@ int fhe_engine_cluster_info(fhe_engine* eng, uint32_t* clusters) {
     API_END
 }
 
+int fhe_engine_keyswitch_info(fhe_engine* eng, uint32_t info[6]) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(info);
+    if (eng->impl->use()) return 1;
+    eng->impl->keyswitch_info(info);
+    return 0;
+    API_END
+}
+
 int fhe_engine_cluster_fallbacks(fhe_engine* eng, uint32_t* count) {
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(count);

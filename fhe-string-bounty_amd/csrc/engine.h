@@ -133,6 +133,9 @@ struct Engine {
     int cluster_mode = -1;          // -1 automatic (by batch size), 0 never, 1 always (FHESTR_CLUSTER)
     uint32_t cluster_max_batch = 0xFFFFFFFFu;
     uint32_t ks_chunks_override = 0; // FHESTR_KS_CHUNKS: K chunks of the matrix-core keyswitch (0 = automatic)
+    // what the last launch_keyswitch launched (fhe_engine_keyswitch_info; recorded only, read by no decision): kernel
+    // (FHE_KS_KERNEL_*), row tiles / samples per workgroup, K chunks (grid.z), K steps / input coefficients per chunk, K steps / in_dim
+    uint32_t ks_last[5] = {0, 0, 0, 0, 0};
     int xcd_per_cu = -1;             // workgroups of the whole-XCD kernel a CU holds (occupancy query, cached)
     uint32_t xcd_auto_max = 16;     // automatic mode: batches up to this size take the whole-XCD kernel (two LWEs per XCD in flight)
     uint32_t cluster_spin_limit = 1u << 22;   // polls before a hand-over wait gives up (FHESTR_CLUSTER_SPIN_LIMIT)
@@ -169,6 +172,7 @@ struct Engine {
     int launch_blind_rotate(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big, uint32_t count, hipStream_t on = nullptr, bool two_per_cu = false,
                             bool one_workgroup_only = false);   // never a kernel that needs several workgroups resident at once (cluster_settle's re-run)
     bool shadow_keyswitch_fits();
+    void keyswitch_info(uint32_t info[6]) const;   // ks_last and the register count shadow_keyswitch_fits judges by; changes nothing
     int ks_pbs_dev(const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint64_t* d_big_out, uint32_t count, bool allow_pipeline = false);
     int ks_pbs_host(const uint64_t* in, const uint32_t* lut_idx, uint64_t* out, uint32_t count);
     int keyswitch_host(const uint64_t* in, uint64_t* out_small, uint32_t count);

@@ -802,6 +802,7 @@ int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t cou
             case 4: hipLaunchKernelGGL(keyswitch_mfma_kernel<4>, grid, dim3(256), 0, s, ma); break;
             default: hipLaunchKernelGGL(keyswitch_mfma_kernel<8>, grid, dim3(512), 0, s, ma); break;
         }
+        ks_last[0] = FHE_KS_KERNEL_MFMA; ks_last[1] = mt; ks_last[2] = chunks; ks_last[3] = spc; ks_last[4] = g.steps;
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -811,11 +812,13 @@ int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t cou
             constexpr int S = 4;
             dim3 pgrid((out_size + KS_COLS - 1) / KS_COLS, (count + S - 1) / S, (in_dim + KS_IC - 1) / KS_IC);
             hipLaunchKernelGGL((keyswitch_dot4_kernel<S, 8>), pgrid, dim3(KS_COLS), (size_t)KS_IC * p.ks_level * S, s, pa);
+            ks_last[0] = FHE_KS_KERNEL_DOT4_SHADOW; ks_last[1] = S; ks_last[2] = pgrid.z; ks_last[3] = KS_IC; ks_last[4] = in_dim;
             HIP_TRY(hipGetLastError());
             return 0;
         }
         dim3 pgrid((out_size + KS_COLS - 1) / KS_COLS, (count + KSD_S - 1) / KSD_S, (in_dim + KS_IC - 1) / KS_IC);
         hipLaunchKernelGGL((keyswitch_dot4_kernel<KSD_S, 2>), pgrid, dim3(KS_COLS), (size_t)KS_IC * p.ks_level * KSD_S, s, pa);
+        ks_last[0] = FHE_KS_KERNEL_DOT4; ks_last[1] = KSD_S; ks_last[2] = pgrid.z; ks_last[3] = KS_IC; ks_last[4] = in_dim;
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -1030,6 +1033,12 @@ bool Engine::shadow_keyswitch_fits() {
         }
     }
     return shadow_fit == 1;
+}
+
+void Engine::keyswitch_info(uint32_t info[6]) const {
+    for (int q = 0; q < 5; q++) info[q] = ks_last[q];
+    hipFuncAttributes fa{};
+    info[5] = variant && hipFuncGetAttributes(&fa, variant->rotate_fn) == hipSuccess ? (uint32_t)fa.numRegs : 0u;
 }
 
 int Engine::ks_pbs_dev(const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint64_t* d_big_out,

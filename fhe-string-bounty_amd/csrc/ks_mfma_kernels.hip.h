@@ -9,7 +9,7 @@
 //     sum_r d_r K_r = sum_t 2^(8 t) ( sum_r d_r s_t(r) )            (mod 2^64)
 // and the inner sums are int8 x int8 -> int32 dot products: v_mfma_i32_32x32x32_i8 (|d s| <= 2^13, rows per workgroup
 // <= 2^15: no int32 overflow -- the host clamps the K chunk, ks_mfma_max_steps).  Nothing is rounded anywhere: the result is bit-identical to the reference's loop
-// (tests/test_gpu_parity.py::test_keyswitch_bit_exact, golden fixtures).
+// (tests/test_gpu_exact_keyswitch.py: every launch shape of this file against exact integers, edge digits and key words included).
 //
 // Shapes: M = batch (32-row tiles, one wave each), N = output columns x 8 digit planes (a workgroup owns 32 columns,
 // every wave carries all 8 planes of its 32 rows x 32 columns, so the planes recombine in registers), K = kN * level key

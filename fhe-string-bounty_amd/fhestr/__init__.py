@@ -125,7 +125,7 @@ _lib = None
 EXPORTS = [
     "fhe_last_error", "fhe_kernel_revision", "fhe_engine_create", "fhe_engine_destroy", "fhe_engine_params",
     "fhe_engine_load_keys", "fhe_engine_generate_keys", "fhe_engine_stream", "fhe_engine_synchronize", "fhe_engine_set_variant",
-    "fhe_engine_set_multibit_combine_max", "fhe_engine_set_cluster_mode", "fhe_engine_set_keep_busy", "fhe_engine_pipeline_input_event", "fhe_engine_cluster_info", "fhe_engine_cluster_fallbacks", "fhe_engine_load_seeded_keys", "fhe_engine_set_pipeline",
+    "fhe_engine_set_multibit_combine_max", "fhe_engine_set_cluster_mode", "fhe_engine_set_keep_busy", "fhe_engine_pipeline_input_event", "fhe_engine_cluster_info", "fhe_engine_keyswitch_info", "fhe_engine_cluster_fallbacks", "fhe_engine_load_seeded_keys", "fhe_engine_set_pipeline",
     "fhe_lut_generate", "fhe_lut_upload", "fhe_lut_download", "fhe_lut_count",
     "fhe_keyswitch_batch", "fhe_pbs_batch", "fhe_ks_pbs_batch", "fhe_ks_pbs_batch_dev", "fhe_pbs_ks_batch",
     "fhe_lwe_lincomb_batch", "fhe_last_kernel_ms", "fhe_kernel_times",
@@ -208,6 +208,7 @@ def lib() -> C.CDLL:
     sig("fhe_engine_set_cluster_mode", vp, i32, u32)
     sig("fhe_engine_set_keep_busy", vp, C.c_int)
     sig("fhe_engine_cluster_info", vp, C.POINTER(u32))
+    sig("fhe_engine_keyswitch_info", vp, C.POINTER(u32))
     sig("fhe_engine_cluster_fallbacks", vp, C.POINTER(u32))
     sig("fhe_engine_load_seeded_keys", vp, vp, vp, vp, vp, vp, vp)
     sig("fhe_engine_expand_seeded_lwe", vp, vp, vp, u32, vp, vp)
@@ -463,6 +464,18 @@ class Engine:
         n = C.c_uint32(0)
         _check(lib().fhe_engine_cluster_info(self._h, C.byref(n)))
         return n.value
+
+    KS_KERNELS = ("none", "mfma", "dot4", "dot4_shadow")
+
+    def keyswitch_info(self) -> dict:
+        """What the last keyswitch launch ran (fhe_engine_keyswitch_info, include/fhestr.h): kernel ("none", "mfma", "dot4",
+        "dot4_shadow"), tile (row tiles or samples per workgroup), chunks of the sum over the input dimension, steps per chunk,
+        steps in all, last_chunk (steps of the last chunk), rotation_regs.  Recorded at launch: no synchronisation."""
+        a = (C.c_uint32 * 6)()
+        _check(lib().fhe_engine_keyswitch_info(self._h, a))
+        kernel, tile, chunks, per_chunk, steps, regs = (int(x) for x in a)
+        return {"kernel": self.KS_KERNELS[kernel], "tile": tile, "chunks": chunks, "steps_per_chunk": per_chunk, "steps": steps,
+                "last_chunk": steps - (chunks - 1) * per_chunk if chunks else 0, "rotation_regs": regs}
 
     def cluster_fallbacks(self) -> int:
         """How often a multi-CU launch gave up (compute units held by another kernel) and was re-run on the one-workgroup kernel."""

@@ -130,6 +130,21 @@ int fhe_engine_set_cluster_mode(fhe_engine *eng, int mode, uint32_t max_batch);
 int fhe_engine_set_keep_busy(fhe_engine *eng, int on);
 /* After a synchronisation: clusters the last cluster launch formed (0 if none ran). */
 int fhe_engine_cluster_info(fhe_engine *eng, uint32_t *clusters);
+/* Which keyswitch kernel the engine's last keyswitch launch ran, as recorded on the host when it was enqueued (no
+ * synchronisation; a query, it changes no decision):
+ *   info[0]  FHE_KS_KERNEL_NONE before the first launch, else the kernel
+ *   info[1]  matrix-core kernel: 32-row tiles per workgroup (1, 2, 4 or 8); byte-plane kernels: samples per workgroup (8, shadow 4)
+ *   info[2]  workgroups the sum over the input dimension is split over (grid.z)
+ *   info[3]  matrix-core kernel: K steps per such chunk (the last chunk holds info[4] - (info[2] - 1) * info[3]);
+ *            byte-plane kernels: input coefficients per chunk
+ *   info[4]  matrix-core kernel: K steps in all; byte-plane kernels: the input dimension k * N
+ *   info[5]  vector registers per lane of the blind-rotation kernel whose occupancy decides whether throughput mode 1
+ *            (fhe_engine_set_pipeline) may run its keyswitch beside it; 0 if the code object does not tell */
+#define FHE_KS_KERNEL_NONE 0u
+#define FHE_KS_KERNEL_MFMA 1u         /* ks_decompose_kernel + keyswitch_mfma_kernel (int8 matrix cores) */
+#define FHE_KS_KERNEL_DOT4 2u         /* keyswitch_dot4_kernel, 8 samples per workgroup (more than 16 levels, FHESTR_KS_MFMA=0) */
+#define FHE_KS_KERNEL_DOT4_SHADOW 3u  /* keyswitch_dot4_kernel, 4 samples per workgroup, beside the previous call's blind rotation */
+int fhe_engine_keyswitch_info(fhe_engine *eng, uint32_t info[6]);
 /* The multi-CU kernels need their whole grid resident at once; when another kernel holds compute units for too long
  * the launch drains with a status instead of hanging, and the engine runs the same batch again on the one-workgroup
  * kernel before the call returns (correct results, that launch's time lost).  count = how often this engine did so. */

@@ -282,3 +282,22 @@ def _chunked(fn, params, args, cts, luts, lut_idx):
     idx = np.zeros(len(cts), dtype=np.int64) if lut_idx is None else np.asarray(lut_idx, dtype=np.int64)
     step = _chunk(params)
     return np.concatenate([fn(params, *args, cts[s:s + step], luts, idx[s:s + step]) for s in range(0, len(cts), step)])
+
+
+def _pbs_rows(job):
+    params, terms, cts, luts, idx = job
+    return pbs_exact_batch(params, terms, cts, luts, idx)
+
+
+def pbs_exact_batch_parallel(params, terms, cts, luts, lut_idx, workers=12):
+    """pbs_exact_batch with the rows spread over fresh numpy-only processes: real n times a hundred LWEs is a minute of
+    single-threaded FFTs otherwise.  Small jobs run in place."""
+    cts = np.asarray(cts, dtype=U64).reshape(-1, params.n + 1)
+    idx = np.asarray(lut_idx, dtype=np.int64)
+    if len(cts) * params.n < 20000:
+        return pbs_exact_batch(params, terms, cts, luts, idx)
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    parts = [p for p in np.array_split(np.arange(len(cts)), workers) if len(p)]
+    with ProcessPoolExecutor(len(parts), mp_context=multiprocessing.get_context("spawn")) as pool:
+        return np.concatenate(list(pool.map(_pbs_rows, [(params, terms, cts[p], luts, idx[p]) for p in parts])))

@@ -14,6 +14,7 @@ import pytest
 
 import oracle as O
 from conftest import torus_distance
+from exact_keyswitch import ExactKeyswitch, edge_big_cts
 from exact_pbs import (edge_small_cts, limb_terms, multi_bit_pbs_exact_batch, pbs_exact_batch, structured_bsk)
 
 pytestmark = pytest.mark.gpu
@@ -127,14 +128,15 @@ def test_n2048_real_n():
 
 def _pipeline_mode2(p, B=96, calls=3):
     """fhe_engine_set_pipeline(2): consecutive apply_lookup_table_dev calls overlapped on two streams.  The keyswitch
-    (bit exact, pinned elsewhere) is taken from the oracle; each call's blind rotation against exact."""
+    is the exact-integer one of tests/exact_keyswitch.py, on all-distinct edge rows; each call's output against the exact
+    PBS of that, bit for bit."""
     import torch
     e = _Exact(p)
     try:
-        sk = O.ServerKey.from_keys(p, e.bsk, e.ksk, fourier=False)
-        big = [e.rng.integers(0, 2**64, size=(B, p.big_size), dtype=np.uint64) for _ in range(calls)]
+        keyswitch = ExactKeyswitch(p, e.ksk)
+        big = [edge_big_cts(p, e.rng, B) for _ in range(calls)]
         sel = [np.arange(B) % N_LUTS for _ in range(calls)]
-        wants = [e.reference(np.stack([sk.keyswitch(c) for c in b]), s) for b, s in zip(big, sel)]
+        wants = [e.reference(keyswitch(b), s) for b, s in zip(big, sel)]
         ins = [torch.from_numpy(b.view(np.int64)).cuda() for b in big]
         idx = [torch.from_numpy(e.ids[s].astype(np.int32)).cuda() for s in sel]
         outs = [torch.zeros_like(t) for t in ins]

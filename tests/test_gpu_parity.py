@@ -179,6 +179,26 @@ def test_lincomb_bit_exact():
                 want += pool[s] * np.uint64(a % 2**64)
             want[-1] += np.uint64(c % 2**64)
             assert np.array_equal(row, want)
+    # real size: 2049 words per ciphertext -- not a multiple of the workgroup's 256 threads, eight passes and one word more;
+    # extreme coefficients, a job of several hundred terms, repeated sources
+    params = O.PARAM_MESSAGE_2_CARRY_2_KS_PBS
+    eng = gpu_engine(keyset(params))
+    pool = rng.integers(0, 2**64, size=(23, params.big_size), dtype=np.uint64)
+    pool[0, :] = 2**64 - 1
+    pool[1, :] = 2**63
+    i32min, i32max = -2**31, 2**31 - 1
+    jobs = [([(0, i32min), (1, i32max), (2, -1)], 2**64 - 1), ([(3, i32max)] * 3 + [(3, i32min), (0, -1), (1, -1)], 2**63),
+            ([(int(s), int(a)) for s, a in zip(rng.integers(0, 23, size=517), rng.integers(i32min, i32max + 1, size=517))], 12345),
+            ([(22, -1)], 0), ([(5, i32min)] * 2, 1)]
+    got = eng.lincomb(pool, jobs)
+    for j, (row, (terms, c)) in enumerate(zip(got, jobs)):
+        want = [0] * params.big_size
+        for s, a in terms:
+            src = pool[s].tolist()
+            want = [w + a * x for w, x in zip(want, src)]
+        want[-1] += c
+        want = np.array([w % 2**64 for w in want], dtype=np.uint64)
+        assert np.array_equal(row, want), f"job {j}: words {np.flatnonzero(row != want)[:8].tolist()} differ"
 
 
 def test_p22_batch_256_decrypts(p22):
