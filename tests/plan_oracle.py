@@ -17,13 +17,14 @@ def lincomb(pool, lv, jobs):
 
 
 class OracleBackend:
-    def __init__(self, plan, sk: O.ServerKey, group=None):
+    def __init__(self, plan, sk: O.ServerKey, group=None, exact=False):
         n_levels = plan.info()["n_levels"]
         self.levels = [plan.export_level(l) for l in range(n_levels + 1)]
         self.luts = plan.export_luts()
         self.plan = plan
         self.sk = sk
         self.group = group
+        self.exact = exact           # True: the oracle's exact-integer PBS (orc_pbs_exact) instead of its f64 transform
         self.big = sk.params.big_size
 
     def alloc_pool(self, slots):
@@ -42,7 +43,7 @@ class OracleBackend:
         ids = sorted(set(int(lv["lut"][j]) for j in jobs))
         luts = np.stack([self.luts[i] for i in ids])
         idx = np.array([ids.index(int(lv["lut"][j])) for j in jobs], dtype=np.uint32)
-        pool[lv["local_base"]: lv["local_base"] + len(jobs)] = self.sk.apply_lookup_table_batch(staged, luts, idx)
+        pool[lv["local_base"]: lv["local_base"] + len(jobs)] = self.sk.apply_lookup_table_batch(staged, luts, idx, exact=self.exact)
 
     def all_gather(self, pool, local_base, e_max, recv_base, world):
         import torch
