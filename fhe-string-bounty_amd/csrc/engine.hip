@@ -61,8 +61,6 @@ struct BrVariant {
     const void* convert_fn;
     bool convert_one_per_block = false;   // the conversion kernel takes one polynomial per workgroup (K1 otherwise)
     const void* rotate_keypf_fn = nullptr; // wide layout with the whole key of a step prefetched (single launches only, see BrWideCfg)
-    bool own_plan = false;                // wide layout on a plan of its own: when it is not the engine's primary variant it reads the
-                                          // dense kernel's copy of the key (same plan), not the primary variant's
     // multi-bit, small batches: build every (LWE, group) GGSW on the whole GPU first, then rotate against them
     const void* combine_fn = nullptr;
     const void* rotate_combined_fn = nullptr;
@@ -112,12 +110,12 @@ BrVariant make_wide_variant() {
     v.threads = CFG::THREADS;
     v.lds_bytes = CFG::LDS_FIXED;
     v.rotate_fn = reinterpret_cast<const void*>(&blind_rotate_wide_kernel<LOGN, LOGR, K1, L>);
-    if constexpr (CFG::OWN_PLAN) {        // FftSwap11 / FftSwap9: the key in that plan's order, one polynomial per workgroup
+    if constexpr (CFG::OWN_PLAN) {        // FftSwap11 (N = 4096, where the wide variant is the shape's only one): the key in that plan's
+                                          // order, one polynomial per workgroup
         v.convert_fn = reinterpret_cast<const void*>(&bsk_convert_wide_kernel<LOGN, LOGR, K1, L>);
         v.convert_threads = CFG::THREADS;
         v.convert_lds = (size_t)CFG::GROUP_SLOTS * 8;
         v.convert_one_per_block = true;
-        v.own_plan = true;
     }
     if constexpr (LOGN == 10 && LOGR == 2 && K1 == 3 && L == 1)         // N = 1024, k = 2: single launches of 257 ... 512 LWEs
         v.rotate_keypf_fn = reinterpret_cast<const void*>(&blind_rotate_wide_kernel<LOGN, LOGR, K1, L, true>);
@@ -681,7 +679,7 @@ int Engine::install_keys(uint64_t* d_ksk_std, uint64_t* d_std) {
     HIP_TRY(hipMalloc((void**)&d_fbsk, bsk_len * 8));   // N u64 -> N/2 c64: same byte count
     if (convert_polys(d_std, d_fbsk, (uint32_t)(bsk_len / p.N))) return 1;
     if (d_fbsk_dense) { HIP_TRY(hipFree(d_fbsk_dense)); d_fbsk_dense = nullptr; }
-    if (variant_large->dense_convert_fn) {      // the copy of the key in FftSwap9's order (N = 1024, k = 2: 54.7 MB): dense and wide kernels
+    if (variant_large->dense_convert_fn) {      // the copy of the key in FftSwap9's order (N = 1024, k = 2: 54.7 MB): the dense kernel's
         HIP_TRY(hipMalloc((void**)&d_fbsk_dense, bsk_len * 8));
         uint32_t n_polys = (uint32_t)(bsk_len / p.N);
         void* cargs[] = {(void*)&d_std, (void*)&d_fbsk_dense, (void*)&n_polys};
@@ -870,12 +868,8 @@ static bool shadow_mode_eligible(const Engine& e, uint32_t count) {
     return e.stream == e.own_stream && !e.variant->large && !e.variant->wide && !e.variant->extprod_fn && count <= (uint32_t)e.cu_count;
 }
 
-// The Fourier key `v` reads: a wide variant on a plan of its own that is not the engine's primary variant takes the dense kernel's copy (nullptr: missing).
-static const double* rotation_key(const Engine& e, const BrVariant* v) { return v->own_plan && v != e.variant ? e.d_fbsk_dense : e.d_fbsk; }
-
 static int rotate_overlapped(Engine& e, const BrVariant* w, BlindRotateArgs a, hipStream_t on) {
     a.fair_shift = e.wide_fair_shift;      // the two launches that share the GPU progress at the same rate (110 k -> 122 k PBS/s)
-    if (!(a.fbsk = rotation_key(e, w))) return fail("wide kernel: the key copy in its plan's order is missing");
     void* args[] = {(void*)&a};
     HIP_TRY(hipLaunchKernel(w->rotate_fn, dim3(a.batch), dim3(w->threads), args, rotate_lds(w, e.p), on));
     return 0;
@@ -989,7 +983,6 @@ static int rotate_plain(Engine& e, const BrVariant* v, BlindRotateArgs a) {
     // its workgroups on them (they recompute and store nothing) -- the part then keeps its clock for the large launch that
     // follows (2.22 -> 2.39 GHz over 14 ms otherwise, profiles/r03_after_idle.txt), at the price of the energy
     if (e.keep_busy && !v->wide && !v->large && a.batch * 2 <= (uint32_t)e.cu_count) grid = a.batch * ((uint32_t)e.cu_count / a.batch);
-    if (!(a.fbsk = rotation_key(e, v))) return fail("wide kernel: the key copy in its plan's order is missing");
     void* args[] = {(void*)&a};
     HIP_TRY(hipLaunchKernel(v->rotate_keypf_fn && v->wide ? v->rotate_keypf_fn : v->rotate_fn, dim3(grid), dim3(v->threads), args,
                             rotate_lds(v, e.p), e.stream));

@@ -250,10 +250,8 @@ struct FftSwap11 {
 // Plan used by the blind-rotation kernels for (log2 P, log2 R).
 template <int LP, int LR>
 struct PlanFor { using type = FftPlan<LP, LR>; };
-#ifndef FHESTR_NO_SWAP_FFT
 template <>
 struct PlanFor<10, 2> { using type = FftSwap10; };
-#endif
 
 // ---- LDS slot swizzle (8-byte slots) ----------------------------------------------------------
 // ds_read_b64 serves a wave as two 32-lane groups (32 distinct slots mod 32 = conflict free),
@@ -439,11 +437,7 @@ __device__ __forceinline__ void fft_init_consts(FftConsts<PL>& c, int tau) {
     }
 }
 
-#ifdef FHESTR_NO_PIN
-#define FHE_PIN_ORDER() do {} while (0)
-#else
 #define FHE_PIN_ORDER() __builtin_amdgcn_sched_barrier(0)
-#endif
 // ---- FftSwap10 building blocks --------------------------------------------------------------
 __device__ __forceinline__ void wave_local_fence() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -539,14 +533,10 @@ __device__ __forceinline__ void idft4_twiddled(cplx* x, const cplx* tw) {
 #pragma unroll
     for (int q = 0; q < 4; q++) x[q] = y[q];
 }
-#ifndef FHESTR_FUSED_IDFT
-#define FHESTR_FUSED_IDFT 1
-#endif
 
-template <bool INV>
 __device__ __forceinline__ void swap10_twiddle(cplx* x, const cplx* tw) {
 #pragma unroll
-    for (int q = 1; q < 4; q++) x[q] = INV ? cmul_conj(x[q], tw[q]) : cmul(x[q], tw[q]);
+    for (int q = 1; q < 4; q++) x[q] = cmul(x[q], tw[q]);
 }
 
 // Forward transform in two halves around its one workgroup barrier.
@@ -558,7 +548,7 @@ __device__ __forceinline__ void swap10_twiddle(cplx* x, const cplx* tw) {
 template <class C>
 __device__ __forceinline__ void swap10_fwd_stage1(cplx* x, const C& c, double* re, double* im, int tau) {
     small_dft<4, false>(x);
-    swap10_twiddle<false>(x, c.tw[0]);
+    swap10_twiddle(x, c.tw[0]);
     swap_regs_lanes(x);
     small_dft<4, false>(x);
     // twiddle and store point by point: the next point's multiplies issue while the LDS write port
@@ -575,7 +565,7 @@ __device__ __forceinline__ void swap10_fwd_stage2(cplx* x, const C& c, const dou
 #pragma unroll
     for (int r = 0; r < 4; r++) { const int a = swap10_side_b(tau, r); x[r].re = re[a]; x[r].im = im[a]; }
     small_dft<4, false>(x);
-    swap10_twiddle<false>(x, c.tw[2]);
+    swap10_twiddle(x, c.tw[2]);
     swap_regs_lanes(x);
     small_dft<4, false>(x);
 }
@@ -618,40 +608,23 @@ __device__ __forceinline__ void swap10_inv_stage1(cplx* x, const C& c, const dou
 }
 template <class C>
 __device__ __forceinline__ void swap10_inv_stage1_compute(cplx* x, const C& c) {
-    if (FHESTR_FUSED_IDFT) {
-        idft4_twiddled(x, c.tw[3]);
-        swap_regs_lanes(x);           // the twiddles of the next pass (c.tw[2]) are folded into stage 2's butterfly
-        return;
-    }
-    swap10_twiddle<true>(x, c.tw[3]);
-    small_dft<4, true>(x);
-    swap_regs_lanes(x);
-    swap10_twiddle<true>(x, c.tw[2]);
+    idft4_twiddled(x, c.tw[3]);
+    swap_regs_lanes(x);           // the twiddles of the next pass (c.tw[2]) are folded into stage 2's butterfly
 }
 template <class C>
 __device__ __forceinline__ void swap10_inv_stage2(const cplx* x, const C& c, double* re, double* im, int tau) {
-    auto store = [&](int r, cplx y) {
+    idft4_twiddled_emit(x, c.tw[2], [&](int r, cplx y) {
         const int a = swap10_side_b(tau, r); re[a] = y.re; im[a] = y.im;
         FHE_PIN_ORDER();
-    };
-    if (FHESTR_FUSED_IDFT) idft4_twiddled_emit(x, c.tw[2], store);
-    else dft4_emit<true>(x, store);
+    });
 }
 template <class C>
 __device__ __forceinline__ void swap10_inv_stage3(cplx* x, const C& c, const double* re, const double* im, int tau) {
 #pragma unroll
     for (int r = 0; r < 4; r++) { const int a = swap10_side_a(tau, r); x[r].re = re[a]; x[r].im = im[a]; }
-    if (FHESTR_FUSED_IDFT) {
-        idft4_twiddled(x, c.tw[1]);
-        swap_regs_lanes(x);
-        idft4_twiddled(x, c.tw[0]);
-        return;
-    }
-    swap10_twiddle<true>(x, c.tw[1]);
-    small_dft<4, true>(x);
+    idft4_twiddled(x, c.tw[1]);
     swap_regs_lanes(x);
-    swap10_twiddle<true>(x, c.tw[0]);
-    small_dft<4, true>(x);
+    idft4_twiddled(x, c.tw[0]);
 }
 template <class C>
 __device__ __forceinline__ void swap10_inverse_tail(cplx* x, const C& c, double* re, double* im, int tau) {
@@ -695,11 +668,6 @@ __device__ __forceinline__ void swap10_inverse(cplx (*x)[4], const FftConsts<Fft
     for (int p = 0; p < NPOLY; p++) swap10_inv_stage3(x[p], c, re0 + p * poly_stride, re0 + p * poly_stride + im_off, tau);
 }
 
-#ifdef FHESTR_ABLATE_DENSE_BARRIERS      // timing experiment only (wrong results): where does the dense kernel's time go?
-#define FHE_DENSE_SYNC() do {} while (0)
-#else
-#define FHE_DENSE_SYNC() __syncthreads()
-#endif
 // FftSwap9: passes 1-4 and both in-wave exchanges are FftSwap10's stages (slab rows 4w + r, two waves); the pass across the
 // waves is a radix-2.
 // The pieces, for callers that put independent work of their own between them (the dense kernel: the previous polynomial's
@@ -733,48 +701,18 @@ __device__ __forceinline__ void swap9_inverse_tail(cplx* x, const C& c, double* 
     wave_local_fence();
     swap10_inv_stage3(x, c, re, im, tau);
 }
-// NPOLY polynomials carried by the same threads, stage by stage (one polynomial's LDS round trip behind the others' butterflies)
-template <int NPOLY>
-__device__ __forceinline__ void swap9_forward_multi(cplx (*x)[4], const FftConsts<FftSwap9>& c, double* re0, int poly_stride, int im_off, int tau) {
-#pragma unroll
-    for (int p = 0; p < NPOLY; p++) swap10_fwd_stage1(x[p], c, re0 + p * poly_stride, re0 + p * poly_stride + im_off, tau);
-    wave_local_fence();
-#pragma unroll
-    for (int p = 0; p < NPOLY; p++) swap10_fwd_stage2(x[p], c, re0 + p * poly_stride, re0 + p * poly_stride + im_off, tau);
-    wave_local_fence();
-#pragma unroll
-    for (int p = 0; p < NPOLY; p++) swap10_fwd_stage3(x[p], c, re0 + p * poly_stride, re0 + p * poly_stride + im_off, tau);
-    __syncthreads();
-#pragma unroll
-    for (int p = 0; p < NPOLY; p++) swap9_forward_tail(x[p], re0 + p * poly_stride, re0 + p * poly_stride + im_off, tau);
-    __syncthreads();             // the other wave reads this wave's rows in its tail: nobody stores into them before both have read
-}
-template <int NPOLY>
-__device__ __forceinline__ void swap9_inverse_multi(cplx (*x)[4], const FftConsts<FftSwap9>& c, double* re0, int poly_stride, int im_off, int tau) {
-#pragma unroll
-    for (int p = 0; p < NPOLY; p++) swap9_inverse_head(x[p], re0 + p * poly_stride, re0 + p * poly_stride + im_off, tau);
-    __syncthreads();
-#pragma unroll
-    for (int p = 0; p < NPOLY; p++) swap10_inv_stage1(x[p], c, re0 + p * poly_stride, re0 + p * poly_stride + im_off, tau);
-    wave_local_fence();
-#pragma unroll
-    for (int p = 0; p < NPOLY; p++) swap10_inv_stage2(x[p], c, re0 + p * poly_stride, re0 + p * poly_stride + im_off, tau);
-    wave_local_fence();
-#pragma unroll
-    for (int p = 0; p < NPOLY; p++) swap10_inv_stage3(x[p], c, re0 + p * poly_stride, re0 + p * poly_stride + im_off, tau);
-}
 __device__ __forceinline__ void swap9_forward(cplx* x, const FftConsts<FftSwap9>& c, double* re, double* im, int tau) {
     swap10_fwd_stage1(x, c, re, im, tau);
     wave_local_fence();
     swap10_fwd_stage2(x, c, re, im, tau);
     wave_local_fence();          // the slab stores below reuse the rows the exchange above read
     swap10_fwd_stage3(x, c, re, im, tau);
-    FHE_DENSE_SYNC();
+    __syncthreads();
     swap9_forward_tail(x, re, im, tau);
 }
 __device__ __forceinline__ void swap9_inverse(cplx* x, const FftConsts<FftSwap9>& c, double* re, double* im, int tau) {
     swap9_inverse_head(x, re, im, tau);
-    FHE_DENSE_SYNC();
+    __syncthreads();
     swap9_inverse_tail(x, c, re, im, tau);
 }
 
@@ -1013,7 +951,7 @@ __device__ __forceinline__ void fft_inverse(cplx* x, const C& c, double* re, dou
                 }
             }
         }
-        if (FHESTR_FUSED_IDFT && R == 4 && s < PL::NTW && lr == PL::LOGR) {      // twiddles folded into the butterflies
+        if (R == 4 && s < PL::NTW && lr == PL::LOGR) {      // twiddles folded into the butterflies
             cplx tw[4];
 #pragma unroll
             for (int q = 1; q < 4; q++) tw[q] = c.get(s, q);
@@ -1087,7 +1025,7 @@ __device__ __forceinline__ void pass_compute(cplx* x, int s, const C& c) {
     constexpr int R = PL::R;
     const int lr = PL::log_radix(s);
     const int rr = 1 << lr;
-    if (FHESTR_FUSED_IDFT && INV && R == 4 && s < PL::NTW && lr == PL::LOGR) {      // twiddles folded into the butterflies
+    if (INV && R == 4 && s < PL::NTW && lr == PL::LOGR) {      // twiddles folded into the butterflies
         cplx tw[4];
 #pragma unroll
         for (int q = 1; q < 4; q++) tw[q] = c.get(s, q);
@@ -1120,9 +1058,6 @@ __device__ __forceinline__ void fft_forward_multi(cplx (*x)[PL::R], const C& c, 
                                                   int poly_stride, int im_off, int tau) {
     if constexpr (PL::SWAP && PL::LOGP == 11) {
         swap11_forward<NPOLY>(x, c, re0, poly_stride, im_off, tau);
-        return;
-    } else if constexpr (PL::SWAP && PL::LOGP == 9) {
-        swap9_forward_multi<NPOLY>(x, c, re0, poly_stride, im_off, tau);
         return;
     } else if constexpr (PL::SWAP) {
         swap10_forward<NPOLY>(x, c, re0, poly_stride, im_off, tau);
@@ -1159,9 +1094,6 @@ __device__ __forceinline__ void fft_inverse_multi(cplx (*x)[PL::R], const C& c, 
     if constexpr (PL::SWAP && PL::LOGP == 11) {
         swap11_inverse<NPOLY>(x, c, re0, poly_stride, im_off, tau);
         return;
-    } else if constexpr (PL::SWAP && PL::LOGP == 9) {
-        swap9_inverse_multi<NPOLY>(x, c, re0, poly_stride, im_off, tau);
-        return;
     } else if constexpr (PL::SWAP) {
         swap10_inverse<NPOLY>(x, c, re0, poly_stride, im_off, tau);
         return;
@@ -1196,7 +1128,6 @@ __device__ __forceinline__ void fft_inverse_multi(cplx (*x)[PL::R], const C& c, 
 
 // torus f64 -> u64: reference commons/math/torus/mod.rs:72-78 (from_torus) =
 // round((x - round(x)) * 2^64) as i64 as u64.
-#ifndef FHESTR_FROM_TORUS_ROUND64
 // Here: the fractional part as fixed point, straight out of the mantissa.  v_fract_f64 is exact
 // (x - floor(x) in [0, 1)); adding 1.0 aligns it to 2^-52, so the 52 mantissa bits of the sum ARE
 // round_to_nearest_even(frac * 2^52) and the torus word is that mantissa << 12 (a sum that rounds
@@ -1211,19 +1142,6 @@ __device__ __forceinline__ uint64_t from_torus(double x) {
     const double u = __builtin_amdgcn_fract(x) + 1.0;
     return (uint64_t)__double_as_longlong(u) << 12;
 }
-#else
-// The reference's formula literally; rint() (ties-to-even) stands in for Rust's round() (ties away):
-// they differ only for exact .5 inputs, by one ulp of the 2^-64 grid.
-__device__ __forceinline__ uint64_t from_torus(double x) {
-    double fr = x - rint(x);
-    double y = rint(fr * 18446744073709551616.0);
-    double h = floor(y * 2.3283064365386963e-10);         // y / 2^32
-    double l = fma(h, -4294967296.0, y);                  // exact, in [0, 2^32)
-    uint32_t hi = (uint32_t)(int32_t)h;                   // v_cvt_i32_f64 (saturating)
-    uint32_t lo = (uint32_t)l;                            // v_cvt_u32_f64
-    return ((uint64_t)hi << 32) | lo;
-}
-#endif
 
 // signed i64 -> f64 (exact for |v| < 2^53, otherwise correctly rounded via two-part sum)
 __device__ __forceinline__ double i64_to_f64(uint64_t v) {

@@ -30,16 +30,13 @@
 #pragma once
 #include "pbs_large_kernels.hip.h"
 
-#ifndef FHESTR_CL_KEY_AUX
-#define FHESTR_CL_KEY_AUX 0       // Fourier-key loads: default policy (shared by the clusters of an XCD through L2)
-#endif
+namespace fhe {
 
+constexpr int CL_KEY_AUX = 0;            // Fourier-key loads: default policy (shared by the clusters of an XCD through L2)
 // cache policy of the loads of exchanged data: sc1 = past the vector L1, served by the XCD's L2.  (Measured and dropped:
 // sc1 | nt on these loads, nt on the key loads, and starting half of an XCD's clusters half a step late -- all within
 // -4 % .. 0 % at 32 clusters, same L2 miss counts)
-#define FHESTR_CL_XCHG_AUX 16
-
-namespace fhe {
+constexpr int CL_XCHG_AUX = 16;
 
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 
@@ -110,14 +107,14 @@ struct BlindRotateClusterArgs {
 
 template <class RSRC>
 __device__ __forceinline__ double2 load_sc1_b128(RSRC rsrc, uint32_t voff) {
-    const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, FHESTR_CL_XCHG_AUX);
+    const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, CL_XCHG_AUX);
     double2 d;
     __builtin_memcpy(&d, &v, 16);
     return d;
 }
 template <class RSRC>
 __device__ __forceinline__ uint64_t load_sc1_b64(RSRC rsrc, uint32_t voff) {
-    const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)voff, 0, FHESTR_CL_XCHG_AUX);
+    const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)voff, 0, CL_XCHG_AUX);
     return ((uint64_t)v.y << 32) | v.x;
 }
 
@@ -126,10 +123,6 @@ __device__ __forceinline__ uint64_t load_sc1_b64(RSRC rsrc, uint32_t voff) {
 // every cluster returns at once, the kernel drains with garbage and the host reports it (Engine::cluster_check).
 // Every wave drains its vector-memory queue completely (vmcnt(0)): waiting for "all but the N youngest" operations would
 // rest on the compiler placing nothing -- no scratch spill either -- behind the caller's prefetches.
-#ifndef FHESTR_CL_SYNC
-#define FHESTR_CL_SYNC 1
-#endif
-#if FHESTR_CL_SYNC == 1
 // No workgroup barrier anywhere in the hand-over: every wave drains its own stores, counts itself in on an LDS counter
 // (the wave that completes the count publishes the workgroup's epoch flag) and then polls the cluster's flag line
 // itself.  A wave that sees all C flags at this epoch knows that every wave of every member -- its own workgroup's
@@ -185,40 +178,6 @@ __device__ __forceinline__ void cluster_sync(uint32_t* flags, uint32_t member, u
     }
     asm volatile("" ::: "memory");
 }
-#else
-template <int C, uint32_t WAVES = 8>
-__device__ __forceinline__ void cluster_sync(uint32_t* flags, uint32_t member, uint32_t& epoch, uint32_t* s_dead_generic,
-                                             ClusterCtl* ctl, ClusterStatus* status, uint32_t spin_limit, uint32_t mute_epoch,
-                                             uint32_t /* need: this variant always waits for everyone */ = 0xFFFFFFFFu) {
-    typedef __attribute__((address_space(3))) volatile uint32_t lds_vu32_t;     // a plain LDS access (a generic pointer would be a
-    lds_vu32_t* s_dead = (lds_vu32_t*)(uintptr_t)lds_address(s_dead_generic);   // flat load: it waits for vmcnt(0) as well)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // this wave's stores have reached L2
-    __syncthreads();
-    ++epoch;
-    if (threadIdx.x < 64 && !*s_dead) {
-        const uint32_t lane = threadIdx.x;
-        if (lane == 0 && epoch != mute_epoch) __hip_atomic_store(flags + member, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        uint32_t spins = 0;
-        for (;;) {
-            const uint32_t v = lane < (uint32_t)C ? __hip_atomic_load(flags + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : epoch;
-            if (__all((int32_t)(v - epoch) >= 0)) break;
-            ++spins;
-            const bool others_gave_up = (spins & 1023u) == 0 && __hip_atomic_load(&ctl->error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (spins > spin_limit || others_gave_up) {
-                if (lane == 0) {
-                    __hip_atomic_store(&ctl->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&status->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    *s_dead = 1u;
-                }
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-    }
-    __syncthreads();
-}
-
-#endif
 
 // Cluster formation, by ONE thread of every workgroup (agent-scope atomics: valid wherever the workgroups landed): a
 // ticket from the counter of the XCD this workgroup runs on, a grid-wide arrival count, then clusters = runs of C
@@ -424,12 +383,10 @@ blind_rotate_cluster_kernel(BlindRotateClusterArgs ca) {
         const uint64_t* lwe = args.lwe_small + (size_t)sample * (n + 1);
         const uint64_t* lut = args.luts + (size_t)(args.lut_idx ? args.lut_idx[sample] : 0) * K1 * N;
         __syncthreads();          // lds_d of the previous sample is no longer read
-        for (uint32_t i = tid; i < n; i += NT) {
-            const uint64_t a = lwe[i];
-            lds_d[i] = a == 0 ? 0xFFFFFFFFu : modulus_switch(a, LOGN);
-        }
+        modswitch_mask<LOGN>(lwe, n, lds_d, NT, false);
 
-        // acc <- LUT * X^{-ms(body)}: this thread's 2R coefficients j = h P + (tau + TA m) P2 + b
+        // acc <- LUT * X^{-ms(body)}: this thread's 2R coefficients j = h P + (tau + TA m) P2 + b.  Written out here and at the
+        // extraction below (not rotated_lut_coeff / extract_store): the helpers changed this kernel's register allocation and loop, CHANGELOG.md.
         uint64_t own[2 * R];
         {
             const uint32_t d = modulus_switch(lwe[n], LOGN);
@@ -467,11 +424,7 @@ blind_rotate_cluster_kernel(BlindRotateClusterArgs ca) {
             // the GGSW rows of this half's first digit polynomial do not depend on the hand-over: request them now
             const auto k_rsrc = __builtin_amdgcn_make_buffer_rsrc(
                 const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(args.fbsk)) +
-#ifdef FHESTR_CL_KEY0      // diagnostic build: every step reads the first GGSW (wrong results; what does the key stream cost?)
-                    (size_t)0 * GGSW_BYTES,
-#else
                     (size_t)i * GGSW_BYTES,
-#endif
                     0, (int)GGSW_BYTES, 0x00020000);
             double2 bv[K1][R];
             auto issue_key = [&](int uu) {
@@ -479,7 +432,7 @@ blind_rotate_cluster_kernel(BlindRotateClusterArgs ca) {
                 for (int col = 0; col < K1; col++) {
 #pragma unroll
                     for (int rho = 0; rho < R; rho++) {
-                        const u32x4_t raw = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, (int)voff_key[uu], (col * P + rho * TB) * 16, FHESTR_CL_KEY_AUX);
+                        const u32x4_t raw = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, (int)voff_key[uu], (col * P + rho * TB) * 16, CL_KEY_AUX);
                         __builtin_memcpy(&bv[col][rho], &raw, 16);
                     }
                 }
@@ -561,7 +514,7 @@ blind_rotate_cluster_kernel(BlindRotateClusterArgs ca) {
                 auto issue_row = [&](int uu) {
 #pragma unroll
                     for (int m = 0; m < R; m++) {
-                        const u32x4_t raw = __builtin_amdgcn_raw_buffer_load_b128(t_rsrc, (int)voff_t2, (uu * P1 * PITCH + TB * m) * 16, FHESTR_CL_XCHG_AUX);
+                        const u32x4_t raw = __builtin_amdgcn_raw_buffer_load_b128(t_rsrc, (int)voff_t2, (uu * P1 * PITCH + TB * m) * 16, CL_XCHG_AUX);
                         __builtin_memcpy(&xin[m], &raw, 16);
                     }
                 };
@@ -627,7 +580,7 @@ blind_rotate_cluster_kernel(BlindRotateClusterArgs ca) {
                 cplx x[R];
 #pragma unroll
                 for (int rho = 0; rho < R; rho++) {
-                    const u32x4_t raw = __builtin_amdgcn_raw_buffer_load_b128(t_rsrc, (int)voff_t3, (16 * rho * PITCH) * 16, FHESTR_CL_XCHG_AUX);
+                    const u32x4_t raw = __builtin_amdgcn_raw_buffer_load_b128(t_rsrc, (int)voff_t3, (16 * rho * PITCH) * 16, CL_XCHG_AUX);
                     double2 v;
                     __builtin_memcpy(&v, &raw, 16);
                     x[rho].re = v.x; x[rho].im = v.y;

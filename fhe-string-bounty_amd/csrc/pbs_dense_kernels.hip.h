@@ -54,23 +54,12 @@ blind_rotate_dense_kernel(BlindRotateArgs args) {
     const uint32_t bL = args.base_log;                     // one decomposition level
     const uint32_t dbias = decomp_bias_constant(bL <= 31 ? bL : 31);
 
-    for (uint32_t i = threadIdx.x; i < n; i += CFG::THREADS) {
-        const uint64_t a = lwe[i];
-        lds_d[i] = a == 0 ? 0xFFFFFFFFu : modulus_switch(a, LOGN);
-    }
+    modswitch_mask<LOGN>(lwe, n, lds_d, CFG::THREADS, false);
 
     FftConsts<PL> fc;
     fft_init_consts<PL>(fc, tau);
     cplx twist[R], twbias[R];
-#pragma unroll
-    for (int m = 0; m < R; m++) {
-        double sn, cs;
-        sincospi((double)PL::point(tau, m) / (double)N, &sn, &cs);
-        twist[m].re = cs; twist[m].im = sn;
-        const double cb = -(double)((1u << (args.base_log - 1)) - 1u);
-        twbias[m].re = cb * (cs - sn);
-        twbias[m].im = cb * (cs + sn);
-    }
+    twist_consts<PL, N>(tau, args.base_log, twist, twbias);
 
     // this thread's own coefficients j = PL::point(tau, m) + h P of polynomial p: slot (j & 1) * 512 + (j >> 1) =
     // own_base + 64 m + 256 h (a constant offset on one address)
@@ -78,23 +67,16 @@ blind_rotate_dense_kernel(BlindRotateArgs args) {
     auto own_slot = [](int p, int m, int h) { return p * N + PL::acc_slot(PL::point(0, m) + h * P); };
     static_assert(PL::acc_slot(PL::point(5, 2) + P) == PL::acc_slot(PL::point(5, 0)) + PL::acc_slot(PL::point(0, 2) + P), "own slots: base + constant");
 
-    // acc <- LUT * X^{-ms(body)}   (bootstrap.rs:254-271, polynomial_algorithms.rs:331-353)
+    // acc <- LUT * X^{-ms(body)}
     {
         const uint32_t d = modulus_switch(lwe[n], LOGN);
-        const uint32_t rem = d & (N - 1);
-        const bool odd = (d >> LOGN) & 1;
 #pragma unroll
         for (int p = 0; p < K1; p++)
 #pragma unroll
             for (int m = 0; m < R; m++)
 #pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const uint32_t j = PL::point(tau, m) + h * P;
-                    const uint32_t src = (j + rem) & (N - 1);
-                    const bool neg = ((j + rem) >= (uint32_t)N) != odd;
-                    uint64_t v = lut[(size_t)p * N + src];
-                    own[own_slot(p, m, h)] = neg ? (0 - v) : v;
-                }
+                for (int h = 0; h < 2; h++)
+                    own[own_slot(p, m, h)] = rotated_lut_coeff<LOGN>(lut + (size_t)p * N, PL::point(tau, m) + h * P, d);
     }
     __syncthreads();
 
@@ -115,11 +97,7 @@ blind_rotate_dense_kernel(BlindRotateArgs args) {
             for (int col = 0; col < K1; col++)
 #pragma unroll
                 for (int rho = 0; rho < R; rho++)
-#ifdef FHESTR_ABLATE_DENSE_KEY
-                    brow[col][rho] = make_double2(1.0 + row + col, 0.5 + rho + (double)i);
-#else
                     brow[col][rho] = key_load(key_rsrc, key_off, (uint32_t)((i * GGSW_ELEMS + ((size_t)row * K1 + col) * P + rho * T) * 16));
-#endif
         };
         cplx outf[K1][R];
         // products of one polynomial's spectrum with its GGSW row (ggsw.rs:560-598)
@@ -159,11 +137,7 @@ blind_rotate_dense_kernel(BlindRotateArgs args) {
                 for (int h = 0; h < 2; h++) {
                     uint32_t address, sm32;
                     rot.source_bytes(m, h, row_base, address, sm32);
-#ifdef FHESTR_ABLATE_DENSE_GATHER
-                    const uint64_t gathered = (uint64_t)address * 0x9E3779B97F4A7C15ull;
-#else
                     const uint64_t gathered = lds_load_u64(address);
-#endif
                     const uint64_t sm = ((uint64_t)sm32 << 32) | sm32;
                     const uint64_t v = (gathered ^ sm) - sm;
                     st[h] = decomp_single_biased(v - own[own_slot(row, m, h)], bL, dbias);
@@ -177,9 +151,9 @@ blind_rotate_dense_kernel(BlindRotateArgs args) {
             wave_local_fence();          // the slab stores below reuse the rows the exchange above read
             swap10_fwd_stage3(xr, fc, xre, xim, tau);
             request_row(row);
-            FHE_DENSE_SYNC();
+            __syncthreads();
             swap9_forward_tail(xr, xre, xim, tau);
-            FHE_DENSE_SYNC();            // the next polynomial's first stores vs the other wave's reads of this one's last pass
+            __syncthreads();            // the next polynomial's first stores vs the other wave's reads of this one's last pass
 #pragma unroll
             for (int rho = 0; rho < R; rho++) spec[rho] = xr[rho];
         }
@@ -199,35 +173,25 @@ blind_rotate_dense_kernel(BlindRotateArgs args) {
         for (int p = 0; p < K1; p++) {
             swap9_inverse_head(outf[p], xre, xim, tau);
             if (p > 0) update_acc(p - 1);
-            FHE_DENSE_SYNC();
+            __syncthreads();
             swap9_inverse_tail(outf[p], fc, xre, xim, tau);
-            if (p + 1 < K1) FHE_DENSE_SYNC();      // the next inverse's first stores land in the other wave's rows
+            if (p + 1 < K1) __syncthreads();      // the next inverse's first stores land in the other wave's rows
         }
         update_acc(K1 - 1);
-        FHE_DENSE_SYNC();
+        __syncthreads();
     }
 
-    // sample extraction (glwe_sample_extraction.rs:91-147)
     uint64_t* out = args.lwe_out + (size_t)sample * ((size_t)(K1 - 1) * N + 1);
 #pragma unroll
     for (int p = 0; p < K1; p++)
 #pragma unroll
         for (int m = 0; m < R; m++)
 #pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const uint32_t j = PL::point(tau, m) + h * P;
-                const uint64_t v = own[own_slot(p, m, h)];
-                if (p == K1 - 1) {
-                    if (j == 0) out[(size_t)(K1 - 1) * N] = v;
-                } else {
-                    if (j == 0) out[(size_t)p * N] = v;
-                    else out[(size_t)p * N + (N - j)] = 0 - v;
-                }
-            }
+            for (int h = 0; h < 2; h++) extract_store<N, K1>(out, p, PL::point(tau, m) + h * P, own[own_slot(p, m, h)]);
 }
 
 // Standard-domain polynomials -> the dense kernel's Fourier layout (FftSwap9's order).  One polynomial per workgroup; the
-// arithmetic of bsk_convert_kernel (forward_as_torus, fft/mod.rs:197-218; the inverse's 1/(N/2) folded in).
+// arithmetic of bsk_convert_kernel.
 template <int LOGN, int K1>
 __global__ void __launch_bounds__((BrDenseCfg<LOGN, K1>::THREADS))
 bsk_convert_dense_kernel(const uint64_t* __restrict__ bsk_std, double* __restrict__ fbsk, uint32_t n_polys) {
@@ -244,15 +208,7 @@ bsk_convert_dense_kernel(const uint64_t* __restrict__ bsk_std, double* __restric
 #pragma unroll
     for (int m = 0; m < R; m++) {
         const int j = PL::point(tau, m);
-        const uint64_t a = bsk_std[(size_t)poly * N + j];
-        const uint64_t b = bsk_std[(size_t)poly * N + j + P];
-        cplx z;
-        z.re = i64_to_f64(a) * (5.421010862427522e-20 / P);
-        z.im = i64_to_f64(b) * (5.421010862427522e-20 / P);
-        double sn, cs;
-        sincospi((double)j / (double)N, &sn, &cs);
-        cplx w; w.re = cs; w.im = sn;
-        x[m] = cmul(z, w);
+        x[m] = torus_point_to_fourier_input<N>(bsk_std[(size_t)poly * N + j], bsk_std[(size_t)poly * N + j + P], j);
     }
     fft_forward<PL>(x, fc, planes, planes + CFG::PLANE, tau);
     double2* out = reinterpret_cast<double2*>(fbsk) + (size_t)poly * P;

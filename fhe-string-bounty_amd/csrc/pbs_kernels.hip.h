@@ -143,6 +143,65 @@ __device__ __forceinline__ uint32_t modulus_switch(uint64_t x, int logN) {
     return (uint32_t)((o + 1) >> 1);
 }
 
+// ---- prologue and epilogue shared by the blind-rotation kernels -----------------------------------------------------------
+// Modulus switch of the whole mask once, into LDS (fft_impl/common.rs:26-43); 0xFFFFFFFF marks a_i == 0, whose CMUX step is
+// skipped (bootstrap.rs:281).  extprod (multi-bit PBS through the two-kernel path): `steps` plain external products, no rotation.
+template <int LOGN>
+__device__ __forceinline__ void modswitch_mask(const uint64_t* lwe, uint32_t steps, uint32_t* lds_d, uint32_t threads, bool extprod) {
+    for (uint32_t i = threadIdx.x; i < steps; i += threads) {
+        const uint64_t a = lwe[i];
+        lds_d[i] = extprod ? 0u : (a == 0 ? 0xFFFFFFFFu : modulus_switch(a, LOGN));
+    }
+}
+// Per-thread twisties e^{i pi j / N} of the points j = PL::point(tau, m), and twbias = -(B/2 - 1)(1 + i) * twist, the single-level
+// digit's bias (decomp_single_biased, digit_point); B = 2^base_log_total.
+template <class PL, int N>
+__device__ __forceinline__ void twist_consts(int tau, uint32_t base_log_total, cplx* twist, cplx* twbias) {
+#pragma unroll
+    for (int m = 0; m < PL::R; m++) {
+        double sn, cs;
+        sincospi((double)PL::point(tau, m) / (double)N, &sn, &cs);
+        twist[m].re = cs; twist[m].im = sn;
+        const double cb = -(double)((1u << (base_log_total - 1)) - 1u);
+        twbias[m].re = cb * (cs - sn);
+        twbias[m].im = cb * (cs + sn);
+    }
+}
+// Coefficient j of LUT * X^{-d}, d = modulus_switch(body) in [0, 2N]: +-lut[(j + rem) mod N]  (bootstrap.rs:254-271,
+// polynomial_algorithms.rs:331-353).  The caller decides where it goes: register, LDS slot or workspace.
+template <int LOGN>
+__device__ __forceinline__ uint64_t rotated_lut_coeff(const uint64_t* lut_poly, uint32_t j, uint32_t d_body) {
+    constexpr uint32_t N = 1u << LOGN;
+    const uint32_t rem = d_body & (N - 1);
+    const bool odd = (d_body >> LOGN) & 1;
+    const bool neg = ((j + rem) >= N) != odd;
+    const uint64_t v = lut_poly[(j + rem) & (N - 1)];
+    return neg ? (0 - v) : v;
+}
+// Sample extraction at degree 0 (glwe_sample_extraction.rs:121-146): coefficient j of accumulator polynomial p goes to out.
+template <int N, int K1>
+__device__ __forceinline__ void extract_store(uint64_t* out, uint32_t p, uint32_t j, uint64_t v) {
+    if (p == (uint32_t)(K1 - 1)) {
+        if (j == 0) out[(size_t)(K1 - 1) * N] = v;         // body = B[0]
+    } else {
+        if (j == 0) out[(size_t)p * N] = v;
+        else out[(size_t)p * N + (N - j)] = 0 - v;         // out[t] = -A[N - t]
+    }
+}
+// Key conversion: coefficients j (a) and j + N/2 (b) of a standard-domain polynomial as one input point of the forward
+// transform.  forward_as_torus: signed value * 2^-64 (fft/mod.rs:197-218); the inverse transform's 1/(N/2)
+// (fft/mod.rs:285-304) is folded in here (linear, exact: a power of two); times the twisty e^{i pi j / N}.
+template <int N>
+__device__ __forceinline__ cplx torus_point_to_fourier_input(uint64_t a, uint64_t b, int j) {
+    cplx z;
+    z.re = i64_to_f64(a) * (5.421010862427522e-20 / (N / 2));
+    z.im = i64_to_f64(b) * (5.421010862427522e-20 / (N / 2));
+    double sn, cs;
+    sincospi((double)j / (double)N, &sn, &cs);
+    cplx w; w.re = cs; w.im = sn;
+    return cmul(z, w);
+}
+
 // The Fourier key as a buffer resource (stride 0, raw): buffer_load_dwordx4 v, v_off, s[rsrc], s_off offen
 // takes its row offset from a scalar register and bounds-checks against the key's size.
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
@@ -277,15 +336,7 @@ bsk_convert_kernel(const uint64_t* __restrict__ bsk_std, double* __restrict__ fb
         const int j = PL::point(tau, m);
         uint64_t a = active ? bsk_std[(size_t)poly * N + j] : 0;
         uint64_t b = active ? bsk_std[(size_t)poly * N + j + P] : 0;
-        // forward_as_torus: signed value * 2^-64 (fft/mod.rs:197-218)
-        cplx z;
-        // the inverse transform's 1/(N/2) (fft/mod.rs:285-304) is folded in here: linear, exact (power of two)
-        z.re = i64_to_f64(a) * (5.421010862427522e-20 / P);
-        z.im = i64_to_f64(b) * (5.421010862427522e-20 / P);
-        double sn, cs;
-        sincospi((double)j / (double)N, &sn, &cs);  // twisty e^{i pi j / N}
-        cplx w; w.re = cs; w.im = sn;
-        x[m] = cmul(z, w);
+        x[m] = torus_point_to_fourier_input<N>(a, b, j);
     }
     fft_forward<PL>(x, fc, xre, xim, tau);
     if (active) {
@@ -347,16 +398,14 @@ blind_rotate_kernel(BlindRotateArgs args) {
     const uint32_t bL = args.base_log * L;
     const uint32_t dbias = decomp_bias_constant(bL <= 31 ? bL : 31);
 
-    // modulus switch of the whole mask once (fft_impl/common.rs:26-43); a_i == 0 is skipped (:281)
     const uint32_t steps = EXTPROD ? n / args.grouping : n;
-    for (uint32_t i = threadIdx.x; i < steps; i += CFG::THREADS) {
-        const uint64_t a = lwe[i];
-        lds_d[i] = EXTPROD ? 0u : (a == 0 ? 0xFFFFFFFFu : modulus_switch(a, LOGN));
-    }
+    modswitch_mask<LOGN>(lwe, steps, lds_d, CFG::THREADS, EXTPROD);
 
     // per-thread constants: inter-pass twiddles and twisties (1/P is folded into the Fourier key)
     FftConsts<PL> fc;
     fft_init_consts<PL>(fc, tau);
+    // Written out here, like the LUT rotation and the sample extraction below, not through twist_consts / rotated_lut_coeff /
+    // extract_store: the helpers changed this kernel's register allocation and CMUX loop, so its copies stay (CHANGELOG.md).
     cplx twist[R], twbias[R];        // twbias: -(B/2 - 1)(1 + i) * twist, the single-level digit's bias (decomp_single_biased)
 #pragma unroll
     for (int m = 0; m < R; m++) {
@@ -637,32 +686,19 @@ blind_rotate_kernel(BlindRotateArgs args) {
 // k+1 independent FFT streams to overlap LDS round trips with butterflies, and the smaller
 // footprint (accumulator copy + exchange planes) lets two LWEs share a CU for batches >= 512.
 // Barriers per CMUX step: forward exchange 0->1, inverse exchange 1->0, accumulator publish.
-// FftSwap11 for N = 4096 (negacyclic_fft.hip.h; -DFHESTR_SWAP11=0: the generic plan).  60 % fewer LDS stores; its twiddles of
+// FftSwap11 for N = 4096 (negacyclic_fft.hip.h).  60 % fewer LDS stores than the generic plan; its twiddles of
 // passes 1-2 come from an LDS table (FftSwapLdsConsts) and the digit bias is subtracted as an integer, because with everything in
 // VGPRs next to the prefetched key rows the kernel spilled 51 registers whose reloads queue behind the key loads (11.9 ms per
 // 256 LWEs against the generic plan's 7.55; now 6.8: profiles/r04_n4096.txt).
-#ifndef FHESTR_SWAP11
-#define FHESTR_SWAP11 1
-#endif
-// FftSwap9 under the N = 1024 two-per-CU kernel as well (three polynomials stage by stage, the dense kernel's key copy): correct
-// (tests, 87 k-PBS soak); with its key loads batched per GGSW row (ROW_BATCH: left alone the compiler serialised them, 10.0 ms per
-// 512 LWEs) it is level with the generic plan, which then took the whole-key prefetch below and is the faster of the two in
-// the overlapped mode; off (profiles/r04_n1024.txt).
-#ifndef FHESTR_WIDE_SWAP9
-#define FHESTR_WIDE_SWAP9 0
-#endif
 template <int LOGN, int LOGR, int K1, int L, bool KEYPF = false>
 struct BrWideCfg {
     static constexpr int N = 1 << LOGN;
     static constexpr int P = N / 2;
     // N = 4096 with four points per thread runs FftSwap11 (round 4); the wide kernel is the only one for that size, so its
     // Fourier key is simply in that plan's order (bsk_convert_wide_kernel)
-    // N = 1024 with four points per thread (k = 2: PARAM_MESSAGE_2_CARRY_1 ...) runs FftSwap9 and reads the key copy the dense
-    // kernel reads (same plan, same order) -- the one-per-CU kernel of that size keeps the generic plan and its own copy
-    static constexpr bool OWN_PLAN = (FHESTR_SWAP11 && LOGN == 12 && LOGR == 2) || (FHESTR_WIDE_SWAP9 && LOGN == 10 && LOGR == 2);
-    static constexpr bool LDS_TWIDDLES = OWN_PLAN && LOGN == 12;        // FftSwapLdsConsts: where the register file is full
-    using PL = typename std::conditional<!OWN_PLAN, typename PlanFor<LOGN - 1, LOGR>::type,
-                                         typename std::conditional<LOGN == 12, FftSwap11, FftSwap9>::type>::type;
+    static constexpr bool OWN_PLAN = LOGN == 12 && LOGR == 2;
+    static constexpr bool LDS_TWIDDLES = OWN_PLAN;                      // FftSwapLdsConsts: where the register file is full
+    using PL = typename std::conditional<OWN_PLAN, FftSwap11, typename PlanFor<LOGN - 1, LOGR>::type>::type;
     static constexpr int R = PL::R;
     static constexpr int T = PL::T;
     static constexpr int THREADS = T;
@@ -676,10 +712,7 @@ struct BrWideCfg {
     // N >= 4096: the accumulator lives in its LDS copy only -- a thread re-reads its own 2 K1 R coefficients at the gather and
     // at the update (the dense kernel's arrangement, pbs_dense_kernels.hip.h) instead of holding them in 4 K1 R VGPRs next to
     // 256 registers' worth of transform state (47 / 67 spilled dwords with one / two levels before)
-#ifndef FHESTR_WIDE_ACC_LDS_LOGN
-#define FHESTR_WIDE_ACC_LDS_LOGN 12
-#endif
-    static constexpr bool ACC_IN_LDS = LOGN >= FHESTR_WIDE_ACC_LDS_LOGN;
+    static constexpr bool ACC_IN_LDS = LOGN >= 12;
     // keep the whole Fourier GGSW of a step in VGPRs only when it is small
     // (also where the twiddles moved to LDS: without the prefetch N = 4096 has no spills but runs 9.5 instead of 7.8 ms)
     // ... or, KEYPF, where the kernel runs one wave per SIMD anyway (N = 1024 with k = 2: three polynomials per thread, 270-300
@@ -688,7 +721,6 @@ struct BrWideCfg {
     // (pipeline mode 2) mostly fail to co-reside (4.15 ms per 256-LWE call in 5 runs of 6, 2.27 in the sixth; the 272-register
     // build: 2.47-2.61 every time) -- profiles/r04_n1024.txt.
     static constexpr bool PREFETCH_ALL = K1 * K1 * R * 4 <= 64 || KEYPF;
-    static constexpr bool ROW_BATCH = !PREFETCH_ALL && OWN_PLAN && L == 1;      // see the products in the kernel
 };
 
 template <int LOGN, int LOGR, int K1, int L, bool KEYPF = false>
@@ -725,6 +757,7 @@ blind_rotate_wide_kernel(BlindRotateArgs args) {
                                                                  // accumulator copy must stay 8N-aligned at the start of the dynamic segment)
     }
 
+    // modswitch_mask written out: the helper changed this kernel's CMUX loop, so the copy stays (CHANGELOG.md)
     for (uint32_t i = threadIdx.x; i < n; i += CFG::THREADS) {
         const uint64_t a = lwe[i];
         lds_d[i] = a == 0 ? 0xFFFFFFFFu : modulus_switch(a, LOGN);
@@ -742,23 +775,13 @@ blind_rotate_wide_kernel(BlindRotateArgs args) {
         fft_init_consts<PL>(fc, tau);
     }
     cplx twist[R], twbias[R];
-#pragma unroll
-    for (int m = 0; m < R; m++) {
-        double sn, cs;
-        sincospi((double)PL::point(tau, m) / (double)N, &sn, &cs);
-        twist[m].re = cs; twist[m].im = sn;
-        const double cb = -(double)((1u << (args.base_log * L - 1)) - 1u);
-        twbias[m].re = cb * (cs - sn);
-        twbias[m].im = cb * (cs + sn);
-    }
+    twist_consts<PL, N>(tau, args.base_log * L, twist, twbias);
 
     constexpr bool ACC_LDS = CFG::ACC_IN_LDS;
     uint64_t acc_lo[ACC_LDS ? 1 : K1][R], acc_hi[ACC_LDS ? 1 : K1][R];
     auto own_slot = [&](int p, int m, int h) { return (size_t)p * N + acc_slot_of<PL>(PL::point(tau, m) + h * P); };
     {
         const uint32_t d = modulus_switch(lwe[n], LOGN);
-        const uint32_t rem = d & (N - 1);
-        const bool odd = (d >> LOGN) & 1;
 #pragma unroll
         for (int p = 0; p < K1; p++)
 #pragma unroll
@@ -766,10 +789,7 @@ blind_rotate_wide_kernel(BlindRotateArgs args) {
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
                     const uint32_t j = PL::point(tau, m) + h * P;
-                    const uint32_t src = (j + rem) & (N - 1);
-                    const bool neg = ((j + rem) >= (uint32_t)N) != odd;
-                    uint64_t v = lut[(size_t)p * N + src];
-                    v = neg ? (0 - v) : v;
+                    const uint64_t v = rotated_lut_coeff<LOGN>(lut + (size_t)p * N, j, d);
                     if constexpr (!ACC_LDS) { if (h == 0) acc_lo[p][m] = v; else acc_hi[p][m] = v; }
                     lds_acc[(size_t)p * N + acc_slot_of<PL>(j)] = v;
                 }
@@ -900,25 +920,11 @@ blind_rotate_wide_kernel(BlindRotateArgs args) {
             const double2* bk = bk0 + (size_t)lvl_idx * K1 * K1 * P;
 #pragma unroll
             for (int row = 0; row < K1; row++) {
-                // FftSwap9 build of this kernel (three polynomials, no key prefetch): a GGSW row is requested as one batch of
-                // K1 R loads and only then multiplied -- left to itself the compiler emitted load, s_waitcnt vmcnt(0), four
-                // FMAs, 36 times per step (10.0 instead of 4.95 ms per 512 LWEs, profiles/r04_n1024.txt)
-                double2 krow[CFG::ROW_BATCH ? K1 : 1][CFG::ROW_BATCH ? R : 1];
-                if constexpr (CFG::ROW_BATCH) {
-#pragma unroll
-                    for (int col = 0; col < K1; col++)
-#pragma unroll
-                        for (int rho = 0; rho < R; rho++)
-                            krow[col][rho] = key_load(key_rsrc, key_off,
-                                (uint32_t)((i * GGSW_ELEMS + (size_t)lvl_idx * K1 * K1 * P + ((size_t)row * K1 + col) * P + rho * T) * 16));
-                    FHE_PIN_ORDER();
-                }
 #pragma unroll
                 for (int col = 0; col < K1; col++)
 #pragma unroll
                     for (int rho = 0; rho < R; rho++) {
-                        const double2 bv = CFG::ROW_BATCH ? krow[CFG::ROW_BATCH ? col : 0][CFG::ROW_BATCH ? rho : 0]
-                                           : (CFG::PREFETCH_ALL && it == 0)
+                        const double2 bv = (CFG::PREFETCH_ALL && it == 0)
                                                ? bpre[CFG::PREFETCH_ALL ? row : 0][CFG::PREFETCH_ALL ? col : 0][rho]
                                                : bk[((size_t)row * K1 + col) * P + rho * T + tau];
                         const cplx f = x[row][rho];
@@ -967,16 +973,10 @@ blind_rotate_wide_kernel(BlindRotateArgs args) {
         for (int m = 0; m < R; m++)
 #pragma unroll
             for (int h = 0; h < 2; h++) {
-                const uint32_t j = PL::point(tau, m) + h * P;
                 uint64_t v;
                 if constexpr (ACC_LDS) v = lds_acc[own_slot(p, m, h)];
                 else v = h == 0 ? acc_lo[p][m] : acc_hi[p][m];
-                if (p == K1 - 1) {
-                    if (j == 0) out[(size_t)(K1 - 1) * N] = v;
-                } else {
-                    if (j == 0) out[(size_t)p * N] = v;
-                    else out[(size_t)p * N + (N - j)] = 0 - v;
-                }
+                extract_store<N, K1>(out, p, PL::point(tau, m) + h * P, v);
             }
 }
 
@@ -999,15 +999,7 @@ bsk_convert_wide_kernel(const uint64_t* __restrict__ bsk_std, double* __restrict
 #pragma unroll
     for (int m = 0; m < R; m++) {
         const int j = PL::point(tau, m);
-        const uint64_t a = bsk_std[(size_t)poly * N + j];
-        const uint64_t b = bsk_std[(size_t)poly * N + j + P];
-        cplx z;
-        z.re = i64_to_f64(a) * (5.421010862427522e-20 / P);
-        z.im = i64_to_f64(b) * (5.421010862427522e-20 / P);
-        double sn, cs;
-        sincospi((double)j / (double)N, &sn, &cs);
-        cplx w; w.re = cs; w.im = sn;
-        x[m] = cmul(z, w);
+        x[m] = torus_point_to_fourier_input<N>(bsk_std[(size_t)poly * N + j], bsk_std[(size_t)poly * N + j + P], j);
     }
     fft_forward<PL>(x, fc, planes, planes + CFG::PLANE, tau);
     double2* out = reinterpret_cast<double2*>(fbsk) + (size_t)poly * P;

@@ -247,7 +247,7 @@ blind_rotate_large_kernel(BlindRotateLargeArgs la) {
     RootTable<CFG> roots;
     roots.init(reinterpret_cast<double2*>(smem + CFG::LDS_PLANES), tid, NT);
 
-    // acc <- LUT * X^{-ms(body)}
+    // acc <- LUT * X^{-ms(body)} (written out, not rotated_lut_coeff: the helper changed this kernel's main loop, CHANGELOG.md)
     {
         const uint32_t d = modulus_switch(lwe[n], LOGN);
         const uint32_t rem = d & (N - 1);
@@ -270,7 +270,7 @@ blind_rotate_large_kernel(BlindRotateLargeArgs la) {
     FHE_STAMP_DECL;
     FHE_STAMP(-1);
     for (uint32_t i = 0; i < steps; i++) {
-        if (tid == 0) {
+        if (tid == 0) {      // not modswitch_mask: this kernel's LDS is full, one mask element is switched per step
             const uint64_t a = lwe[i];
             s_d = EXTPROD ? 0u : (a == 0 ? 0xFFFFFFFFu : modulus_switch(a, LOGN));
         }
@@ -450,17 +450,10 @@ blind_rotate_large_kernel(BlindRotateLargeArgs la) {
             g_stamps[((size_t)blockIdx.x * 8 + (threadIdx.x >> 6)) * STAMP_SEGS + sg] = stamp_acc[sg];
 #endif
 
-    // sample extraction at degree 0 (glwe_sample_extraction.rs:121-146)
     uint64_t* out = args.lwe_out + (size_t)sample * ((size_t)(K1 - 1) * N + 1);
     for (int e = tid; e < K1 * N; e += NT) {
         const uint32_t p = e >> LOGN, j = e & (N - 1);
-        const uint64_t v = acc[(size_t)p * N + CFG::aix(j)];
-        if (p == K1 - 1) {
-            if (j == 0) out[(size_t)(K1 - 1) * N] = v;
-        } else {
-            if (j == 0) out[(size_t)p * N] = v;
-            else out[(size_t)p * N + (N - j)] = 0 - v;
-        }
+        extract_store<N, K1>(out, p, j, acc[(size_t)p * N + CFG::aix(j)]);
     }
 }
 

@@ -287,7 +287,8 @@ blind_rotate_multibit_kernel(BlindRotateArgs args) {
     }
     const uint32_t c_tau = multibit_slot_exponent<N>(tau);
 
-    // acc <- LUT * X^{-ms(body)}
+    // acc <- LUT * X^{-ms(body)}; written out here and at the extraction below (not rotated_lut_coeff / extract_store): the
+    // helpers changed this kernel's register allocation (CHANGELOG.md).  The mask is a sum per selector, not modswitch_mask's element-wise switch.
     uint64_t acc_lo[R], acc_hi[R];
     {
         const uint32_t d = modulus_switch(lwe[n], LOGN);

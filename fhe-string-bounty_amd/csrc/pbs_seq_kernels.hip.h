@@ -59,14 +59,7 @@ bsk_convert_seq_kernel(const uint64_t* __restrict__ bsk_std, double* __restrict_
 #pragma unroll
         for (int m = 0; m < R; m++) {
             const int j = PL::point(tau, m);
-            // forward_as_torus (fft/mod.rs:197-218) with the inverse transform's 1/(N/2) folded in, as bsk_convert_kernel
-            cplx z;
-            z.re = i64_to_f64(bsk_std[(size_t)poly * N + j]) * (5.421010862427522e-20 / P);
-            z.im = i64_to_f64(bsk_std[(size_t)poly * N + j + P]) * (5.421010862427522e-20 / P);
-            double sn, cs;
-            sincospi((double)j / (double)N, &sn, &cs);
-            cplx w; w.re = cs; w.im = sn;
-            x[m] = cmul(z, w);
+            x[m] = torus_point_to_fourier_input<N>(bsk_std[(size_t)poly * N + j], bsk_std[(size_t)poly * N + j + P], j);
         }
         fft_forward<PL>(x, fc, re, im, tau);
         double2* out = reinterpret_cast<double2*>(fbsk) + (size_t)poly * P;
@@ -119,16 +112,14 @@ blind_rotate_seq_kernel(BlindRotateLargeArgs la) {
     const uint32_t tau8 = (uint32_t)tau * 8u;
     const uint32_t bL = args.base_log * L;
 
-    for (uint32_t i = threadIdx.x; i < steps; i += CFG::THREADS) {
-        const uint64_t a = lwe[i];
-        lds_d[i] = EXTPROD ? 0u : (a == 0 ? 0xFFFFFFFFu : modulus_switch(a, LOGN));
-    }
+    modswitch_mask<LOGN>(lwe, steps, lds_d, CFG::THREADS, EXTPROD);
     typename CFG::TW fc;
     CFG::TW::fill(lds_tw, tau, CFG::THREADS);
     fc.init(lds_tw, tau);
     // twisty of point tau + T m: e^{i pi tau / N} * e^{i pi m T / N}; the second factor is a compile-time constant, so
     // only the first is kept (2 VGPR pairs instead of 2 R) and the product is formed where it is used -- the
-    // transforms need the registers (opaque per step, or the compiler hoists all R products back out of the loop)
+    // transforms need the registers (opaque per step, or the compiler hoists all R products back out of the loop).
+    // Not twist_consts: that keeps one twisty per point in registers, and several levels need no digit bias.
     cplx twist0;
     {
         double sn, cs;
@@ -143,17 +134,12 @@ blind_rotate_seq_kernel(BlindRotateLargeArgs la) {
         return m == 0 ? twist0 : cmul(twist0, c);
     };
 
-    // acc <- LUT * X^{-ms(body)}   (bootstrap.rs:254-271)
+    // acc <- LUT * X^{-ms(body)}
     {
         const uint32_t d = modulus_switch(lwe[n], LOGN);
-        const uint32_t rem = d & (N - 1);
-        const bool odd = (d >> LOGN) & 1;
         for (int e = tau; e < K1 * N; e += CFG::THREADS) {
             const uint32_t p = e >> LOGN, j = e & (N - 1);
-            const uint32_t src = (j + rem) & (N - 1);
-            const bool neg = ((j + rem) >= (uint32_t)N) != odd;
-            const uint64_t v = lut[(size_t)p * N + src];
-            acc_poly((int)p)[j] = neg ? (0 - v) : v;
+            acc_poly((int)p)[j] = rotated_lut_coeff<LOGN>(lut + (size_t)p * N, j, d);
         }
     }
     __syncthreads();
@@ -260,17 +246,10 @@ blind_rotate_seq_kernel(BlindRotateLargeArgs la) {
         __syncthreads();     // the accumulator update is visible to the next step's rotated reads (same CU, same L1)
     }
 
-    // sample extraction at degree 0 (glwe_sample_extraction.rs:121-146)
     uint64_t* out = args.lwe_out + (size_t)sample * ((size_t)(K1 - 1) * N + 1);
     for (int e = tau; e < K1 * N; e += CFG::THREADS) {
         const uint32_t p = e >> LOGN, j = e & (N - 1);
-        const uint64_t v = acc_poly((int)p)[j];
-        if (p == (uint32_t)K1 - 1) {
-            if (j == 0) out[(size_t)(K1 - 1) * N] = v;           // body = B[0]
-        } else {
-            if (j == 0) out[(size_t)p * N] = v;
-            else out[(size_t)p * N + (N - j)] = 0 - v;           // out[t] = -A[N - t]
-        }
+        extract_store<N, K1>(out, p, j, acc_poly((int)p)[j]);
     }
 }
 

@@ -28,17 +28,15 @@
 #pragma once
 #include "pbs_cluster_kernels.hip.h"
 
+namespace fhe {
+
 // Cache policy of this kernel's Fourier-key loads: nt (2) -- streamed, not retained by the XCD's L2.  The 2 MB GGSW of a step is
 // read once per cluster; with the default policy (0) the two clusters' key streams (4 MB per step pair) push the exchange
 // matrices (2 x 1.6 MB) out of the 4 MB L2: L2 hit rate 0.64, 5.2 MB of fabric traffic per LWE-step, 18.5 ms per 16 LWEs; with
 // nt the exchange reads hit (0.78: the misses left are the key itself), 3.7 MB per LWE-step, 17.4 ms
 // (profiles/r04_xcd_history.txt).  The 8-CU cluster kernel keeps the default policy: its four clusters per XCD run in step and
 // share the key through L2 (nt there: 1,054 instead of 1,113 PBS/s, profiles/r03_cluster_history.txt).
-#ifndef FHESTR_XCD_KEY_AUX
-#define FHESTR_XCD_KEY_AUX 2
-#endif
-
-namespace fhe {
+constexpr int XCD_KEY_AUX = 2;
 
 template <int LOGN, int K1, int L>
 struct BrXcdCfg {
@@ -189,12 +187,9 @@ blind_rotate_xcd_kernel(BlindRotateClusterArgs ca) {
         const uint64_t* lwe = args.lwe_small + (size_t)sample * (n + 1);
         const uint64_t* lut = args.luts + (size_t)(args.lut_idx ? args.lut_idx[sample] : 0) * K1 * N;
         __syncthreads();          // lds_d of the previous sample is no longer read
-        for (uint32_t i = tid; i < n; i += NT) {
-            const uint64_t a = lwe[i];
-            lds_d[i] = a == 0 ? 0xFFFFFFFFu : modulus_switch(a, LOGN);
-        }
+        modswitch_mask<LOGN>(lwe, n, lds_d, NT, false);
 
-        // acc <- LUT * X^{-ms(body)}: an owner thread's 2R coefficients j = h P + (tau + TA m) P2 + b
+        // acc <- LUT * X^{-ms(body)}: an owner thread's 2R coefficients j = h P + (tau + TA m) P2 + b (written out as in the cluster kernel)
         uint64_t own[2 * R];
 #pragma unroll
         for (int q = 0; q < 2 * R; q++) own[q] = 0;
@@ -240,7 +235,7 @@ blind_rotate_xcd_kernel(BlindRotateClusterArgs ca) {
                 for (int col = 0; col < K1; col++) {
 #pragma unroll
                     for (int rho = 0; rho < R; rho++) {
-                        const u32x4_t raw = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, (int)voff_key, (col * P + rho * TB) * 16, FHESTR_XCD_KEY_AUX);
+                        const u32x4_t raw = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, (int)voff_key, (col * P + rho * TB) * 16, XCD_KEY_AUX);
                         __builtin_memcpy(&bv[col][rho], &raw, 16);
                     }
                 }
@@ -323,7 +318,7 @@ blind_rotate_xcd_kernel(BlindRotateClusterArgs ca) {
                 cplx x[R];
 #pragma unroll
                 for (int m = 0; m < R; m++) {
-                    const u32x4_t raw = __builtin_amdgcn_raw_buffer_load_b128(t_rsrc, (int)voff_t2f, (TB * m) * 16, FHESTR_CL_XCHG_AUX);
+                    const u32x4_t raw = __builtin_amdgcn_raw_buffer_load_b128(t_rsrc, (int)voff_t2f, (TB * m) * 16, CL_XCHG_AUX);
                     double2 v;
                     __builtin_memcpy(&v, &raw, 16);
                     x[m].re = v.x; x[m].im = v.y;
@@ -376,7 +371,7 @@ blind_rotate_xcd_kernel(BlindRotateClusterArgs ca) {
                 cplx x[R];
 #pragma unroll
                 for (int rho = 0; rho < R; rho++) {
-                    const u32x4_t raw = __builtin_amdgcn_raw_buffer_load_b128(t_rsrc, (int)voff_t3, (16 * rho * PITCH) * 16, FHESTR_CL_XCHG_AUX);
+                    const u32x4_t raw = __builtin_amdgcn_raw_buffer_load_b128(t_rsrc, (int)voff_t3, (16 * rho * PITCH) * 16, CL_XCHG_AUX);
                     double2 v;
                     __builtin_memcpy(&v, &raw, 16);
                     x[rho].re = v.x; x[rho].im = v.y;
@@ -433,13 +428,7 @@ blind_rotate_xcd_kernel(BlindRotateClusterArgs ca) {
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
                     const uint32_t j = (uint32_t)h * P + (uint32_t)(tau + TA * m) * P2 + (uint32_t)b;
-                    const uint64_t v = own[2 * m + h];
-                    if (pA == K1 - 1) {
-                        if (j == 0) out[(size_t)(K1 - 1) * N] = v;
-                    } else {
-                        if (j == 0) out[(size_t)pA * N] = v;
-                        else out[(size_t)pA * N + (N - j)] = 0 - v;
-                    }
+                    extract_store<N, K1>(out, pA, j, own[2 * m + h]);
                 }
             }
         }
