@@ -192,6 +192,37 @@ int fhe_engine_keyswitch_info(fhe_engine* eng, uint32_t info[6]) {
     API_END
 }
 
+int fhe_engine_load_packing_key(fhe_engine* eng, const fhe_packing_params_t* pp, const uint64_t* pksk) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(pp); CHECK_PTR(pksk);
+    return eng->impl->load_packing_key(*pp, pksk);
+    API_END
+}
+
+int fhe_engine_pack_lwes(fhe_engine* eng, const uint64_t* cts, uint32_t count, uint64_t* glwes_host) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    if (count) { CHECK_PTR(cts); CHECK_PTR(glwes_host); }
+    return eng->impl->pack_lwes_host(cts, count, glwes_host);
+    API_END
+}
+
+int fhe_engine_pack_lwes_dev(fhe_engine* eng, const uint64_t* d_cts, uint32_t count, uint64_t* d_glwes) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    if (count) { CHECK_PTR(d_cts); CHECK_PTR(d_glwes); }
+    return eng->impl->pack_lwes_dev(d_cts, count, d_glwes);
+    API_END
+}
+
+int fhe_engine_packing_info(fhe_engine* eng, uint32_t info[5]) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(info);
+    for (int q = 0; q < 5; q++) info[q] = eng->impl->pack_last[q];
+    return 0;
+    API_END
+}
+
 int fhe_engine_cluster_fallbacks(fhe_engine* eng, uint32_t* count) {
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(count);

@@ -18,6 +18,7 @@
 
 #include "det_math.h"
 #include "engine.h"
+#include "noise_model.h"
 
 namespace fhe {
 
@@ -125,6 +126,34 @@ struct ClientKey {
             }
         }
     }
+    // lwe_packing_keyswitch_key_generation.rs:19-96: key bit i, level l -> GLWE encryption of the constant s_i << (64 - base_log l)
+    void gen_packing_key_range(const fhe_packing_params_t& pp, const Seed256& key_seed, uint64_t* pksk, size_t lo, size_t hi) const {
+        const size_t glwe_len = (size_t)(p.k + 1) * p.N;
+        for (size_t i = lo; i < hi; i++) {
+            Rng r(key_seed, 0x504B534B00000000ull + i);
+            for (uint32_t it = 0; it < pp.level; it++) {
+                const uint32_t level = pp.level - it;
+                uint64_t* glwe = pksk + (i * pp.level + it) * glwe_len;
+                uint64_t* body = glwe + (size_t)p.k * p.N;
+                std::memset(body, 0, p.N * sizeof(uint64_t));
+                body[0] = glwe_sk[i] << (64 - pp.base_log * level);
+                glwe_encrypt_assign(glwe, r);
+            }
+        }
+    }
+    // glwe_encryption.rs:438-470 (decrypt_glwe_ciphertext): body - sum_q A_q S_q, by shifted adds for the binary key
+    void glwe_phase(const uint64_t* glwe, uint64_t* out) const {
+        const uint32_t N = p.N, k = p.k;
+        std::memcpy(out, glwe + (size_t)k * N, N * sizeof(uint64_t));
+        for (uint32_t q = 0; q < k; q++) {
+            const uint64_t *a = glwe + (size_t)q * N, *s = glwe_sk.data() + (size_t)q * N;
+            for (uint32_t t = 0; t < N; t++) {
+                if (!s[t]) continue;
+                for (uint32_t c = 0; c < N - t; c++) out[c + t] -= a[c];
+                for (uint32_t c = N - t; c < N; c++) out[c + t - N] += a[c];
+            }
+        }
+    }
     void gen_bsk(uint64_t* bsk, int threads) const {
         if (threads < 1) threads = 1;
         const std::vector<uint64_t> bits = ggsw_bits();
@@ -136,6 +165,90 @@ struct ClientKey {
         for (auto& th : pool) th.join();
     }
 };
+
+// ---- packing keyswitch (lwe_packing_keyswitch.rs): parameter checks, default decomposition, the plain host loop ----
+constexpr uint64_t kPackingKeyMaxBytes = 1ull << 32;
+
+static uint64_t packing_key_words(const fhe_params_t& p, const fhe_packing_params_t& pp) {
+    return (uint64_t)p.k * p.N * pp.level * (p.k + 1) * p.N;
+}
+
+int packing_params_check(const fhe_params_t& p, const fhe_packing_params_t& pp) {
+    if (p.k < 1 || p.N < 32 || (p.N & (p.N - 1))) return fail("packing keyswitch: polynomial size must be a power of two >= 32");
+    if (pp.base_log < 1 || pp.base_log > 7 || pp.level < 1 || pp.level > 16 || pp.base_log * pp.level > 63)
+        return fail("unsupported packing decomposition (base_log 1..7, level 1..16, base_log * level <= 63)");
+    if (packing_key_words(p, pp) * 8 > kPackingKeyMaxBytes)
+        return fail("unsupported parameter set for the packing keyswitch: the key would hold " +
+                    std::to_string(packing_key_words(p, pp) * 8) + " bytes (limit 4 GiB)");
+    return 0;
+}
+
+// Variance (torus = 1) the packing adds to a coefficient of a full GLWE.  Every one of the N packed LWEs brings one noise
+// coefficient of each of its k N level key encryptions to EVERY coefficient (the rotation only moves them), so the key term
+// of NoiseModel::v_ks counts N times, with the GLWE noise; the rounding of the mask against the binary key is the
+// coefficient's own LWE's alone.
+static double packing_variance(const fhe_params_t& p, const fhe_packing_params_t& pp) {
+    const double kN = (double)p.k * p.N, B = ldexp(1.0, (int)pp.base_log);
+    return (double)p.N * kN * pp.level * (B * B + 2) / 12.0 * p.glwe_std * p.glwe_std +
+           kN / 2.0 / 12.0 * ldexp(1.0, -2 * (int)(pp.base_log * pp.level));
+}
+
+// The bound a plan enforces at every PBS input (default_noise_budget): the failure probability of the reference-shaped
+// worst case, with the same slack and the same safety on shapes whose V_pbs is unmeasured.  A packed coefficient is a PBS
+// output (one nominal variance) plus the packing's own terms, decoded at delta / 2.
+static bool packing_meets_bound(const fhe_params_t& p, const fhe_packing_params_t& pp) {
+    const double max_level = (double)(p.msg_mod * p.carry_mod - 1) / (double)(p.msg_mod > 1 ? p.msg_mod - 1 : 1);
+    NoiseModel m = noise_model(p);
+    if (!noise_model_is_calibrated(p)) m.v_pbs *= kUncalibratedSafety;
+    const double target = m.log2_pfail(max_level * max_level) + (p.grouping_factor == 2 ? 0.0 : kPfailSlackLog2);
+    NoiseModel packed = m;
+    packed.v_ks = packing_variance(p, pp);
+    packed.v_ms = 0;
+    return packed.log2_pfail(1.0) <= target;
+}
+
+static inline void packing_decompose(uint64_t x, uint32_t bl, uint32_t L, int64_t* digits) {   // level L first (iter.rs:101-127)
+    const uint32_t rep = bl * L;
+    const uint64_t mask = (1ull << bl) - 1;
+    uint64_t state = (((x >> (63 - rep)) + 1) >> 1) & ((1ull << rep) - 1);
+    for (uint32_t lv = 0; lv < L; lv++) {
+        uint64_t res = state & mask;
+        state >>= bl;
+        uint64_t carry = (((res - 1ull) | state) & res) >> (bl - 1);
+        state += carry;
+        digits[lv] = (int64_t)res - (int64_t)(carry << bl);
+    }
+}
+
+static void packing_keyswitch_host(const fhe_params_t& p, const fhe_packing_params_t& pp, const uint64_t* pksk, const uint64_t* cts,
+                                   uint32_t count, uint64_t* glwes) {
+    const uint32_t N = p.N;
+    const size_t in_dim = (size_t)p.k * N, glwe_len = (size_t)(p.k + 1) * N;
+    std::memset(glwes, 0, (size_t)((count + N - 1) / N) * glwe_len * 8);
+    std::vector<uint64_t> t(glwe_len);
+    int64_t digits[16];
+    for (uint32_t j = 0; j < count; j++) {
+        const uint64_t* ct = cts + (size_t)j * (in_dim + 1);
+        std::fill(t.begin(), t.end(), 0);
+        t[(size_t)p.k * N] = ct[in_dim];
+        for (size_t i = 0; i < in_dim; i++) {
+            packing_decompose(ct[i], pp.base_log, pp.level, digits);
+            for (uint32_t lv = 0; lv < pp.level; lv++) {
+                if (!digits[lv]) continue;
+                const uint64_t d = (uint64_t)digits[lv], *row = pksk + (i * pp.level + lv) * glwe_len;
+                for (size_t c = 0; c < glwe_len; c++) t[c] -= d * row[c];
+            }
+        }
+        uint64_t* out = glwes + (size_t)(j / N) * glwe_len;
+        const uint32_t d = j % N;                                              // times X^d in Z[X] / (X^N + 1)
+        for (uint32_t q = 0; q <= p.k; q++) {
+            uint64_t* o = out + (size_t)q * N;
+            const uint64_t* src = t.data() + (size_t)q * N;
+            for (uint32_t c = 0; c < N - d; c++) o[c + d] += src[c];
+            for (uint32_t c = N - d; c < N; c++) o[c + d - N] -= src[c];
+        }
+    }
+}
 
 }  // namespace fhe
 
@@ -229,6 +342,79 @@ int fhe_client_gen_compact_public_key(fhe_client_key* ck, const uint8_t seed[32]
     } catch (const std::exception& e) {
         return fhe::fail(e.what());
     }
+}
+
+int fhe_packing_default_params(const fhe_params_t* params, fhe_packing_params_t* out) {
+    if (!params || !out) return fhe::fail("null pointer");
+    out->base_log = out->level = 0;
+    for (uint32_t level = 1; level <= 16; level++)
+        for (uint32_t base_log = 7; base_log >= 1; base_log--) {
+            const fhe_packing_params_t pp{base_log, level};
+            if (base_log * level > 63 || !fhe::packing_meets_bound(*params, pp)) continue;
+            if (fhe::packing_params_check(*params, pp)) return 1;       // the cheapest pair that decrypts is already too large
+            *out = pp;
+            return 0;
+        }
+    return fhe::fail("packing keyswitch: no decomposition meets the failure bound for this parameter set");
+}
+
+size_t fhe_packing_key_len(const fhe_params_t* params, const fhe_packing_params_t* pp) {
+    if (!params || !pp || fhe::packing_params_check(*params, *pp)) return 0;
+    return (size_t)fhe::packing_key_words(*params, *pp);
+}
+
+size_t fhe_packed_glwe_len(const fhe_params_t* params, uint32_t count) {
+    if (!params || !params->N) return 0;
+    return (size_t)((count + params->N - 1) / params->N) * (params->k + 1) * params->N;
+}
+
+int fhe_client_gen_packing_key(fhe_client_key* ck, const fhe_packing_params_t* pp, const uint8_t seed[32], uint64_t* pksk_out,
+                               int threads) {
+    if (!ck || !pp || !seed || !pksk_out) return fhe::fail("null pointer");
+    try {
+        const auto& c = *ck->impl;
+        if (fhe::packing_params_check(c.p, *pp)) return 1;
+        threads = std::max(1, std::min(threads, 64));
+        const fhe::Seed256 key_seed = fhe::seed_from_bytes(seed);
+        const fhe_packing_params_t dec = *pp;
+        const size_t rows = c.glwe_sk.size();
+        std::vector<std::thread> pool;
+        for (int t = 0; t < threads; t++)
+            pool.emplace_back([&, t] { c.gen_packing_key_range(dec, key_seed, pksk_out, rows * t / threads, rows * (t + 1) / threads); });
+        for (auto& th : pool) th.join();
+    } catch (const std::exception& e) {
+        return fhe::fail(e.what());
+    }
+    return 0;
+}
+
+int fhe_client_decrypt_packed(fhe_client_key* ck, const uint64_t* glwes, uint32_t count, uint64_t* msgs) {
+    if (!ck || (count && (!glwes || !msgs))) return fhe::fail("null pointer");
+    try {
+        const auto& c = *ck->impl;
+        const uint32_t N = c.p.N;
+        const size_t glwe_len = (size_t)(c.p.k + 1) * N;
+        std::vector<uint64_t> ph(N);
+        for (uint32_t g = 0; g * N < count; g++) {
+            c.glwe_phase(glwes + (size_t)g * glwe_len, ph.data());
+            for (uint32_t j = g * N; j < count && j < (g + 1) * N; j++) msgs[j] = c.decode(ph[j - g * N]);
+        }
+    } catch (const std::exception& e) {
+        return fhe::fail(e.what());
+    }
+    return 0;
+}
+
+int fhe_packing_keyswitch_host(const fhe_params_t* params, const fhe_packing_params_t* pp, const uint64_t* pksk, const uint64_t* cts,
+                               uint32_t count, uint64_t* glwes) {
+    if (!params || !pp || !pksk || !glwes || (count && !cts)) return fhe::fail("null pointer");
+    try {
+        if (fhe::packing_params_check(*params, *pp)) return 1;
+        fhe::packing_keyswitch_host(*params, *pp, pksk, cts, count, glwes);
+    } catch (const std::exception& e) {
+        return fhe::fail(e.what());
+    }
+    return 0;
 }
 
 int fhe_client_secret_keys(fhe_client_key* ck, uint64_t* glwe_sk, uint64_t* small_sk) {

@@ -136,6 +136,14 @@ struct Engine {
     // what the last launch_keyswitch launched (fhe_engine_keyswitch_info; recorded only, read by no decision): kernel
     // (FHE_KS_KERNEL_*), row tiles / samples per workgroup, K chunks (grid.z), K steps / input coefficients per chunk, K steps / in_dim
     uint32_t ks_last[5] = {0, 0, 0, 0, 0};
+    // packing keyswitch (packing_ks_kernels.hip.h): the key's digit planes, its decomposition, and the batch's digit fragments
+    int8_t* d_pksk_mfma = nullptr;
+    fhe_packing_params_t pack_pp{0, 0};
+    int8_t* d_pack_digits = nullptr;  // same reuse rules as d_ks_digits: zeroed at allocation, grown, rows past the batch never read
+    size_t cap_pack_digits = 0;
+    uint64_t *d_pack_in = nullptr, *d_pack_out = nullptr;   // staging of fhe_engine_pack_lwes (host ciphertexts)
+    size_t cap_pack_in = 0, cap_pack_out = 0;
+    uint32_t pack_last[5] = {0, 0, 0, 0, 0};   // fhe_engine_packing_info: ran, MT, K chunks, K steps per chunk, K steps
     int xcd_per_cu = -1;             // workgroups of the whole-XCD kernel a CU holds (occupancy query, cached)
     uint32_t xcd_auto_max = 16;     // automatic mode: batches up to this size take the whole-XCD kernel (two LWEs per XCD in flight)
     uint32_t cluster_spin_limit = 1u << 22;   // polls before a hand-over wait gives up (FHESTR_CLUSTER_SPIN_LIMIT)
@@ -172,6 +180,9 @@ struct Engine {
     int launch_blind_rotate(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big, uint32_t count, hipStream_t on = nullptr, bool two_per_cu = false,
                             bool one_workgroup_only = false);   // never a kernel that needs several workgroups resident at once (cluster_settle's re-run)
     bool shadow_keyswitch_fits();
+    int load_packing_key(const fhe_packing_params_t& pp, const uint64_t* pksk);
+    int pack_lwes_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_glwes);
+    int pack_lwes_host(const uint64_t* cts, uint32_t count, uint64_t* glwes);
     void keyswitch_info(uint32_t info[6]) const;   // ks_last and the register count shadow_keyswitch_fits judges by; changes nothing
     int ks_pbs_dev(const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint64_t* d_big_out, uint32_t count, bool allow_pipeline = false);
     int ks_pbs_host(const uint64_t* in, const uint32_t* lut_idx, uint64_t* out, uint32_t count);
@@ -199,6 +210,8 @@ size_t compact_dim(const fhe_params_t& p);
 int compact_pk_generate(const fhe_params_t& p, const uint64_t* big_sk, const Seed256& seed, uint64_t* pk, int threads);
 
 int params_supported(const fhe_params_t& p);   // 0, or 1 with the reason in fhe_last_error (no device needed)
+// client.cpp: the same answer for a packing keyswitch decomposition on a parameter set
+int packing_params_check(const fhe_params_t& p, const fhe_packing_params_t& pp);
 
 }  // namespace fhe
 

@@ -18,6 +18,7 @@
 #include "keygen_kernels.hip.h"   // first: asserts fp contract(off); the FFT header turns fusion on after it
 #include "lwe_kernels.hip.h"
 #include "ks_mfma_kernels.hip.h"
+#include "packing_ks_kernels.hip.h"
 #include "pbs_kernels.hip.h"
 #include "pbs_dense_kernels.hip.h"
 #include "pbs_large_kernels.hip.h"
@@ -362,6 +363,7 @@ Engine::~Engine() {
     auto rel = [](void* ptr) { if (ptr) (void)hipFree(ptr); };
     rel(d_ksk_packed); rel(d_ksk_rowsum); rel(d_fbsk); rel(d_fbsk_dense); rel(d_luts); rel(d_in); rel(d_small); rel(d_small2); rel(d_out); rel(d_idx);
     rel(d_pool); rel(d_meta); rel(d_ws); rel(d_slot_exp); rel(d_cluster_ws); rel(d_cluster_ctl); rel(d_ksk_mfma); rel(d_ks_digits); rel(d_compact);
+    rel(d_pksk_mfma); rel(d_pack_digits); rel(d_pack_in); rel(d_pack_out);
     for (int q = 0; q < OVL_MAX; q++) { rel(ovl_digits[q]); rel(ovl_small[q]); if (ovl_done[q]) (void)hipEventDestroy(ovl_done[q]); if (q >= 2 && ovl_stream[q]) (void)hipStreamDestroy(ovl_stream[q]); }
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : ring) if (e) (void)hipEventDestroy(e);
@@ -821,6 +823,106 @@ int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t cou
         return 0;
     }
     return fail("keyswitch key not installed");
+}
+
+// ---- packing keyswitch (packing_ks_kernels.hip.h) ---------------------------------------------------------------------
+// The key [kN][level][k+1][N] goes up once and is rewritten into balanced base-256 digit planes by the keyswitch's own
+// ksk_repack_mfma_kernel with (k+1) N columns; the 64-bit layout is then released.
+int Engine::load_packing_key(const fhe_packing_params_t& pp, const uint64_t* pksk) {
+    if (use()) return 1;
+    if (packing_params_check(p, pp)) return 1;
+    if (sync_all_streams()) return 1;                       // a launch in flight may still read the previous key or its digits
+    if (d_pksk_mfma) { HIP_TRY(hipFree(d_pksk_mfma)); d_pksk_mfma = nullptr; }
+    if (d_pack_digits) { HIP_TRY(hipFree(d_pack_digits)); d_pack_digits = nullptr; }   // the pad slots depend on the level count
+    cap_pack_digits = 0;
+    for (auto& w : pack_last) w = 0;
+    const KsMfmaGeom g = ks_mfma_geom(p.k * p.N, (p.k + 1) * p.N, pp.level, pp.base_log);
+    const size_t words = (size_t)g.in_dim * pp.level * g.out_size;
+    uint64_t* d_std = nullptr;
+    HIP_TRY(hipMalloc((void**)&d_std, words * 8));
+    hipError_t e = hipMalloc((void**)&d_pksk_mfma, (size_t)g.col_groups * g.steps * 8 * 1024);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_std, pksk, words * 8, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(ksk_repack_mfma_kernel, dim3(g.col_groups, g.steps), dim3(64), 0, stream, d_std, d_pksk_mfma, g);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    (void)hipFree(d_std);
+    if (e != hipSuccess) {
+        if (d_pksk_mfma) { (void)hipFree(d_pksk_mfma); d_pksk_mfma = nullptr; }
+        return fail(std::string("load_packing_key: ") + hipGetErrorString(e));
+    }
+    pack_pp = pp;
+    return 0;
+}
+
+// count big-key LWEs at d_cts -> ceil(count / N) GLWEs at d_glwes: memset, digits, product with the rotate-and-sum
+// epilogue.  Ordered on the engine's stream; nothing synchronises -- except in the throughput modes
+// (fhe_engine_set_pipeline 1 / 2), whose calls write their outputs on other streams: there the call first waits for every
+// stream and ends the pipelined run, like any serial call (include/fhestr.h says so).
+int Engine::pack_lwes_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_glwes) {
+    if (use()) return 1;
+    if (!d_pksk_mfma) return fail("packing key not loaded");
+    if (count == 0) return 0;
+    if (count > 65535u) return fail("batch too large for one packing launch (max 65535 LWEs)");   // grid.y of the digit kernel
+    if (pipeline) {                                         // pipelined calls may still write the input on another stream
+        if (sync_all_streams()) return 1;
+        end_pipeline_run();
+    }
+    const uint32_t in_dim = p.k * p.N, out_size = (p.k + 1) * p.N;
+    const KsMfmaGeom g = ks_mfma_geom(in_dim, out_size, pack_pp.level, pack_pp.base_log);
+    const uint32_t n_glwe = (count + p.N - 1) / p.N;
+    HIP_TRY(hipMemsetAsync(d_glwes, 0, (size_t)n_glwe * out_size * 8, stream));
+    const uint32_t row_tiles = (count + 31) / 32;
+    const size_t need = (size_t)row_tiles * g.steps * 1024;
+    if (need > cap_pack_digits) {
+        if (d_pack_digits) { if (sync_all_streams()) return 1; HIP_TRY(hipFree(d_pack_digits)); }
+        d_pack_digits = nullptr; cap_pack_digits = 0;
+        HIP_TRY(hipMalloc((void**)&d_pack_digits, need));
+        HIP_TRY(hipMemsetAsync(d_pack_digits, 0, need, stream));
+        cap_pack_digits = need;
+    }
+    KsDecomposeArgs da{d_cts, d_pack_digits, g, count};
+    hipLaunchKernelGGL(ks_decompose_kernel, dim3((2 * g.steps + 255) / 256, count), dim3(256), 0, stream, da);
+    uint32_t mt = 1;
+    while (mt < 8 && mt < row_tiles) mt *= 2;
+    const uint32_t gy = (row_tiles + mt - 1) / mt;
+    // K chunks as for the keyswitch (launch_keyswitch): fill the SIMDs about one and a half times; every chunk costs up to
+    // 63 atomics per (tile, column group).  FHESTR_KS_CHUNKS overrides; the int32 accumulators bound the chunk length.
+    uint32_t chunks = (6u * (uint32_t)cu_count + g.col_groups * gy * mt / 2) / (g.col_groups * gy * mt);
+    if (ks_chunks_override) chunks = ks_chunks_override;
+    chunks = std::max(1u, std::min(chunks, (g.steps + 7) / 8));
+    chunks = std::max(chunks, (g.steps + ks_mfma_max_steps(pack_pp.base_log) - 1) / ks_mfma_max_steps(pack_pp.base_log));
+    const uint32_t spc = (g.steps + chunks - 1) / chunks;
+    chunks = (g.steps + spc - 1) / spc;
+    PackKsArgs pa{d_cts, d_pksk_mfma, d_pack_digits, d_glwes, g, count, row_tiles, spc, p.N, p.k * p.N / 32};
+    const dim3 grid(g.col_groups, gy, chunks);
+    switch (mt) {
+        case 1: hipLaunchKernelGGL(packing_ks_mfma_kernel<1>, grid, dim3(64), 0, stream, pa); break;
+        case 2: hipLaunchKernelGGL(packing_ks_mfma_kernel<2>, grid, dim3(128), 0, stream, pa); break;
+        case 4: hipLaunchKernelGGL(packing_ks_mfma_kernel<4>, grid, dim3(256), 0, stream, pa); break;
+        default: hipLaunchKernelGGL(packing_ks_mfma_kernel<8>, grid, dim3(512), 0, stream, pa); break;
+    }
+    pack_last[0] = 1; pack_last[1] = mt; pack_last[2] = chunks; pack_last[3] = spc; pack_last[4] = g.steps;
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int Engine::pack_lwes_host(const uint64_t* cts, uint32_t count, uint64_t* glwes) {
+    if (use()) return 1;
+    if (!d_pksk_mfma) return fail("packing key not loaded");
+    if (count == 0) return 0;
+    const size_t big = (size_t)p.k * p.N + 1, out_words = (size_t)((count + p.N - 1) / p.N) * (p.k + 1) * p.N;
+    if (cap_pack_in < count * big * 8 || cap_pack_out < out_words * 8) {
+        if (sync_all_streams()) return 1;
+        if (ensure((void**)&d_pack_in, &cap_pack_in, count * big * 8)) return 1;
+        if (ensure((void**)&d_pack_out, &cap_pack_out, out_words * 8)) return 1;
+    }
+    HIP_TRY(hipMemcpyAsync(d_pack_in, cts, count * big * 8, hipMemcpyHostToDevice, stream));
+    if (pack_lwes_dev(d_pack_in, count, d_pack_out)) return 1;
+    HIP_TRY(hipMemcpyAsync(glwes, d_pack_out, out_words * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return 0;
 }
 
 // ---- blind-rotation dispatch: choose_rotate_path is the map, then one launch function per path ----------------------

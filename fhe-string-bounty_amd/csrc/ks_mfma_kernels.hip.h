@@ -133,6 +133,8 @@ struct KsMfmaArgs {
 };
 
 // MT waves per workgroup = MT row tiles (32 samples each); grid (column groups, ceil(row tiles / MT), K chunks).
+// KEEP IN STEP: packing_ks_mfma_kernel (packing_ks_kernels.hip.h) carries a copy of the staging pipeline and the MFMA loop
+// below with another epilogue; a change to one belongs in the other too.
 template <int MT>
 __global__ void __launch_bounds__(64 * MT) keyswitch_mfma_kernel(KsMfmaArgs a) {
     constexpr int NT = 64 * MT;

@@ -361,4 +361,107 @@ int fhe_wire_read_compact_public_key(const fhe_params_t* p, const uint8_t* in, s
     return 0;
 }
 
+// ---- packing keyswitch objects ---------------------------------------------------------------------------------------
+//   LwePackingKeyswitchKey<Vec<u64>> { data, decomp_base_log, decomp_level_count, output_glwe_size, output_polynomial_size,
+//                                      ciphertext_modulus }                       entities/lwe_packing_keyswitch_key.rs
+//   GlweCiphertext<Vec<u64>>         { data, polynomial_size, ciphertext_modulus }   entities/glwe_ciphertext.rs:286-293
+int fhe_wire_write_packing_key(const fhe_params_t* p, const fhe_packing_params_t* pp, const uint64_t* pksk, uint8_t* out,
+                               size_t out_cap, size_t* written) {
+    if (!p || !pp || !pksk) return fail("null pointer");
+    const size_t words = fhe_packing_key_len(p, pp);
+    if (!words) return 1;                                   // reason set by the parameter check
+    Writer w{out, out_cap};
+    w.vec_u64(pksk, words);
+    w.u64(pp->base_log);
+    w.u64(pp->level);
+    w.u64((uint64_t)p->k + 1);
+    w.u64(p->N);
+    w.native_modulus_u64();
+    return finish(w, written);
+}
+
+int fhe_wire_read_packing_key(const fhe_params_t* p, const uint8_t* in, size_t in_len, fhe_packing_params_t* pp, uint64_t* pksk,
+                              size_t pksk_cap_words, size_t* consumed) {
+    if (!p || !in || !pp) return fail("null pointer");
+    Reader r{in, in_len};
+    const uint64_t n = r.u64();                             // the data come first: step over them to the dimensions
+    if (r.err.empty() && n > (r.len - r.pos) / 8) r.err = "truncated input";
+    if (!r.err.empty()) return fail("LwePackingKeyswitchKey: " + r.err);
+    const size_t data_pos = r.pos;
+    r.pos += (size_t)n * 8;
+    const uint64_t base_log = r.u64(), level = r.u64(), glwe_size = r.u64(), poly = r.u64();
+    r.native_modulus_u64();
+    if (!r.err.empty()) return fail("LwePackingKeyswitchKey: " + r.err);
+    if (base_log > 64 || level > 64) return fail("LwePackingKeyswitchKey: decomposition out of range");
+    const fhe_packing_params_t got{(uint32_t)base_log, (uint32_t)level};
+    const size_t want = fhe_packing_key_len(p, &got);
+    if (!want) return 1;
+    if (glwe_size != (uint64_t)p->k + 1 || poly != p->N || n != want)
+        return fail("LwePackingKeyswitchKey does not match the parameter set (GLWE size " + std::to_string(glwe_size) +
+                    ", polynomial size " + std::to_string(poly) + ", " + std::to_string(n) + " words)");
+    *pp = got;
+    if (pksk) {
+        if (pksk_cap_words < want) return fail("LwePackingKeyswitchKey: destination holds fewer than " + std::to_string(want) + " words");
+        std::memcpy(pksk, in + data_pos, want * 8);
+    }
+    if (consumed) *consumed = r.pos;
+    return 0;
+}
+
+static void glwe_body_write(Writer& w, const fhe_params_t* p, const uint64_t* glwe) {
+    w.vec_u64(glwe, (size_t)(p->k + 1) * p->N);
+    w.u64(p->N);
+    w.native_modulus_u64();
+}
+
+static int glwe_body_read(Reader& r, const fhe_params_t* p, uint64_t* glwe) {
+    const size_t want = (size_t)(p->k + 1) * p->N;
+    const size_t n = r.vec_u64(glwe, want);
+    const uint64_t poly = r.u64();
+    r.native_modulus_u64();
+    if (!r.err.empty()) return fail("GlweCiphertext: " + r.err);
+    if (poly != p->N || n != want)
+        return fail("GlweCiphertext does not match the parameter set (polynomial size " + std::to_string(poly) + ", " +
+                    std::to_string(n) + " words)");
+    return 0;
+}
+
+int fhe_wire_write_glwe_ciphertext(const fhe_params_t* p, const uint64_t* glwe, uint8_t* out, size_t out_cap, size_t* written) {
+    if (!p || !glwe) return fail("null pointer");
+    Writer w{out, out_cap};
+    glwe_body_write(w, p, glwe);
+    return finish(w, written);
+}
+
+int fhe_wire_read_glwe_ciphertext(const fhe_params_t* p, const uint8_t* in, size_t in_len, uint64_t* glwe, size_t* consumed) {
+    if (!p || !in || !glwe) return fail("null pointer");
+    Reader r{in, in_len};
+    if (glwe_body_read(r, p, glwe)) return 1;
+    if (consumed) *consumed = r.pos;
+    return 0;
+}
+
+int fhe_wire_write_glwe_list(const fhe_params_t* p, const uint64_t* glwes, uint32_t n_glwes, uint8_t* out, size_t out_cap,
+                             size_t* written) {
+    if (!p || (n_glwes && !glwes)) return fail("null pointer");
+    Writer w{out, out_cap};
+    w.u64(n_glwes);
+    for (uint32_t g = 0; g < n_glwes; g++) glwe_body_write(w, p, glwes + (size_t)g * (p->k + 1) * p->N);
+    return finish(w, written);
+}
+
+int fhe_wire_read_glwe_list(const fhe_params_t* p, const uint8_t* in, size_t in_len, uint64_t* glwes, uint32_t max_glwes,
+                            uint32_t* n_glwes, size_t* consumed) {
+    if (!p || !in || !n_glwes || (max_glwes && !glwes)) return fail("null pointer");
+    Reader r{in, in_len};
+    const uint64_t n = r.u64();
+    if (!r.err.empty()) return fail("GLWE list: " + r.err);
+    if (n > max_glwes) return fail("GLWE list: " + std::to_string(n) + " ciphertexts, the destination holds " + std::to_string(max_glwes));
+    for (uint64_t g = 0; g < n; g++)
+        if (glwe_body_read(r, p, glwes + (size_t)g * (p->k + 1) * p->N)) return 1;
+    *n_glwes = (uint32_t)n;
+    if (consumed) *consumed = r.pos;
+    return 0;
+}
+
 }  // extern "C"

@@ -120,6 +120,10 @@ PARAM_MESSAGE_1_CARRY_1_KS_PBS = Params(684, 3, 512, 18, 1, 4, 3, 2, 2,
                                         0.00002043784477291318, 0.0000000000034525330484572114,
                                         "PARAM_MESSAGE_1_CARRY_1_KS_PBS")
 
+class _PackingParams(C.Structure):
+    _fields_ = [("base_log", C.c_uint32), ("level", C.c_uint32)]
+
+
 _lib = None
 
 EXPORTS = [
@@ -158,6 +162,10 @@ EXPORTS = [
     "fhe_plan_lut_count", "fhe_plan_export_lut", "fhe_engine_set_stream", "fhe_engine_reset_stream",
     "fhe_str_len", "fhe_str_is_empty", "fhe_str_strip_prefix_clear", "fhe_str_strip_suffix_clear",
     "fhe_str_strip_prefix", "fhe_str_strip_suffix", "fhe_str_replace_general", "fhe_str_replace_clear_general",
+    "fhe_packing_default_params", "fhe_packing_key_len", "fhe_packed_glwe_len", "fhe_client_gen_packing_key",
+    "fhe_client_decrypt_packed", "fhe_packing_keyswitch_host", "fhe_engine_load_packing_key", "fhe_engine_pack_lwes",
+    "fhe_engine_pack_lwes_dev", "fhe_engine_packing_info", "fhe_wire_write_packing_key", "fhe_wire_read_packing_key",
+    "fhe_wire_write_glwe_ciphertext", "fhe_wire_read_glwe_ciphertext", "fhe_wire_write_glwe_list", "fhe_wire_read_glwe_list",
 ] + [f"fhe_str_{n}{s}" for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat")
      for s in ("", "_clear")] + ["fhe_str_repeat_clear"]
 
@@ -295,6 +303,19 @@ def lib() -> C.CDLL:
     sig("fhe_str_replace_clear", vp, vp, u32, vp, vp, u32, vp)
     sig("fhe_str_to_upper", vp, vp, u32, vp)
     sig("fhe_str_to_lower", vp, vp, u32, vp)
+    KP = C.POINTER(_PackingParams)
+    sig("fhe_packing_default_params", PP, KP)
+    L.fhe_packing_key_len.restype = C.c_size_t
+    L.fhe_packing_key_len.argtypes = [PP, KP]
+    L.fhe_packed_glwe_len.restype = C.c_size_t
+    L.fhe_packed_glwe_len.argtypes = [PP, u32]
+    sig("fhe_client_gen_packing_key", vp, KP, vp, vp, i32)
+    sig("fhe_client_decrypt_packed", vp, vp, u32, vp)
+    sig("fhe_packing_keyswitch_host", PP, KP, vp, vp, u32, vp)
+    sig("fhe_engine_load_packing_key", vp, KP, vp)
+    sig("fhe_engine_pack_lwes", vp, vp, u32, vp)
+    sig("fhe_engine_pack_lwes_dev", vp, vp, u32, vp)
+    sig("fhe_engine_packing_info", vp, C.POINTER(u32))
     for name in ("fhe_params_ksk_len", "fhe_params_bsk_len"):
         getattr(L, name).restype = C.c_size_t
         getattr(L, name).argtypes = [PP]
@@ -383,6 +404,7 @@ class Engine:
 
     def __init__(self, params: Params, device: int = 0, log2_points: int = 0):
         self.params = params
+        self.device = device
         self._h = C.c_void_p()
         _check(lib().fhe_engine_create(C.byref(params.c()), device, C.byref(self._h)))
         if log2_points:
@@ -489,6 +511,8 @@ class Engine:
 
     def close(self):
         if self._h:
+            for ops in list(getattr(self, "_string_ops", ())):    # their cached plans point into this engine: they go first
+                ops.close()
             lib().fhe_engine_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -566,6 +590,53 @@ class Engine:
         acc = np.zeros(self.params.glwe_len, dtype=np.uint64)
         _check(lib().fhe_lut_download(self._h, lut_id, _ptr(acc)))
         return acc
+
+    def load_packing_key(self, pp, pksk):
+        """Upload a packing keyswitch key (ClientKey.gen_packing_key) and rewrite it into the kernel's digit planes."""
+        pksk = _u64(pksk).reshape(-1)
+        n = packing_key_len(self.params, pp)
+        if not n:
+            raise FheError(lib().fhe_last_error().decode())
+        if pksk.size != n:
+            raise FheError("packing key: size does not match the parameter set and decomposition")
+        _check(lib().fhe_engine_load_packing_key(self._h, C.byref(_pp(pp)), _ptr(pksk)))
+
+    def pack(self, cts=None, count: int | None = None, d_in: int | None = None, d_out: int | None = None):
+        """Packing keyswitch on the GPU (csrc/packing_ks_kernels.hip.h): big-key LWEs -> ceil(count / N) GLWEs, LWE j at
+        coefficient j % N of GLWE j // N.  cts: a host array (count, kN+1) -> returns (n_glwe, k+1, N); or a torch device
+        tensor / d_in + count: the buffer apply_lookup_table_dev or Plan.run_batch_dev wrote, packed where it lies.  With
+        d_out the GLWEs are written there (asynchronous on the engine's stream) and nothing is returned; without it
+        they come back as a host array."""
+        p = self.params
+        if cts is not None and hasattr(cts, "data_ptr"):
+            if count is None:
+                count = cts.numel() // p.big_size
+            keep, d_in = cts, cts.data_ptr()
+        if d_in:
+            if count is None:
+                raise FheError("pack: a device buffer needs a count")
+            if d_out:
+                _check(lib().fhe_engine_pack_lwes_dev(self._h, C.c_void_p(d_in), count, C.c_void_p(d_out)))
+                return None
+            import torch
+            n_glwe = -(-count // p.N)
+            out = torch.empty((n_glwe, p.k + 1, p.N), dtype=torch.int64, device=f"cuda:{self.device}")
+            torch.cuda.synchronize()
+            _check(lib().fhe_engine_pack_lwes_dev(self._h, C.c_void_p(d_in), count, C.c_void_p(out.data_ptr())))
+            self.synchronize()
+            return out.cpu().numpy().view(np.uint64)
+        cts = _u64(cts).reshape(-1, p.big_size)
+        out = np.zeros((-(-cts.shape[0] // p.N), p.k + 1, p.N), dtype=np.uint64)
+        _check(lib().fhe_engine_pack_lwes(self._h, _ptr(cts), cts.shape[0], _ptr(out)))
+        return out
+
+    def packing_info(self) -> dict:
+        """What the last pack launch ran (fhe_engine_packing_info): row tiles per workgroup, K chunks, K steps per chunk."""
+        a = (C.c_uint32 * 5)()
+        _check(lib().fhe_engine_packing_info(self._h, a))
+        ran, tile, chunks, spc, steps = (int(x) for x in a)
+        return {"ran": bool(ran), "tile": tile, "chunks": chunks, "steps_per_chunk": spc, "steps": steps,
+                "last_chunk": steps - (chunks - 1) * spc if ran else 0}
 
     def keyswitch(self, cts) -> np.ndarray:
         p = self.params
@@ -701,12 +772,68 @@ class ClientKey:
         _check(lib().fhe_client_gen_compact_public_key(self._h, sb, _ptr(pk)))
         return CompactPublicKey(p, pk)
 
+    def gen_packing_key(self, pp=None, seed=0, threads: int | None = None):
+        """Packing keyswitch key for this client's keys (fhe_client_gen_packing_key): returns ((base_log, level), words).
+        pp=None takes packing_default_params.  `seed` (32 bytes or an int) drives its masks and noise."""
+        p = self.params
+        pp = tuple(pp) if pp is not None else packing_default_params(p)
+        n = packing_key_len(p, pp)
+        if not n:
+            raise FheError(lib().fhe_last_error().decode())
+        pksk = np.zeros(n, dtype=np.uint64)
+        sb = (C.c_uint8 * 32)(*seed_bytes(seed))
+        _check(lib().fhe_client_gen_packing_key(self._h, C.byref(_pp(pp)), sb, _ptr(pksk), threads or min(16, os.cpu_count() or 1)))
+        return pp, pksk
+
+    def decrypt_packed(self, glwes, count: int) -> np.ndarray:
+        """message-and-carry value of the first `count` coefficients of packed results (Engine.pack)."""
+        glwes = _u64(glwes).reshape(-1)
+        if glwes.size != packed_glwe_len(self.params, count):
+            raise FheError(f"decrypt_packed: {glwes.size} words do not hold {count} packed ciphertexts of this parameter set")
+        out = np.zeros(count, dtype=np.uint64)
+        _check(lib().fhe_client_decrypt_packed(self._h, _ptr(glwes), count, _ptr(out)))
+        return out.astype(np.int64)
+
     def secret_keys(self):
         p = self.params
         g = np.zeros(p.k * p.N, dtype=np.uint64)
         s = np.zeros(p.n, dtype=np.uint64)
         _check(lib().fhe_client_secret_keys(self._h, _ptr(g), _ptr(s)))
         return g, s
+
+
+def _pp(pp) -> _PackingParams:
+    base_log, level = pp
+    return _PackingParams(int(base_log), int(level))
+
+
+def packing_default_params(params: Params):
+    """(base_log, level) of the cheapest packing keyswitch key whose packed results still decode within the failure bound
+    plans enforce (fhe_packing_default_params).  Raises for parameter sets whose key would exceed 4 GiB."""
+    out = _PackingParams()
+    _check(lib().fhe_packing_default_params(C.byref(params.c()), C.byref(out)))
+    return int(out.base_log), int(out.level)
+
+
+def packing_key_len(params: Params, pp) -> int:
+    """Words of a packing keyswitch key k N * level * (k+1) N; 0 = this (parameter set, decomposition) is refused."""
+    return int(lib().fhe_packing_key_len(C.byref(params.c()), C.byref(_pp(pp))))
+
+
+def packed_glwe_len(params: Params, count: int) -> int:
+    return int(lib().fhe_packed_glwe_len(C.byref(params.c()), count))
+
+
+def packing_keyswitch_host(params: Params, pp, pksk, cts) -> np.ndarray:
+    """The packing keyswitch as a plain CPU loop (fhe_packing_keyswitch_host): cts (count, kN+1) ->
+    (ceil(count / N), k+1, N).  Bit-identical to Engine.pack."""
+    cts = _u64(cts).reshape(-1, params.big_size)
+    pksk = _u64(pksk).reshape(-1)
+    if pksk.size != packing_key_len(params, pp) or not pksk.size:
+        raise FheError(lib().fhe_last_error().decode() if not packing_key_len(params, pp) else "packing key: size does not match the parameter set")
+    out = np.zeros((-(-cts.shape[0] // params.N), params.k + 1, params.N), dtype=np.uint64)
+    _check(lib().fhe_packing_keyswitch_host(C.byref(params.c()), C.byref(_pp(pp)), _ptr(pksk), _ptr(cts), cts.shape[0], _ptr(out)))
+    return out
 
 
 def compact_pk_len(params: Params) -> int:
@@ -991,13 +1118,51 @@ class FheStringOps:
         self.engine = engine
         self.bpc = blocks_per_char(engine.params)
         self._alloc = out_alloc or (lambda shape: np.zeros(shape, dtype=np.uint64))
+        self._plans = {}            # plans of the packed route, destroyed before their engine (Engine.close)
+        if not hasattr(engine, "_string_ops"):
+            import weakref
+            engine._string_ops = weakref.WeakSet()
+        engine._string_ops.add(self)
+
+    def close(self):
+        """Destroy the cached plans of the packed route (Engine.close does it for every FheStringOps over it)."""
+        for plan in self._plans.values():
+            plan.close()
+        self._plans.clear()
+
+    def _packed(self, op, a_cap, b_cap, clear, operands):
+        """packed=True on any method: the operation's plan runs on device buffers, its output goes through the packing
+        keyswitch where it lies (Engine.load_packing_key first) and only the GLWEs come back: (n_glwe, k+1, N), output block
+        j at coefficient j % N of GLWE j // N; decrypt with ClientKey.decrypt_packed.  The result LWEs never cross PCIe.
+        Plans are kept per (operation, capacities, clear pattern)."""
+        import torch
+        big = self.engine.params.big_size
+        key = (op, a_cap, b_cap, bytes(clear) if clear is not None else None)
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = Plan.string_op(self.engine, op, a_cap, b_cap, bytes(clear) if clear is not None else None)
+        info = plan.info()
+        inputs = np.concatenate([_u64(x).reshape(-1, big) for x in operands])
+        if inputs.shape[0] != info["n_inputs"]:
+            raise FheError(f"{op}: the plan takes {info['n_inputs']} input blocks, got {inputs.shape[0]}")
+        dev = f"cuda:{self.engine.device}"
+        d_in = torch.from_numpy(inputs.view(np.int64)).to(dev)
+        d_out = torch.empty((info["n_outputs"], big), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()                            # torch's stream is not ordered with the engine's
+        plan.run_dev(d_in.data_ptr(), d_out.data_ptr())
+        return self.engine.pack(d_out, count=info["n_outputs"])
 
     def _cap(self, ct):
         ct = _u64(ct).reshape(-1, self.engine.params.big_size)
         return ct, ct.shape[0] // self.bpc
 
-    def _binary(self, op, a, b):
+    def _binary(self, op, a, b, packed=False):
         a, a_cap = self._cap(a)
+        if packed:
+            if isinstance(b, (bytes, bytearray)):
+                return self._packed(op + "_clear", a_cap, 0, b, [a])
+            b, b_cap = self._cap(b)
+            return self._packed(op, a_cap, b_cap, None, [a, b])
         n_dig = 0
         while (self.engine.params.msg_mod ** n_dig) < a_cap + 1:
             n_dig += 1
@@ -1011,7 +1176,7 @@ class FheStringOps:
             _check(getattr(lib(), f"fhe_str_{op}")(self.engine.handle, _ptr(a), a_cap, _ptr(b), b_cap, _ptr(out)))
         return out
 
-    def op_many(self, op, rows, b=None):
+    def op_many(self, op, rows, b=None, packed=False):
         """`op` on every row against ONE second operand in a single pass (fhe_str_op_many): rows (count, cap*blocks, kN+1);
         b: an encrypted (zero padded) string, clear bytes, or None for unary operations.  Returns (count, n_outputs, kN+1)."""
         big = self.engine.params.big_size
@@ -1022,6 +1187,9 @@ class FheStringOps:
         clear = b if isinstance(b, (bytes, bytearray)) else None
         enc = None if (b is None or clear is not None) else self._cap(b)
         name = op + ("_clear" if clear is not None else "")
+        if packed:
+            # every row's outputs after one another: output o of row r is packed block r * n_outputs + o
+            return self._packed_many(name, rows, a_cap, enc, clear)
         buf = (C.c_uint8 * max(1, len(clear)))(*clear) if clear is not None else None
         args = (self.engine.handle, name.encode(), _ptr(rows), a_cap, count, _ptr(enc[0]) if enc else None, enc[1] if enc else 0,
                 buf, len(clear) if clear is not None else 0)
@@ -1031,6 +1199,26 @@ class FheStringOps:
         _check(lib().fhe_str_op_many(*args, _ptr(out), C.byref(n_out)))
         return out
 
+    def _packed_many(self, name, rows, a_cap, enc, clear):
+        import torch
+        big = self.engine.params.big_size
+        key = (name, a_cap, enc[1] if enc else 0, bytes(clear) if clear is not None else None)
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = Plan.string_op(self.engine, name, a_cap, enc[1] if enc else 0, bytes(clear) if clear is not None else None)
+        info = plan.info()
+        count = rows.shape[0]
+        inputs = rows if not enc else np.concatenate([rows, np.broadcast_to(enc[0], (count,) + enc[0].shape)], axis=1)
+        inputs = np.ascontiguousarray(inputs)
+        if inputs.shape[1] != info["n_inputs"]:
+            raise FheError(f"{name}: the plan takes {info['n_inputs']} input blocks per row, got {inputs.shape[1]}")
+        dev = f"cuda:{self.engine.device}"
+        d_in = torch.from_numpy(inputs.view(np.int64)).to(dev)
+        d_out = torch.empty((count, info["n_outputs"], big), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        plan.run_batch_dev(d_in.data_ptr(), d_out.data_ptr(), count)
+        return self.engine.pack(d_out, count=count * info["n_outputs"])
+
     def eq_many(self, rows, b): return self.op_many("eq", rows, b)[:, 0]
     def ne_many(self, rows, b): return self.op_many("ne", rows, b)[:, 0]
     def contains_many(self, rows, b): return self.op_many("contains", rows, b)[:, 0]
@@ -1038,18 +1226,18 @@ class FheStringOps:
     def ends_with_many(self, rows, b): return self.op_many("ends_with", rows, b)[:, 0]
     def find_many(self, rows, b): return self.op_many("find", rows, b)
 
-    def eq(self, a, b): return self._binary("eq", a, b)[0]
-    def ne(self, a, b): return self._binary("ne", a, b)[0]
-    def starts_with(self, a, b): return self._binary("starts_with", a, b)[0]
-    def ends_with(self, a, b): return self._binary("ends_with", a, b)[0]
-    def contains(self, a, b): return self._binary("contains", a, b)[0]
-    def find(self, a, b): return self._binary("find", a, b)
-    def rfind(self, a, b): return self._binary("rfind", a, b)
-    def eq_ignore_case(self, a, b): return self._binary("eq_ignore_case", a, b)[0]
-    def lt(self, a, b): return self._binary("lt", a, b)[0]
-    def le(self, a, b): return self._binary("le", a, b)[0]
-    def gt(self, a, b): return self._binary("gt", a, b)[0]
-    def ge(self, a, b): return self._binary("ge", a, b)[0]
+    def eq(self, a, b, packed=False): return self._binary("eq", a, b, packed)[0]
+    def ne(self, a, b, packed=False): return self._binary("ne", a, b, packed)[0]
+    def starts_with(self, a, b, packed=False): return self._binary("starts_with", a, b, packed)[0]
+    def ends_with(self, a, b, packed=False): return self._binary("ends_with", a, b, packed)[0]
+    def contains(self, a, b, packed=False): return self._binary("contains", a, b, packed)[0]
+    def find(self, a, b, packed=False): return self._binary("find", a, b, packed)
+    def rfind(self, a, b, packed=False): return self._binary("rfind", a, b, packed)
+    def eq_ignore_case(self, a, b, packed=False): return self._binary("eq_ignore_case", a, b, packed)[0]
+    def lt(self, a, b, packed=False): return self._binary("lt", a, b, packed)[0]
+    def le(self, a, b, packed=False): return self._binary("le", a, b, packed)[0]
+    def gt(self, a, b, packed=False): return self._binary("gt", a, b, packed)[0]
+    def ge(self, a, b, packed=False): return self._binary("ge", a, b, packed)[0]
 
     def _n_digits(self, cap):
         n = 0
@@ -1057,21 +1245,31 @@ class FheStringOps:
             n += 1
         return n
 
-    def len(self, a):
+    def len(self, a, packed=False):
         a, a_cap = self._cap(a)
+        if packed:
+            return self._packed("len", a_cap, 0, None, [a])
         out = self._alloc((self._n_digits(a_cap), self.engine.params.big_size))
         _check(lib().fhe_str_len(self.engine.handle, _ptr(a), a_cap, _ptr(out)))
         return out
 
-    def is_empty(self, a):
+    def is_empty(self, a, packed=False):
         a, a_cap = self._cap(a)
+        if packed:
+            return self._packed("is_empty", a_cap, 0, None, [a])[0]
         out = self._alloc((1, self.engine.params.big_size))
         _check(lib().fhe_str_is_empty(self.engine.handle, _ptr(a), a_cap, _ptr(out)))
         return out[0]
 
-    def _strip_affix(self, op, a, pat):
-        """pat: clear bytes, or an encrypted (zero padded) pattern."""
+    def _strip_affix(self, op, a, pat, packed=False):
+        """pat: clear bytes, or an encrypted (zero padded) pattern.  packed=True: ONE packed array, the flag at
+        coefficient 0 and the string's blocks after it."""
         a, a_cap = self._cap(a)
+        if packed:
+            if isinstance(pat, (bytes, bytearray)):
+                return self._packed(op + "_clear", a_cap, 0, pat, [a])
+            pat, p_cap = self._cap(pat)
+            return self._packed(op, a_cap, p_cap, None, [a, pat])
         out = self._alloc((1 + a.shape[0], self.engine.params.big_size))
         if isinstance(pat, (bytes, bytearray)):
             buf = (C.c_uint8 * max(1, len(pat)))(*pat)
@@ -1081,20 +1279,22 @@ class FheStringOps:
             _check(getattr(lib(), f"fhe_str_{op}")(self.engine.handle, _ptr(a), a_cap, _ptr(pat), p_cap, _ptr(out)))
         return out[0], out[1:]
 
-    def strip_prefix(self, a, pat): return self._strip_affix("strip_prefix", a, pat)
-    def strip_suffix(self, a, pat): return self._strip_affix("strip_suffix", a, pat)
+    def strip_prefix(self, a, pat, packed=False): return self._strip_affix("strip_prefix", a, pat, packed)
+    def strip_suffix(self, a, pat, packed=False): return self._strip_affix("strip_suffix", a, pat, packed)
 
-    def _unary(self, op, a):
+    def _unary(self, op, a, packed=False):
         a, a_cap = self._cap(a)
+        if packed:
+            return self._packed(op, a_cap, 0, None, [a])
         out = self._alloc(a.shape)
         _check(getattr(lib(), f"fhe_str_{op}")(self.engine.handle, _ptr(a), a_cap, _ptr(out)))
         return out
 
-    def trim_start(self, a): return self._unary("trim_start", a)
-    def trim_end(self, a): return self._unary("trim_end", a)
-    def strip(self, a): return self._unary("strip", a)
+    def trim_start(self, a, packed=False): return self._unary("trim_start", a, packed)
+    def trim_end(self, a, packed=False): return self._unary("trim_end", a, packed)
+    def strip(self, a, packed=False): return self._unary("strip", a, packed)
 
-    def replace(self, a, frm, to, out_cap: int | None = None):
+    def replace(self, a, frm, to, out_cap: int | None = None, packed=False):
         """Replace every leftmost non-overlapping occurrence of frm by to (bytes.replace).  frm / to: both
         clear bytes, or both encrypted strings.  out_cap=None: the equal-length in-place form (encrypted
         operands unpadded).  With out_cap: any lengths, encrypted operands may be zero padded, the result
@@ -1102,6 +1302,18 @@ class FheStringOps:
         a, a_cap = self._cap(a)
         big = self.engine.params.big_size
         clear = isinstance(frm, (bytes, bytearray))
+        if packed:
+            if clear:
+                if out_cap is None and len(frm) != len(to):
+                    raise FheError("replace: `from` and `to` of different lengths need an output capacity (out_cap)")
+                name = "replace_clear" if out_cap is None else f"replace_clear:{len(frm)}:{out_cap}"
+                return self._packed(name, a_cap, 0, bytes(frm) + bytes(to), [a])
+            frm, f_cap = self._cap(frm)
+            to, t_cap = self._cap(to)
+            if out_cap is None and f_cap != t_cap:
+                raise FheError("replace: `from` and `to` of different capacities need an output capacity (out_cap)")
+            name = "replace" if out_cap is None else f"replace:{f_cap}:{out_cap}"
+            return self._packed(name, a_cap, f_cap + t_cap, None, [a, frm, to])
         if out_cap is None:
             out = self._alloc(a.shape)
             if clear:
@@ -1131,9 +1343,14 @@ class FheStringOps:
                                                  _ptr(to) if t_cap else None, t_cap, out_cap, _ptr(out)))
         return out
 
-    def concat(self, a, b):
+    def concat(self, a, b, packed=False):
         """a ++ b (padding of a removed); b encrypted (any capacity) or clear bytes."""
         a, a_cap = self._cap(a)
+        if packed:
+            if isinstance(b, (bytes, bytearray)):
+                return self._packed("concat_clear", a_cap, 0, b, [a])
+            b, b_cap = self._cap(b)
+            return self._packed("concat", a_cap, b_cap, None, [a, b])
         if isinstance(b, (bytes, bytearray)):
             out = self._alloc(((a_cap + len(b)) * self.bpc, self.engine.params.big_size))
             buf = (C.c_uint8 * max(1, len(b)))(*b)
@@ -1144,11 +1361,13 @@ class FheStringOps:
             _check(lib().fhe_str_concat(self.engine.handle, _ptr(a), a_cap, _ptr(b), b_cap, _ptr(out)))
         return out
 
-    def repeat(self, a, count: int):
+    def repeat(self, a, count: int, packed=False):
         a, a_cap = self._cap(a)
+        if packed:
+            return self._packed("repeat_clear", a_cap, 0, bytes([count]), [a])
         out = self._alloc((count * a_cap * self.bpc, self.engine.params.big_size))
         _check(lib().fhe_str_repeat_clear(self.engine.handle, _ptr(a), a_cap, count, _ptr(out)))
         return out
 
-    def to_upper(self, a): return self._unary("to_upper", a)
-    def to_lower(self, a): return self._unary("to_lower", a)
+    def to_upper(self, a, packed=False): return self._unary("to_upper", a, packed)
+    def to_lower(self, a, packed=False): return self._unary("to_lower", a, packed)

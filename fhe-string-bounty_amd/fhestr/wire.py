@@ -7,7 +7,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import CompactPublicKey, FheError, Params, _check, _ptr, _u64, compact_list_len, compact_pk_len, lib
+from . import (CompactPublicKey, FheError, Params, _check, _PackingParams, _pp, _ptr, _u64, compact_list_len, compact_pk_len, lib,
+               packing_key_len)
 
 
 class _Meta(C.Structure):
@@ -67,6 +68,12 @@ def _sigs():
                                                      C.POINTER(C.c_uint64), szp]),
             ("fhe_wire_write_compact_public_key", [PP, vp, vp, sz, szp]),
             ("fhe_wire_read_compact_public_key", [PP, vp, sz, vp, szp]),
+            ("fhe_wire_write_packing_key", [PP, C.POINTER(_PackingParams), vp, vp, sz, szp]),
+            ("fhe_wire_read_packing_key", [PP, vp, sz, C.POINTER(_PackingParams), vp, sz, szp]),
+            ("fhe_wire_write_glwe_ciphertext", [PP, vp, vp, sz, szp]),
+            ("fhe_wire_read_glwe_ciphertext", [PP, vp, sz, vp, szp]),
+            ("fhe_wire_write_glwe_list", [PP, vp, C.c_uint32, vp, sz, szp]),
+            ("fhe_wire_read_glwe_list", [PP, vp, sz, vp, C.c_uint32, C.POINTER(C.c_uint32), szp]),
             ("fhe_wire_write_shortint_ciphertext", [vp, sz, C.POINTER(_Meta), C.c_int, vp, sz, szp]),
             ("fhe_wire_read_shortint_ciphertext", [vp, sz, C.c_int, C.c_uint64, vp, sz, szp, C.POINTER(_Meta), szp])):
         fn = getattr(L, name)
@@ -398,3 +405,49 @@ def read_compact_public_key(params: Params, data: bytes) -> CompactPublicKey:
     pk, used = np.zeros(n, dtype=np.uint64), C.c_size_t()
     _check(_sigs().fhe_wire_read_compact_public_key(C.byref(params.c()), _in(data), len(data), _ptr(pk), C.byref(used)))
     return CompactPublicKey(params, pk)
+
+
+def write_packing_key(params: Params, pp, pksk) -> bytes:
+    """LwePackingKeyswitchKey<Vec<u64>> of a key from ClientKey.gen_packing_key."""
+    pksk = _u64(pksk).reshape(-1)
+    if pksk.size != packing_key_len(params, pp) or not pksk.size:
+        raise FheError("packing key: size does not match the parameter set and decomposition")
+    return _write(lambda out, cap, n: _sigs().fhe_wire_write_packing_key(C.byref(params.c()), C.byref(_pp(pp)), _ptr(pksk), out, cap, n))
+
+
+def read_packing_key(params: Params, data: bytes):
+    """-> ((base_log, level), key words); every dimension checked against the parameter set."""
+    got, used, buf = _PackingParams(), C.c_size_t(), _in(data)
+    _check(_sigs().fhe_wire_read_packing_key(C.byref(params.c()), buf, len(data), C.byref(got), None, 0, C.byref(used)))
+    pp = (int(got.base_log), int(got.level))
+    pksk = np.zeros(packing_key_len(params, pp), dtype=np.uint64)
+    _check(_sigs().fhe_wire_read_packing_key(C.byref(params.c()), buf, len(data), C.byref(got), _ptr(pksk), pksk.size, C.byref(used)))
+    return pp, pksk
+
+
+def write_glwe_ciphertext(params: Params, glwe) -> bytes:
+    glwe = _u64(glwe).reshape(-1)
+    if glwe.size != params.glwe_len:
+        raise FheError("GLWE ciphertext: size does not match the parameter set")
+    return _write(lambda out, cap, n: _sigs().fhe_wire_write_glwe_ciphertext(C.byref(params.c()), _ptr(glwe), out, cap, n))
+
+
+def read_glwe_ciphertext(params: Params, data: bytes):
+    """-> ((k+1, N) words, bytes consumed)"""
+    glwe = np.zeros((params.k + 1, params.N), dtype=np.uint64)
+    used = C.c_size_t()
+    _check(_sigs().fhe_wire_read_glwe_ciphertext(C.byref(params.c()), _in(data), len(data), _ptr(glwe), C.byref(used)))
+    return glwe, used.value
+
+
+def write_glwe_list(params: Params, glwes) -> bytes:
+    """Packed results (Engine.pack) as a bincode Vec<GlweCiphertext>."""
+    glwes = _u64(glwes).reshape(-1, params.glwe_len)
+    return _write(lambda out, cap, n: _sigs().fhe_wire_write_glwe_list(C.byref(params.c()), _ptr(glwes), glwes.shape[0], out, cap, n))
+
+
+def read_glwe_list(params: Params, data: bytes, max_glwes: int = 64) -> np.ndarray:
+    glwes = np.zeros((max_glwes, params.k + 1, params.N), dtype=np.uint64)
+    n, used = C.c_uint32(), C.c_size_t()
+    _check(_sigs().fhe_wire_read_glwe_list(C.byref(params.c()), _in(data), len(data), _ptr(glwes), max_glwes, C.byref(n), C.byref(used)))
+    return glwes[:n.value].copy()

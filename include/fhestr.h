@@ -450,6 +450,52 @@ int fhe_engine_expand_compact_list_dev(fhe_engine *eng, const uint64_t *d_list, 
  * (slice_semi_reverse_negacyclic_convolution; known answer (1, 2, 3), (4, 5, 6) -> (-17, 5, 32)). */
 int fhe_compact_conv(const uint64_t *lhs, const uint64_t *rhs, uint32_t n, uint64_t *out, int threads);
 
+/* ---- packing keyswitch: results go back as GLWE ciphertexts ----------------------------------------
+ * keyswitch_lwe_ciphertext_list_and_pack_in_glwe_ciphertext of the reference
+ * (core_crypto/algorithms/lwe_packing_keyswitch.rs:102-187,297-380): up to N big-key LWEs become the coefficients of ONE
+ * GLWE ciphertext of (k+1) N words under the client's own GLWE key -- the 1024 result blocks of a 256-character string
+ * under PARAM_MESSAGE_2_CARRY_2 are 32 KB instead of 16.8 MB.  For LWE number d of a group,
+ *     T_d[p][c]  = [p == k and c == 0] * body_d - sum_{i, lv} digit(a_i, lv) * PKSK[i][lv][p][c]     (mod 2^64)
+ *     out[p]    += X^d * T_d[p]                                               in Z[X] / (X^N + 1)
+ * with the signed digits of closest_representable(a_i), level L first, as in the LWE keyswitch.  Nothing is rounded:
+ * host and GPU give the same words.
+ *   key    [kN][level, level L first][k+1][N] u64            (entities/lwe_packing_keyswitch_key.rs)
+ *   output ceil(count / N) GLWEs of [k+1][N] u64; LWE j is coefficient j % N of GLWE j / N, unused coefficients
+ *          encrypt nothing (0)
+ * 1 <= base_log <= 7, level <= 16, base_log * level <= 63; a key above 4 GiB (N >= 16384) is refused and
+ * fhe_packing_key_len returns 0. */
+typedef struct fhe_packing_params_t {
+    uint32_t base_log, level;
+} fhe_packing_params_t;
+/* Fewest levels, then largest base, for which a packed PBS output decoded at delta / 2 stays within the failure bound
+ * a plan enforces at its PBS inputs (csrc/noise_model.h). */
+int fhe_packing_default_params(const fhe_params_t *params, fhe_packing_params_t *out);
+size_t fhe_packing_key_len(const fhe_params_t *params, const fhe_packing_params_t *pp);   /* words; 0 = refused */
+size_t fhe_packed_glwe_len(const fhe_params_t *params, uint32_t count);                   /* words of the output */
+/* lwe_packing_keyswitch_key_generation.rs:19-96: for key bit s_i and level l a GLWE encryption of the constant
+ * polynomial s_i << (64 - base_log * l) under the GLWE key, noise glwe_std.  ChaCha20 under `seed`, one stream per key
+ * bit: the same key whatever `threads` is. */
+int fhe_client_gen_packing_key(fhe_client_key *ck, const fhe_packing_params_t *pp, const uint8_t seed[32],
+                               uint64_t *pksk_out, int threads);
+/* Coefficient j % N of the phase body - sum_q A_q S_q of GLWE j / N, decoded like fhe_client_decrypt. */
+int fhe_client_decrypt_packed(fhe_client_key *ck, const uint64_t *glwes, uint32_t count, uint64_t *msgs);
+/* The plain loop on the host (parity; callers without a GPU). */
+int fhe_packing_keyswitch_host(const fhe_params_t *params, const fhe_packing_params_t *pp, const uint64_t *pksk,
+                               const uint64_t *cts, uint32_t count, uint64_t *glwes);
+/* Upload the key and rewrite it once into digit planes (csrc/packing_ks_kernels.hip.h); replaces a key loaded before. */
+int fhe_engine_load_packing_key(fhe_engine *eng, const fhe_packing_params_t *pp, const uint64_t *pksk);
+/* Host ciphertexts in, host GLWEs out; synchronises. */
+int fhe_engine_pack_lwes(fhe_engine *eng, const uint64_t *cts, uint32_t count, uint64_t *glwes_host);
+/* Device buffers (what fhe_ks_pbs_batch_dev / fhe_plan_run_batch_dev write); asynchronous on the engine's stream.
+ * With a throughput mode on (fhe_engine_set_pipeline 1 or 2) the producing calls run on other streams: the call then
+ * waits on the host for all of them first and ends the pipelined run, like a serial call does; the packing itself is
+ * still only enqueued. */
+int fhe_engine_pack_lwes_dev(fhe_engine *eng, const uint64_t *d_cts, uint32_t count, uint64_t *d_glwes);
+/* What the last packing launch ran, recorded on the host when it was enqueued: info[0] 1 once a launch ran, info[1]
+ * 32-row tiles per workgroup (1, 2, 4 or 8), info[2] K chunks (grid.z; FHESTR_KS_CHUNKS overrides as for the
+ * keyswitch), info[3] K steps per chunk, info[4] K steps in all. */
+int fhe_engine_packing_info(fhe_engine *eng, uint32_t info[5]);
+
 /* ---- tfhe-rs wire format (serde + bincode 1.x, fixed-width little endian) ---------------------- */
 /* Byte forms of core_crypto's LweCiphertext<Vec<u64>>, LweKeyswitchKey<Vec<u64>>, standard-domain
  * LweBootstrapKey<Vec<u64>> and shortint::Ciphertext as tfhe-rs 0.5 writes them with bincode::serialize /
@@ -579,6 +625,23 @@ int fhe_wire_read_shortint_compact_list(const fhe_params_t *p, const uint8_t *in
                                         uint64_t *num_blocks_per_integer, size_t *consumed);
 int fhe_wire_write_compact_public_key(const fhe_params_t *p, const uint64_t *pk, uint8_t *out, size_t out_cap, size_t *written);
 int fhe_wire_read_compact_public_key(const fhe_params_t *p, const uint8_t *in, size_t in_len, uint64_t *pk, size_t *consumed);
+
+/* LwePackingKeyswitchKey<Vec<u64>> { data, decomp_base_log, decomp_level_count, output_glwe_size, output_polynomial_size,
+ * ciphertext_modulus } (entities/lwe_packing_keyswitch_key.rs) and GlweCiphertext<Vec<u64>> { data, polynomial_size,
+ * ciphertext_modulus } (glwe_ciphertext.rs:286-293); a GLWE list is a bincode Vec of them (u64 length first).  Readers
+ * check every dimension against the parameter set and the container lengths against them, refuse more than max_glwes
+ * ciphertexts and never read past in_len.  Parity unpinned, as above. */
+int fhe_wire_write_packing_key(const fhe_params_t *p, const fhe_packing_params_t *pp, const uint64_t *pksk, uint8_t *out,
+                               size_t out_cap, size_t *written);
+/* pksk may be NULL to read the decomposition only (then size the buffer with fhe_packing_key_len and call again) */
+int fhe_wire_read_packing_key(const fhe_params_t *p, const uint8_t *in, size_t in_len, fhe_packing_params_t *pp,
+                              uint64_t *pksk, size_t pksk_cap_words, size_t *consumed);
+int fhe_wire_write_glwe_ciphertext(const fhe_params_t *p, const uint64_t *glwe, uint8_t *out, size_t out_cap, size_t *written);
+int fhe_wire_read_glwe_ciphertext(const fhe_params_t *p, const uint8_t *in, size_t in_len, uint64_t *glwe, size_t *consumed);
+int fhe_wire_write_glwe_list(const fhe_params_t *p, const uint64_t *glwes, uint32_t n_glwes, uint8_t *out, size_t out_cap,
+                             size_t *written);
+int fhe_wire_read_glwe_list(const fhe_params_t *p, const uint8_t *in, size_t in_len, uint64_t *glwes, uint32_t max_glwes,
+                            uint32_t *n_glwes, size_t *consumed);
 
 #ifdef __cplusplus
 }
