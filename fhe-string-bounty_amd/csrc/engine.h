@@ -52,6 +52,7 @@ struct EngineEnv {
     int cluster_mode = -2;            // FHESTR_CLUSTER              fhe_engine_set_cluster_mode at creation (-1 .. 2)
     int cluster_spin_limit = -1;      // FHESTR_CLUSTER_SPIN_LIMIT   polls before a hand-over wait gives up
     int multibit_combine_max = -1;    // FHESTR_MULTIBIT_COMBINE_MAX fhe_engine_set_multibit_combine_max at creation
+    int multibit_ws_cap = -1;         // FHESTR_MULTIBIT_WS_CAP      bytes of prepared GGSWs (+ rotation workspace) the two-kernel multi-bit path keeps at once
     int cluster_test_fault = -1;      // FHESTR_CLUSTER_TEST_FAULT   honoured by the -DFHESTR_TEST_HOOKS build only
     int dense_per_cu = -1;            // FHESTR_DENSE_PER_CU         LWEs per CU beyond which the dense wide kernel runs (0 = never)
     int cluster_fallback = -1;        // FHESTR_CLUSTER_FALLBACK     0: a multi-CU launch that gave up is an error, not re-run
@@ -116,7 +117,7 @@ struct Engine {
     uint64_t *d_in = nullptr, *d_small = nullptr, *d_small2 = nullptr, *d_out = nullptr, *d_pool = nullptr;
     uint32_t* d_idx = nullptr;
     uint32_t* d_slot_exp = nullptr;   // multi-bit two-kernel path: exponent of w = e^{i pi / N} each Fourier slot evaluates at
-    size_t multibit_workspace_cap = 0;   // bytes of prepared GGSWs kept at once, larger batches run in sub-batches (0 = from free memory)
+    size_t multibit_workspace_cap = 0;   // bytes of prepared GGSWs kept at once, larger batches run in sub-batches (0 = from free memory; FHESTR_MULTIBIT_WS_CAP)
     void* d_meta = nullptr;
     uint64_t* d_compact = nullptr;   // a compact ciphertext list on its way to compact_expand_kernel
     size_t cap_compact = 0;

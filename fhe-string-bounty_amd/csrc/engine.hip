@@ -316,6 +316,7 @@ EngineEnv EngineEnv::read() {
     num("FHESTR_CLUSTER", v.cluster_mode);
     num("FHESTR_CLUSTER_SPIN_LIMIT", v.cluster_spin_limit);
     num("FHESTR_MULTIBIT_COMBINE_MAX", v.multibit_combine_max);
+    num("FHESTR_MULTIBIT_WS_CAP", v.multibit_ws_cap);
     num("FHESTR_CLUSTER_TEST_FAULT", v.cluster_test_fault);
     return v;
 }
@@ -344,6 +345,8 @@ int Engine::create(const fhe_params_t& p, int device, Engine** out) {
     if (env.cluster_spin_limit >= 0) e->cluster_spin_limit = (uint32_t)std::max(64, env.cluster_spin_limit);
     if (env.cluster_mode > -2) e->cluster_mode = std::min(2, std::max(-1, env.cluster_mode));
     if (env.multibit_combine_max >= 0) e->multibit_combine_max = (uint32_t)std::min(1024, env.multibit_combine_max);
+    // in bytes (an int: up to 2 GB, enough to split the toy shapes of the tests); 0 or unset: the automatic cap from free memory
+    if (env.multibit_ws_cap > 0) e->multibit_workspace_cap = (size_t)env.multibit_ws_cap;
 #ifdef FHESTR_TEST_HOOKS      // fault injection exists only in the test build (make testhooks), never in the product library
     if (env.cluster_test_fault >= 0) e->cluster_test_fault = (uint32_t)env.cluster_test_fault;
 #endif

@@ -56,6 +56,9 @@ N2048_TWIN = O.Params(24, 1, 2048, 23, 1, 3, 5, 4, 4, 1e-13, 1e-17, "TOY_N2048_K
 STRUCTURED_SHAPES = [O.TOY_K1, O.TOY_K2, N2048_TWIN] + O.TOY_SHAPES
 MULTI_BIT_TOYS = [(O.TOY_MULTI_BIT_N256, 2), (O.TOY_MULTI_BIT_N256_G3, 3), (O.TOY_MULTI_BIT_N128_K2, 2),
                   (O.TOY_MULTI_BIT_N512_K3_G3, 3)]
+# the real n of tests/test_gpu_exact_multibit.py: hundreds of groups, each one more rounding of the whole accumulator
+MULTI_BIT_REAL_N = [(O.PARAM_MULTI_BIT_MESSAGE_2_CARRY_2_GROUP_2_KS_PBS, 2), (O.PARAM_MULTI_BIT_MESSAGE_2_CARRY_2_GROUP_3_KS_PBS, 3),
+                    (O.PARAM_MULTI_BIT_MESSAGE_1_CARRY_1_GROUP_3_KS_PBS, 3)]
 
 
 @pytest.mark.parametrize("params", STRUCTURED_SHAPES, ids=lambda p: p.name)
@@ -121,7 +124,7 @@ def test_numpy_multi_bit_pbs_equals_the_oracles_exact_path(params, G):
     assert np.array_equal(multi_bit_pbs_exact_batch(params, G, limb_terms(sk.bsk.reshape(shape)), cts, luts, idx), want)
 
 
-@pytest.mark.parametrize("params,G", MULTI_BIT_TOYS + [(O.TOY_MULTI_BIT_N2048_G3, 3), (O.TOY_MULTI_BIT_N8192, 2)],
+@pytest.mark.parametrize("params,G", MULTI_BIT_TOYS + [(O.TOY_MULTI_BIT_N2048_G3, 3), (O.TOY_MULTI_BIT_N8192, 2)] + MULTI_BIT_REAL_N,
                          ids=lambda x: getattr(x, "name", f"G{x}"))
 def test_oracle_f64_multi_bit_pbs_is_bit_exact_under_structured_keys(params, G):
     rng = np.random.default_rng(G * 1000 + params.N)

@@ -251,14 +251,15 @@ def test_two_operand_entry_points(p):
 
 # ---- many instances in one pass -------------------------------------------------------------------------------------------
 
-def _crossing_count(plan):
-    """Smallest instance count for which jobs x instances of the plan's widest level exceeds the device's compute units
-    (256 on an MI355X): choose_rotate_path (csrc/engine.hip) then takes the variant that shares a CU between two LWEs.
-    The count follows the device, so the case cannot go stale against that threshold."""
+def _crossing_count(plan, limit=None):
+    """Smallest instance count for which jobs x instances of the plan's widest level exceeds `limit`; by default the
+    device's compute units (256 on an MI355X): choose_rotate_path (csrc/engine.hip) then takes the variant that shares a
+    CU between two LWEs.  The count follows the device, so the case cannot go stale against that threshold."""
     import torch
     cus = torch.cuda.get_device_properties(0).multi_processor_count
+    limit = cus if limit is None else limit
     widest = max(plan.level_info(l)["jobs"] for l in range(plan.info()["n_levels"]))
-    return cus // widest + 1, widest, cus
+    return limit // widest + 1, widest, limit
 
 
 @pytest.mark.parametrize("p,op", [(N2048, "eq"), (N2048, "find"), (O.TOY_K1, "contains")], ids=["N2048-eq", "N2048-find", "TOY_K1-contains"])
@@ -280,6 +281,21 @@ def test_run_batch(p, op):
             _assert_outputs(plan.run_batch(inputs[:count]), want[:count], f"{op}, batch of {count}")
         # another window of the same rows: instance 0 of this call is not instance 0 of the last one
         _assert_outputs(plan.run_batch(inputs[5:8]), want[5:8], f"{op}, batch of 3 from instance 5")
+
+
+def test_run_batch_multi_bit_fused_kernel():
+    """Multi-bit, grouping 2: the widest level at the last instance count that still fits multibit_combine_max = 64 rows (the
+    combined prepass, as in test_plan_run_other_shapes) and at the first one beyond it, where choose_rotate_path takes the
+    fused kernel; narrower levels of the same pass stay in the prepass."""
+    with _rig(MB_G2, 2) as rig:
+        plan = rig.string_op("find", 3, 2)
+        cross, widest, limit = _crossing_count(plan, 64)
+        assert limit == 64 and widest * (cross - 1) <= 64 < widest * cross
+        assert min(plan.level_info(l)["jobs"] for l in range(plan.info()["n_levels"])) * cross <= 64
+        inputs = rig.cts(cross, plan.info()["n_inputs"])
+        want = rig.exact_outputs(plan, inputs)
+        for count in (cross - 1, cross) if cross > 1 else (cross,):
+            _assert_outputs(plan.run_batch(inputs[:count]), want[:count], f"find, multi-bit, batch of {count}")
 
 
 @pytest.mark.parametrize("p", [N2048, O.TOY_K1], ids=lambda p: p.name)

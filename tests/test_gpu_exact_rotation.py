@@ -5,7 +5,10 @@ every value of a correct f64 PBS lies on the engine's from_torus grid with a wid
 that premise on the CPU oracle), so the whole output ciphertext -- mask and body -- must equal the exact integer PBS bit
 for bit.  A transform that lost precision, a wrong twiddle, a swapped GGSW block, level or sign shows as a mismatch.
 Each path is reached through the public setters and batch sizes only (choose_rotate_path in csrc/engine.hip is
-the map; an MI355X has 256 CUs).
+the map; an MI355X has 256 CUs).  Multi-bit here runs B = 5 on every shape; its batch regimes -- the combined prepass's chunks
+of 8 up to multibit_combine_max = 64, the fused kernel from 65 on and beyond the CU count, the two-kernel path's sub-batch
+loop (reached through the environment switch FHESTR_MULTIBIT_WS_CAP, bytes, read when an engine is created) and real n --
+are in tests/test_gpu_exact_multibit.py, on this file's rig.
 
 Tier 2, full scale: uniformly random keys and LWEs with exactly one non-zero mask element (one CMUX, no decomposition
 digit can differ): the engine's per-coefficient error against exact must have the spread of the oracle's f64 path."""
