@@ -223,6 +223,30 @@ int fhe_engine_packing_info(fhe_engine* eng, uint32_t info[5]) {
     API_END
 }
 
+int fhe_engine_unpack_glwes(fhe_engine* eng, const uint64_t* glwes_host, uint32_t first, uint32_t count, int refresh, uint64_t* cts_host) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    if (count) { CHECK_PTR(glwes_host); CHECK_PTR(cts_host); }
+    return eng->impl->unpack_glwes_host(glwes_host, first, count, refresh, cts_host);
+    API_END
+}
+
+int fhe_engine_unpack_glwes_dev(fhe_engine* eng, const uint64_t* d_glwes, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    if (count) { CHECK_PTR(d_glwes); CHECK_PTR(d_cts); }
+    return eng->impl->unpack_glwes_dev(d_glwes, first, count, refresh, d_cts);
+    API_END
+}
+
+int fhe_engine_unpack_info(fhe_engine* eng, uint32_t info[4]) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(info);
+    for (int q = 0; q < 4; q++) info[q] = eng->impl->unpack_last[q];
+    return 0;
+    API_END
+}
+
 int fhe_engine_cluster_fallbacks(fhe_engine* eng, uint32_t* count) {
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(count);

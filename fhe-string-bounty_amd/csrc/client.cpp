@@ -207,6 +207,34 @@ static bool packing_meets_bound(const fhe_params_t& p, const fhe_packing_params_
     return packed.log2_pfail(1.0) <= target;
 }
 
+// A packed PBS output extracted again (glwe_extract_kernels.hip.h moves words, it adds nothing): the PBS output's one
+// nominal variance plus the packing keyswitch's, in units of V_pbs -- what a plan would have to declare for such an input.
+// out[1]: the budget a plan enforces at its PBS inputs, which the refreshing PBS of fhe_engine_unpack_glwes must meet.
+void packing_unpack_noise(const fhe_params_t& p, const fhe_packing_params_t& pp, double out[2]) {
+    out[0] = 1.0 + packing_variance(p, pp) / noise_model(p).v_pbs;
+    out[1] = default_noise_budget(p);
+}
+
+// glwe_sample_extraction.rs:91-147 at coefficient c: the mask of polynomial q reversed from c downwards, the wrapped part
+// negated; the body is B[c]
+static void glwe_sample_extract_host(const fhe_params_t& p, const uint64_t* glwes, uint32_t first, uint32_t count, uint64_t* cts) {
+    const uint32_t N = p.N, k = p.k;
+    const size_t glwe_len = (size_t)(k + 1) * N, big = (size_t)k * N + 1;
+    for (uint32_t r = 0; r < count; r++) {
+        const uint64_t block = (uint64_t)first + r;
+        const uint32_t c = (uint32_t)(block % N);
+        const uint64_t* glwe = glwes + (size_t)(block / N) * glwe_len;
+        uint64_t* ct = cts + (size_t)r * big;
+        for (uint32_t q = 0; q < k; q++) {
+            const uint64_t* a = glwe + (size_t)q * N;
+            uint64_t* o = ct + (size_t)q * N;
+            for (uint32_t i = 0; i <= c; i++) o[i] = a[c - i];
+            for (uint32_t i = c + 1; i < N; i++) o[i] = 0 - a[N + c - i];
+        }
+        ct[(size_t)k * N] = glwe[(size_t)k * N + c];
+    }
+}
+
 static inline void packing_decompose(uint64_t x, uint32_t bl, uint32_t L, int64_t* digits) {   // level L first (iter.rs:101-127)
     const uint32_t rep = bl * L;
     const uint64_t mask = (1ull << bl) - 1;
@@ -414,6 +442,25 @@ int fhe_packing_keyswitch_host(const fhe_params_t* params, const fhe_packing_par
     } catch (const std::exception& e) {
         return fhe::fail(e.what());
     }
+    return 0;
+}
+
+int fhe_glwe_sample_extract_host(const fhe_params_t* params, const uint64_t* glwes, uint32_t first, uint32_t count, uint64_t* cts) {
+    if (!params || (count && (!glwes || !cts))) return fhe::fail("null pointer");
+    if (params->k < 1 || params->N < 1) return fhe::fail("glwe sample extraction: k >= 1 and N >= 1");
+    try {
+        fhe::glwe_sample_extract_host(*params, glwes, first, count, cts);
+    } catch (const std::exception& e) {
+        return fhe::fail(e.what());
+    }
+    return 0;
+}
+
+int fhe_packing_unpack_noise(const fhe_params_t* params, const fhe_packing_params_t* pp, double out[2]) {
+    if (!params || !pp || !out) return fhe::fail("null pointer");
+    out[0] = out[1] = 0;
+    if (fhe::packing_params_check(*params, *pp)) return 1;
+    fhe::packing_unpack_noise(*params, *pp, out);
     return 0;
 }
 

@@ -145,6 +145,12 @@ struct Engine {
     uint64_t *d_pack_in = nullptr, *d_pack_out = nullptr;   // staging of fhe_engine_pack_lwes (host ciphertexts)
     size_t cap_pack_in = 0, cap_pack_out = 0;
     uint32_t pack_last[5] = {0, 0, 0, 0, 0};   // fhe_engine_packing_info: ran, MT, K chunks, K steps per chunk, K steps
+    // packed inputs (glwe_extract_kernels.hip.h): staging of fhe_engine_unpack_glwes, the refresh's table indices
+    uint64_t *d_unpack_in = nullptr, *d_unpack_out = nullptr;
+    size_t cap_unpack_in = 0, cap_unpack_out = 0;
+    uint32_t* d_unpack_idx = nullptr;          // the identity table's id, once per block of the largest refresh so far
+    size_t cap_unpack_idx = 0;
+    uint32_t unpack_last[4] = {0, 0, 0, 0};    // fhe_engine_unpack_info: ran, rows, workgroups, refreshed
     int xcd_per_cu = -1;             // workgroups of the whole-XCD kernel a CU holds (occupancy query, cached)
     uint32_t xcd_auto_max = 16;     // automatic mode: batches up to this size take the whole-XCD kernel (two LWEs per XCD in flight)
     uint32_t cluster_spin_limit = 1u << 22;   // polls before a hand-over wait gives up (FHESTR_CLUSTER_SPIN_LIMIT)
@@ -184,6 +190,8 @@ struct Engine {
     int load_packing_key(const fhe_packing_params_t& pp, const uint64_t* pksk);
     int pack_lwes_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_glwes);
     int pack_lwes_host(const uint64_t* cts, uint32_t count, uint64_t* glwes);
+    int unpack_glwes_dev(const uint64_t* d_glwes, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts);
+    int unpack_glwes_host(const uint64_t* glwes, uint32_t first, uint32_t count, int refresh, uint64_t* cts);
     void keyswitch_info(uint32_t info[6]) const;   // ks_last and the register count shadow_keyswitch_fits judges by; changes nothing
     int ks_pbs_dev(const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint64_t* d_big_out, uint32_t count, bool allow_pipeline = false);
     int ks_pbs_host(const uint64_t* in, const uint32_t* lut_idx, uint64_t* out, uint32_t count);
@@ -213,6 +221,8 @@ int compact_pk_generate(const fhe_params_t& p, const uint64_t* big_sk, const See
 int params_supported(const fhe_params_t& p);   // 0, or 1 with the reason in fhe_last_error (no device needed)
 // client.cpp: the same answer for a packing keyswitch decomposition on a parameter set
 int packing_params_check(const fhe_params_t& p, const fhe_packing_params_t& pp);
+// client.cpp: out[0] variance of a raw extracted block of a packed PBS output in nominal units, out[1] the PBS-input budget
+void packing_unpack_noise(const fhe_params_t& p, const fhe_packing_params_t& pp, double out[2]);
 
 }  // namespace fhe
 

@@ -19,6 +19,7 @@
 #include "lwe_kernels.hip.h"
 #include "ks_mfma_kernels.hip.h"
 #include "packing_ks_kernels.hip.h"
+#include "glwe_extract_kernels.hip.h"
 #include "pbs_kernels.hip.h"
 #include "pbs_dense_kernels.hip.h"
 #include "pbs_large_kernels.hip.h"
@@ -367,6 +368,7 @@ Engine::~Engine() {
     rel(d_ksk_packed); rel(d_ksk_rowsum); rel(d_fbsk); rel(d_fbsk_dense); rel(d_luts); rel(d_in); rel(d_small); rel(d_small2); rel(d_out); rel(d_idx);
     rel(d_pool); rel(d_meta); rel(d_ws); rel(d_slot_exp); rel(d_cluster_ws); rel(d_cluster_ctl); rel(d_ksk_mfma); rel(d_ks_digits); rel(d_compact);
     rel(d_pksk_mfma); rel(d_pack_digits); rel(d_pack_in); rel(d_pack_out);
+    rel(d_unpack_in); rel(d_unpack_out); rel(d_unpack_idx);
     for (int q = 0; q < OVL_MAX; q++) { rel(ovl_digits[q]); rel(ovl_small[q]); if (ovl_done[q]) (void)hipEventDestroy(ovl_done[q]); if (q >= 2 && ovl_stream[q]) (void)hipStreamDestroy(ovl_stream[q]); }
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : ring) if (e) (void)hipEventDestroy(e);
@@ -926,6 +928,70 @@ int Engine::pack_lwes_host(const uint64_t* cts, uint32_t count, uint64_t* glwes)
     HIP_TRY(hipMemcpyAsync(glwes, d_pack_out, out_words * 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
+}
+
+// ---- packed inputs (glwe_extract_kernels.hip.h) -----------------------------------------------------------------------
+// Blocks first .. first + count - 1 of the packed GLWEs at d_glwes (block j = coefficient j % N of GLWE j / N, the layout
+// pack_lwes_dev writes) -> count big-key LWEs at d_cts.  Ordered on the engine's stream, nothing synchronises -- except,
+// like pack_lwes_dev, in the throughput modes, and once per engine when the first refresh uploads the identity table.
+// refresh: the extracted blocks carry the packing keyswitch's noise on top of a PBS output's, a plan's inputs are declared
+// nominal (circuit.cpp: noise = 1.0); one ks_pbs level with the identity table over the whole message-and-carry space
+// brings them back, in place.  Refused where the model puts a raw block above the PBS-input budget.
+int Engine::unpack_glwes_dev(const uint64_t* d_glwes, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts) {
+    if (use()) return 1;
+    if (count == 0) return 0;
+    const uint32_t kN = p.k * p.N;
+    if (p.N < 2 || (p.N & (p.N - 1))) return fail("unpack_glwes: polynomial size must be a power of two");
+    if (refresh) {
+        if (!d_pksk_mfma) return fail("unpack_glwes: the refresh needs the loaded packing key's decomposition to judge the blocks' noise; none is loaded");
+        double v[2];
+        packing_unpack_noise(p, pack_pp, v);
+        if (!(v[0] <= v[1]))
+            return fail("unpack_glwes: refresh refused, a raw extracted block carries " + std::to_string(v[0]) +
+                        " nominal variances, the PBS-input budget is " + std::to_string(v[1]));
+    }
+    if (pipeline) {                                         // pipelined calls may still read or write these buffers on other streams
+        if (sync_all_streams()) return 1;
+        end_pipeline_run();
+    }
+    const uint32_t chunks = (kN / 2 + GLWE_EXTRACT_PAIRS_PER_WG - 1) / GLWE_EXTRACT_PAIRS_PER_WG;
+    if ((uint64_t)count * chunks > 0x7FFFFFFFull) return fail("unpack_glwes: too many ciphertexts for one launch");
+    hipLaunchKernelGGL(glwe_sample_extract_kernel, dim3(count * chunks), dim3(256), 0, stream, d_glwes, d_cts, p.N, kN, first, count, chunks);
+    unpack_last[0] = 1; unpack_last[1] = count; unpack_last[2] = count * chunks; unpack_last[3] = 0;
+    HIP_TRY(hipGetLastError());
+    if (!refresh) return 0;
+    const uint32_t M = p.msg_mod * p.carry_mod;
+    std::vector<uint64_t> table(M), acc;
+    for (uint32_t x = 0; x < M; x++) table[x] = x;
+    fill_accumulator(table.data(), acc);
+    uint32_t id = 0;
+    if (lut_upload_dedup(acc, &id)) return 1;
+    if ((size_t)count * 4 > cap_unpack_idx) {
+        if (d_unpack_idx && sync_all_streams()) return 1;   // an earlier refresh may still read the smaller array
+        if (ensure((void**)&d_unpack_idx, &cap_unpack_idx, (size_t)count * 4)) return 1;
+    }
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_unpack_idx, (int)id, count, stream));
+    if (ks_pbs_dev(d_cts, d_unpack_idx, d_cts, count)) return 1;   // the keyswitch has read every row before the rotation writes one
+    unpack_last[3] = 1;
+    return 0;
+}
+
+int Engine::unpack_glwes_host(const uint64_t* glwes, uint32_t first, uint32_t count, int refresh, uint64_t* cts) {
+    if (use()) return 1;
+    if (count == 0) return 0;
+    const size_t big = (size_t)p.k * p.N + 1, glwe_len = (size_t)(p.k + 1) * p.N;
+    const uint64_t g_lo = first / p.N, g_hi = ((uint64_t)first + count - 1) / p.N;      // only the GLWEs the range touches go up
+    const size_t in_words = (size_t)(g_hi - g_lo + 1) * glwe_len;
+    if (cap_unpack_in < in_words * 8 || cap_unpack_out < count * big * 8) {
+        if (sync_all_streams()) return 1;
+        if (ensure((void**)&d_unpack_in, &cap_unpack_in, in_words * 8)) return 1;
+        if (ensure((void**)&d_unpack_out, &cap_unpack_out, count * big * 8)) return 1;
+    }
+    HIP_TRY(hipMemcpyAsync(d_unpack_in, glwes + (size_t)g_lo * glwe_len, in_words * 8, hipMemcpyHostToDevice, stream));
+    if (unpack_glwes_dev(d_unpack_in, first % p.N, count, refresh, d_unpack_out)) return 1;
+    HIP_TRY(hipMemcpyAsync(cts, d_unpack_out, count * big * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return refresh ? cluster_check() : 0;
 }
 
 // ---- blind-rotation dispatch: choose_rotate_path is the map, then one launch function per path ----------------------

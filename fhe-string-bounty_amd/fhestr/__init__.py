@@ -166,6 +166,8 @@ EXPORTS = [
     "fhe_client_decrypt_packed", "fhe_packing_keyswitch_host", "fhe_engine_load_packing_key", "fhe_engine_pack_lwes",
     "fhe_engine_pack_lwes_dev", "fhe_engine_packing_info", "fhe_wire_write_packing_key", "fhe_wire_read_packing_key",
     "fhe_wire_write_glwe_ciphertext", "fhe_wire_read_glwe_ciphertext", "fhe_wire_write_glwe_list", "fhe_wire_read_glwe_list",
+    "fhe_glwe_sample_extract_host", "fhe_packing_unpack_noise", "fhe_engine_unpack_glwes", "fhe_engine_unpack_glwes_dev",
+    "fhe_engine_unpack_info",
 ] + [f"fhe_str_{n}{s}" for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat")
      for s in ("", "_clear")] + ["fhe_str_repeat_clear"]
 
@@ -316,6 +318,11 @@ def lib() -> C.CDLL:
     sig("fhe_engine_pack_lwes", vp, vp, u32, vp)
     sig("fhe_engine_pack_lwes_dev", vp, vp, u32, vp)
     sig("fhe_engine_packing_info", vp, C.POINTER(u32))
+    sig("fhe_glwe_sample_extract_host", PP, vp, u32, u32, vp)
+    sig("fhe_packing_unpack_noise", PP, KP, C.POINTER(C.c_double))
+    sig("fhe_engine_unpack_glwes", vp, vp, u32, u32, i32, vp)
+    sig("fhe_engine_unpack_glwes_dev", vp, vp, u32, u32, i32, vp)
+    sig("fhe_engine_unpack_info", vp, C.POINTER(u32))
     for name in ("fhe_params_ksk_len", "fhe_params_bsk_len"):
         getattr(L, name).restype = C.c_size_t
         getattr(L, name).argtypes = [PP]
@@ -638,6 +645,54 @@ class Engine:
         return {"ran": bool(ran), "tile": tile, "chunks": chunks, "steps_per_chunk": spc, "steps": steps,
                 "last_chunk": steps - (chunks - 1) * spc if ran else 0}
 
+    def unpack(self, glwes=None, count: int | None = None, first: int = 0, refresh: bool = True, d_in: int | None = None,
+               d_out: int | None = None):
+        """Packed results back into big-key LWEs on the GPU (csrc/glwe_extract_kernels.hip.h): blocks first .. first +
+        count - 1 of the GLWEs (block j = coefficient j % N of GLWE j // N, what Engine.pack returns) -> (count, kN+1).
+        refresh=True sends them through one keyswitch + PBS with the identity table, after which they carry nominal noise
+        and are valid inputs of every plan (needs the server keys and a loaded packing key, whose decomposition decides
+        whether the refresh is admissible: packing_unpack_noise); refresh=False returns the raw extracted words.
+        glwes: a host array, or a torch device tensor / d_in: the GLWEs where they lie.  With d_out (a device pointer to
+        count x big_size words, 8-byte aligned: what Plan.run_dev reads) the call only enqueues on the engine's stream
+        and returns nothing.  The GLWEs must hold block first + count - 1."""
+        p = self.params
+        if glwes is not None and hasattr(glwes, "data_ptr"):
+            keep, d_in = glwes, glwes.data_ptr()
+        if count is None:
+            count = getattr(glwes, "count", None)
+        if count is None:
+            raise FheError("unpack: a block count is required")
+        if d_in:
+            if d_out:
+                _check(lib().fhe_engine_unpack_glwes_dev(self._h, C.c_void_p(d_in), first, count, int(bool(refresh)), C.c_void_p(d_out)))
+                return None
+            import torch
+            out = torch.empty((count, p.big_size), dtype=torch.int64, device=f"cuda:{self.device}")
+            torch.cuda.synchronize()
+            _check(lib().fhe_engine_unpack_glwes_dev(self._h, C.c_void_p(d_in), first, count, int(bool(refresh)), C.c_void_p(out.data_ptr())))
+            self.synchronize()
+            return out.cpu().numpy().view(np.uint64)
+        glwes = _u64(glwes).reshape(-1)
+        if glwes.size < packed_glwe_len(p, first + count) or glwes.size % ((p.k + 1) * p.N):
+            raise FheError(f"unpack: {glwes.size} words do not hold packed block {first + count - 1} of this parameter set")
+        if d_out:
+            import torch
+            d_glwes = torch.from_numpy(glwes.view(np.int64)).to(f"cuda:{self.device}")
+            torch.cuda.synchronize()
+            _check(lib().fhe_engine_unpack_glwes_dev(self._h, C.c_void_p(d_glwes.data_ptr()), first, count, int(bool(refresh)), C.c_void_p(d_out)))
+            self.synchronize()                              # d_glwes is released on return
+            return None
+        out = np.zeros((count, p.big_size), dtype=np.uint64)
+        _check(lib().fhe_engine_unpack_glwes(self._h, _ptr(glwes), first, count, int(bool(refresh)), _ptr(out)))
+        return out
+
+    def unpack_info(self) -> dict:
+        """What the last unpack launched (fhe_engine_unpack_info), recorded when it was enqueued."""
+        a = (C.c_uint32 * 4)()
+        _check(lib().fhe_engine_unpack_info(self._h, a))
+        ran, rows, workgroups, refreshed = (int(x) for x in a)
+        return {"ran": bool(ran), "rows": rows, "workgroups": workgroups, "refreshed": bool(refreshed)}
+
     def keyswitch(self, cts) -> np.ndarray:
         p = self.params
         cts = _u64(cts).reshape(-1, p.big_size)
@@ -834,6 +889,42 @@ def packing_keyswitch_host(params: Params, pp, pksk, cts) -> np.ndarray:
     out = np.zeros((-(-cts.shape[0] // params.N), params.k + 1, params.N), dtype=np.uint64)
     _check(lib().fhe_packing_keyswitch_host(C.byref(params.c()), C.byref(_pp(pp)), _ptr(pksk), _ptr(cts), cts.shape[0], _ptr(out)))
     return out
+
+
+def glwe_sample_extract_host(params: Params, glwes, count: int, first: int = 0) -> np.ndarray:
+    """Sample extraction as a plain CPU loop (fhe_glwe_sample_extract_host): blocks first .. first + count - 1 of packed
+    GLWEs -> (count, kN+1) big-key LWEs.  Bit-identical to Engine.unpack(..., refresh=False)."""
+    glwes = _u64(glwes).reshape(-1)
+    glwe_len = (params.k + 1) * params.N
+    if glwes.size % glwe_len or (first + count + params.N - 1) // params.N * glwe_len > glwes.size:
+        raise FheError(f"glwe_sample_extract_host: {glwes.size} words do not hold packed block {first + count - 1} of this parameter set")
+    out = np.zeros((count, params.big_size), dtype=np.uint64)
+    _check(lib().fhe_glwe_sample_extract_host(C.byref(params.c()), _ptr(glwes), first, count, _ptr(out)))
+    return out
+
+
+def packing_unpack_noise(params: Params, pp) -> tuple:
+    """(variance of a raw block extracted from a packed PBS output, in nominal units; the default PBS-input budget):
+    fhe_packing_unpack_noise.  Engine.unpack(refresh=True) is refused where the first exceeds the second."""
+    a = (C.c_double * 2)()
+    _check(lib().fhe_packing_unpack_noise(C.byref(params.c()), C.byref(_pp(pp)), a))
+    return float(a[0]), float(a[1])
+
+
+class PackedString(np.ndarray):
+    """Packed results as a value that goes back in: the GLWE words (n_glwe, k+1, N) as Engine.pack returns them -- it IS
+    that array, ClientKey.decrypt_packed and the wire writers take it unchanged -- with `count`, the blocks it holds
+    (block j at coefficient j % N of GLWE j // N), and `capacity`, count // blocks per character.  Every FheStringOps
+    method accepts it in place of an expanded operand.  Views (x[0]) keep both attributes."""
+
+    def __new__(cls, glwes, count: int, capacity: int):
+        obj = _u64(glwes).view(cls)
+        obj.count, obj.capacity = int(count), int(capacity)
+        return obj
+
+    def __array_finalize__(self, obj):
+        self.count = getattr(obj, "count", 0)
+        self.capacity = getattr(obj, "capacity", 0)
 
 
 def compact_pk_len(params: Params) -> int:
@@ -1130,39 +1221,77 @@ class FheStringOps:
             plan.close()
         self._plans.clear()
 
-    def _packed(self, op, a_cap, b_cap, clear, operands):
-        """packed=True on any method: the operation's plan runs on device buffers, its output goes through the packing
-        keyswitch where it lies (Engine.load_packing_key first) and only the GLWEs come back: (n_glwe, k+1, N), output block
-        j at coefficient j % N of GLWE j // N; decrypt with ClientKey.decrypt_packed.  The result LWEs never cross PCIe.
-        Plans are kept per (operation, capacities, clear pattern)."""
-        import torch
-        big = self.engine.params.big_size
+    def _plan(self, op, a_cap, b_cap, clear):
         key = (op, a_cap, b_cap, bytes(clear) if clear is not None else None)
         plan = self._plans.get(key)
         if plan is None:
             plan = self._plans[key] = Plan.string_op(self.engine, op, a_cap, b_cap, bytes(clear) if clear is not None else None)
-        info = plan.info()
-        inputs = np.concatenate([_u64(x).reshape(-1, big) for x in operands])
-        if inputs.shape[0] != info["n_inputs"]:
-            raise FheError(f"{op}: the plan takes {info['n_inputs']} input blocks, got {inputs.shape[0]}")
+        return plan
+
+    def _stage(self, d_in, placed):
+        """Fill the plan's device input buffer d_in (rows of big_size words).  placed: (first row, operand) pairs; an
+        expanded operand is uploaded as it is, a PackedString goes up as GLWEs and is unpacked -- extracted and refreshed
+        -- into its rows on the device (Engine.unpack): its expanded form never crosses PCIe."""
+        import torch
         dev = f"cuda:{self.engine.device}"
-        d_in = torch.from_numpy(inputs.view(np.int64)).to(dev)
-        d_out = torch.empty((info["n_outputs"], big), dtype=torch.int64, device=dev)
+        flat = d_in.view(-1, self.engine.params.big_size)
+        todo = []
+        for row, x in placed:
+            if isinstance(x, PackedString):
+                todo.append((row, x.count, torch.from_numpy(np.ascontiguousarray(x).view(np.int64).reshape(-1)).to(dev)))
+            else:
+                flat[row:row + x.shape[0]].copy_(torch.from_numpy(x.view(np.int64)))
         torch.cuda.synchronize()                            # torch's stream is not ordered with the engine's
+        for row, count, d_glwes in todo:
+            self.engine.unpack(d_in=d_glwes.data_ptr(), count=count, refresh=True, d_out=flat[row].data_ptr())
+        return todo                                         # keeps the GLWEs alive until the caller has synchronised
+
+    def _finish(self, d_out, n_blocks, packed):
+        if packed:
+            out = self.engine.pack(d_out, count=n_blocks)   # synchronises
+            return PackedString(out, n_blocks, n_blocks // self.bpc)
+        self.engine.synchronize()
+        return d_out.cpu().numpy().view(np.uint64)
+
+    def _packed(self, op, a_cap, b_cap, clear, operands, packed=True):
+        """The device route, taken with packed=True and whenever an operand is a PackedString: the operation's plan runs
+        on device buffers.  Packed operands are unpacked into the plan's input buffer there (_stage).  packed=True: the
+        output goes through the packing keyswitch where it lies (Engine.load_packing_key first) and only the GLWEs come
+        back, as a PackedString: (n_glwe, k+1, N), output block j at coefficient j % N of GLWE j // N; decrypt with
+        ClientKey.decrypt_packed, or pass it to the next operation.  Otherwise the output LWEs are downloaded.
+        Plans are kept per (operation, capacities, clear pattern)."""
+        import torch
+        big = self.engine.params.big_size
+        plan = self._plan(op, a_cap, b_cap, clear)
+        info = plan.info()
+        sizes = [x.count if isinstance(x, PackedString) else x.shape[0] for x in operands]
+        if sum(sizes) != info["n_inputs"]:
+            raise FheError(f"{op}: the plan takes {info['n_inputs']} input blocks, got {sum(sizes)}")
+        dev = f"cuda:{self.engine.device}"
+        d_in = torch.empty((info["n_inputs"], big), dtype=torch.int64, device=dev)
+        d_out = torch.empty((info["n_outputs"], big), dtype=torch.int64, device=dev)
+        keep = self._stage(d_in, list(zip(np.cumsum([0] + sizes[:-1]).tolist(), operands)))
         plan.run_dev(d_in.data_ptr(), d_out.data_ptr())
-        return self.engine.pack(d_out, count=info["n_outputs"])
+        return self._finish(d_out, info["n_outputs"], packed)
 
     def _cap(self, ct):
+        if isinstance(ct, PackedString):
+            return ct, ct.count // self.bpc
         ct = _u64(ct).reshape(-1, self.engine.params.big_size)
         return ct, ct.shape[0] // self.bpc
 
+    @staticmethod
+    def _dev(packed, *operands):
+        """Does this call take the device route?  (packed output asked for, or a packed operand given)"""
+        return bool(packed) or any(isinstance(x, PackedString) for x in operands)
+
     def _binary(self, op, a, b, packed=False):
         a, a_cap = self._cap(a)
-        if packed:
+        if self._dev(packed, a, b):
             if isinstance(b, (bytes, bytearray)):
-                return self._packed(op + "_clear", a_cap, 0, b, [a])
+                return self._packed(op + "_clear", a_cap, 0, b, [a], packed)
             b, b_cap = self._cap(b)
-            return self._packed(op, a_cap, b_cap, None, [a, b])
+            return self._packed(op, a_cap, b_cap, None, [a, b], packed)
         n_dig = 0
         while (self.engine.params.msg_mod ** n_dig) < a_cap + 1:
             n_dig += 1
@@ -1177,19 +1306,27 @@ class FheStringOps:
         return out
 
     def op_many(self, op, rows, b=None, packed=False):
-        """`op` on every row against ONE second operand in a single pass (fhe_str_op_many): rows (count, cap*blocks, kN+1);
-        b: an encrypted (zero padded) string, clear bytes, or None for unary operations.  Returns (count, n_outputs, kN+1)."""
+        """`op` on every row against ONE second operand in a single pass (fhe_str_op_many): rows (count, cap*blocks, kN+1),
+        or a sequence of PackedString of one capacity (one per row); b: an encrypted (zero padded) string -- expanded or a
+        PackedString --, clear bytes, or None for unary operations.  Returns (count, n_outputs, kN+1); with packed=True
+        one PackedString, output o of row r at block r * n_outputs + o."""
         big = self.engine.params.big_size
+        clear = b if isinstance(b, (bytes, bytearray)) else None
+        enc = None if (b is None or clear is not None) else self._cap(b)
+        name = op + ("_clear" if clear is not None else "")
+        if isinstance(rows, (list, tuple)) and any(isinstance(r, PackedString) for r in rows):
+            rows = [self._cap(r)[0] for r in rows]
+            sizes = {r.count if isinstance(r, PackedString) else r.shape[0] for r in rows}
+            if len(sizes) != 1:
+                raise FheError("op_many expects rows of one capacity")
+            return self._packed_many(name, rows, sizes.pop() // self.bpc, enc, clear, packed)
         rows = _u64(rows)
         if rows.ndim != 3 or rows.shape[2] != big:
             raise FheError(f"op_many expects rows of shape (count, cap*blocks, {big})")
         count, a_cap = rows.shape[0], rows.shape[1] // self.bpc
-        clear = b if isinstance(b, (bytes, bytearray)) else None
-        enc = None if (b is None or clear is not None) else self._cap(b)
-        name = op + ("_clear" if clear is not None else "")
-        if packed:
+        if self._dev(packed, enc[0] if enc else None):
             # every row's outputs after one another: output o of row r is packed block r * n_outputs + o
-            return self._packed_many(name, rows, a_cap, enc, clear)
+            return self._packed_many(name, list(rows), a_cap, enc, clear, packed)
         buf = (C.c_uint8 * max(1, len(clear)))(*clear) if clear is not None else None
         args = (self.engine.handle, name.encode(), _ptr(rows), a_cap, count, _ptr(enc[0]) if enc else None, enc[1] if enc else 0,
                 buf, len(clear) if clear is not None else 0)
@@ -1199,25 +1336,32 @@ class FheStringOps:
         _check(lib().fhe_str_op_many(*args, _ptr(out), C.byref(n_out)))
         return out
 
-    def _packed_many(self, name, rows, a_cap, enc, clear):
+    def _packed_many(self, name, rows, a_cap, enc, clear, packed=True):
+        """The device route of op_many (see _packed): rows is a list of expanded (cap*blocks, kN+1) arrays or PackedStrings."""
         import torch
         big = self.engine.params.big_size
-        key = (name, a_cap, enc[1] if enc else 0, bytes(clear) if clear is not None else None)
-        plan = self._plans.get(key)
-        if plan is None:
-            plan = self._plans[key] = Plan.string_op(self.engine, name, a_cap, enc[1] if enc else 0, bytes(clear) if clear is not None else None)
+        plan = self._plan(name, a_cap, enc[1] if enc else 0, clear)
         info = plan.info()
-        count = rows.shape[0]
-        inputs = rows if not enc else np.concatenate([rows, np.broadcast_to(enc[0], (count,) + enc[0].shape)], axis=1)
-        inputs = np.ascontiguousarray(inputs)
-        if inputs.shape[1] != info["n_inputs"]:
-            raise FheError(f"{name}: the plan takes {info['n_inputs']} input blocks per row, got {inputs.shape[1]}")
+        count, n_a = len(rows), a_cap * self.bpc
+        n_b = (enc[0].count if isinstance(enc[0], PackedString) else enc[0].shape[0]) if enc else 0
+        if n_a + n_b != info["n_inputs"]:
+            raise FheError(f"{name}: the plan takes {info['n_inputs']} input blocks per row, got {n_a + n_b}")
         dev = f"cuda:{self.engine.device}"
-        d_in = torch.from_numpy(inputs.view(np.int64)).to(dev)
+        d_in = torch.empty((count, info["n_inputs"], big), dtype=torch.int64, device=dev)
         d_out = torch.empty((count, info["n_outputs"], big), dtype=torch.int64, device=dev)
-        torch.cuda.synchronize()
+        placed = [(r * info["n_inputs"], x) for r, x in enumerate(rows)]
+        if enc and isinstance(enc[0], PackedString):        # unpacked once, into row 0's slot, then copied on the device
+            placed.append((n_a, enc[0]))
+        elif enc:
+            d_in[:, n_a:].copy_(torch.from_numpy(enc[0].view(np.int64)).to(dev))
+        keep = self._stage(d_in, placed)
+        if enc and isinstance(enc[0], PackedString) and count > 1:
+            self.engine.synchronize()
+            d_in[1:, n_a:].copy_(d_in[0, n_a:])
+            torch.cuda.synchronize()
         plan.run_batch_dev(d_in.data_ptr(), d_out.data_ptr(), count)
-        return self.engine.pack(d_out, count=count * info["n_outputs"])
+        out = self._finish(d_out, count * info["n_outputs"], packed)
+        return out if packed else out.reshape(count, info["n_outputs"], big)
 
     def eq_many(self, rows, b): return self.op_many("eq", rows, b)[:, 0]
     def ne_many(self, rows, b): return self.op_many("ne", rows, b)[:, 0]
@@ -1247,16 +1391,16 @@ class FheStringOps:
 
     def len(self, a, packed=False):
         a, a_cap = self._cap(a)
-        if packed:
-            return self._packed("len", a_cap, 0, None, [a])
+        if self._dev(packed, a):
+            return self._packed("len", a_cap, 0, None, [a], packed)
         out = self._alloc((self._n_digits(a_cap), self.engine.params.big_size))
         _check(lib().fhe_str_len(self.engine.handle, _ptr(a), a_cap, _ptr(out)))
         return out
 
     def is_empty(self, a, packed=False):
         a, a_cap = self._cap(a)
-        if packed:
-            return self._packed("is_empty", a_cap, 0, None, [a])[0]
+        if self._dev(packed, a):
+            return self._packed("is_empty", a_cap, 0, None, [a], packed)[0]
         out = self._alloc((1, self.engine.params.big_size))
         _check(lib().fhe_str_is_empty(self.engine.handle, _ptr(a), a_cap, _ptr(out)))
         return out[0]
@@ -1265,11 +1409,13 @@ class FheStringOps:
         """pat: clear bytes, or an encrypted (zero padded) pattern.  packed=True: ONE packed array, the flag at
         coefficient 0 and the string's blocks after it."""
         a, a_cap = self._cap(a)
-        if packed:
+        if self._dev(packed, a, pat):
             if isinstance(pat, (bytes, bytearray)):
-                return self._packed(op + "_clear", a_cap, 0, pat, [a])
-            pat, p_cap = self._cap(pat)
-            return self._packed(op, a_cap, p_cap, None, [a, pat])
+                out = self._packed(op + "_clear", a_cap, 0, pat, [a], packed)
+            else:
+                pat, p_cap = self._cap(pat)
+                out = self._packed(op, a_cap, p_cap, None, [a, pat], packed)
+            return out if packed else (out[0], out[1:])
         out = self._alloc((1 + a.shape[0], self.engine.params.big_size))
         if isinstance(pat, (bytes, bytearray)):
             buf = (C.c_uint8 * max(1, len(pat)))(*pat)
@@ -1284,8 +1430,8 @@ class FheStringOps:
 
     def _unary(self, op, a, packed=False):
         a, a_cap = self._cap(a)
-        if packed:
-            return self._packed(op, a_cap, 0, None, [a])
+        if self._dev(packed, a):
+            return self._packed(op, a_cap, 0, None, [a], packed)
         out = self._alloc(a.shape)
         _check(getattr(lib(), f"fhe_str_{op}")(self.engine.handle, _ptr(a), a_cap, _ptr(out)))
         return out
@@ -1302,18 +1448,18 @@ class FheStringOps:
         a, a_cap = self._cap(a)
         big = self.engine.params.big_size
         clear = isinstance(frm, (bytes, bytearray))
-        if packed:
+        if self._dev(packed, a, frm, to):
             if clear:
                 if out_cap is None and len(frm) != len(to):
                     raise FheError("replace: `from` and `to` of different lengths need an output capacity (out_cap)")
                 name = "replace_clear" if out_cap is None else f"replace_clear:{len(frm)}:{out_cap}"
-                return self._packed(name, a_cap, 0, bytes(frm) + bytes(to), [a])
+                return self._packed(name, a_cap, 0, bytes(frm) + bytes(to), [a], packed)
             frm, f_cap = self._cap(frm)
             to, t_cap = self._cap(to)
             if out_cap is None and f_cap != t_cap:
                 raise FheError("replace: `from` and `to` of different capacities need an output capacity (out_cap)")
             name = "replace" if out_cap is None else f"replace:{f_cap}:{out_cap}"
-            return self._packed(name, a_cap, f_cap + t_cap, None, [a, frm, to])
+            return self._packed(name, a_cap, f_cap + t_cap, None, [a, frm, to], packed)
         if out_cap is None:
             out = self._alloc(a.shape)
             if clear:
@@ -1346,11 +1492,11 @@ class FheStringOps:
     def concat(self, a, b, packed=False):
         """a ++ b (padding of a removed); b encrypted (any capacity) or clear bytes."""
         a, a_cap = self._cap(a)
-        if packed:
+        if self._dev(packed, a, b):
             if isinstance(b, (bytes, bytearray)):
-                return self._packed("concat_clear", a_cap, 0, b, [a])
+                return self._packed("concat_clear", a_cap, 0, b, [a], packed)
             b, b_cap = self._cap(b)
-            return self._packed("concat", a_cap, b_cap, None, [a, b])
+            return self._packed("concat", a_cap, b_cap, None, [a, b], packed)
         if isinstance(b, (bytes, bytearray)):
             out = self._alloc(((a_cap + len(b)) * self.bpc, self.engine.params.big_size))
             buf = (C.c_uint8 * max(1, len(b)))(*b)
@@ -1363,8 +1509,8 @@ class FheStringOps:
 
     def repeat(self, a, count: int, packed=False):
         a, a_cap = self._cap(a)
-        if packed:
-            return self._packed("repeat_clear", a_cap, 0, bytes([count]), [a])
+        if self._dev(packed, a):
+            return self._packed("repeat_clear", a_cap, 0, bytes([count]), [a], packed)
         out = self._alloc((count * a_cap * self.bpc, self.engine.params.big_size))
         _check(lib().fhe_str_repeat_clear(self.engine.handle, _ptr(a), a_cap, count, _ptr(out)))
         return out

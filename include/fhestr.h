@@ -496,6 +496,40 @@ int fhe_engine_pack_lwes_dev(fhe_engine *eng, const uint64_t *d_cts, uint32_t co
  * keyswitch), info[3] K steps per chunk, info[4] K steps in all. */
 int fhe_engine_packing_info(fhe_engine *eng, uint32_t info[5]);
 
+/* ---- packed GLWE ciphertexts as inputs: sample extraction at any coefficient -----------------------
+ * The inverse of the packing above, extract_lwe_sample_from_glwe_ciphertext of the reference
+ * (core_crypto/algorithms/glwe_sample_extraction.rs:91-147): block j of packed results is coefficient c = j % N of GLWE
+ * j / N, and under the flattened GLWE key -- the big LWE key every operation reads -- it is the LWE with
+ *     mask[q N + i] = A_q[c - i] for i <= c,  -A_q[N + c - i] for i > c        (q < k),        body = B[c].
+ * No key is involved and nothing is rounded: host and GPU give the same words.
+ *   input  GLWEs of [k+1][N] u64 (what fhe_engine_pack_lwes writes, or fhe_wire_read_glwe_list returns)
+ *   output rows first .. first + count - 1 as count x (kN+1) words
+ * The GLWEs must hold block first + count - 1: ceil((first + count) / N) of them is the caller's contract, it cannot be
+ * checked here.  count == 0 succeeds and touches nothing. */
+/* The plain loop on the host (parity; callers without a GPU). */
+int fhe_glwe_sample_extract_host(const fhe_params_t *params, const uint64_t *glwes, uint32_t first, uint32_t count, uint64_t *cts);
+/* Noise of a block extracted from a packed PBS output, by the model fhe_packing_default_params judges with: out[0] its
+ * variance in nominal units (1 + packing keyswitch variance / V_pbs of fhe_noise_model), out[1] the default PBS-input
+ * budget (fhe_noise_model's out[4]).  A plan's inputs are declared nominal, so extracted blocks are refreshed first. */
+int fhe_packing_unpack_noise(const fhe_params_t *params, const fhe_packing_params_t *pp, double out[2]);
+/* On the GPU (csrc/glwe_extract_kernels.hip.h).  refresh = 0: the raw extracted LWEs.  refresh = 1: every extracted block
+ * then goes through one keyswitch + PBS with the identity table over the whole message-and-carry space (the batch path
+ * of fhe_ks_pbs_batch_dev, server keys required): the blocks carry nominal noise again and are valid inputs of every plan.
+ * The refresh is judged with the decomposition of the loaded packing key: refused when no packing key is loaded, and
+ * when out[0] > out[1] of fhe_packing_unpack_noise; the reason is in fhe_last_error.  refresh = 0 needs no key at all.
+ * fhe_engine_unpack_glwes: host GLWEs in, host ciphertexts out; synchronises.
+ * _dev: device buffers, asynchronous on the engine's stream under the contract of fhe_engine_pack_lwes_dev (a throughput
+ * mode makes the call wait for every stream first); the first refresh on an engine uploads the identity table and
+ * waits for that copy.  d_cts is what fhe_ks_pbs_batch_dev and fhe_plan_run_batch_dev read; it needs 8-byte alignment
+ * only. */
+int fhe_engine_unpack_glwes(fhe_engine *eng, const uint64_t *glwes_host, uint32_t first, uint32_t count, int refresh,
+                            uint64_t *cts_host);
+int fhe_engine_unpack_glwes_dev(fhe_engine *eng, const uint64_t *d_glwes, uint32_t first, uint32_t count, int refresh,
+                                uint64_t *d_cts);
+/* What the last extraction launched, recorded on the host when it was enqueued: info[0] 1 once a launch ran, info[1]
+ * rows (= count), info[2] workgroups, info[3] 1 if the rows were refreshed. */
+int fhe_engine_unpack_info(fhe_engine *eng, uint32_t info[4]);
+
 /* ---- tfhe-rs wire format (serde + bincode 1.x, fixed-width little endian) ---------------------- */
 /* Byte forms of core_crypto's LweCiphertext<Vec<u64>>, LweKeyswitchKey<Vec<u64>>, standard-domain
  * LweBootstrapKey<Vec<u64>> and shortint::Ciphertext as tfhe-rs 0.5 writes them with bincode::serialize /
