@@ -10,13 +10,6 @@
 
 namespace fhe {
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess)                                                                 \
-            return fail(std::string(#expr) + ": " + hipGetErrorString(_e));                   \
-    } while (0)
-
 Circuit::Circuit(const fhe_params_t& params, Engine* eng) : p_(params), eng_(eng) {
     noise_budget_ = default_noise_budget(params);
 }
@@ -375,20 +368,13 @@ int Circuit::upload_meta() {
     };
     for (auto& lv : levels_) fill(lv);
     fill(out_);
-    if (d_meta_) { HIP_TRY(hipFree(d_meta_)); d_meta_ = nullptr; }
-    HIP_TRY(hipMalloc(&d_meta_, total ? total : 8));
+    if (d_meta_.alloc(total ? total : 8)) return 1;
     HIP_TRY(hipMemcpyAsync(d_meta_, host.data(), total, hipMemcpyHostToDevice, eng_->stream));
     HIP_TRY(hipStreamSynchronize(eng_->stream));
     size_t max_jobs = 1;
     for (auto& lv : levels_) max_jobs = std::max(max_jobs, (size_t)lv.local_size);
     const size_t big = (size_t)p_.k * p_.N + 1;
-    if (stage_cap_ < max_jobs * big * 8) {
-        if (d_stage_) HIP_TRY(hipFree(d_stage_));
-        d_stage_ = nullptr;
-        HIP_TRY(hipMalloc((void**)&d_stage_, max_jobs * big * 8));
-        stage_cap_ = max_jobs * big * 8;
-    }
-    return 0;
+    return d_stage_.reserve(max_jobs * big * 8);
 }
 
 int Circuit::run_level_rank(uint64_t* d_pool, uint32_t l, uint32_t rank) {
@@ -400,8 +386,8 @@ int Circuit::run_level_rank(uint64_t* d_pool, uint32_t l, uint32_t rank) {
     if (lo >= hi) return 0;
     if (eng_->use()) return 1;
     const size_t big = (size_t)p_.k * p_.N + 1;
-    if ((size_t)(hi - lo) * big * 8 > stage_cap_) return fail("internal: stage buffer smaller than a level slice");
-    const unsigned char* m = reinterpret_cast<const unsigned char*>(d_meta_);
+    if ((size_t)(hi - lo) * big * 8 > d_stage_.bytes) return fail("internal: stage buffer smaller than a level slice");
+    const unsigned char* m = d_meta_;
     const uint32_t* d_off = reinterpret_cast<const uint32_t*>(m + lv.meta_off) + lo;
     const uint32_t* d_src = reinterpret_cast<const uint32_t*>(m + lv.meta_src);
     const int32_t* d_coeff = reinterpret_cast<const int32_t*>(m + lv.meta_coeff);
@@ -414,7 +400,7 @@ int Circuit::run_level_rank(uint64_t* d_pool, uint32_t l, uint32_t rank) {
 int Circuit::gather_outputs(const uint64_t* d_pool, uint64_t* d_out) {
     if (!eng_) return fail("offline plan: no engine bound (there is no CPU execution path)");
     if (eng_->use()) return 1;
-    const unsigned char* m = reinterpret_cast<const unsigned char*>(d_meta_);
+    const unsigned char* m = d_meta_;
     return eng_->lincomb_dev(d_pool, reinterpret_cast<const uint32_t*>(m + out_.meta_off),
                              reinterpret_cast<const uint32_t*>(m + out_.meta_src),
                              reinterpret_cast<const int32_t*>(m + out_.meta_coeff),
@@ -434,8 +420,8 @@ int Circuit::run_host_parts(const uint64_t* const* parts, const uint32_t* counts
     if (eng_->use()) return 1;
     if (world_ != 1) return fail("run_host needs a plan finalised for world = 1");
     const size_t big = (size_t)p_.k * p_.N + 1;
-    if (!d_own_pool_) HIP_TRY(hipMalloc((void**)&d_own_pool_, (size_t)std::max<uint32_t>(pool_slots_, 1) * big * 8));
-    if (!d_own_out_) HIP_TRY(hipMalloc((void**)&d_own_out_, (size_t)std::max<uint32_t>(n_outputs(), 1) * big * 8));
+    if (!d_own_pool_ && d_own_pool_.alloc((size_t)std::max<uint32_t>(pool_slots_, 1) * big * 8)) return 1;
+    if (!d_own_out_ && d_own_out_.alloc((size_t)std::max<uint32_t>(n_outputs(), 1) * big * 8)) return 1;
     uint32_t placed = 0;
     for (uint32_t i = 0; i < n_parts; i++) {
         if (!counts[i]) continue;
@@ -453,15 +439,6 @@ int Circuit::run_host_parts(const uint64_t* const* parts, const uint32_t* counts
     return eng_->cluster_check();
 }
 
-static int grow(void** ptr, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return 0;
-    if (*ptr) HIP_TRY(hipFree(*ptr));
-    *ptr = nullptr; *cap = 0;
-    HIP_TRY(hipMalloc(ptr, bytes));
-    *cap = bytes;
-    return 0;
-}
-
 // ---- many instances of a plan in one pass ----
 int Circuit::batch_prepare(uint32_t M) {
     if (!eng_) return fail("offline plan: no engine bound (there is no CPU execution path)");
@@ -472,12 +449,9 @@ int Circuit::batch_prepare(uint32_t M) {
     for (auto& lv : levels_) max_jobs = std::max(max_jobs, lv.jobs.size());
     if ((uint64_t)pool_slots_ * M > 0x7FFFFFFFull || (uint64_t)max_jobs * M > 0x7FFFFFFFull) return fail("run_batch: too many instances");
     // the streams of an earlier pass may still read these buffers while they are being replaced
-    if (bpool_cap_ < (size_t)pool_slots_ * M * big * 8 || bstage_cap_ < max_jobs * M * big * 8 || blut_cap_ < max_jobs * M * 4)
-        if (eng_->sync_all_streams()) return 1;
-    if (grow((void**)&d_bpool_, &bpool_cap_, (size_t)std::max<uint32_t>(pool_slots_, 1) * M * big * 8)) return 1;
-    if (grow((void**)&d_bstage_, &bstage_cap_, max_jobs * M * big * 8)) return 1;
-    if (grow((void**)&d_blut_, &blut_cap_, max_jobs * M * 4)) return 1;
-    return 0;
+    if (eng_->reserve_idle(d_bpool_, (size_t)std::max<uint32_t>(pool_slots_, 1) * M * big * 8)) return 1;
+    if (eng_->reserve_idle(d_bstage_, max_jobs * M * big * 8)) return 1;
+    return eng_->reserve_idle(d_blut_, max_jobs * M * 4);
 }
 
 // input slots [first, first + count) of every instance <- d_src row (s * in_slot + i * in_inst); in_inst = 0 replicates
@@ -489,7 +463,7 @@ int Circuit::batch_load(const uint64_t* d_src, uint32_t first, uint32_t count, u
 
 int Circuit::batch_execute(uint64_t* d_outputs, uint32_t M) {
     const size_t big = (size_t)p_.k * p_.N + 1;
-    const unsigned char* m = reinterpret_cast<const unsigned char*>(d_meta_);
+    const unsigned char* m = d_meta_;
     for (const Level& lv : levels_) {
         const uint32_t J = (uint32_t)lv.jobs.size();
         if (!J) continue;
@@ -522,8 +496,7 @@ int Circuit::run_batch_host(const uint64_t* rows, uint32_t row_count, const uint
     const uint32_t n_shared = n_inputs_ - row_count;
     const size_t rows_words = (size_t)row_count * instances * big, shared_words = (size_t)n_shared * big,
                  out_words = (size_t)n_outputs() * instances * big;
-    if (bio_cap_ < (rows_words + shared_words + out_words) * 8 && eng_->sync_all_streams()) return 1;
-    if (grow((void**)&d_bio_, &bio_cap_, (rows_words + shared_words + out_words) * 8)) return 1;
+    if (eng_->reserve_idle(d_bio_, (rows_words + shared_words + out_words) * 8)) return 1;
     uint64_t *d_rows = d_bio_, *d_shared = d_bio_ + rows_words, *d_out = d_shared + shared_words;
     if (rows_words) HIP_TRY(hipMemcpyAsync(d_rows, rows, rows_words * 8, hipMemcpyHostToDevice, eng_->stream));
     if (shared_words) HIP_TRY(hipMemcpyAsync(d_shared, shared, shared_words * 8, hipMemcpyHostToDevice, eng_->stream));
@@ -536,16 +509,8 @@ int Circuit::run_batch_host(const uint64_t* rows, uint32_t row_count, const uint
 }
 
 Circuit::~Circuit() {
-    if (!eng_) return;
-    (void)hipSetDevice(eng_->device);
-    if (d_bpool_) (void)hipFree(d_bpool_);
-    if (d_bstage_) (void)hipFree(d_bstage_);
-    if (d_bio_) (void)hipFree(d_bio_);
-    if (d_blut_) (void)hipFree(d_blut_);
-    if (d_meta_) (void)hipFree(d_meta_);
-    if (d_stage_) (void)hipFree(d_stage_);
-    if (d_own_pool_) (void)hipFree(d_own_pool_);
-    if (d_own_out_) (void)hipFree(d_own_out_);
+    if (!eng_) return;      // an offline plan never allocated
+    (void)hipSetDevice(eng_->device);      // the members are destroyed after this body: the buffers are freed on the engine's device
 }
 
 }  // namespace fhe

@@ -195,16 +195,13 @@ private:
     std::map<std::vector<uint8_t>, uint32_t> box_lut_cache_;   // plan-local ids of the -/+ delta/2 tables, by their 0/1 table
     double noise_budget_ = 0.0, max_pbs_input_noise_ = 0.0;
     std::string error_;
-    void* d_meta_ = nullptr;
-    uint64_t* d_stage_ = nullptr;   // lincomb output / keyswitch input of one level slice
-    size_t stage_cap_ = 0;
-    uint64_t* d_own_pool_ = nullptr;
-    uint64_t* d_own_out_ = nullptr;
+    DeviceBuffer<unsigned char> d_meta_;
+    DeviceBuffer<uint64_t> d_stage_;   // lincomb output / keyswitch input of one level slice
+    DeviceBuffer<uint64_t> d_own_pool_, d_own_out_;
     // batch execution (grown on demand): slot-major pool [slot][instance], one level's gathered rows, their table ids,
     // staging of host inputs / outputs
-    uint64_t *d_bpool_ = nullptr, *d_bstage_ = nullptr, *d_bio_ = nullptr;
-    uint32_t* d_blut_ = nullptr;
-    size_t bpool_cap_ = 0, bstage_cap_ = 0, bio_cap_ = 0, blut_cap_ = 0;
+    DeviceBuffer<uint64_t> d_bpool_, d_bstage_, d_bio_;
+    DeviceBuffer<uint32_t> d_blut_;
 };
 
 }  // namespace fhe

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/fhestr.h"
+#include "device_buffer.h"
 
 // bumped whenever a device kernel changes; profiles/r03_counters.json records the revision its
 // rocprofv3 counters were taken on and bench.py only attaches them to a matching build
@@ -32,7 +33,6 @@ void aes128_round_keys(const uint8_t key[16], uint8_t rk[11][16]);   // seeded_k
 const uint8_t* aes_sbox();
 
 extern thread_local std::string g_last_error;
-int fail(const std::string& msg);
 
 struct BrVariant;
 
@@ -90,42 +90,43 @@ struct Engine {
     // them waits for that stream's latest ovl_done: stream order then covers all of its earlier calls -- ADVICE r3)
     struct ByteRange { const char* lo; const char* hi; };
     std::vector<ByteRange> ovl_ins[OVL_MAX], ovl_outs[OVL_MAX];
-    uint64_t* ovl_small[OVL_MAX] = {nullptr, nullptr, nullptr, nullptr};      // small-ciphertext buffer per stream
-    size_t ovl_cap_small[OVL_MAX] = {0, 0, 0, 0};
-    int8_t* ovl_digits[OVL_MAX] = {nullptr, nullptr, nullptr, nullptr};       // keyswitch digit fragments per stream (slot 0: d_ks_digits)
-    size_t ovl_cap_digits[OVL_MAX] = {0, 0, 0, 0};
+    DeviceBuffer<uint64_t> ovl_small[OVL_MAX];      // small-ciphertext buffer per stream
+    DeviceBuffer<int8_t> ovl_digits[OVL_MAX];       // keyswitch digit fragments per stream (slot 0: d_ks_digits)
     int sync_all_streams();
+    // Grow a buffer that launches in flight on any of the engine's streams may still read: they finish before the old
+    // allocation goes.  Nothing can be reading an empty buffer, so a first allocation does not wait.
+    template <class T>
+    int reserve_idle(DeviceBuffer<T>& b, size_t need) {
+        if (b.bytes >= need) return 0;
+        if (b.ptr && sync_all_streams()) return 1;
+        return b.reserve(need);
+    }
     void end_pipeline_run();
     uint64_t pipe_calls = 0;
     int shadow_fit = -1;                      // -1 unknown, else whether a 64-VGPR wave fits next to the rotation's
     uint32_t multibit_combine_max = 64;       // multi-bit PBS: batches up to this size prepare their GGSWs on the whole GPU first
 
     // resident keys / tables
-    uint32_t* d_ksk_packed = nullptr; // [rows/4][8][n+1] byte planes for keyswitch_dot4_kernel
-    uint64_t* d_ksk_rowsum = nullptr; // [kN / KS_IC][n+1] sums of every tile's key rows (bias removal)
-    int8_t* d_ksk_mfma = nullptr;     // balanced base-256 digit planes of the KSK in MFMA B-fragment order (ks_mfma_kernels.hip.h)
-    int8_t* d_ks_digits = nullptr;    // A fragments: signed decomposition digits of the batch being keyswitched
-    size_t cap_ks_digits = 0;
+    DeviceBuffer<uint32_t> d_ksk_packed; // [rows/4][8][n+1] byte planes for keyswitch_dot4_kernel
+    DeviceBuffer<uint64_t> d_ksk_rowsum; // [kN / KS_IC][n+1] sums of every tile's key rows (bias removal)
+    DeviceBuffer<int8_t> d_ksk_mfma;  // balanced base-256 digit planes of the KSK in MFMA B-fragment order (ks_mfma_kernels.hip.h)
+    DeviceBuffer<int8_t> d_ks_digits; // A fragments: signed decomposition digits of the batch being keyswitched
     bool ks_mfma_enabled = true;      // FHESTR_KS_MFMA=0: byte-plane dot4 kernel everywhere
-    double* d_fbsk = nullptr;
-    double* d_fbsk_dense = nullptr;          // the same key in the dense wide kernel's Fourier order (N = 1024, k = 2 only)
-    uint64_t* d_luts = nullptr;
-    size_t luts_cap = 0;
+    DeviceBuffer<double> d_fbsk;
+    DeviceBuffer<double> d_fbsk_dense;       // the same key in the dense wide kernel's Fourier order (N = 1024, k = 2 only)
+    DeviceBuffer<uint64_t> d_luts;
     uint32_t n_luts = 0;
 
     // staging / scratch (grown on demand)
-    uint64_t *d_in = nullptr, *d_small = nullptr, *d_small2 = nullptr, *d_out = nullptr, *d_pool = nullptr;
-    uint32_t* d_idx = nullptr;
-    uint32_t* d_slot_exp = nullptr;   // multi-bit two-kernel path: exponent of w = e^{i pi / N} each Fourier slot evaluates at
+    DeviceBuffer<uint64_t> d_in, d_small, d_small2, d_out, d_pool;
+    DeviceBuffer<uint32_t> d_idx;
+    DeviceBuffer<uint32_t> d_slot_exp;   // multi-bit two-kernel path: exponent of w = e^{i pi / N} each Fourier slot evaluates at
     size_t multibit_workspace_cap = 0;   // bytes of prepared GGSWs kept at once, larger batches run in sub-batches (0 = from free memory; FHESTR_MULTIBIT_WS_CAP)
-    void* d_meta = nullptr;
-    uint64_t* d_compact = nullptr;   // a compact ciphertext list on its way to compact_expand_kernel
-    size_t cap_compact = 0;
-    void* d_ws = nullptr;      // per-LWE HBM workspace of the large-N blind rotation
-    size_t cap_ws = 0;
-    void* d_cluster_ws = nullptr;   // cluster kernel: 1.5 MB of exchange matrices per cluster (L2-resident by design)
-    size_t cap_cluster_ws = 0;
-    void* d_cluster_ctl = nullptr;  // ClusterCtl (tickets, flags; zeroed per launch) + ClusterStatus (sticky)
+    DeviceBuffer<unsigned char> d_meta;
+    DeviceBuffer<uint64_t> d_compact;   // a compact ciphertext list on its way to compact_expand_kernel
+    DeviceBuffer<unsigned char> d_ws;   // per-LWE HBM workspace of the large-N blind rotation
+    DeviceBuffer<unsigned char> d_cluster_ws;   // cluster kernel: 1.5 MB of exchange matrices per cluster (L2-resident by design)
+    DeviceBuffer<void> d_cluster_ctl;   // ClusterCtl (tickets, flags; zeroed per launch) + ClusterStatus (sticky)
     bool cluster_unchecked = false; // a cluster launch whose status words have not been read yet
     uint32_t cluster_last = 0;      // clusters the last checked launch formed
     bool cluster_fallback = true;   // a multi-CU launch that gave up is re-run on the one-workgroup kernel (cluster_settle)
@@ -138,25 +139,20 @@ struct Engine {
     // (FHE_KS_KERNEL_*), row tiles / samples per workgroup, K chunks (grid.z), K steps / input coefficients per chunk, K steps / in_dim
     uint32_t ks_last[5] = {0, 0, 0, 0, 0};
     // packing keyswitch (packing_ks_kernels.hip.h): the key's digit planes, its decomposition, and the batch's digit fragments
-    int8_t* d_pksk_mfma = nullptr;
+    DeviceBuffer<int8_t> d_pksk_mfma;
     fhe_packing_params_t pack_pp{0, 0};
-    int8_t* d_pack_digits = nullptr;  // same reuse rules as d_ks_digits: zeroed at allocation, grown, rows past the batch never read
-    size_t cap_pack_digits = 0;
-    uint64_t *d_pack_in = nullptr, *d_pack_out = nullptr;   // staging of fhe_engine_pack_lwes (host ciphertexts)
-    size_t cap_pack_in = 0, cap_pack_out = 0;
+    DeviceBuffer<int8_t> d_pack_digits;  // same reuse rules as d_ks_digits: zeroed at allocation, grown, rows past the batch never read
+    DeviceBuffer<uint64_t> d_pack_in, d_pack_out;   // staging of fhe_engine_pack_lwes (host ciphertexts)
     uint32_t pack_last[5] = {0, 0, 0, 0, 0};   // fhe_engine_packing_info: ran, MT, K chunks, K steps per chunk, K steps
     // packed inputs (glwe_extract_kernels.hip.h): staging of fhe_engine_unpack_glwes, the refresh's table indices
-    uint64_t *d_unpack_in = nullptr, *d_unpack_out = nullptr;
-    size_t cap_unpack_in = 0, cap_unpack_out = 0;
-    uint32_t* d_unpack_idx = nullptr;          // the identity table's id, once per block of the largest refresh so far
-    size_t cap_unpack_idx = 0;
+    DeviceBuffer<uint64_t> d_unpack_in, d_unpack_out;
+    DeviceBuffer<uint32_t> d_unpack_idx;       // the identity table's id, once per block of the largest refresh so far
     uint32_t unpack_last[4] = {0, 0, 0, 0};    // fhe_engine_unpack_info: ran, rows, workgroups, refreshed
     int xcd_per_cu = -1;             // workgroups of the whole-XCD kernel a CU holds (occupancy query, cached)
     uint32_t xcd_auto_max = 16;     // automatic mode: batches up to this size take the whole-XCD kernel (two LWEs per XCD in flight)
     uint32_t cluster_spin_limit = 1u << 22;   // polls before a hand-over wait gives up (FHESTR_CLUSTER_SPIN_LIMIT)
     uint32_t cluster_test_fault = 0;          // tests only (FHESTR_CLUSTER_TEST_FAULT): epoch one workgroup stays silent at
     int cluster_check();            // after a synchronisation: did a cluster launch give up on a hand-over?
-    size_t cap_in = 0, cap_small = 0, cap_small2 = 0, cap_out = 0, cap_idx = 0, cap_pool = 0, cap_meta = 0;
 
     static int create(const fhe_params_t& p, int device, Engine** out);
     ~Engine();
@@ -171,7 +167,7 @@ struct Engine {
     int expand_compact_list_dev(const uint64_t* d_list, uint32_t count, uint64_t* d_out);
     int generate_keys(const uint64_t* glwe_sk, const uint64_t* small_sk, const uint8_t seed[32],
                       uint64_t* bsk_std_out, uint64_t* ksk_out);
-    int install_keys(uint64_t* d_ksk_std, uint64_t* d_bsk_std);
+    int install_keys(DeviceBuffer<uint64_t>&& d_ksk_std, DeviceBuffer<uint64_t>&& d_bsk_std);
     int convert_polys(const uint64_t* d_std, double* d_out, uint32_t n_polys);
     int cluster_settle(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big, uint32_t count);
     int probe_slot_exponents();

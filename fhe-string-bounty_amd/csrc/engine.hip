@@ -39,13 +39,6 @@ int fail(const std::string& msg) {
     return 1;
 }
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess)                                                                 \
-            return fail(std::string(#expr) + ": " + hipGetErrorString(_e));                   \
-    } while (0)
-
 // ---- blind-rotation variant registry ----------------------------------------------------------
 struct BrVariant {
     int logN, k1, L, logR;
@@ -364,17 +357,13 @@ int Engine::create(const fhe_params_t& p, int device, Engine** out) {
 Engine::~Engine() {
     (void)hipSetDevice(device);
     if (stream) (void)sync_all_streams();
-    auto rel = [](void* ptr) { if (ptr) (void)hipFree(ptr); };
-    rel(d_ksk_packed); rel(d_ksk_rowsum); rel(d_fbsk); rel(d_fbsk_dense); rel(d_luts); rel(d_in); rel(d_small); rel(d_small2); rel(d_out); rel(d_idx);
-    rel(d_pool); rel(d_meta); rel(d_ws); rel(d_slot_exp); rel(d_cluster_ws); rel(d_cluster_ctl); rel(d_ksk_mfma); rel(d_ks_digits); rel(d_compact);
-    rel(d_pksk_mfma); rel(d_pack_digits); rel(d_pack_in); rel(d_pack_out);
-    rel(d_unpack_in); rel(d_unpack_out); rel(d_unpack_idx);
-    for (int q = 0; q < OVL_MAX; q++) { rel(ovl_digits[q]); rel(ovl_small[q]); if (ovl_done[q]) (void)hipEventDestroy(ovl_done[q]); if (q >= 2 && ovl_stream[q]) (void)hipStreamDestroy(ovl_stream[q]); }
+    for (int q = 0; q < OVL_MAX; q++) { if (ovl_done[q]) (void)hipEventDestroy(ovl_done[q]); if (q >= 2 && ovl_stream[q]) (void)hipStreamDestroy(ovl_stream[q]); }
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : ring) if (e) (void)hipEventDestroy(e);
     for (auto& e : pipe_ev) if (e) (void)hipEventDestroy(e);
     if (ks_stream) (void)hipStreamDestroy(ks_stream);
     if (own_stream) (void)hipStreamDestroy(own_stream);
+    // the members are destroyed after this body: every DeviceBuffer is freed once the streams are idle and gone
 }
 
 int Engine::set_stream(hipStream_t s, bool use_own) {
@@ -395,14 +384,9 @@ int Engine::lut_upload_dedup(const std::vector<uint64_t>& acc, uint32_t* id) {
 
 int Engine::use() { HIP_TRY(hipSetDevice(device)); return 0; }
 
-static int ensure(void** ptr, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return 0;
-    if (*ptr) HIP_TRY(hipFree(*ptr));
-    *ptr = nullptr; *cap = 0;
-    HIP_TRY(hipMalloc(ptr, bytes));
-    *cap = bytes;
-    return 0;
-}
+// The error of a HIP call, or of a DeviceBuffer operation, under the name of the function that met it.
+static int under(const char* who, hipError_t e) { return e == hipSuccess ? 0 : fail(std::string(who) + ": " + hipGetErrorString(e)); }
+static int under(const char* who, int rc) { return rc ? fail(std::string(who) + ": " + g_last_error) : 0; }
 
 int Engine::set_variant(int logR) {
     const BrVariantPair vp = find_variant_pair(p, logR);
@@ -427,19 +411,12 @@ int Engine::load_keys(const uint64_t* bsk_std, const uint64_t* ksk) {
     if (use()) return 1;
     const size_t ksk_len = (size_t)p.k * p.N * p.ks_level * (p.n + 1);
     const size_t bsk_len = (size_t)n_ggsw(p) * p.pbs_level * (p.k + 1) * (p.k + 1) * p.N;
-    uint64_t *d_ksk_std = nullptr, *d_bsk_std = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_ksk_std, ksk_len * 8));
-    if (hipMalloc((void**)&d_bsk_std, bsk_len * 8) != hipSuccess) {
-        (void)hipFree(d_ksk_std);
-        return fail("hipMalloc of the standard-domain bootstrap key failed");
-    }
-    hipError_t e = hipMemcpyAsync(d_ksk_std, ksk, ksk_len * 8, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_bsk_std, bsk_std, bsk_len * 8, hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) {
-        (void)hipFree(d_ksk_std); (void)hipFree(d_bsk_std);
-        return fail(std::string("key upload: ") + hipGetErrorString(e));
-    }
-    return install_keys(d_ksk_std, d_bsk_std);
+    DeviceBuffer<uint64_t> d_ksk_std, d_bsk_std;
+    if (d_ksk_std.alloc(ksk_len * 8) || d_bsk_std.alloc(bsk_len * 8)) return 1;
+    if (under("key upload", hipMemcpyAsync(d_ksk_std, ksk, ksk_len * 8, hipMemcpyHostToDevice, stream)) ||
+        under("key upload", hipMemcpyAsync(d_bsk_std, bsk_std, bsk_len * 8, hipMemcpyHostToDevice, stream)))
+        return 1;
+    return install_keys(std::move(d_ksk_std), std::move(d_bsk_std));
 }
 
 // A tfhe-rs client's CompressedServerKey (shortint/server_key/compressed.rs): upload the bodies, expand the masks from
@@ -450,37 +427,35 @@ int Engine::load_seeded_keys(const uint8_t ksk_seed[16], const uint64_t* ksk_bod
     const uint64_t ksk_rows = (uint64_t)p.k * p.N * p.ks_level, bsk_rows = (uint64_t)n_ggsw(p) * p.pbs_level * (p.k + 1);
     const size_t ksk_len = ksk_rows * (p.n + 1), bsk_len = bsk_rows * (p.k + 1) * p.N;
     const size_t bsk_body_words = bsk_rows * p.N;
-    uint64_t *d_ksk_std = nullptr, *d_bsk_std = nullptr, *d_bodies = nullptr;
-    uint8_t* d_sbox = nullptr;
-    auto cleanup = [&] { (void)hipFree(d_ksk_std); (void)hipFree(d_bsk_std); (void)hipFree(d_bodies); (void)hipFree(d_sbox); };
-    hipError_t e = hipMalloc((void**)&d_ksk_std, ksk_len * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_bsk_std, bsk_len * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_bodies, (bsk_body_words + ksk_rows) * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_sbox, 256);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_sbox, aes_sbox(), 256, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_bodies, bsk_bodies, bsk_body_words * 8, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_bodies + bsk_body_words, ksk_bodies, ksk_rows * 8, hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) { cleanup(); return fail(std::string("load_seeded_keys: ") + hipGetErrorString(e)); }
+    const char* const who = "load_seeded_keys";
+    DeviceBuffer<uint64_t> d_ksk_std, d_bsk_std, d_bodies;
+    DeviceBuffer<uint8_t> d_sbox;
+    if (under(who, d_ksk_std.alloc(ksk_len * 8)) || under(who, d_bsk_std.alloc(bsk_len * 8)) ||
+        under(who, d_bodies.alloc((bsk_body_words + ksk_rows) * 8)) || under(who, d_sbox.alloc(256)) ||
+        under(who, hipMemcpyAsync(d_sbox, aes_sbox(), 256, hipMemcpyHostToDevice, stream)) ||
+        under(who, hipMemcpyAsync(d_bodies, bsk_bodies, bsk_body_words * 8, hipMemcpyHostToDevice, stream)) ||
+        under(who, hipMemcpyAsync(d_bodies + bsk_body_words, ksk_bodies, ksk_rows * 8, hipMemcpyHostToDevice, stream)))
+        return 1;
     SeededExpandArgs ka{}, ba{};
     aes128_round_keys(ksk_seed, ka.round_keys);
     ka.out = d_ksk_std; ka.rows = ksk_rows; ka.mask_per_row = p.n; ka.row_words = p.n + 1;
     aes128_round_keys(bsk_seed, ba.round_keys);
     ba.out = d_bsk_std; ba.rows = bsk_rows; ba.mask_per_row = p.k * p.N; ba.row_words = (p.k + 1) * p.N;
     const unsigned grid = (unsigned)cu_count * 8;
-    hipLaunchKernelGGL(seeded_expand_kernel, dim3(grid), dim3(256), 0, stream, ka, d_sbox);
-    hipLaunchKernelGGL(seeded_expand_kernel, dim3(grid), dim3(256), 0, stream, ba, d_sbox);
-    hipLaunchKernelGGL(seeded_scatter_bodies_kernel, dim3(grid), dim3(256), 0, stream, d_bodies + bsk_body_words, d_ksk_std, ksk_rows,
+    hipLaunchKernelGGL(seeded_expand_kernel, dim3(grid), dim3(256), 0, stream, ka, d_sbox.ptr);
+    hipLaunchKernelGGL(seeded_expand_kernel, dim3(grid), dim3(256), 0, stream, ba, d_sbox.ptr);
+    hipLaunchKernelGGL(seeded_scatter_bodies_kernel, dim3(grid), dim3(256), 0, stream, d_bodies + bsk_body_words, d_ksk_std.ptr, ksk_rows,
                        p.n, p.n + 1);
-    hipLaunchKernelGGL(seeded_scatter_bodies_kernel, dim3(grid), dim3(256), 0, stream, d_bodies, d_bsk_std, bsk_rows, p.k * p.N,
+    hipLaunchKernelGGL(seeded_scatter_bodies_kernel, dim3(grid), dim3(256), 0, stream, d_bodies.ptr, d_bsk_std.ptr, bsk_rows, p.k * p.N,
                        (p.k + 1) * p.N);
-    e = hipGetLastError();
-    if (e == hipSuccess && ksk_out) e = hipMemcpyAsync(ksk_out, d_ksk_std, ksk_len * 8, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && bsk_std_out) e = hipMemcpyAsync(bsk_std_out, d_bsk_std, bsk_len * 8, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_bodies); d_bodies = nullptr;
-    (void)hipFree(d_sbox); d_sbox = nullptr;
-    if (e != hipSuccess) { cleanup(); return fail(std::string("load_seeded_keys: ") + hipGetErrorString(e)); }
-    return install_keys(d_ksk_std, d_bsk_std);
+    if (under(who, hipGetLastError()) ||
+        (ksk_out && under(who, hipMemcpyAsync(ksk_out, d_ksk_std, ksk_len * 8, hipMemcpyDeviceToHost, stream))) ||
+        (bsk_std_out && under(who, hipMemcpyAsync(bsk_std_out, d_bsk_std, bsk_len * 8, hipMemcpyDeviceToHost, stream))) ||
+        under(who, hipStreamSynchronize(stream)))
+        return 1;
+    d_bodies.release();      // before install_keys allocates the Fourier key: key loading peaks no higher than it must
+    d_sbox.release();
+    return install_keys(std::move(d_ksk_std), std::move(d_bsk_std));
 }
 
 // Compressed big-key ciphertexts -> full ciphertexts in HBM (d_out, count x (kN+1) words) and/or host_out.
@@ -489,25 +464,20 @@ int Engine::expand_seeded_lwe(const uint8_t* seeds, const uint64_t* bodies, uint
     if (count == 0) return 0;
     const uint32_t dim = p.k * p.N;
     const size_t words = (size_t)count * (dim + 1);
-    uint8_t *d_seeds = nullptr, *d_sbox = nullptr;
-    uint64_t *d_bodies = nullptr, *d_tmp = nullptr;
-    auto cleanup = [&] { (void)hipFree(d_seeds); (void)hipFree(d_sbox); (void)hipFree(d_bodies); (void)hipFree(d_tmp); };
-    hipError_t e = hipMalloc((void**)&d_seeds, (size_t)count * 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_sbox, 256);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_bodies, (size_t)count * 8);
-    if (e == hipSuccess && !d_out) e = hipMalloc((void**)&d_tmp, words * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_seeds, seeds, (size_t)count * 16, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_sbox, aes_sbox(), 256, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_bodies, bodies, (size_t)count * 8, hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) { cleanup(); return fail(std::string("expand_seeded_lwe: ") + hipGetErrorString(e)); }
-    uint64_t* target = d_out ? d_out : d_tmp;
-    hipLaunchKernelGGL(seeded_lwe_expand_kernel, dim3(count), dim3(64), 0, stream, d_seeds, d_bodies, d_sbox, target, dim);
-    e = hipGetLastError();
-    if (e == hipSuccess && host_out) e = hipMemcpyAsync(host_out, target, words * 8, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    cleanup();
-    if (e != hipSuccess) return fail(std::string("expand_seeded_lwe: ") + hipGetErrorString(e));
-    return 0;
+    const char* const who = "expand_seeded_lwe";
+    DeviceBuffer<uint8_t> d_seeds, d_sbox;
+    DeviceBuffer<uint64_t> d_bodies, d_tmp;
+    if (under(who, d_seeds.alloc((size_t)count * 16)) || under(who, d_sbox.alloc(256)) || under(who, d_bodies.alloc((size_t)count * 8)) ||
+        (!d_out && under(who, d_tmp.alloc(words * 8))) ||
+        under(who, hipMemcpyAsync(d_seeds, seeds, (size_t)count * 16, hipMemcpyHostToDevice, stream)) ||
+        under(who, hipMemcpyAsync(d_sbox, aes_sbox(), 256, hipMemcpyHostToDevice, stream)) ||
+        under(who, hipMemcpyAsync(d_bodies, bodies, (size_t)count * 8, hipMemcpyHostToDevice, stream)))
+        return 1;
+    uint64_t* target = d_out ? d_out : d_tmp.ptr;
+    hipLaunchKernelGGL(seeded_lwe_expand_kernel, dim3(count), dim3(64), 0, stream, d_seeds.ptr, d_bodies.ptr, d_sbox.ptr, target, dim);
+    if (under(who, hipGetLastError()) || (host_out && under(who, hipMemcpyAsync(host_out, target, words * 8, hipMemcpyDeviceToHost, stream))))
+        return 1;
+    return under(who, hipStreamSynchronize(stream));
 }
 
 // A public-key client's compact ciphertext list (shortint CompactCiphertextList, compact_kernels.hip.h) -> count big-key
@@ -532,19 +502,15 @@ int Engine::expand_compact_list(const uint64_t* list, uint32_t count, uint64_t* 
     const uint32_t dim = p.k * p.N;
     if (dim < 2 || (dim & (dim - 1))) return fail("compact lists need a power-of-two encryption key dimension, k*N = " + std::to_string(dim));
     const size_t list_words = (size_t)((count + dim - 1) / dim) * dim + count, words = (size_t)count * (dim + 1);
-    if (ensure((void**)&d_compact, &cap_compact, list_words * 8)) return 1;
-    uint64_t* d_tmp = nullptr;
-    if (!d_out) HIP_TRY(hipMalloc((void**)&d_tmp, words * 8));
-    uint64_t* target = d_out ? d_out : d_tmp;
-    hipError_t e = hipMemcpyAsync(d_compact, list, list_words * 8, hipMemcpyHostToDevice, stream);
-    int rc = 0;
-    if (e == hipSuccess) rc = expand_compact_list_dev(d_compact, count, target);
-    if (e == hipSuccess && rc == 0 && host_out) e = hipMemcpyAsync(host_out, target, words * 8, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && rc == 0) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_tmp);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(std::string("expand_compact_list: ") + hipGetErrorString(e));
-    return 0;
+    const char* const who = "expand_compact_list";
+    if (d_compact.reserve(list_words * 8)) return 1;
+    DeviceBuffer<uint64_t> d_tmp;
+    if (!d_out && d_tmp.alloc(words * 8)) return 1;
+    uint64_t* target = d_out ? d_out : d_tmp.ptr;
+    if (under(who, hipMemcpyAsync(d_compact, list, list_words * 8, hipMemcpyHostToDevice, stream))) return 1;
+    if (expand_compact_list_dev(d_compact, count, target)) return 1;
+    if (host_out && under(who, hipMemcpyAsync(host_out, target, words * 8, hipMemcpyDeviceToHost, stream))) return 1;
+    return under(who, hipStreamSynchronize(stream));
 }
 
 // Server-key generation on the device (keygen_kernels.hip.h); replaces ServerKey::new
@@ -564,36 +530,29 @@ int Engine::generate_keys(const uint64_t* glwe_sk, const uint64_t* small_sk, con
     std::vector<uint64_t> bits(ng);
     for (uint32_t i = 0; i < ng; i++)
         bits[i] = gf == 1 ? small_sk[i] : multi_bit_key_bit(small_sk + (size_t)(i >> gf) * gf, gf, i & ((1u << gf) - 1));
-    uint64_t *d_gsk = nullptr, *d_ssk = nullptr, *d_bits = nullptr, *d_ksk_std = nullptr, *d_bsk_std = nullptr;
-    auto cleanup = [&] {
-        (void)hipFree(d_gsk); (void)hipFree(d_ssk); (void)hipFree(d_bits); (void)hipFree(d_ksk_std); (void)hipFree(d_bsk_std);
-    };
-    hipError_t e = hipMalloc((void**)&d_gsk, in_dim * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_ssk, (size_t)p.n * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_bits, (size_t)ng * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_bits, bits.data(), (size_t)ng * 8, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_ksk_std, ksk_len * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_bsk_std, bsk_len * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_gsk, glwe_sk, in_dim * 8, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ssk, small_sk, (size_t)p.n * 8, hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) { cleanup(); return fail(std::string("generate_keys: ") + hipGetErrorString(e)); }
+    const char* const who = "generate_keys";
+    DeviceBuffer<uint64_t> d_gsk, d_ssk, d_bits, d_ksk_std, d_bsk_std;
+    if (under(who, d_gsk.alloc(in_dim * 8)) || under(who, d_ssk.alloc((size_t)p.n * 8)) || under(who, d_bits.alloc((size_t)ng * 8)) ||
+        under(who, hipMemcpyAsync(d_bits, bits.data(), (size_t)ng * 8, hipMemcpyHostToDevice, stream)) ||
+        under(who, d_ksk_std.alloc(ksk_len * 8)) || under(who, d_bsk_std.alloc(bsk_len * 8)) ||
+        under(who, hipMemcpyAsync(d_gsk, glwe_sk, in_dim * 8, hipMemcpyHostToDevice, stream)) ||
+        under(who, hipMemcpyAsync(d_ssk, small_sk, (size_t)p.n * 8, hipMemcpyHostToDevice, stream)))
+        return 1;
     KeygenArgs a{d_gsk, d_ssk, d_bits, d_ksk_std, d_bsk_std, seed_from_bytes(seed), p.n, p.k, p.N,
                  p.pbs_base_log, p.pbs_level, p.ks_base_log, p.ks_level, p.lwe_std, p.glwe_std};
     hipLaunchKernelGGL(ksk_gen_kernel, dim3((unsigned)((in_dim + 63) / 64)), dim3(64), 0, stream, a);
     hipLaunchKernelGGL(bsk_gen_kernel, dim3(ng), dim3(256), 0, stream, a);
-    e = hipGetLastError();
-    if (e == hipSuccess && ksk_out) e = hipMemcpyAsync(ksk_out, d_ksk_std, ksk_len * 8, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && bsk_std_out) e = hipMemcpyAsync(bsk_std_out, d_bsk_std, bsk_len * 8, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_gsk); d_gsk = nullptr;
-    (void)hipFree(d_ssk); d_ssk = nullptr;
-    (void)hipFree(d_bits); d_bits = nullptr;
-    if (e != hipSuccess) { cleanup(); return fail(std::string("generate_keys: ") + hipGetErrorString(e)); }
-    return install_keys(d_ksk_std, d_bsk_std);
+    if (under(who, hipGetLastError()) ||
+        (ksk_out && under(who, hipMemcpyAsync(ksk_out, d_ksk_std, ksk_len * 8, hipMemcpyDeviceToHost, stream))) ||
+        (bsk_std_out && under(who, hipMemcpyAsync(bsk_std_out, d_bsk_std, bsk_len * 8, hipMemcpyDeviceToHost, stream))) ||
+        under(who, hipStreamSynchronize(stream)))
+        return 1;
+    d_gsk.release();      // as in load_seeded_keys: gone before install_keys allocates
+    d_ssk.release();
+    d_bits.release();
+    return install_keys(std::move(d_ksk_std), std::move(d_bsk_std));
 }
 
-// Takes ownership of the two standard-domain device buffers: repacks the KSK into byte planes and
-// converts the BSK to the active variant's Fourier layout, then releases them.
 // Standard-domain polynomials -> the variant's Fourier layout (bsk_convert_kernel / bsk_convert_large_kernel).
 int Engine::convert_polys(const uint64_t* d_std, double* d_out, uint32_t n_polys) {
     const uint32_t k1 = p.k + 1;
@@ -601,15 +560,14 @@ int Engine::convert_polys(const uint64_t* d_std, double* d_out, uint32_t n_polys
                                 (int)variant->convert_lds));
     if (variant->large) {
         const uint32_t blocks = n_polys < (uint32_t)cu_count ? n_polys : (uint32_t)cu_count;
-        void* d_cws = nullptr;
-        HIP_TRY(hipMalloc(&d_cws, (size_t)blocks * variant->convert_ws));
+        DeviceBuffer<void> cws;
+        if (cws.alloc((size_t)blocks * variant->convert_ws)) return 1;
+        void* d_cws = cws;
         void* args[] = {(void*)&d_std, (void*)&d_out, (void*)&n_polys, (void*)&d_cws};
-        hipError_t e = hipLaunchKernel(variant->convert_fn, dim3(blocks), dim3(variant->convert_threads), args,
-                                       variant->convert_lds, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        (void)hipFree(d_cws);
-        if (e != hipSuccess) return fail(std::string("bsk conversion: ") + hipGetErrorString(e));
-        return 0;
+        if (under("bsk conversion", hipLaunchKernel(variant->convert_fn, dim3(blocks), dim3(variant->convert_threads), args,
+                                                    variant->convert_lds, stream)))
+            return 1;
+        return under("bsk conversion", hipStreamSynchronize(stream));
     }
     void* args[] = {(void*)&d_std, (void*)&d_out, (void*)&n_polys};
     HIP_TRY(hipLaunchKernel(variant->convert_fn, dim3(variant->convert_one_per_block ? n_polys : (n_polys + k1 - 1) / k1),
@@ -624,17 +582,15 @@ int Engine::probe_slot_exponents() {
     const uint32_t k1 = p.k + 1, P = p.N / 2;
     std::vector<uint64_t> mono((size_t)k1 * p.N, 0);
     for (uint32_t r = 0; r < k1; r++) mono[(size_t)r * p.N + 1] = 1;
-    uint64_t* d_mono = nullptr;
-    double* d_spec = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_mono, mono.size() * 8));
-    HIP_TRY(hipMalloc((void**)&d_spec, mono.size() * 8));
-    HIP_TRY(hipMemcpy(d_mono, mono.data(), mono.size() * 8, hipMemcpyHostToDevice));
-    int rc = convert_polys(d_mono, d_spec, k1);
     std::vector<double> spec((size_t)P * 2);
-    if (!rc && hipMemcpy(spec.data(), d_spec, spec.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = fail("slot probe: copy");
-    (void)hipFree(d_mono);
-    (void)hipFree(d_spec);
-    if (rc) return rc;
+    {
+        DeviceBuffer<uint64_t> d_mono;
+        DeviceBuffer<double> d_spec;
+        if (d_mono.alloc(mono.size() * 8) || d_spec.alloc(mono.size() * 8)) return 1;
+        HIP_TRY(hipMemcpy(d_mono, mono.data(), mono.size() * 8, hipMemcpyHostToDevice));
+        if (convert_polys(d_mono, d_spec, k1)) return 1;
+        if (hipMemcpy(spec.data(), d_spec, spec.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail("slot probe: copy");
+    }
     std::vector<uint32_t> expo(P);
     const double pi = 3.14159265358979323846;
     for (uint32_t s = 0; s < P; s++) {
@@ -644,52 +600,49 @@ int Engine::probe_slot_exponents() {
         if (std::fabs(turns - (double)e) > 0.01 || (expo[s] & 1) == 0)     // roots of X^N + 1 are the odd powers of w
             return fail("slot probe: the conversion kernel did not return a root of X^N + 1");
     }
-    if (d_slot_exp) { HIP_TRY(hipFree(d_slot_exp)); d_slot_exp = nullptr; }
-    HIP_TRY(hipMalloc((void**)&d_slot_exp, (size_t)P * 4));
+    if (d_slot_exp.alloc((size_t)P * 4)) return 1;
     HIP_TRY(hipMemcpy(d_slot_exp, expo.data(), (size_t)P * 4, hipMemcpyHostToDevice));
     return 0;
 }
 
-int Engine::install_keys(uint64_t* d_ksk_std, uint64_t* d_std) {
-    struct Guard {
-        uint64_t*& a; uint64_t*& b;
-        ~Guard() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); }
-    } guard{d_ksk_std, d_std};
+// Takes ownership of the two standard-domain device buffers: repacks the KSK into byte planes and
+// converts the BSK to the active variant's Fourier layout; they are released when it returns, on every path.
+int Engine::install_keys(DeviceBuffer<uint64_t>&& ksk_std, DeviceBuffer<uint64_t>&& bsk_std) {
+    const DeviceBuffer<uint64_t> d_ksk_std = std::move(ksk_std), d_bsk_std = std::move(bsk_std);
+    const uint64_t* d_std = d_bsk_std;
     const size_t bsk_len = (size_t)n_ggsw(p) * p.pbs_level * (p.k + 1) * (p.k + 1) * p.N;
-    if (d_fbsk) { HIP_TRY(hipFree(d_fbsk)); d_fbsk = nullptr; }
-    if (d_ksk_packed) { HIP_TRY(hipFree(d_ksk_packed)); d_ksk_packed = nullptr; }
-    {   // repack into byte planes once; the 64-bit layout is then released
+    d_fbsk.release();
+    {   // repack into byte planes once
         const uint32_t rows = p.k * p.N * p.ks_level, osz = p.n + 1;
-        HIP_TRY(hipMalloc((void**)&d_ksk_packed, (size_t)(rows / 4) * 8 * osz * 4));
+        if (d_ksk_packed.alloc((size_t)(rows / 4) * 8 * osz * 4)) return 1;
         hipLaunchKernelGGL(ksk_pack_kernel, dim3((osz + 255) / 256, rows / 4), dim3(256), 0, stream,
-                           d_ksk_std, d_ksk_packed, rows, osz);
+                           d_ksk_std.ptr, d_ksk_packed.ptr, rows, osz);
         const uint32_t tiles = (p.k * p.N + KS_IC - 1) / KS_IC;
-        if (d_ksk_rowsum) { HIP_TRY(hipFree(d_ksk_rowsum)); d_ksk_rowsum = nullptr; }
-        HIP_TRY(hipMalloc((void**)&d_ksk_rowsum, (size_t)tiles * osz * 8));
+        if (d_ksk_rowsum.alloc((size_t)tiles * osz * 8)) return 1;
         hipLaunchKernelGGL(ksk_rowsum_kernel, dim3((osz + 255) / 256, tiles), dim3(256), 0, stream,
-                           d_ksk_std, d_ksk_rowsum, rows, osz, (uint32_t)KS_IC * p.ks_level);
+                           d_ksk_std.ptr, d_ksk_rowsum.ptr, rows, osz, (uint32_t)KS_IC * p.ks_level);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));
     }
-    if (d_ksk_mfma) { HIP_TRY(hipFree(d_ksk_mfma)); d_ksk_mfma = nullptr; }
+    d_ksk_mfma.release();
     // balanced base-256 digit planes in MFMA fragment order (ks_mfma_kernels.hip.h); a 16-slot group holds whole mask
     // elements with all their levels, so more than 16 levels (PARAM_MESSAGE_3_CARRY_4_COMPACT_PK_PBS_KS: 22) stay on the
     // byte-plane dot4 kernel
     if (ks_mfma_enabled && ks_mfma_supported(p.ks_level)) {
         const KsMfmaGeom g = ks_mfma_geom(p.k * p.N, p.n + 1, p.ks_level, p.ks_base_log);
         const size_t bytes = (size_t)g.col_groups * g.steps * 8 * 1024;
-        HIP_TRY(hipMalloc((void**)&d_ksk_mfma, bytes));
-        hipLaunchKernelGGL(ksk_repack_mfma_kernel, dim3(g.col_groups, g.steps), dim3(64), 0, stream, d_ksk_std, d_ksk_mfma, g);
+        if (d_ksk_mfma.alloc(bytes)) return 1;
+        hipLaunchKernelGGL(ksk_repack_mfma_kernel, dim3(g.col_groups, g.steps), dim3(64), 0, stream, d_ksk_std.ptr, d_ksk_mfma.ptr, g);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));
     }
-    HIP_TRY(hipMalloc((void**)&d_fbsk, bsk_len * 8));   // N u64 -> N/2 c64: same byte count
+    if (d_fbsk.alloc(bsk_len * 8)) return 1;   // N u64 -> N/2 c64: same byte count
     if (convert_polys(d_std, d_fbsk, (uint32_t)(bsk_len / p.N))) return 1;
-    if (d_fbsk_dense) { HIP_TRY(hipFree(d_fbsk_dense)); d_fbsk_dense = nullptr; }
+    d_fbsk_dense.release();
     if (variant_large->dense_convert_fn) {      // the copy of the key in FftSwap9's order (N = 1024, k = 2: 54.7 MB): the dense kernel's
-        HIP_TRY(hipMalloc((void**)&d_fbsk_dense, bsk_len * 8));
+        if (d_fbsk_dense.alloc(bsk_len * 8)) return 1;
         uint32_t n_polys = (uint32_t)(bsk_len / p.N);
-        void* cargs[] = {(void*)&d_std, (void*)&d_fbsk_dense, (void*)&n_polys};
+        void* cargs[] = {(void*)&d_std, (void*)&d_fbsk_dense.ptr, (void*)&n_polys};
         HIP_TRY(hipLaunchKernel(variant_large->dense_convert_fn, dim3(n_polys), dim3(variant_large->dense_convert_threads), cargs, 0, stream));
         HIP_TRY(hipStreamSynchronize(stream));
     }
@@ -728,17 +681,14 @@ uint64_t fill_accumulator(const fhe_params_t& p, const uint64_t* table, std::vec
 int Engine::lut_upload(const uint64_t* acc, uint32_t* id) {
     if (use()) return 1;
     const size_t glwe = (size_t)(p.k + 1) * p.N;
-    if ((size_t)(n_luts + 1) * glwe * 8 > luts_cap) {
-        size_t new_cap = luts_cap ? luts_cap * 2 : 64 * glwe * 8;
-        uint64_t* nl = nullptr;
-        HIP_TRY(hipMalloc((void**)&nl, new_cap));
+    if ((size_t)(n_luts + 1) * glwe * 8 > d_luts.bytes) {      // grow and copy: the tables uploaded so far keep their ids
+        DeviceBuffer<uint64_t> nl;
+        if (nl.alloc(d_luts.bytes ? d_luts.bytes * 2 : 64 * glwe * 8)) return 1;
         if (d_luts) {
             if (sync_all_streams()) return 1;      // pipelined calls on the other streams may still read the old table array
             HIP_TRY(hipMemcpy(nl, d_luts, (size_t)n_luts * glwe * 8, hipMemcpyDeviceToDevice));
-            HIP_TRY(hipFree(d_luts));
         }
-        d_luts = nl;
-        luts_cap = new_cap;
+        d_luts = std::move(nl);
     }
     HIP_TRY(hipMemcpyAsync(d_luts + (size_t)n_luts * glwe, acc, glwe * 8, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -757,10 +707,46 @@ int Engine::lut_download(uint32_t id, uint64_t* acc) {
 
 int Engine::ensure_batch(uint32_t count) {
     const size_t big = (size_t)p.k * p.N + 1, small = (size_t)p.n + 1;
-    if (ensure((void**)&d_in, &cap_in, count * big * 8)) return 1;
-    if (ensure((void**)&d_out, &cap_out, count * big * 8)) return 1;
-    if (ensure((void**)&d_small, &cap_small, count * small * 8)) return 1;
-    if (ensure((void**)&d_idx, &cap_idx, (size_t)count * 4)) return 1;
+    return d_in.reserve(count * big * 8) || d_out.reserve(count * big * 8) || d_small.reserve(count * small * 8) || d_idx.reserve((size_t)count * 4);
+}
+
+// ---- matrix-core keyswitch: the host plan its two users share (launch_keyswitch, pack_lwes_dev) ------------------------
+// int8 matrix product on the matrix cores: digits -> A fragments, then 32x32x32 tiles over (samples, columns x planes, rows)
+struct KsMfmaLaunch {
+    uint32_t row_tiles, mt, gy;   // 32-sample tiles; of them per workgroup (64 mt threads); grid.y
+    uint32_t chunks, spc;         // K chunks (grid.z), K steps per chunk
+    size_t digit_bytes;           // A fragments of the batch
+    dim3 grid(const KsMfmaGeom& g) const { return dim3(g.col_groups, gy, chunks); }
+    void info(uint32_t out[5], uint32_t first, const KsMfmaGeom& g) const { out[0] = first; out[1] = mt; out[2] = chunks; out[3] = spc; out[4] = g.steps; }
+};
+static KsMfmaLaunch ks_mfma_plan(const KsMfmaGeom& g, uint32_t count, uint32_t base_log, int cu_count, uint32_t chunks_override) {
+    KsMfmaLaunch l{};
+    l.row_tiles = (count + 31) / 32;
+    l.digit_bytes = (size_t)l.row_tiles * g.steps * 1024;
+    l.mt = 1;
+    while (l.mt < 8 && l.mt < l.row_tiles) l.mt *= 2;
+    l.gy = (l.row_tiles + l.mt - 1) / l.mt;
+    // K split over workgroups: enough waves to fill the 1024 SIMDs about one and a half times, no more -- every extra
+    // chunk adds batch x columns 64-bit atomics (measured at 256 LWEs: 8 chunks 55 us, 32 chunks 89 us for memset +
+    // digits + product; scripts/ks_bench.py; the packing product: up to 63 atomics per (tile, column group) and chunk)
+    uint32_t chunks = (6u * (uint32_t)cu_count + g.col_groups * l.gy * l.mt / 2) / (g.col_groups * l.gy * l.mt);
+    if (chunks_override) chunks = chunks_override;      // FHESTR_KS_CHUNKS
+    chunks = std::max(1u, std::min(chunks, (g.steps + 7) / 8));
+    chunks = std::max(chunks, (g.steps + ks_mfma_max_steps(base_log) - 1) / ks_mfma_max_steps(base_log));   // int32 accumulators
+    l.spc = (g.steps + chunks - 1) / chunks;
+    l.chunks = (g.steps + l.spc - 1) / l.spc;
+    return l;
+}
+// The batch's digit fragments on stream s.  The buffer is zeroed when it is allocated and only grows: the pad slots stay
+// zero, rows past the batch are never read.  Another stream's launch may still read the allocation being replaced.
+static int ks_mfma_digits(Engine& e, DeviceBuffer<int8_t>& digits, const KsMfmaLaunch& l, const KsMfmaGeom& g, const uint64_t* d_lwes,
+                          uint32_t count, hipStream_t s) {
+    if (digits.bytes < l.digit_bytes) {
+        if (e.reserve_idle(digits, l.digit_bytes)) return 1;
+        HIP_TRY(hipMemsetAsync(digits, 0, l.digit_bytes, s));
+    }
+    KsDecomposeArgs da{d_lwes, digits, g, count};
+    hipLaunchKernelGGL(ks_decompose_kernel, dim3((2 * g.steps + 255) / 256, count), dim3(256), 0, s, da);
     return 0;
 }
 
@@ -772,62 +758,35 @@ int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t cou
     const uint32_t in_dim = p.k * p.N, out_size = p.n + 1;
     HIP_TRY(hipMemsetAsync(d_sm, 0, (size_t)count * out_size * 8, s));
     if (d_ksk_mfma && !shadow) {
-        // int8 matrix product on the matrix cores: digits -> A fragments, then 32x32x32 tiles over (samples, columns x planes, rows)
         const KsMfmaGeom g = ks_mfma_geom(in_dim, out_size, p.ks_level, p.ks_base_log);
-        const uint32_t row_tiles = (count + 31) / 32;
-        const size_t need = (size_t)row_tiles * g.steps * 1024;
-        int8_t*& digits = digits_slot ? ovl_digits[digits_slot] : d_ks_digits;     // own buffer per overlapped stream
-        size_t& cap_digits = digits_slot ? ovl_cap_digits[digits_slot] : cap_ks_digits;
-        if (need > cap_digits) {
-            if (digits) { if (sync_all_streams()) return 1; HIP_TRY(hipFree(digits)); }
-            digits = nullptr; cap_digits = 0;
-            HIP_TRY(hipMalloc((void**)&digits, need));
-            HIP_TRY(hipMemsetAsync(digits, 0, need, s));
-            cap_digits = need;
+        const KsMfmaLaunch l = ks_mfma_plan(g, count, p.ks_base_log, cu_count, ks_chunks_override);
+        DeviceBuffer<int8_t>& digits = digits_slot ? ovl_digits[digits_slot] : d_ks_digits;     // own buffer per overlapped stream
+        if (ks_mfma_digits(*this, digits, l, g, d_big, count, s)) return 1;
+        KsMfmaArgs ma{d_big, d_ksk_mfma, digits, d_sm, g, count, l.row_tiles, l.spc};
+        switch (l.mt) {
+            case 1: hipLaunchKernelGGL(keyswitch_mfma_kernel<1>, l.grid(g), dim3(64), 0, s, ma); break;
+            case 2: hipLaunchKernelGGL(keyswitch_mfma_kernel<2>, l.grid(g), dim3(128), 0, s, ma); break;
+            case 4: hipLaunchKernelGGL(keyswitch_mfma_kernel<4>, l.grid(g), dim3(256), 0, s, ma); break;
+            default: hipLaunchKernelGGL(keyswitch_mfma_kernel<8>, l.grid(g), dim3(512), 0, s, ma); break;
         }
-        KsDecomposeArgs da{d_big, digits, g, count};
-        hipLaunchKernelGGL(ks_decompose_kernel, dim3((2 * g.steps + 255) / 256, count), dim3(256), 0, s, da);
-        uint32_t mt = 1;
-        while (mt < 8 && mt < row_tiles) mt *= 2;
-        const uint32_t gy = (row_tiles + mt - 1) / mt;
-        // K split over workgroups: enough waves to fill the 1024 SIMDs about one and a half times, no more -- every extra
-        // chunk adds batch x columns 64-bit atomics (measured at 256 LWEs: 8 chunks 55 us, 32 chunks 89 us for memset +
-        // digits + product; scripts/ks_bench.py)
-        uint32_t chunks = (6u * (uint32_t)cu_count + g.col_groups * gy * mt / 2) / (g.col_groups * gy * mt);
-        if (ks_chunks_override) chunks = ks_chunks_override;
-        chunks = std::max(1u, std::min(chunks, (g.steps + 7) / 8));
-        chunks = std::max(chunks, (g.steps + ks_mfma_max_steps(p.ks_base_log) - 1) / ks_mfma_max_steps(p.ks_base_log));   // int32 accumulators
-        const uint32_t spc = (g.steps + chunks - 1) / chunks;
-        chunks = (g.steps + spc - 1) / spc;
-        KsMfmaArgs ma{d_big, d_ksk_mfma, digits, d_sm, g, count, row_tiles, spc};
-        const dim3 grid(g.col_groups, gy, chunks);
-        switch (mt) {
-            case 1: hipLaunchKernelGGL(keyswitch_mfma_kernel<1>, grid, dim3(64), 0, s, ma); break;
-            case 2: hipLaunchKernelGGL(keyswitch_mfma_kernel<2>, grid, dim3(128), 0, s, ma); break;
-            case 4: hipLaunchKernelGGL(keyswitch_mfma_kernel<4>, grid, dim3(256), 0, s, ma); break;
-            default: hipLaunchKernelGGL(keyswitch_mfma_kernel<8>, grid, dim3(512), 0, s, ma); break;
-        }
-        ks_last[0] = FHE_KS_KERNEL_MFMA; ks_last[1] = mt; ks_last[2] = chunks; ks_last[3] = spc; ks_last[4] = g.steps;
+        l.info(ks_last, FHE_KS_KERNEL_MFMA, g);
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    if (d_ksk_packed) {
-        KeyswitchPackedArgs pa{d_big, d_ksk_packed, d_ksk_rowsum, d_sm, in_dim, out_size, p.ks_base_log, p.ks_level, count};
-        if (shadow) {     // small-register variant: co-resident with the blind rotation of the previous batch
-            constexpr int S = 4;
-            dim3 pgrid((out_size + KS_COLS - 1) / KS_COLS, (count + S - 1) / S, (in_dim + KS_IC - 1) / KS_IC);
-            hipLaunchKernelGGL((keyswitch_dot4_kernel<S, 8>), pgrid, dim3(KS_COLS), (size_t)KS_IC * p.ks_level * S, s, pa);
-            ks_last[0] = FHE_KS_KERNEL_DOT4_SHADOW; ks_last[1] = S; ks_last[2] = pgrid.z; ks_last[3] = KS_IC; ks_last[4] = in_dim;
-            HIP_TRY(hipGetLastError());
-            return 0;
-        }
-        dim3 pgrid((out_size + KS_COLS - 1) / KS_COLS, (count + KSD_S - 1) / KSD_S, (in_dim + KS_IC - 1) / KS_IC);
-        hipLaunchKernelGGL((keyswitch_dot4_kernel<KSD_S, 2>), pgrid, dim3(KS_COLS), (size_t)KS_IC * p.ks_level * KSD_S, s, pa);
-        ks_last[0] = FHE_KS_KERNEL_DOT4; ks_last[1] = KSD_S; ks_last[2] = pgrid.z; ks_last[3] = KS_IC; ks_last[4] = in_dim;
+    KeyswitchPackedArgs pa{d_big, d_ksk_packed, d_ksk_rowsum, d_sm, in_dim, out_size, p.ks_base_log, p.ks_level, count};
+    if (shadow) {     // small-register variant: co-resident with the blind rotation of the previous batch
+        constexpr int S = 4;
+        dim3 pgrid((out_size + KS_COLS - 1) / KS_COLS, (count + S - 1) / S, (in_dim + KS_IC - 1) / KS_IC);
+        hipLaunchKernelGGL((keyswitch_dot4_kernel<S, 8>), pgrid, dim3(KS_COLS), (size_t)KS_IC * p.ks_level * S, s, pa);
+        ks_last[0] = FHE_KS_KERNEL_DOT4_SHADOW; ks_last[1] = S; ks_last[2] = pgrid.z; ks_last[3] = KS_IC; ks_last[4] = in_dim;
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    return fail("keyswitch key not installed");
+    dim3 pgrid((out_size + KS_COLS - 1) / KS_COLS, (count + KSD_S - 1) / KSD_S, (in_dim + KS_IC - 1) / KS_IC);
+    hipLaunchKernelGGL((keyswitch_dot4_kernel<KSD_S, 2>), pgrid, dim3(KS_COLS), (size_t)KS_IC * p.ks_level * KSD_S, s, pa);
+    ks_last[0] = FHE_KS_KERNEL_DOT4; ks_last[1] = KSD_S; ks_last[2] = pgrid.z; ks_last[3] = KS_IC; ks_last[4] = in_dim;
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // ---- packing keyswitch (packing_ks_kernels.hip.h) ---------------------------------------------------------------------
@@ -837,26 +796,22 @@ int Engine::load_packing_key(const fhe_packing_params_t& pp, const uint64_t* pks
     if (use()) return 1;
     if (packing_params_check(p, pp)) return 1;
     if (sync_all_streams()) return 1;                       // a launch in flight may still read the previous key or its digits
-    if (d_pksk_mfma) { HIP_TRY(hipFree(d_pksk_mfma)); d_pksk_mfma = nullptr; }
-    if (d_pack_digits) { HIP_TRY(hipFree(d_pack_digits)); d_pack_digits = nullptr; }   // the pad slots depend on the level count
-    cap_pack_digits = 0;
+    const char* const who = "load_packing_key";
+    d_pksk_mfma.release();
+    d_pack_digits.release();      // the pad slots depend on the level count
     for (auto& w : pack_last) w = 0;
     const KsMfmaGeom g = ks_mfma_geom(p.k * p.N, (p.k + 1) * p.N, pp.level, pp.base_log);
     const size_t words = (size_t)g.in_dim * pp.level * g.out_size;
-    uint64_t* d_std = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_std, words * 8));
-    hipError_t e = hipMalloc((void**)&d_pksk_mfma, (size_t)g.col_groups * g.steps * 8 * 1024);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_std, pksk, words * 8, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(ksk_repack_mfma_kernel, dim3(g.col_groups, g.steps), dim3(64), 0, stream, d_std, d_pksk_mfma, g);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_std);
-    if (e != hipSuccess) {
-        if (d_pksk_mfma) { (void)hipFree(d_pksk_mfma); d_pksk_mfma = nullptr; }
-        return fail(std::string("load_packing_key: ") + hipGetErrorString(e));
-    }
+    DeviceBuffer<uint64_t> d_std;
+    DeviceBuffer<int8_t> planes;      // becomes the resident key only once it is complete
+    if (d_std.alloc(words * 8)) return 1;
+    if (under(who, planes.alloc((size_t)g.col_groups * g.steps * 8 * 1024)) ||
+        under(who, hipMemcpyAsync(d_std, pksk, words * 8, hipMemcpyHostToDevice, stream)))
+        return 1;
+    hipLaunchKernelGGL(ksk_repack_mfma_kernel, dim3(g.col_groups, g.steps), dim3(64), 0, stream, d_std.ptr, planes.ptr, g);
+    if (under(who, hipGetLastError()) || under(who, hipStreamSynchronize(stream))) return 1;
+    d_std.release();      // the 64-bit layout (3.2 GB at N = 8192) goes as soon as the repack is done
+    d_pksk_mfma = std::move(planes);
     pack_pp = pp;
     return 0;
 }
@@ -878,37 +833,16 @@ int Engine::pack_lwes_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_glw
     const KsMfmaGeom g = ks_mfma_geom(in_dim, out_size, pack_pp.level, pack_pp.base_log);
     const uint32_t n_glwe = (count + p.N - 1) / p.N;
     HIP_TRY(hipMemsetAsync(d_glwes, 0, (size_t)n_glwe * out_size * 8, stream));
-    const uint32_t row_tiles = (count + 31) / 32;
-    const size_t need = (size_t)row_tiles * g.steps * 1024;
-    if (need > cap_pack_digits) {
-        if (d_pack_digits) { if (sync_all_streams()) return 1; HIP_TRY(hipFree(d_pack_digits)); }
-        d_pack_digits = nullptr; cap_pack_digits = 0;
-        HIP_TRY(hipMalloc((void**)&d_pack_digits, need));
-        HIP_TRY(hipMemsetAsync(d_pack_digits, 0, need, stream));
-        cap_pack_digits = need;
+    const KsMfmaLaunch l = ks_mfma_plan(g, count, pack_pp.base_log, cu_count, ks_chunks_override);
+    if (ks_mfma_digits(*this, d_pack_digits, l, g, d_cts, count, stream)) return 1;
+    PackKsArgs pa{d_cts, d_pksk_mfma, d_pack_digits, d_glwes, g, count, l.row_tiles, l.spc, p.N, p.k * p.N / 32};
+    switch (l.mt) {
+        case 1: hipLaunchKernelGGL(packing_ks_mfma_kernel<1>, l.grid(g), dim3(64), 0, stream, pa); break;
+        case 2: hipLaunchKernelGGL(packing_ks_mfma_kernel<2>, l.grid(g), dim3(128), 0, stream, pa); break;
+        case 4: hipLaunchKernelGGL(packing_ks_mfma_kernel<4>, l.grid(g), dim3(256), 0, stream, pa); break;
+        default: hipLaunchKernelGGL(packing_ks_mfma_kernel<8>, l.grid(g), dim3(512), 0, stream, pa); break;
     }
-    KsDecomposeArgs da{d_cts, d_pack_digits, g, count};
-    hipLaunchKernelGGL(ks_decompose_kernel, dim3((2 * g.steps + 255) / 256, count), dim3(256), 0, stream, da);
-    uint32_t mt = 1;
-    while (mt < 8 && mt < row_tiles) mt *= 2;
-    const uint32_t gy = (row_tiles + mt - 1) / mt;
-    // K chunks as for the keyswitch (launch_keyswitch): fill the SIMDs about one and a half times; every chunk costs up to
-    // 63 atomics per (tile, column group).  FHESTR_KS_CHUNKS overrides; the int32 accumulators bound the chunk length.
-    uint32_t chunks = (6u * (uint32_t)cu_count + g.col_groups * gy * mt / 2) / (g.col_groups * gy * mt);
-    if (ks_chunks_override) chunks = ks_chunks_override;
-    chunks = std::max(1u, std::min(chunks, (g.steps + 7) / 8));
-    chunks = std::max(chunks, (g.steps + ks_mfma_max_steps(pack_pp.base_log) - 1) / ks_mfma_max_steps(pack_pp.base_log));
-    const uint32_t spc = (g.steps + chunks - 1) / chunks;
-    chunks = (g.steps + spc - 1) / spc;
-    PackKsArgs pa{d_cts, d_pksk_mfma, d_pack_digits, d_glwes, g, count, row_tiles, spc, p.N, p.k * p.N / 32};
-    const dim3 grid(g.col_groups, gy, chunks);
-    switch (mt) {
-        case 1: hipLaunchKernelGGL(packing_ks_mfma_kernel<1>, grid, dim3(64), 0, stream, pa); break;
-        case 2: hipLaunchKernelGGL(packing_ks_mfma_kernel<2>, grid, dim3(128), 0, stream, pa); break;
-        case 4: hipLaunchKernelGGL(packing_ks_mfma_kernel<4>, grid, dim3(256), 0, stream, pa); break;
-        default: hipLaunchKernelGGL(packing_ks_mfma_kernel<8>, grid, dim3(512), 0, stream, pa); break;
-    }
-    pack_last[0] = 1; pack_last[1] = mt; pack_last[2] = chunks; pack_last[3] = spc; pack_last[4] = g.steps;
+    l.info(pack_last, 1, g);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -918,11 +852,7 @@ int Engine::pack_lwes_host(const uint64_t* cts, uint32_t count, uint64_t* glwes)
     if (!d_pksk_mfma) return fail("packing key not loaded");
     if (count == 0) return 0;
     const size_t big = (size_t)p.k * p.N + 1, out_words = (size_t)((count + p.N - 1) / p.N) * (p.k + 1) * p.N;
-    if (cap_pack_in < count * big * 8 || cap_pack_out < out_words * 8) {
-        if (sync_all_streams()) return 1;
-        if (ensure((void**)&d_pack_in, &cap_pack_in, count * big * 8)) return 1;
-        if (ensure((void**)&d_pack_out, &cap_pack_out, out_words * 8)) return 1;
-    }
+    if (reserve_idle(d_pack_in, count * big * 8) || reserve_idle(d_pack_out, out_words * 8)) return 1;
     HIP_TRY(hipMemcpyAsync(d_pack_in, cts, count * big * 8, hipMemcpyHostToDevice, stream));
     if (pack_lwes_dev(d_pack_in, count, d_pack_out)) return 1;
     HIP_TRY(hipMemcpyAsync(glwes, d_pack_out, out_words * 8, hipMemcpyDeviceToHost, stream));
@@ -966,11 +896,8 @@ int Engine::unpack_glwes_dev(const uint64_t* d_glwes, uint32_t first, uint32_t c
     fill_accumulator(table.data(), acc);
     uint32_t id = 0;
     if (lut_upload_dedup(acc, &id)) return 1;
-    if ((size_t)count * 4 > cap_unpack_idx) {
-        if (d_unpack_idx && sync_all_streams()) return 1;   // an earlier refresh may still read the smaller array
-        if (ensure((void**)&d_unpack_idx, &cap_unpack_idx, (size_t)count * 4)) return 1;
-    }
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_unpack_idx, (int)id, count, stream));
+    if (reserve_idle(d_unpack_idx, (size_t)count * 4)) return 1;   // an earlier refresh may still read the smaller array
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_unpack_idx.ptr, (int)id, count, stream));
     if (ks_pbs_dev(d_cts, d_unpack_idx, d_cts, count)) return 1;   // the keyswitch has read every row before the rotation writes one
     unpack_last[3] = 1;
     return 0;
@@ -982,11 +909,7 @@ int Engine::unpack_glwes_host(const uint64_t* glwes, uint32_t first, uint32_t co
     const size_t big = (size_t)p.k * p.N + 1, glwe_len = (size_t)(p.k + 1) * p.N;
     const uint64_t g_lo = first / p.N, g_hi = ((uint64_t)first + count - 1) / p.N;      // only the GLWEs the range touches go up
     const size_t in_words = (size_t)(g_hi - g_lo + 1) * glwe_len;
-    if (cap_unpack_in < in_words * 8 || cap_unpack_out < count * big * 8) {
-        if (sync_all_streams()) return 1;
-        if (ensure((void**)&d_unpack_in, &cap_unpack_in, in_words * 8)) return 1;
-        if (ensure((void**)&d_unpack_out, &cap_unpack_out, count * big * 8)) return 1;
-    }
+    if (reserve_idle(d_unpack_in, in_words * 8) || reserve_idle(d_unpack_out, count * big * 8)) return 1;
     HIP_TRY(hipMemcpyAsync(d_unpack_in, glwes + (size_t)g_lo * glwe_len, in_words * 8, hipMemcpyHostToDevice, stream));
     if (unpack_glwes_dev(d_unpack_in, first % p.N, count, refresh, d_unpack_out)) return 1;
     HIP_TRY(hipMemcpyAsync(cts, d_unpack_out, count * big * 8, hipMemcpyDeviceToHost, stream));
@@ -1048,13 +971,13 @@ static int rotate_overlapped(Engine& e, const BrVariant* w, BlindRotateArgs a, h
 
 static int rotate_multibit_combined(Engine& e, const BrVariant* v, const BlindRotateArgs& a) {
     const size_t groups = e.p.n / e.p.grouping_factor;
-    if (ensure(&e.d_ws, &e.cap_ws, (size_t)a.batch * groups * v->combined_bytes)) return 1;
-    MultiBitCombineArgs ca{a, reinterpret_cast<double2*>(e.d_ws)};
+    if (e.d_ws.reserve((size_t)a.batch * groups * v->combined_bytes)) return 1;
+    MultiBitCombineArgs ca{a, reinterpret_cast<double2*>(e.d_ws.ptr)};
     void* cargs[] = {(void*)&ca};
     HIP_TRY(hipLaunchKernel(v->combine_fn, dim3((unsigned)groups, (unsigned)v->combine_grid_y, (a.batch + v->combine_chunk - 1) / v->combine_chunk),
                             dim3(v->threads), cargs, v->combine_lds, e.stream));
     BlindRotateArgs b = a;
-    b.fbsk = reinterpret_cast<const double*>(e.d_ws);
+    b.fbsk = reinterpret_cast<const double*>(e.d_ws.ptr);
     void* bargs[] = {(void*)&b};
     HIP_TRY(hipLaunchKernel(v->rotate_combined_fn, dim3(a.batch), dim3(v->threads), bargs, rotate_lds(v, e.p), e.stream));
     return 0;
@@ -1070,23 +993,23 @@ static int rotate_multibit_two_kernel(Engine& e, const BrVariant* v, const Blind
     if (cap == 0) {       // automatic: half of what is free now (plus what the workspace already holds), at most 64 GB
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        cap = std::min<size_t>((size_t)64 << 30, (free_b + e.cap_ws) / 2);
+        cap = std::min<size_t>((size_t)64 << 30, (free_b + e.d_ws.bytes) / 2);
     }
     const uint32_t sub_max = (uint32_t)std::max<size_t>(1, std::min<size_t>(count, cap / (per_lwe + rot_ws)));
-    if (ensure(&e.d_ws, &e.cap_ws, (size_t)sub_max * (per_lwe + rot_ws))) return 1;
-    unsigned char* rot_base = reinterpret_cast<unsigned char*>(e.d_ws) + (size_t)sub_max * per_lwe;
+    if (e.d_ws.reserve((size_t)sub_max * (per_lwe + rot_ws))) return 1;
+    unsigned char* rot_base = e.d_ws + (size_t)sub_max * per_lwe;
     const uint32_t logN = (uint32_t)v->logN, ggsw_elems = (uint32_t)(v->combined_bytes / 16);
     const size_t combine_lds = ((size_t)(1u << ((logN + 1) / 2)) + (size_t)(1u << (logN + 1 - (logN + 1) / 2))) * 16;
     const size_t big = (size_t)p.k * p.N + 1;
     for (uint32_t first = 0; first < count; first += sub_max) {
         const uint32_t sub = std::min(sub_max, count - first);
-        MultiBitCombineGenericArgs ca{a.lwe_small + (size_t)first * (p.n + 1), reinterpret_cast<const double2*>(e.d_fbsk), e.d_slot_exp,
-                                      reinterpret_cast<double2*>(e.d_ws), p.n, logN, p.N / 2, ggsw_elems, sub};
+        MultiBitCombineGenericArgs ca{a.lwe_small + (size_t)first * (p.n + 1), reinterpret_cast<const double2*>(e.d_fbsk.ptr), e.d_slot_exp,
+                                      reinterpret_cast<double2*>(e.d_ws.ptr), p.n, logN, p.N / 2, ggsw_elems, sub};
         void* cargs[] = {(void*)&ca};
         HIP_TRY(hipLaunchKernel(v->combine_generic_fn, dim3((unsigned)groups, (ggsw_elems + 511) / 512, (sub + 7) / 8), dim3(256),
                                 cargs, combine_lds, e.stream));
         BlindRotateLargeArgs la{{a.lwe_small + (size_t)first * (p.n + 1), a.lut_idx ? a.lut_idx + first : nullptr, a.luts,
-                                 reinterpret_cast<const double*>(e.d_ws), a.lwe_out + (size_t)first * big, p.n, p.pbs_base_log, sub,
+                                 reinterpret_cast<const double*>(e.d_ws.ptr), a.lwe_out + (size_t)first * big, p.n, p.pbs_base_log, sub,
                                  p.grouping_factor}, rot_base};
         void* largs[] = {v->large ? (void*)&la : (void*)&la.base};      // the HBM-workspace kernels take theirs behind the same arguments
         HIP_TRY(hipLaunchKernel(v->extprod_fn, dim3(sub), dim3(v->threads), largs, rotate_lds(v, p), e.stream));
@@ -1103,15 +1026,15 @@ static int rotate_multi_cu(Engine& e, const BlindRotateArgs& a, const void* fn, 
     const uint32_t max_clusters = std::min<uint32_t>((uint32_t)CLUSTER_MAX, ((uint32_t)e.cu_count / quantum) * 8 * rounds);
     const uint32_t grid = (std::min(a.batch, max_clusters) + 7) / 8 * quantum;
     if (grid <= (uint32_t)e.cu_count) lds = std::max(lds, lds_one_per_cu);
-    if (ensure(&e.d_cluster_ws, &e.cap_cluster_ws, (size_t)max_clusters * ws_per_cluster)) return 1;
+    if (e.d_cluster_ws.reserve((size_t)max_clusters * ws_per_cluster)) return 1;
     if (!e.d_cluster_ctl) {
-        HIP_TRY(hipMalloc((void**)&e.d_cluster_ctl, sizeof(ClusterCtl) + sizeof(ClusterStatus)));
+        if (e.d_cluster_ctl.alloc(sizeof(ClusterCtl) + sizeof(ClusterStatus))) return 1;
         HIP_TRY(hipMemsetAsync(e.d_cluster_ctl, 0, sizeof(ClusterCtl) + sizeof(ClusterStatus), e.stream));
     }
     // tickets and flags start from zero; the status words behind them are sticky (read by cluster_status())
     HIP_TRY(hipMemsetAsync(e.d_cluster_ctl, 0, sizeof(ClusterCtl), e.stream));
-    ClusterCtl* ctl = reinterpret_cast<ClusterCtl*>(e.d_cluster_ctl);
-    BlindRotateClusterArgs ka{a, reinterpret_cast<unsigned char*>(e.d_cluster_ws), ctl, reinterpret_cast<ClusterStatus*>(ctl + 1),
+    ClusterCtl* ctl = static_cast<ClusterCtl*>(e.d_cluster_ctl.ptr);
+    BlindRotateClusterArgs ka{a, e.d_cluster_ws, ctl, reinterpret_cast<ClusterStatus*>(ctl + 1),
                               e.cluster_spin_limit, e.cluster_test_fault};
     void* kargs[] = {(void*)&ka};
     HIP_TRY(hipLaunchKernel(fn, dim3(grid), dim3(threads), kargs, lds, e.stream));
@@ -1133,8 +1056,8 @@ static int rotate_whole_xcd(Engine& e, const BrVariant* v, const BlindRotateArgs
 }
 
 static int rotate_large(Engine& e, const BrVariant* v, const BlindRotateArgs& a) {
-    if (ensure(&e.d_ws, &e.cap_ws, (size_t)a.batch * v->ws_bytes)) return 1;
-    BlindRotateLargeArgs la{a, reinterpret_cast<unsigned char*>(e.d_ws)};
+    if (e.d_ws.reserve((size_t)a.batch * v->ws_bytes)) return 1;
+    BlindRotateLargeArgs la{a, e.d_ws};
     void* largs[] = {(void*)&la};
     HIP_TRY(hipLaunchKernel(v->rotate_fn, dim3(a.batch), dim3(v->threads), largs, rotate_lds(v, e.p), e.stream));
     return 0;
@@ -1210,7 +1133,7 @@ int Engine::ks_pbs_dev(const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint
     if (use()) return 1;
     if (count == 0) return 0;
     const size_t small = (size_t)p.n + 1;
-    if (ensure((void**)&d_small, &cap_small, count * small * 8)) return 1;
+    if (d_small.reserve(count * small * 8)) return 1;
     // HIP events on the launch stream: per-call kernel durations without host synchronisation
     constexpr size_t RING = 1024;
     if (ring.empty()) {
@@ -1241,7 +1164,7 @@ int Engine::ks_pbs_dev(const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint
             if (!ovl_done[q]) HIP_TRY(hipEventCreateWithFlags(&ovl_done[q], hipEventDisableTiming));
         const int slot = (int)(pipe_calls % (uint64_t)ns);
         hipStream_t s = slot == 0 ? stream : slot == 1 ? ks_stream : ovl_stream[slot];
-        if (ensure((void**)&ovl_small[slot], &ovl_cap_small[slot], count * small * 8)) return 1;
+        if (ovl_small[slot].reserve(count * small * 8)) return 1;
         uint64_t* sm = ovl_small[slot];
         const size_t big = (size_t)p.k * p.N + 1;
         const char *in_lo = (const char*)d_big_in, *in_hi = in_lo + (size_t)count * big * 8;
@@ -1290,7 +1213,7 @@ int Engine::ks_pbs_dev(const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint
             HIP_TRY(hipStreamCreateWithFlags(&ks_stream, hipStreamNonBlocking));
             for (auto& e : pipe_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
-        if (ensure((void**)&d_small2, &cap_small2, count * small * 8)) return 1;
+        if (d_small2.reserve(count * small * 8)) return 1;
         const int slot = (int)(pipe_calls & 1);
         uint64_t* sm = slot ? d_small2 : d_small;
         const size_t big = (size_t)p.k * p.N + 1;
@@ -1394,7 +1317,7 @@ int Engine::pbs_ks_host(const uint64_t* in_small, const uint32_t* lut_idx, uint6
     if (check_lut_idx(lut_idx, count)) return 1;
     if (ensure_batch(count)) return 1;
     const size_t small = (size_t)p.n + 1;
-    if (ensure((void**)&d_small2, &cap_small2, count * small * 8)) return 1;
+    if (d_small2.reserve(count * small * 8)) return 1;
     HIP_TRY(hipMemcpyAsync(d_small, in_small, count * small * 8, hipMemcpyHostToDevice, stream));
     if (lut_idx) HIP_TRY(hipMemcpyAsync(d_idx, lut_idx, (size_t)count * 4, hipMemcpyHostToDevice, stream));
     if (launch_blind_rotate(d_small, lut_idx ? d_idx : nullptr, d_out, count)) return 1;
@@ -1443,15 +1366,14 @@ int Engine::lincomb_host(const uint64_t* pool, uint32_t pool_count, const uint32
     const uint32_t terms = off[jobs];
     for (uint32_t t = 0; t < terms; t++)
         if (src[t] >= pool_count) return fail("lincomb source index out of range");
-    if (ensure((void**)&d_pool, &cap_pool, (size_t)pool_count * big * 8)) return 1;
-    if (ensure((void**)&d_out, &cap_out, (size_t)jobs * big * 8)) return 1;
+    if (d_pool.reserve((size_t)pool_count * big * 8) || d_out.reserve((size_t)jobs * big * 8)) return 1;
     // meta: off | src | coeff | cst (8-byte aligned)
     const size_t o_off = 0, o_src = o_off + ((size_t)(jobs + 1) * 4 + 7) / 8 * 8;
     const size_t o_coeff = o_src + ((size_t)terms * 4 + 7) / 8 * 8;
     const size_t o_cst = o_coeff + ((size_t)terms * 4 + 7) / 8 * 8;
     const size_t meta_bytes = o_cst + (size_t)jobs * 8;
-    if (ensure((void**)&d_meta, &cap_meta, meta_bytes)) return 1;
-    unsigned char* m = reinterpret_cast<unsigned char*>(d_meta);
+    if (d_meta.reserve(meta_bytes)) return 1;
+    unsigned char* m = d_meta;
     HIP_TRY(hipMemcpyAsync(d_pool, pool, (size_t)pool_count * big * 8, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyAsync(m + o_off, off, (size_t)(jobs + 1) * 4, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyAsync(m + o_src, src, (size_t)terms * 4, hipMemcpyHostToDevice, stream));
@@ -1535,7 +1457,7 @@ void Engine::end_pipeline_run() {
 int Engine::cluster_settle(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big, uint32_t count) {
     if (!cluster_fallback) { cluster_unchecked = true; return 0; }
     ClusterStatus st{};
-    ClusterStatus* d_st = reinterpret_cast<ClusterStatus*>(reinterpret_cast<ClusterCtl*>(d_cluster_ctl) + 1);
+    ClusterStatus* d_st = reinterpret_cast<ClusterStatus*>(static_cast<ClusterCtl*>(d_cluster_ctl.ptr) + 1);
     HIP_TRY(hipMemcpyAsync(&st, d_st, sizeof(st), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     cluster_last = st.clusters;
@@ -1549,11 +1471,11 @@ int Engine::cluster_settle(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint
 int Engine::cluster_check() {
     if (!cluster_unchecked || !d_cluster_ctl) return 0;
     ClusterStatus st{};
-    HIP_TRY(hipMemcpy(&st, reinterpret_cast<ClusterCtl*>(d_cluster_ctl) + 1, sizeof(st), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&st, static_cast<ClusterCtl*>(d_cluster_ctl.ptr) + 1, sizeof(st), hipMemcpyDeviceToHost));
     cluster_unchecked = false;
     cluster_last = st.clusters;
     if (st.error) {
-        HIP_TRY(hipMemset(reinterpret_cast<ClusterCtl*>(d_cluster_ctl) + 1, 0, sizeof(st)));
+        HIP_TRY(hipMemset(static_cast<ClusterCtl*>(d_cluster_ctl.ptr) + 1, 0, sizeof(st)));
         return fail("blind_rotate_cluster_kernel: a cluster hand-over timed out (code " + std::to_string(st.error) +
                     "); results of that launch are invalid");
     }

@@ -12,6 +12,7 @@ fhe_engine_unpack_info, so a host fallback could not pass.
                             within 15 % of fhe_packing_unpack_noise's out[0] * V_pbs
   test_refresh              refreshed blocks decrypt to the inputs, a second PBS on them stays within the parity tests'
                             8 sigma; the refusals (no packing key; a decomposition the model puts above the budget)
+  test_refresh_index_array_grows  refreshes of 3, 40, 3 blocks on one engine: the table-index array is allocated, grown, reused
   test_end_to_end_p22       contains(to_upper(hay, packed=True), pat) with the packed result passed straight back in,
                             op_many over packed rows, packed=True on a packed operand"""
 import functools
@@ -261,6 +262,24 @@ def test_refresh():
     print(f"refresh {P.name} pp={pp}: raw block {nominal:.2f} nominal (budget {budget:.1f}); max phase error after the refresh {e1:.3e}, "
           f"after a second PBS {e2:.3e}, 8 sigma {tol:.3e}")
     assert e1 <= tol and e2 <= tol
+
+
+def test_refresh_index_array_grows():
+    """The refresh keeps one table index per block of its largest batch so far.  An engine of its own: the shared twin's
+    first refresh already has 70 blocks."""
+    rig = _Rig(TWIN, 0x5EED0C60)
+    try:
+        P, eng, ck = rig.P, rig.eng, rig.ck
+        rig.packing_key()
+        msgs = (np.arange(40) * 3 + 2) % (P.msg_mod * P.carry_mod)
+        glwes = eng.pack(ck.encrypt(msgs))
+        for count in (3, 40, 3):
+            fresh = eng.unpack(glwes, count)
+            assert eng.unpack_info() == {"ran": True, "rows": count, "workgroups": _workgroups(P.N, P.k, count), "refreshed": True}
+            assert np.array_equal(ck.decrypt(fresh), msgs[:count])
+    finally:
+        rig.eng.close()
+        rig.ck.close()
 
 
 def test_refresh_refused_above_the_budget():

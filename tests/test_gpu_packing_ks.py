@@ -11,9 +11,13 @@ kernel can still go wrong:
   test_levels_and_chunks    (7, 2), (3, 5), (1, 16) x FHESTR_KS_CHUNKS = 1, the clamped maximum, a last chunk shorter than DEPTH
   test_edge_material        edge key x edge rows: accumulator columns at their extreme magnitude and sign
   test_buffer_reuse         2 N + 37, 5, 2 N + 37 LWEs on one engine
+  test_key_replaced_digits_grown  (7, 2) then (3, 5) on one engine: the first key's digit buffer is dropped, the second's is
+                            allocated for 5 LWEs, grown for 2 N + 37, reused for 5
   test_n8192_three_levels   the default (7, 3) of the N = 8192 sets: a 3.2 GB key, 3.4 GB of digit planes, sparse masks
   test_device_path          pack_lwes_dev on the buffer fhe_ks_pbs_batch_dev just wrote = the host loop on the downloaded
                             LWEs (fhe_packing_keyswitch_host) = the host-array entry point; also with throughput mode 1 on
+  test_host_staging_grows_under_throughput_mode  the host-array entry point grows its staging while a pipelined call's
+                            streams are live, then reuses it
   test_engine_close_...     the packed route's cached plans are destroyed before their engine
   test_end_to_end           toy-n twin of PARAM_MESSAGE_2_CARRY_2, device-generated server keys: to_lower and eq with
                             packed=True, decrypt_packed = Python bytes semantics = the unpacked run's decryption"""
@@ -51,15 +55,21 @@ class _Rig:
 
     def __init__(self, monkeypatch, p, pp, env, key):
         import fhestr
-        self.p, self.pp = p, pp
-        rng = np.random.default_rng(_seed(p, pp, 77))
-        self.key = (edge_pksk(p, pp, rng) if key == "edge" else
-                    rng.integers(0, 2**64, size=(p.k * p.N * pp[1], p.k + 1, p.N), dtype=np.uint64))
+        self.p = p
         for name, value in env:
             monkeypatch.setenv(name, str(value))
         self.eng = fhestr.Engine(_fp(p), 0)
         assert not self.eng.packing_info()["ran"]
+        self.load(pp, key)
+
+    def load(self, pp, key="uniform"):
+        """A key for the decomposition pp, replacing whatever the engine held; nothing has run under it yet."""
+        p, self.pp = self.p, pp
+        rng = np.random.default_rng(_seed(p, pp, 77))
+        self.key = (edge_pksk(p, pp, rng) if key == "edge" else
+                    rng.integers(0, 2**64, size=(p.k * p.N * pp[1], p.k + 1, p.N), dtype=np.uint64))
         self.eng.load_packing_key(pp, self.key)
+        assert not self.eng.packing_info()["ran"]
         self.ref = ExactPacking(p, pp, self.key)
 
     def inputs(self, B, salt=0):
@@ -223,6 +233,19 @@ def test_buffer_reuse(monkeypatch):
         _check(rig, B, "buffer_reuse", salt=salt + 1)
 
 
+def test_key_replaced_digits_grown(monkeypatch):
+    """The digit fragments' pad slots depend on the level count: a new key drops the buffer.  test_buffer_reuse starts at its
+    largest batch; here the buffer of the second key starts small and has to grow."""
+    rig = _Rig(monkeypatch, K5, (7, 2), (), "uniform")       # an engine of its own: the shared rigs keep their key
+    try:
+        _check(rig, 5, "key_replaced_digits_grown")
+        rig.load((3, 5))
+        for salt, B in enumerate((5, 2 * K5.N + 37, 5)):
+            _check(rig, B, "key_replaced_digits_grown", salt=salt + 1)
+    finally:
+        rig.eng.close()
+
+
 def test_n8192_three_levels():
     """PARAM_MULTI_BIT_MESSAGE_3_CARRY_3's default decomposition on the toy-n twin of its shape: 820 K steps of five mask
     elements (one pad slot per group, two ragged elements in the last), 512 column groups.  The whole key cannot be multiplied
@@ -318,6 +341,36 @@ def test_device_path(e2e):
         eng.set_pipeline(0)
     lwes2 = d_out.cpu().numpy().view(np.uint64)
     _assert_words(d_glwe2.cpu().numpy().view(np.uint64), fhestr.packing_keyswitch_host(P, e2e.pp, e2e.key, lwes2), "packing behind pipelined calls")
+
+
+def test_host_staging_grows_under_throughput_mode(e2e):
+    """fhe_engine_pack_lwes replaces its staging buffers while the streams of a pipelined call are live (it waits for them
+    first), then reuses them for a smaller batch behind a second pipelined call."""
+    import fhestr
+    import torch
+    P, eng, ck = e2e.P, e2e.eng, e2e.ck
+    M = P.msg_mod * P.carry_mod
+    B = 70
+    msgs = (np.arange(B) * 5 + 1) % M
+    lut_id, _ = eng.generate_lookup_table(lambda x: (3 * x + 1) % M)
+    d_in = torch.from_numpy(ck.encrypt(msgs).view(np.int64)).cuda()
+    d_idx = torch.full((B,), lut_id, dtype=torch.int32).cuda()
+    d_out = torch.zeros_like(d_in)
+    torch.cuda.synchronize()
+    got = []
+    eng.set_pipeline(1)
+    try:
+        for count in (150, 33):                             # 150: more than any host-array pack of this module before it
+            host = ck.encrypt((np.arange(count) * 7 + 2) % M)
+            eng.apply_lookup_table_dev(d_in.data_ptr(), d_idx.data_ptr(), d_out.data_ptr(), B)
+            got.append((host, eng.pack(host)))
+        eng.synchronize()
+    finally:
+        eng.set_pipeline(0)
+    for host, glwes in got:
+        info = f"{len(host)} host LWEs behind a pipelined call"
+        _assert_words(glwes, fhestr.packing_keyswitch_host(P, e2e.pp, e2e.key, host), info)
+    assert np.array_equal(ck.decrypt(d_out.cpu().numpy().view(np.uint64)), (3 * msgs + 1) % M)
 
 
 def test_end_to_end(e2e):

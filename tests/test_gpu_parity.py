@@ -80,6 +80,39 @@ def test_keyswitch_with_many_levels_bit_exact(ks_level, ks_base_log):
         eng.close()
 
 
+def test_keys_replaced_on_a_live_engine():
+    """fhe_engine_load_keys on an engine that already holds keys and has run under them: every resident key buffer is
+    allocated again with its predecessor present.  The engine then computes, word for word, what a fresh engine with the
+    second keys computes."""
+    import fhestr
+    p = O.TOY_K1
+    M = p.msg_mod * p.carry_mod
+    f = lambda x: (3 * x + 2) % M
+    cks = [O.ClientKey(p, seed) for seed in (0x5EED00A0, 0x5EED00B0)]
+    sks = [O.ServerKey(ck) for ck in cks]
+    cts = [ck.encrypt_many(range(M)) for ck in cks]
+    assert not np.array_equal(sks[0].ksk, sks[1].ksk)
+
+    def run(eng, which):
+        lut_id, _ = eng.generate_lookup_table(f)
+        return eng.apply_lookup_table(cts[which], np.full(M, lut_id, dtype=np.uint32))
+
+    live, fresh = fhestr.Engine(to_fhestr_params(p), 0), fhestr.Engine(to_fhestr_params(p), 0)
+    try:
+        live.load_keys(sks[0].bsk, sks[0].ksk)
+        out_a = run(live, 0)
+        live.load_keys(sks[1].bsk, sks[1].ksk)
+        out_b = run(live, 1)
+        fresh.load_keys(sks[1].bsk, sks[1].ksk)
+        assert np.array_equal(out_b, run(fresh, 1))
+    finally:
+        live.close()
+        fresh.close()
+    want = np.array([f(m) for m in range(M)])
+    assert np.array_equal(cks[0].decrypt_many(out_a), want)
+    assert np.array_equal(cks[1].decrypt_many(out_b), want)
+
+
 @pytest.mark.parametrize("params", PARAM_SETS, ids=lambda p: p.name)
 def test_lut_generation_matches_oracle(params):
     ks = keyset(params)
