@@ -142,9 +142,17 @@ int fhe_engine_set_pipeline(fhe_engine* eng, int on) {
 int fhe_engine_pipeline_input_event(fhe_engine* eng, void* hip_event) {
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng);
-    eng->impl->pipe_input_ready = reinterpret_cast<hipEvent_t>(hip_event);
+    eng->impl->pipe.input_ready = reinterpret_cast<hipEvent_t>(hip_event);
     return 0;
     API_END
+}
+
+// Not part of include/fhestr.h (tests only): the pipelined calls of the current run -- 0 again after any serial call or
+// synchronisation -- so a test can tell that its calls took a throughput mode and none fell back to the serial path.
+int fhe_debug_pipeline_calls(fhe_engine* eng) {
+    if (!eng) return -1;
+    LOCK_ENGINE(eng);
+    return (int)eng->impl->pipe.calls;
 }
 
 int fhe_engine_set_multibit_combine_max(fhe_engine* eng, uint32_t max_batch) {

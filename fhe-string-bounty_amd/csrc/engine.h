@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <string>
@@ -59,6 +60,65 @@ struct EngineEnv {
     static EngineEnv read();
 };
 
+// ---- the ks_pbs throughput modes (Engine::ks_pbs_dev): their streams, events, buffers and hazard records -----------------
+struct ByteRange { const char* lo; const char* hi; };
+inline bool overlap(const ByteRange& a, const ByteRange& b) { return a.lo < b.hi && b.lo < a.hi; }
+
+// One stream a pipelined call can run on, with what its calls need.  Lane 0 runs on the engine's current stream, which it
+// does not own (`stream` stays null: Pipeline::stream_of); lanes 1 .. 3 own theirs.  Lane 0's buffers are also those of every
+// serial call; lane 1's small buffer is the second one of mode 1 and of pbs_ks_host.
+struct PipeLane {
+    hipStream_t stream = nullptr;
+    hipEvent_t done = nullptr;          // behind the lane's latest mode-2 call
+    DeviceBuffer<uint64_t> small;       // small ciphertexts: the keyswitch's output, the blind rotation's input
+    DeviceBuffer<int8_t> digits;        // A fragments: signed decomposition digits of the batch being keyswitched
+    // byte ranges every mode-2 call of the current run read / wrote on this lane (a later call on ANOTHER lane that touches one
+    // of them waits for this lane's latest `done`: stream order then covers all of its earlier calls -- ADVICE r3)
+    std::vector<ByteRange> ins, outs;
+    // must a call on another lane that reads `in` and writes `out` come after this lane's calls?
+    bool blocks(const ByteRange& in, const ByteRange& out) const {
+        for (const auto& w : outs)
+            if (overlap(in, w) || overlap(out, w)) return true;
+        for (const auto& r : ins)
+            if (overlap(out, r)) return true;
+        return false;
+    }
+    void remember(const ByteRange& in, const ByteRange& out) { add(ins, in); add(outs, out); }
+    static void add(std::vector<ByteRange>& rs, const ByteRange& a) {
+        for (auto& r : rs)
+            if (r.lo == a.lo && r.hi == a.hi) return;
+        if (rs.size() < 32) { rs.push_back(a); return; }
+        rs[0].lo = std::min(rs[0].lo, a.lo);          // many distinct buffers: fold into one conservative range
+        rs[0].hi = std::max(rs[0].hi, a.hi);
+    }
+};
+
+struct Pipeline {
+    static constexpr int MAX_LANES = 4;
+    PipeLane lane[MAX_LANES];
+    int ready = 0;                      // lanes ensure() has set up
+    int width = 2;                      // lanes the calls of mode 2 rotate over (FHESTR_OVERLAP_STREAMS)
+    uint64_t calls = 0;                 // pipelined calls of the current run
+    hipEvent_t input_ready = nullptr;   // caller's event the next pipelined keyswitch waits for (one shot)
+    // mode 1 hands its two small buffers between the keyswitch stream and the engine's: keyswitch done [slot], blind rotation done [slot]
+    hipEvent_t ks_done[2] = {nullptr, nullptr}, rot_done[2] = {nullptr, nullptr};
+    ByteRange prev_out[2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // mode 1: what the last call on each buffer wrote
+    hipEvent_t run_start = nullptr;     // what the engine's stream held before the run's first call
+
+    template <class F> void each_event(F f) {      // the nine events: they are created together, with the first lanes
+        for (auto& l : lane) f(l.done);
+        for (int s = 0; s < 2; s++) { f(ks_done[s]); f(rot_done[s]); }
+        f(run_start);
+    }
+    int ensure(int n);                  // lanes 0 .. n-1 exist; what is missing is created whole or not at all, so a failed call can be repeated
+    hipStream_t stream_of(int q, hipStream_t engine) const { return q ? lane[q].stream : engine; }
+    int wait_others();                  // on the host, for every lane but the engine's
+    int wait_all(hipStream_t engine);   // and for the engine's
+    void end_run();                     // every lane is idle, or will only be used behind the engine's stream: the next pipelined call starts a new run
+    void destroy(int keep = 0);         // after the waits: the streams of lanes keep .. 3 and, with keep = 0, the events
+    ~Pipeline() { destroy(); }
+};
+
 struct Engine {
     std::recursive_mutex mu;      // taken by every C ABI entry point that touches this engine (c_api.cpp, LOCK_ENGINE)
     fhe_params_t p{};
@@ -66,33 +126,17 @@ struct Engine {
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;
     std::map<std::vector<uint64_t>, uint32_t> lut_dedup;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // scratch triple (unused slots of the ring below)
-    std::vector<hipEvent_t> ring;   // 4 events per recorded ks_pbs call
+    std::vector<hipEvent_t> ring;   // 4 events per recorded ks_pbs call (timing_events)
     size_t ring_used = 0;           // calls recorded since the last reset
     const BrVariant* variant = nullptr;       // layout used up to one LWE per CU
     const BrVariant* variant_large = nullptr; // same Fourier-key layout, used for larger batches (may equal variant)
     int cu_count = 256;
-    int pipeline = 0;                         // ks_pbs_dev throughput modes: 1 = keyswitch of call k+1 in the shadow of the blind rotation of call k; 2 = whole calls overlapped on two streams
-    hipStream_t ks_stream = nullptr;
-    hipEvent_t pipe_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // keyswitch done [slot], blind rotation done [slot], engine stream so far
-    hipEvent_t pipe_input_ready = nullptr;    // caller's event the next pipelined keyswitch waits for (one shot)
-    const void* pipe_out[2] = {nullptr, nullptr};
-    size_t pipe_out_bytes[2] = {0, 0};
-    // mode 2 (overlapped batches): calls rotate over ovl_streams streams (slot 0 = the engine stream, 1 = ks_stream)
-    static constexpr int OVL_MAX = 4;
-    int ovl_streams = 2;
+    int pipeline = 0;                         // ks_pbs_dev throughput modes: 1 = keyswitch of call k+1 in the shadow of the blind rotation of call k; 2 = whole calls overlapped on pipe.width lanes
     uint32_t wide_fair_shift = 13;           // two-LWEs-per-CU kernel: log2 ticks (100 MHz) of the priority time slice, 0 = off (FHESTR_WIDE_FAIR)
     uint32_t dense_per_cu = 2;               // N = 1024, k = 2: the four-workgroups-per-CU kernel beyond this many LWEs per CU (0 = never)
     bool keep_busy = false;                  // small launches carry replicas on the idle CUs (fhe_engine_set_keep_busy, FHESTR_KEEP_BUSY)
-    hipStream_t ovl_stream[OVL_MAX] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ovl_done[OVL_MAX] = {nullptr, nullptr, nullptr, nullptr};
-    // byte ranges every call of the current run read / wrote, per stream (a later call on ANOTHER stream that touches one of
-    // them waits for that stream's latest ovl_done: stream order then covers all of its earlier calls -- ADVICE r3)
-    struct ByteRange { const char* lo; const char* hi; };
-    std::vector<ByteRange> ovl_ins[OVL_MAX], ovl_outs[OVL_MAX];
-    DeviceBuffer<uint64_t> ovl_small[OVL_MAX];      // small-ciphertext buffer per stream
-    DeviceBuffer<int8_t> ovl_digits[OVL_MAX];       // keyswitch digit fragments per stream (slot 0: d_ks_digits)
-    int sync_all_streams();
+    Pipeline pipe;                           // streams, events, buffers and hazard records of the throughput modes; lane 0's buffers serve every serial call
+    int sync_all_streams() { return pipe.wait_all(stream); }
     // Grow a buffer that launches in flight on any of the engine's streams may still read: they finish before the old
     // allocation goes.  Nothing can be reading an empty buffer, so a first allocation does not wait.
     template <class T>
@@ -101,8 +145,6 @@ struct Engine {
         if (b.ptr && sync_all_streams()) return 1;
         return b.reserve(need);
     }
-    void end_pipeline_run();
-    uint64_t pipe_calls = 0;
     int shadow_fit = -1;                      // -1 unknown, else whether a 64-VGPR wave fits next to the rotation's
     uint32_t multibit_combine_max = 64;       // multi-bit PBS: batches up to this size prepare their GGSWs on the whole GPU first
 
@@ -110,7 +152,6 @@ struct Engine {
     DeviceBuffer<uint32_t> d_ksk_packed; // [rows/4][8][n+1] byte planes for keyswitch_dot4_kernel
     DeviceBuffer<uint64_t> d_ksk_rowsum; // [kN / KS_IC][n+1] sums of every tile's key rows (bias removal)
     DeviceBuffer<int8_t> d_ksk_mfma;  // balanced base-256 digit planes of the KSK in MFMA B-fragment order (ks_mfma_kernels.hip.h)
-    DeviceBuffer<int8_t> d_ks_digits; // A fragments: signed decomposition digits of the batch being keyswitched
     bool ks_mfma_enabled = true;      // FHESTR_KS_MFMA=0: byte-plane dot4 kernel everywhere
     DeviceBuffer<double> d_fbsk;
     DeviceBuffer<double> d_fbsk_dense;       // the same key in the dense wide kernel's Fourier order (N = 1024, k = 2 only)
@@ -118,7 +159,7 @@ struct Engine {
     uint32_t n_luts = 0;
 
     // staging / scratch (grown on demand)
-    DeviceBuffer<uint64_t> d_in, d_small, d_small2, d_out, d_pool;
+    DeviceBuffer<uint64_t> d_in, d_out, d_pool;   // the small ciphertexts between keyswitch and rotation: pipe.lane[q].small
     DeviceBuffer<uint32_t> d_idx;
     DeviceBuffer<uint32_t> d_slot_exp;   // multi-bit two-kernel path: exponent of w = e^{i pi / N} each Fourier slot evaluates at
     size_t multibit_workspace_cap = 0;   // bytes of prepared GGSWs kept at once, larger batches run in sub-batches (0 = from free memory; FHESTR_MULTIBIT_WS_CAP)
@@ -141,7 +182,7 @@ struct Engine {
     // packing keyswitch (packing_ks_kernels.hip.h): the key's digit planes, its decomposition, and the batch's digit fragments
     DeviceBuffer<int8_t> d_pksk_mfma;
     fhe_packing_params_t pack_pp{0, 0};
-    DeviceBuffer<int8_t> d_pack_digits;  // same reuse rules as d_ks_digits: zeroed at allocation, grown, rows past the batch never read
+    DeviceBuffer<int8_t> d_pack_digits;  // same reuse rules as PipeLane::digits: zeroed at allocation, grown, rows past the batch never read
     DeviceBuffer<uint64_t> d_pack_in, d_pack_out;   // staging of fhe_engine_pack_lwes (host ciphertexts)
     uint32_t pack_last[5] = {0, 0, 0, 0, 0};   // fhe_engine_packing_info: ran, MT, K chunks, K steps per chunk, K steps
     // packed inputs (glwe_extract_kernels.hip.h): staging of fhe_engine_unpack_glwes, the refresh's table indices
@@ -177,9 +218,10 @@ struct Engine {
     int lut_upload(const uint64_t* acc, uint32_t* id);
     int lut_download(uint32_t id, uint64_t* acc);
     int ensure_batch(uint32_t count);
+    int timing_events(hipEvent_t*& e4);   // the next recorded call's: keyswitch start / end, blind rotation start / end
     int check_lut_idx(const uint32_t* lut_idx, uint32_t count) const;
 
-    int launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t count, hipStream_t on = nullptr, bool shadow = false, int digits_slot = 0);
+    int launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t count, DeviceBuffer<int8_t>& digits, hipStream_t on = nullptr, bool shadow = false);
     int launch_blind_rotate(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big, uint32_t count, hipStream_t on = nullptr, bool two_per_cu = false,
                             bool one_workgroup_only = false);   // never a kernel that needs several workgroups resident at once (cluster_settle's re-run)
     bool shadow_keyswitch_fits();

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 
 #include "keygen_kernels.hip.h"   // first: asserts fp contract(off); the FFT header turns fusion on after it
@@ -323,7 +324,7 @@ int Engine::create(const fhe_params_t& p, int device, Engine** out) {
     if (count <= 0) return fail("no HIP device: libfhestr has no CPU fallback");
     if (device < 0 || device >= count) return fail("bad device index");
     HIP_TRY(hipSetDevice(device));
-    Engine* e = new Engine();
+    std::unique_ptr<Engine> e(new Engine());   // freed by every early return below
     e->p = p;
     e->device = device;
     const BrVariantPair vp = find_variant_pair(p, env.log2_points);
@@ -333,7 +334,7 @@ int Engine::create(const fhe_params_t& p, int device, Engine** out) {
     if (env.dense_per_cu >= 0) e->dense_per_cu = (uint32_t)env.dense_per_cu;
     if (env.cluster_fallback >= 0) e->cluster_fallback = env.cluster_fallback != 0;
     if (env.keep_busy >= 0) e->keep_busy = env.keep_busy != 0;
-    if (env.overlap_streams >= 0) e->ovl_streams = std::min((int)Engine::OVL_MAX, std::max(2, env.overlap_streams));
+    if (env.overlap_streams >= 0) e->pipe.width = std::min((int)Pipeline::MAX_LANES, std::max(2, env.overlap_streams));
     if (env.ks_mfma >= 0) e->ks_mfma_enabled = env.ks_mfma != 0;
     if (env.ks_chunks >= 0) e->ks_chunks_override = (uint32_t)env.ks_chunks;
     if (env.cluster_spin_limit >= 0) e->cluster_spin_limit = (uint32_t)std::max(64, env.cluster_spin_limit);
@@ -349,27 +350,22 @@ int Engine::create(const fhe_params_t& p, int device, Engine** out) {
     e->cu_count = prop.multiProcessorCount;
     HIP_TRY(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
     e->stream = e->own_stream;
-    for (auto& ev : e->ev) HIP_TRY(hipEventCreate(&ev));
-    *out = e;
+    *out = e.release();
     return 0;
 }
 
 Engine::~Engine() {
     (void)hipSetDevice(device);
     if (stream) (void)sync_all_streams();
-    for (int q = 0; q < OVL_MAX; q++) { if (ovl_done[q]) (void)hipEventDestroy(ovl_done[q]); if (q >= 2 && ovl_stream[q]) (void)hipStreamDestroy(ovl_stream[q]); }
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : ring) if (e) (void)hipEventDestroy(e);
-    for (auto& e : pipe_ev) if (e) (void)hipEventDestroy(e);
-    if (ks_stream) (void)hipStreamDestroy(ks_stream);
+    pipe.destroy();
     if (own_stream) (void)hipStreamDestroy(own_stream);
     // the members are destroyed after this body: every DeviceBuffer is freed once the streams are idle and gone
 }
 
 int Engine::set_stream(hipStream_t s, bool use_own) {
     if (use()) return 1;
-    if (ks_stream) HIP_TRY(hipStreamSynchronize(ks_stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    if (sync_all_streams()) return 1;
     stream = use_own ? own_stream : s;   // s == nullptr is HIP's default (null) stream
     return 0;
 }
@@ -707,7 +703,7 @@ int Engine::lut_download(uint32_t id, uint64_t* acc) {
 
 int Engine::ensure_batch(uint32_t count) {
     const size_t big = (size_t)p.k * p.N + 1, small = (size_t)p.n + 1;
-    return d_in.reserve(count * big * 8) || d_out.reserve(count * big * 8) || d_small.reserve(count * small * 8) || d_idx.reserve((size_t)count * 4);
+    return d_in.reserve(count * big * 8) || d_out.reserve(count * big * 8) || reserve_idle(pipe.lane[0].small, count * small * 8) || d_idx.reserve((size_t)count * 4);
 }
 
 // ---- matrix-core keyswitch: the host plan its two users share (launch_keyswitch, pack_lwes_dev) ------------------------
@@ -750,7 +746,7 @@ static int ks_mfma_digits(Engine& e, DeviceBuffer<int8_t>& digits, const KsMfmaL
     return 0;
 }
 
-int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t count, hipStream_t on, bool shadow, int digits_slot) {
+int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t count, DeviceBuffer<int8_t>& digits, hipStream_t on, bool shadow) {
     if (!d_ksk_packed) return fail("keys not loaded");
     hipStream_t s = on ? on : stream;
     // grid.y = sample tiles; HIP caps grid.y at 65535
@@ -760,7 +756,6 @@ int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t cou
     if (d_ksk_mfma && !shadow) {
         const KsMfmaGeom g = ks_mfma_geom(in_dim, out_size, p.ks_level, p.ks_base_log);
         const KsMfmaLaunch l = ks_mfma_plan(g, count, p.ks_base_log, cu_count, ks_chunks_override);
-        DeviceBuffer<int8_t>& digits = digits_slot ? ovl_digits[digits_slot] : d_ks_digits;     // own buffer per overlapped stream
         if (ks_mfma_digits(*this, digits, l, g, d_big, count, s)) return 1;
         KsMfmaArgs ma{d_big, d_ksk_mfma, digits, d_sm, g, count, l.row_tiles, l.spc};
         switch (l.mt) {
@@ -827,7 +822,7 @@ int Engine::pack_lwes_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_glw
     if (count > 65535u) return fail("batch too large for one packing launch (max 65535 LWEs)");   // grid.y of the digit kernel
     if (pipeline) {                                         // pipelined calls may still write the input on another stream
         if (sync_all_streams()) return 1;
-        end_pipeline_run();
+        pipe.end_run();
     }
     const uint32_t in_dim = p.k * p.N, out_size = (p.k + 1) * p.N;
     const KsMfmaGeom g = ks_mfma_geom(in_dim, out_size, pack_pp.level, pack_pp.base_log);
@@ -882,7 +877,7 @@ int Engine::unpack_glwes_dev(const uint64_t* d_glwes, uint32_t first, uint32_t c
     }
     if (pipeline) {                                         // pipelined calls may still read or write these buffers on other streams
         if (sync_all_streams()) return 1;
-        end_pipeline_run();
+        pipe.end_run();
     }
     const uint32_t chunks = (kN / 2 + GLWE_EXTRACT_PAIRS_PER_WG - 1) / GLWE_EXTRACT_PAIRS_PER_WG;
     if ((uint64_t)count * chunks > 0x7FFFFFFFull) return fail("unpack_glwes: too many ciphertexts for one launch");
@@ -1128,137 +1123,122 @@ void Engine::keyswitch_info(uint32_t info[6]) const {
     info[5] = variant && hipFuncGetAttributes(&fa, variant->rotate_fn) == hipSuccess ? (uint32_t)fa.numRegs : 0u;
 }
 
-int Engine::ks_pbs_dev(const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint64_t* d_big_out,
-                       uint32_t count, bool allow_pipeline) {
-    if (use()) return 1;
-    if (count == 0) return 0;
-    const size_t small = (size_t)p.n + 1;
-    if (d_small.reserve(count * small * 8)) return 1;
-    // HIP events on the launch stream: per-call kernel durations without host synchronisation
+// HIP events on the launch stream: per-call kernel durations without host synchronisation.  The ring is created whole or not at all.
+int Engine::timing_events(hipEvent_t*& e4) {
     constexpr size_t RING = 1024;
     if (ring.empty()) {
-        ring.resize(RING * 4);
-        for (auto& e : ring) HIP_TRY(hipEventCreate(&e));
+        std::vector<hipEvent_t> fresh(RING * 4, nullptr);
+        hipError_t err = hipSuccess;
+        for (auto& e : fresh) if (err == hipSuccess) err = hipEventCreate(&e);
+        if (err != hipSuccess) for (auto& e : fresh) if (e) (void)hipEventDestroy(e);
+        HIP_TRY(err);
+        ring.swap(fresh);
     }
-    hipEvent_t* e4 = &ring[(ring_used % RING) * 4];     // keyswitch start / end, blind rotation start / end
-    ring_used++;
-    if (allow_pipeline && pipeline == 2 && overlapped_mode_eligible(*this, count)) {
-        // Overlapped batches (fhe_engine_set_pipeline(2)): consecutive calls alternate between ovl_streams (2) streams and
-        // run on the two-LWEs-per-CU kernel with time-sliced priorities (BlindRotateArgs::fair_shift), so two 256-LWE
-        // launches share every CU and progress at the same rate -- the pace of a 512-LWE launch (2.09 ms per call,
-        // 122 k PBS/s) although every batch has 256 LWEs; the price is each call's latency (4.1 ms).  Three streams
-        // measured slower (119 k): the third launch's keyswitch waits for idle CUs.  Same ordering rules as mode 1, plus
-        // write-after-write / write-after-read against the calls still in flight on the other streams.  Results are
-        // those of the large-batch kernel.
-        const int ns = ovl_streams;
-        if (!ks_stream) {
-            HIP_TRY(hipStreamCreateWithFlags(&ks_stream, hipStreamNonBlocking));
-            for (auto& e : pipe_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        for (int q = 2; q < ns; q++)
-            if (!ovl_stream[q]) {
-                HIP_TRY(hipStreamCreateWithFlags(&ovl_stream[q], hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&ovl_done[q], hipEventDisableTiming));
-            }
-        for (int q = 0; q < 2; q++)
-            if (!ovl_done[q]) HIP_TRY(hipEventCreateWithFlags(&ovl_done[q], hipEventDisableTiming));
-        const int slot = (int)(pipe_calls % (uint64_t)ns);
-        hipStream_t s = slot == 0 ? stream : slot == 1 ? ks_stream : ovl_stream[slot];
-        if (ovl_small[slot].reserve(count * small * 8)) return 1;
-        uint64_t* sm = ovl_small[slot];
-        const size_t big = (size_t)p.k * p.N + 1;
-        const char *in_lo = (const char*)d_big_in, *in_hi = in_lo + (size_t)count * big * 8;
-        const char *out_lo = (const char*)d_big_out, *out_hi = out_lo + (size_t)count * big * 8;
-        if (pipe_calls == 0) HIP_TRY(hipEventRecord(pipe_ev[4], stream));       // what the engine stream held before this run
-        if (pipe_calls < (uint64_t)ns && slot != 0) HIP_TRY(hipStreamWaitEvent(s, pipe_ev[4], 0));
-        if (pipe_input_ready) {
-            HIP_TRY(hipStreamWaitEvent(s, pipe_input_ready, 0));
-            pipe_input_ready = nullptr;
-        }
-        auto overlaps = [](const char* a_lo, const char* a_hi, const std::vector<ByteRange>& rs) {
-            for (const auto& r : rs)
-                if (a_lo < r.hi && r.lo < a_hi) return true;
-            return false;
-        };
-        for (int q = 0; q < ns; q++) {       // every call of this run on the other streams, not only their latest
-            if (q == slot || !ovl_done[q] || (ovl_ins[q].empty() && ovl_outs[q].empty())) continue;
-            if (overlaps(in_lo, in_hi, ovl_outs[q]) || overlaps(out_lo, out_hi, ovl_outs[q]) || overlaps(out_lo, out_hi, ovl_ins[q]))
-                HIP_TRY(hipStreamWaitEvent(s, ovl_done[q], 0));
-        }
-        auto remember = [](std::vector<ByteRange>& rs, const char* lo, const char* hi) {
-            for (auto& r : rs)
-                if (r.lo == lo && r.hi == hi) return;
-            if (rs.size() < 32) { rs.push_back({lo, hi}); return; }
-            rs[0].lo = std::min(rs[0].lo, lo);          // many distinct buffers: fold into one conservative range
-            rs[0].hi = std::max(rs[0].hi, hi);
-        };
-        remember(ovl_ins[slot], in_lo, in_hi);
-        remember(ovl_outs[slot], out_lo, out_hi);
-        HIP_TRY(hipEventRecord(e4[0], s));
-        if (launch_keyswitch(d_big_in, sm, count, s, false, slot)) return 1;
-        HIP_TRY(hipEventRecord(e4[1], s));
-        HIP_TRY(hipEventRecord(e4[2], s));
-        if (launch_blind_rotate(sm, d_lut_idx, d_big_out, count, s, true)) return 1;
-        HIP_TRY(hipEventRecord(e4[3], s));
-        HIP_TRY(hipEventRecord(ovl_done[slot], s));
-        pipe_calls++;
-        return 0;
-    }
-    if (allow_pipeline && pipeline == 1 && shadow_mode_eligible(*this, count) && shadow_keyswitch_fits()) {
-        // Pipelined mode (fhe_engine_set_pipeline): the keyswitch of this call runs on a second stream, in a 64-VGPR
-        // variant whose waves fit next to the two 220-VGPR waves per SIMD of the blind rotation still running for the
-        // previous call, into the other of two small-ciphertext buffers.  Calls are independent unless this call's
-        // input overlaps the previous call's output (older outputs are ordered by the buffer hand-over below).
-        if (!ks_stream) {
-            HIP_TRY(hipStreamCreateWithFlags(&ks_stream, hipStreamNonBlocking));
-            for (auto& e : pipe_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        if (d_small2.reserve(count * small * 8)) return 1;
-        const int slot = (int)(pipe_calls & 1);
-        uint64_t* sm = slot ? d_small2 : d_small;
-        const size_t big = (size_t)p.k * p.N + 1;
-        const char *in_lo = (const char*)d_big_in, *in_hi = in_lo + (size_t)count * big * 8;
-        const char* prev = (const char*)pipe_out[slot ^ 1];
-        if (pipe_calls == 0) {
-            // first pipelined call after anything else: whatever the engine stream already holds -- a serial call's
-            // keyswitch / blind rotation that still use d_small, uploads, a caller's kernels -- comes first
-            HIP_TRY(hipEventRecord(pipe_ev[4], stream));
-            HIP_TRY(hipStreamWaitEvent(ks_stream, pipe_ev[4], 0));
-        }
-        if (pipe_input_ready) {       // fhe_engine_pipeline_input_event: the producer of this call's input
-            HIP_TRY(hipStreamWaitEvent(ks_stream, pipe_input_ready, 0));
-            pipe_input_ready = nullptr;
-        }
-        if (pipe_calls >= 1 && prev && in_lo < prev + pipe_out_bytes[slot ^ 1] && prev < in_hi)
-            HIP_TRY(hipStreamWaitEvent(ks_stream, pipe_ev[2 + (slot ^ 1)], 0));              // chained: input = previous output
-        if (pipe_calls >= 2) HIP_TRY(hipStreamWaitEvent(ks_stream, pipe_ev[2 + slot], 0));    // blind rotation that read `sm` two calls ago
-        HIP_TRY(hipEventRecord(e4[0], ks_stream));
-        if (launch_keyswitch(d_big_in, sm, count, ks_stream, true)) return 1;
-        HIP_TRY(hipEventRecord(e4[1], ks_stream));
-        HIP_TRY(hipEventRecord(pipe_ev[slot], ks_stream));
-        HIP_TRY(hipStreamWaitEvent(stream, pipe_ev[slot], 0));
-        HIP_TRY(hipEventRecord(e4[2], stream));
-        if (launch_blind_rotate(sm, d_lut_idx, d_big_out, count)) return 1;
-        HIP_TRY(hipEventRecord(e4[3], stream));
-        HIP_TRY(hipEventRecord(pipe_ev[2 + slot], stream));
-        pipe_out[slot] = d_big_out;
-        pipe_out_bytes[slot] = (size_t)count * big * 8;
-        pipe_calls++;
-        return 0;
-    }
-    if (ks_stream && pipe_calls) {        // a serial call after pipelined ones: the other streams must be done with the shared buffers
-        HIP_TRY(hipStreamSynchronize(ks_stream));
-        for (int q = 2; q < OVL_MAX; q++) if (ovl_stream[q]) HIP_TRY(hipStreamSynchronize(ovl_stream[q]));
-        end_pipeline_run();
-    }
-    pipe_input_ready = nullptr;           // serial calls are stream-ordered: nothing to wait for
-    HIP_TRY(hipEventRecord(e4[0], stream));
-    if (launch_keyswitch(d_big_in, d_small, count)) return 1;
-    HIP_TRY(hipEventRecord(e4[1], stream));
-    HIP_TRY(hipEventRecord(e4[2], stream));
-    if (launch_blind_rotate(d_small, d_lut_idx, d_big_out, count)) return 1;
-    HIP_TRY(hipEventRecord(e4[3], stream));
+    e4 = &ring[(ring_used++ % RING) * 4];   // keyswitch start / end, blind rotation start / end
     return 0;
+}
+
+// One call on one lane and stream, the lane's small buffer large enough: the keyswitch into it, the blind rotation out of it, the call's timing events around them.
+static int ks_pbs_on_lane(Engine& e, PipeLane& lane, hipStream_t s, bool two_per_cu, const uint64_t* d_big_in, const uint32_t* d_lut_idx,
+                          uint64_t* d_big_out, uint32_t count, hipEvent_t* e4) {
+    HIP_TRY(hipEventRecord(e4[0], s));
+    if (e.launch_keyswitch(d_big_in, lane.small, count, lane.digits, s)) return 1;
+    HIP_TRY(hipEventRecord(e4[1], s));
+    HIP_TRY(hipEventRecord(e4[2], s));
+    if (e.launch_blind_rotate(lane.small, d_lut_idx, d_big_out, count, s, two_per_cu)) return 1;
+    HIP_TRY(hipEventRecord(e4[3], s));
+    return 0;
+}
+
+// Overlapped batches (fhe_engine_set_pipeline(2)): consecutive calls alternate between pipe.width (2) lanes and
+// run on the two-LWEs-per-CU kernel with time-sliced priorities (BlindRotateArgs::fair_shift), so two 256-LWE
+// launches share every CU and progress at the same rate -- the pace of a 512-LWE launch (2.09 ms per call,
+// 122 k PBS/s) although every batch has 256 LWEs; the price is each call's latency (4.1 ms).  Three streams
+// measured slower (119 k): the third launch's keyswitch waits for idle CUs.  Same ordering rules as mode 1, plus
+// write-after-write / write-after-read against the calls still in flight on the other streams.  Results are
+// those of the large-batch kernel.
+static int ks_pbs_overlapped(Engine& e, const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint64_t* d_big_out, uint32_t count, hipEvent_t* e4) {
+    Pipeline& pl = e.pipe;
+    const int ns = pl.width, slot = (int)(pl.calls % (uint64_t)pl.width);
+    if (pl.ensure(ns)) return 1;
+    PipeLane& lane = pl.lane[slot];
+    hipStream_t s = pl.stream_of(slot, e.stream);
+    if (e.reserve_idle(lane.small, count * ((size_t)e.p.n + 1) * 8)) return 1;   // the lane's previous rotation may still read it
+    const size_t bytes = (size_t)count * ((size_t)e.p.k * e.p.N + 1) * 8;
+    const ByteRange in{(const char*)d_big_in, (const char*)d_big_in + bytes}, out{(const char*)d_big_out, (const char*)d_big_out + bytes};
+    if (pl.calls == 0) HIP_TRY(hipEventRecord(pl.run_start, e.stream));       // what the engine stream held before this run
+    if (pl.calls < (uint64_t)ns && slot != 0) HIP_TRY(hipStreamWaitEvent(s, pl.run_start, 0));
+    if (pl.input_ready) {
+        HIP_TRY(hipStreamWaitEvent(s, pl.input_ready, 0));
+        pl.input_ready = nullptr;
+    }
+    for (int q = 0; q < ns; q++)         // every call of this run on the other streams, not only their latest
+        if (q != slot && pl.lane[q].blocks(in, out)) HIP_TRY(hipStreamWaitEvent(s, pl.lane[q].done, 0));
+    lane.remember(in, out);
+    if (ks_pbs_on_lane(e, lane, s, true, d_big_in, d_lut_idx, d_big_out, count, e4)) return 1;
+    HIP_TRY(hipEventRecord(lane.done, s));
+    pl.calls++;
+    return 0;
+}
+
+// Pipelined mode (fhe_engine_set_pipeline): the keyswitch of this call runs on a second stream, in a 64-VGPR
+// variant whose waves fit next to the two 220-VGPR waves per SIMD of the blind rotation still running for the
+// previous call, into the other of two small-ciphertext buffers.  Calls are independent unless this call's
+// input overlaps the previous call's output (older outputs are ordered by the buffer hand-over below).
+static int ks_pbs_shadow(Engine& e, const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint64_t* d_big_out, uint32_t count, hipEvent_t* e4) {
+    Pipeline& pl = e.pipe;
+    if (pl.ensure(2)) return 1;
+    const int slot = (int)(pl.calls & 1);
+    hipStream_t ks_stream = pl.stream_of(1, e.stream);
+    if (e.reserve_idle(pl.lane[slot].small, count * ((size_t)e.p.n + 1) * 8)) return 1;
+    uint64_t* sm = pl.lane[slot].small;
+    const size_t bytes = (size_t)count * ((size_t)e.p.k * e.p.N + 1) * 8;
+    const ByteRange in{(const char*)d_big_in, (const char*)d_big_in + bytes};
+    if (pl.calls == 0) {
+        // first pipelined call after anything else: whatever the engine stream already holds -- a serial call's
+        // keyswitch / blind rotation that still use lane 0's small buffer, uploads, a caller's kernels -- comes first
+        HIP_TRY(hipEventRecord(pl.run_start, e.stream));
+        HIP_TRY(hipStreamWaitEvent(ks_stream, pl.run_start, 0));
+    }
+    if (pl.input_ready) {       // fhe_engine_pipeline_input_event: the producer of this call's input
+        HIP_TRY(hipStreamWaitEvent(ks_stream, pl.input_ready, 0));
+        pl.input_ready = nullptr;
+    }
+    if (pl.calls >= 1 && overlap(in, pl.prev_out[slot ^ 1]))
+        HIP_TRY(hipStreamWaitEvent(ks_stream, pl.rot_done[slot ^ 1], 0));              // chained: input = previous output
+    if (pl.calls >= 2) HIP_TRY(hipStreamWaitEvent(ks_stream, pl.rot_done[slot], 0));    // blind rotation that read `sm` two calls ago
+    HIP_TRY(hipEventRecord(e4[0], ks_stream));
+    if (e.launch_keyswitch(d_big_in, sm, count, pl.lane[slot].digits, ks_stream, true)) return 1;
+    HIP_TRY(hipEventRecord(e4[1], ks_stream));
+    HIP_TRY(hipEventRecord(pl.ks_done[slot], ks_stream));
+    HIP_TRY(hipStreamWaitEvent(e.stream, pl.ks_done[slot], 0));
+    HIP_TRY(hipEventRecord(e4[2], e.stream));
+    if (e.launch_blind_rotate(sm, d_lut_idx, d_big_out, count)) return 1;
+    HIP_TRY(hipEventRecord(e4[3], e.stream));
+    HIP_TRY(hipEventRecord(pl.rot_done[slot], e.stream));
+    pl.prev_out[slot] = {(const char*)d_big_out, (const char*)d_big_out + bytes};
+    pl.calls++;
+    return 0;
+}
+
+static int ks_pbs_serial(Engine& e, const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint64_t* d_big_out, uint32_t count, hipEvent_t* e4) {
+    if (e.pipe.calls && e.pipe.wait_others()) return 1;   // a serial call after pipelined ones: the other streams must be done with the shared buffers
+    e.pipe.end_run();
+    e.pipe.input_ready = nullptr;         // serial calls are stream-ordered: nothing to wait for
+    if (e.reserve_idle(e.pipe.lane[0].small, count * ((size_t)e.p.n + 1) * 8)) return 1;
+    return ks_pbs_on_lane(e, e.pipe.lane[0], e.stream, false, d_big_in, d_lut_idx, d_big_out, count, e4);
+}
+
+int Engine::ks_pbs_dev(const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint64_t* d_big_out, uint32_t count, bool allow_pipeline) {
+    if (use()) return 1;
+    if (count == 0) return 0;
+    hipEvent_t* e4 = nullptr;
+    if (timing_events(e4)) return 1;
+    if (allow_pipeline && pipeline == 2 && overlapped_mode_eligible(*this, count))
+        return ks_pbs_overlapped(*this, d_big_in, d_lut_idx, d_big_out, count, e4);
+    if (allow_pipeline && pipeline == 1 && shadow_mode_eligible(*this, count) && shadow_keyswitch_fits())
+        return ks_pbs_shadow(*this, d_big_in, d_lut_idx, d_big_out, count, e4);
+    return ks_pbs_serial(*this, d_big_in, d_lut_idx, d_big_out, count, e4);
 }
 
 int Engine::check_lut_idx(const uint32_t* lut_idx, uint32_t count) const {
@@ -1289,8 +1269,9 @@ int Engine::keyswitch_host(const uint64_t* in, uint64_t* out_small, uint32_t cou
     if (ensure_batch(count)) return 1;
     const size_t big = (size_t)p.k * p.N + 1, small = (size_t)p.n + 1;
     HIP_TRY(hipMemcpyAsync(d_in, in, count * big * 8, hipMemcpyHostToDevice, stream));
-    if (launch_keyswitch(d_in, d_small, count)) return 1;
-    HIP_TRY(hipMemcpyAsync(out_small, d_small, count * small * 8, hipMemcpyDeviceToHost, stream));
+    PipeLane& lane = pipe.lane[0];
+    if (launch_keyswitch(d_in, lane.small, count, lane.digits)) return 1;
+    HIP_TRY(hipMemcpyAsync(out_small, lane.small, count * small * 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
 }
@@ -1301,6 +1282,7 @@ int Engine::pbs_host(const uint64_t* in_small, const uint32_t* lut_idx, uint64_t
     if (check_lut_idx(lut_idx, count)) return 1;
     if (ensure_batch(count)) return 1;
     const size_t big = (size_t)p.k * p.N + 1, small = (size_t)p.n + 1;
+    uint64_t* d_small = pipe.lane[0].small;
     HIP_TRY(hipMemcpyAsync(d_small, in_small, count * small * 8, hipMemcpyHostToDevice, stream));
     if (lut_idx) HIP_TRY(hipMemcpyAsync(d_idx, lut_idx, (size_t)count * 4, hipMemcpyHostToDevice, stream));
     if (launch_blind_rotate(d_small, lut_idx ? d_idx : nullptr, d_out, count)) return 1;
@@ -1315,13 +1297,16 @@ int Engine::pbs_ks_host(const uint64_t* in_small, const uint32_t* lut_idx, uint6
     if (use()) return 1;
     if (count == 0) return 0;
     if (check_lut_idx(lut_idx, count)) return 1;
-    if (ensure_batch(count)) return 1;
+    // lane 1's small buffer is the second one here: a mode-2 call may still use it on its own stream
+    if ((pipe.calls && pipe.wait_others()) || ensure_batch(count)) return 1;
+    pipe.end_run();
     const size_t small = (size_t)p.n + 1;
-    if (d_small2.reserve(count * small * 8)) return 1;
+    if (reserve_idle(pipe.lane[1].small, count * small * 8)) return 1;
+    uint64_t *d_small = pipe.lane[0].small, *d_small2 = pipe.lane[1].small;
     HIP_TRY(hipMemcpyAsync(d_small, in_small, count * small * 8, hipMemcpyHostToDevice, stream));
     if (lut_idx) HIP_TRY(hipMemcpyAsync(d_idx, lut_idx, (size_t)count * 4, hipMemcpyHostToDevice, stream));
     if (launch_blind_rotate(d_small, lut_idx ? d_idx : nullptr, d_out, count)) return 1;
-    if (launch_keyswitch(d_out, d_small2, count)) return 1;
+    if (launch_keyswitch(d_out, d_small2, count, pipe.lane[0].digits)) return 1;
     HIP_TRY(hipMemcpyAsync(out_small, d_small2, count * small * 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return cluster_check();
@@ -1430,21 +1415,45 @@ extern "C" int fhe_debug_read_stamps(unsigned long long* out, size_t count) {
 int Engine::synchronize() {
     if (use()) return 1;
     if (sync_all_streams()) return 1;
-    end_pipeline_run();                   // every stream is idle: the next pipelined call starts a new run
+    pipe.end_run();                       // every stream is idle: the next pipelined call starts a new run
     return cluster_check();
 }
 
-int Engine::sync_all_streams() {
-    if (ks_stream) HIP_TRY(hipStreamSynchronize(ks_stream));
-    for (int q = 2; q < OVL_MAX; q++) if (ovl_stream[q]) HIP_TRY(hipStreamSynchronize(ovl_stream[q]));
-    HIP_TRY(hipStreamSynchronize(stream));
+int Pipeline::ensure(int n) {
+    if (n <= ready) return 0;
+    hipError_t err = hipSuccess;
+    for (int q = std::max(ready, 1); q < n && err == hipSuccess; q++) err = hipStreamCreateWithFlags(&lane[q].stream, hipStreamNonBlocking);
+    if (!ready) each_event([&](hipEvent_t& e) { if (err == hipSuccess) err = hipEventCreateWithFlags(&e, hipEventDisableTiming); });
+    if (err != hipSuccess) destroy(ready);     // all or nothing: what this call created goes, the next call tries again
+    HIP_TRY(err);
+    ready = n;
     return 0;
 }
 
-void Engine::end_pipeline_run() {
-    pipe_calls = 0;
-    pipe_out[0] = pipe_out[1] = nullptr;
-    for (int q = 0; q < OVL_MAX; q++) { ovl_ins[q].clear(); ovl_outs[q].clear(); }
+int Pipeline::wait_others() {
+    for (int q = 1; q < ready; q++) HIP_TRY(hipStreamSynchronize(lane[q].stream));
+    return 0;
+}
+
+int Pipeline::wait_all(hipStream_t engine) {
+    if (wait_others()) return 1;
+    HIP_TRY(hipStreamSynchronize(engine));
+    return 0;
+}
+
+void Pipeline::end_run() {
+    calls = 0;
+    prev_out[0] = prev_out[1] = {nullptr, nullptr};
+    for (auto& l : lane) { l.ins.clear(); l.outs.clear(); }
+}
+
+void Pipeline::destroy(int keep) {
+    if (!keep) each_event([](hipEvent_t& e) { if (e) (void)hipEventDestroy(e); e = nullptr; });
+    for (int q = std::max(keep, 1); q < MAX_LANES; q++) {
+        if (lane[q].stream) (void)hipStreamDestroy(lane[q].stream);
+        lane[q].stream = nullptr;
+    }
+    ready = keep;
 }
 
 // The cluster kernel never hangs on a hand-over that does not arrive: it gives up, finishes with garbage and says so

@@ -27,6 +27,12 @@ construction of a fresh engine; engines are kept for the module and closed at it
   bits of the shadow kernel's code are those of test_dot4_*, of the matrix cores' those above)
     test_shadow_kernel          set_pipeline(1): keyswitch_dot4_kernel<4, 8> beside the previous call's rotation, B = 96 and 3
     test_overlapped_mode_growing_batches   set_pipeline(2): a digit buffer per stream, reallocated when a larger batch arrives
+    test_overlapped_mode_three_and_four_streams   FHESTR_OVERLAP_STREAMS = 3, 4: nine calls of 5 / 96 / 37 LWEs over every lane
+    test_overlapped_mode_every_lane_grows   the same engines: a round of 5 LWEs per lane, then a round of 130
+    test_overlapped_mode_dependent_calls   the same two engines: a chain, two calls into one buffer, an overwritten input -- against
+                                serial calls on the same kernel (variant selector 16 | 2), five times over
+    test_small_key_right_after_shadow_calls   apply_lookup_table_small_key at once after four set_pipeline(1) calls: its second
+                                small-ciphertext buffer is the one those calls use
     test_small_key_order        blind rotation first, then the keyswitch of its output buffer"""
 import numpy as np
 import pytest
@@ -268,16 +274,38 @@ def test_dot4_many_levels(monkeypatch, p):
 
 # ---- through the blind rotation: shadow kernel, overlapped mode, small-key order -----------------------------------------------
 
-def _through_rotation(rig, mode, batches, test, expect):
+_EXACT = {}     # (shape, batches) -> the exact case below: rigs of one shape differ in their environment switches only
+
+
+def _exact_case(rig, batches):
+    """Distinct inputs per call, their table choices, exact keyswitch and exact PBS of it; computed once per shape and batch list."""
+    p = rig.p
+    k = (p.name, tuple(batches))
+    if k not in _EXACT:
+        big = [rig.inputs(B, salt=100 + i) for i, B in enumerate(batches)]
+        sel = [(np.arange(B) + i) % N_LUTS for i, B in enumerate(batches)]
+        smalls = [rig.ref(b) for b in big]
+        want_all = pbs_exact_batch_parallel(p, rig.terms, np.concatenate(smalls), rig.luts, np.concatenate(sel))
+        _EXACT[k] = (rig.ksk, rig.luts, big, sel, smalls, np.split(want_all, np.cumsum(batches)[:-1]))
+    ksk, luts, big, sel, smalls, wants = _EXACT[k]
+    assert np.array_equal(ksk, rig.ksk) and np.array_equal(luts, rig.luts), "the shared exact case is another key's"
+    return big, sel, smalls, wants
+
+
+def _pipelined_calls(eng):
+    """Pipelined calls of the engine's current run (fhe_debug_pipeline_calls, c_api.cpp): a call that falls back to the serial
+    path, and any synchronisation, ends the run and sets it to 0."""
+    import fhestr
+    return fhestr.lib().fhe_debug_pipeline_calls(eng._h)
+
+
+def _through_rotation(rig, mode, batches, test, expect, all_pipelined=False):
     """Consecutive apply_lookup_table_dev calls under set_pipeline(mode), distinct inputs per call; every output against
-    the exact PBS of the exact keyswitch.  expect(info, B) judges what the query reports after each call is enqueued."""
+    the exact PBS of the exact keyswitch.  expect(info, B) judges what the query reports after each call is enqueued.
+    all_pipelined: every call must have taken the throughput mode, none the serial path."""
     import torch
     p = rig.p
-    big = [rig.inputs(B, salt=100 + i) for i, B in enumerate(batches)]
-    sel = [(np.arange(B) + i) % N_LUTS for i, B in enumerate(batches)]
-    smalls = [rig.ref(b) for b in big]
-    want_all = pbs_exact_batch_parallel(p, rig.terms, np.concatenate(smalls), rig.luts, np.concatenate(sel))
-    wants = np.split(want_all, np.cumsum(batches)[:-1])
+    big, sel, smalls, wants = _exact_case(rig, batches)
     ins = [torch.from_numpy(b.view(np.int64)).cuda() for b in big]
     idx = [torch.from_numpy(rig.ids[s].astype(np.int32)).cuda() for s in sel]
     outs = [torch.zeros_like(t) for t in ins]
@@ -288,6 +316,7 @@ def _through_rotation(rig, mode, batches, test, expect):
         for i, o, x, B in zip(ins, outs, idx, batches):
             rig.eng.apply_lookup_table_dev(i.data_ptr(), x.data_ptr(), o.data_ptr(), B)
             infos.append(rig.eng.keyswitch_info())
+        taken = _pipelined_calls(rig.eng)
         rig.eng.synchronize()
     finally:
         rig.eng.set_pipeline(0)
@@ -295,6 +324,8 @@ def _through_rotation(rig, mode, batches, test, expect):
         _report(test, p, B, info)
     for call, (info, B) in enumerate(zip(infos, batches)):
         expect(info, B, call)
+    if all_pipelined:
+        assert taken == len(batches), f"{taken} of {len(batches)} calls ran in throughput mode {mode} after the last serial one"
     for call, (o, want, small) in enumerate(zip(outs, wants, smalls)):
         got = o.cpu().numpy().view(np.uint64)
         # a wrong keyswitch word moves the rotation: name the LWEs, then the words
@@ -325,6 +356,112 @@ def test_overlapped_mode_growing_batches(monkeypatch):
         mt, chunks, spc, steps = _mfma_geometry(rig.p, B)
         assert (info["kernel"], info["tile"], info["chunks"], info["steps_per_chunk"]) == ("mfma", mt, chunks, spc)
     _through_rotation(rig, 2, [33, 40, 96, 200, 64], "overlapped_mode", expect)
+
+
+STREAMS = [3, 4]
+
+
+def _streams_rig(monkeypatch, ns):
+    return _rig(monkeypatch, N2048, env=(("FHESTR_OVERLAP_STREAMS", ns),), structured=True)
+
+
+def _expect_mfma(rig):
+    def expect(info, B, call):
+        mt, chunks, spc, steps = _mfma_geometry(rig.p, B)
+        assert (info["kernel"], info["tile"], info["chunks"], info["steps_per_chunk"]) == ("mfma", mt, chunks, spc)
+    return expect
+
+
+@pytest.mark.parametrize("ns", STREAMS, ids=lambda n: f"streams{n}")
+def test_overlapped_mode_three_and_four_streams(monkeypatch, ns):
+    """set_pipeline(2) over three and four lanes (lanes 2 and 3 exist under these settings only).  Nine calls of 5, 96, 37 LWEs
+    in turn.  With three lanes every lane keeps its batch size (lane 0: 5, lane 1: 96, lane 2: 37).  With four, lane 0 meets
+    5, 96, 37 and lane 3 meets 5, 96: their small-ciphertext and digit buffers are replaced while the other lanes are busy;
+    lane 1 (96, 37) and lane 2 (37, 5) do not grow -- test_overlapped_mode_every_lane_grows is for that."""
+    rig = _streams_rig(monkeypatch, ns)
+    _through_rotation(rig, 2, [5, 96, 37] * 3, f"overlapped_mode_{ns}_streams", _expect_mfma(rig), all_pipelined=True)
+
+
+@pytest.mark.parametrize("ns", STREAMS, ids=lambda n: f"streams{n}")
+def test_overlapped_mode_every_lane_grows(monkeypatch, ns):
+    """One round of 5 LWEs on every lane, then one of 130 (more than any other call on these engines, five row tiles instead
+    of one): in the second round every lane, lanes 2 and 3 included, replaces its small-ciphertext and its digit buffer while
+    the calls of the other lanes are in flight."""
+    rig = _streams_rig(monkeypatch, ns)
+    _through_rotation(rig, 2, [5] * ns + [130] * ns, f"overlapped_mode_{ns}_streams_grow", _expect_mfma(rig), all_pipelined=True)
+
+
+@pytest.mark.parametrize("ns", STREAMS, ids=lambda n: f"streams{n}")
+def test_overlapped_mode_dependent_calls(monkeypatch, ns):
+    """Eight dependent calls on the engines above: a chain of four (every call reads the previous call's output, on another
+    lane), two calls into one output buffer, and a call that overwrites the input of the call before it.  Five times over
+    in mode 2, bit for bit what the same calls give one after the other on the same kernel (variant selector 16 | 2, for
+    the reference only: under a forced selector no call is eligible for mode 2).  Every mode-2 call must have been pipelined."""
+    import torch
+    rig = _streams_rig(monkeypatch, ns)
+    eng, B = rig.eng, 37
+    x = [torch.from_numpy(rig.inputs(B, salt=200 + i).view(np.int64)).cuda() for i in range(2)]
+    idx = torch.from_numpy(rig.ids[np.arange(B) % N_LUTS].astype(np.int32)).cuda()
+    names = [f"chain[{i}]" for i in range(4)] + ["same", "war_out", "scratch"]
+
+    def run(mode):
+        eng.set_pipeline(mode)
+        try:
+            chain = [torch.zeros_like(x[0]) for _ in range(4)]
+            same, war_out, scratch = torch.zeros_like(x[0]), torch.zeros_like(x[0]), x[1].clone()
+            torch.cuda.synchronize()            # torch's stream is not ordered with the engine's: its fills and the clone land first
+            calls = [(x[0], chain[0]), (chain[0], chain[1]), (chain[1], chain[2]), (chain[2], chain[3]),
+                     (x[0], same), (chain[0], same), (scratch, war_out), (x[0], scratch)]
+            for src, dst in calls:
+                eng.apply_lookup_table_dev(src.data_ptr(), idx.data_ptr(), dst.data_ptr(), B)
+            taken = _pipelined_calls(eng)
+            eng.synchronize()
+        finally:
+            eng.set_pipeline(0)
+        return [t.cpu().numpy() for t in chain + [same, war_out, scratch]], taken
+
+    eng.set_variant(16 | 2)                     # the serial reference on the kernel mode 2 uses
+    try:
+        want, taken = run(0)
+    finally:
+        eng.set_variant(0)
+    assert taken == 0
+    for rep in range(5):
+        got, taken = run(2)
+        assert taken == 8, f"{ns} streams, repetition {rep}: {taken} of 8 calls ran overlapped after the last serial one"
+        differ = [(nm, int((a != b).any(axis=1).sum())) for nm, a, b in zip(names, want, got) if not np.array_equal(a, b)]
+        assert not differ, f"{ns} streams, repetition {rep}: (output, LWEs that differ) {differ}"
+    assert not np.array_equal(want[0], want[1]) and not np.array_equal(want[4], want[0])     # the calls did compute something
+
+
+def test_small_key_right_after_shadow_calls(monkeypatch):
+    """apply_lookup_table_small_key writes its keyswitch into lane 1's small-ciphertext buffer, which every second
+    set_pipeline(1) call uses as well.  Four such calls, then the small-key call at once -- no synchronisation by the test,
+    the mode left on: the same words as before those calls.  (The call itself waits for the keyswitch stream before it
+    enqueues anything, and mode 1's rotations are on the engine's stream: this pins which buffer is used and that the
+    call ends the run, it cannot show a race.)"""
+    import torch
+    rig = _rig(monkeypatch, N2048, structured=True)
+    p, eng, B = rig.p, rig.eng, 96
+    small = edge_small_cts(p, np.random.default_rng(_seed(p, 70, 6)), 70)
+    sel = rig.ids[np.arange(70) % N_LUTS]
+    want = eng.apply_lookup_table_small_key(small, sel)
+    ins = [torch.from_numpy(rig.inputs(B, salt=300 + i).view(np.int64)).cuda() for i in range(4)]
+    outs = [torch.zeros_like(t) for t in ins]
+    idx = torch.from_numpy(rig.ids[np.arange(B) % N_LUTS].astype(np.int32)).cuda()
+    torch.cuda.synchronize()
+    eng.set_pipeline(1)
+    try:
+        for i, o in zip(ins, outs):
+            eng.apply_lookup_table_dev(i.data_ptr(), idx.data_ptr(), o.data_ptr(), B)
+        info, taken = eng.keyswitch_info(), _pipelined_calls(eng)
+        got = eng.apply_lookup_table_small_key(small, sel)
+        assert _pipelined_calls(eng) == 0
+    finally:
+        eng.set_pipeline(0)
+    assert info["kernel"] == "dot4_shadow" and taken == 4, f"the four calls did not all take mode 1: {taken}, {info}"
+    _assert_words(got, want, f"{p.name} small-key order after four mode-1 calls")
+    assert all(o.any().item() for o in outs)
 
 
 def test_small_key_order(monkeypatch):
