@@ -1,4 +1,5 @@
-// engine.h -- internal C++ interface of the engine (the public surface is include/fhestr.h).
+// engine.h -- internal C++ interface of the engine (the public surface is include/fhestr.h).  Its members are defined in
+// engine.hip, and in blind_rotate.hip where they need a blind-rotation kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,8 +35,11 @@ void aes128_round_keys(const uint8_t key[16], uint8_t rk[11][16]);   // seeded_k
 const uint8_t* aes_sbox();
 
 extern thread_local std::string g_last_error;
+// The error of a HIP call, or of a DeviceBuffer operation, under the name of the function that met it.
+inline int under(const char* who, hipError_t e) { return e == hipSuccess ? 0 : fail(std::string(who) + ": " + hipGetErrorString(e)); }
+inline int under(const char* who, int rc) { return rc ? fail(std::string(who) + ": " + g_last_error) : 0; }
 
-struct BrVariant;
+struct BrVariant;   // blind_rotate.h
 
 // fill_accumulator: shortint/engine/mod.rs:72-128 (host side, no device needed)
 uint64_t fill_accumulator(const fhe_params_t& p, const uint64_t* table, std::vector<uint64_t>& acc);
@@ -193,12 +197,12 @@ struct Engine {
     uint32_t xcd_auto_max = 16;     // automatic mode: batches up to this size take the whole-XCD kernel (two LWEs per XCD in flight)
     uint32_t cluster_spin_limit = 1u << 22;   // polls before a hand-over wait gives up (FHESTR_CLUSTER_SPIN_LIMIT)
     uint32_t cluster_test_fault = 0;          // tests only (FHESTR_CLUSTER_TEST_FAULT): epoch one workgroup stays silent at
-    int cluster_check();            // after a synchronisation: did a cluster launch give up on a hand-over?
+    int cluster_check();            // after a synchronisation: did a cluster launch give up on a hand-over?  (blind_rotate.hip)
 
     static int create(const fhe_params_t& p, int device, Engine** out);
     ~Engine();
     int use();
-    int set_variant(int logR);
+    int set_variant(int logR);   // blind_rotate.hip, like every member below that names a variant's kernel
     int allow_rotate_lds();   // hipFuncAttributeMaxDynamicSharedMemorySize of the variants' rotation kernels
     int load_keys(const uint64_t* bsk_std, const uint64_t* ksk);
     int load_seeded_keys(const uint8_t ksk_seed[16], const uint64_t* ksk_bodies, const uint8_t bsk_seed[16], const uint64_t* bsk_bodies,
@@ -210,6 +214,7 @@ struct Engine {
                       uint64_t* bsk_std_out, uint64_t* ksk_out);
     int install_keys(DeviceBuffer<uint64_t>&& d_ksk_std, DeviceBuffer<uint64_t>&& d_bsk_std);
     int convert_polys(const uint64_t* d_std, double* d_out, uint32_t n_polys);
+    int convert_dense_key(const uint64_t* d_std, uint32_t n_polys);   // d_fbsk_dense, where variant_large has a dense kernel
     int cluster_settle(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big, uint32_t count);
     int probe_slot_exponents();
     uint64_t fill_accumulator(const uint64_t* table, std::vector<uint64_t>& acc) const { return fhe::fill_accumulator(p, table, acc); }
@@ -230,6 +235,7 @@ struct Engine {
     int pack_lwes_host(const uint64_t* cts, uint32_t count, uint64_t* glwes);
     int unpack_glwes_dev(const uint64_t* d_glwes, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts);
     int unpack_glwes_host(const uint64_t* glwes, uint32_t first, uint32_t count, int refresh, uint64_t* cts);
+    uint32_t rotate_registers() const;             // VGPRs of variant's rotation kernel, 0 if unknown
     void keyswitch_info(uint32_t info[6]) const;   // ks_last and the register count shadow_keyswitch_fits judges by; changes nothing
     int ks_pbs_dev(const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint64_t* d_big_out, uint32_t count, bool allow_pipeline = false);
     int ks_pbs_host(const uint64_t* in, const uint32_t* lut_idx, uint64_t* out, uint32_t count);

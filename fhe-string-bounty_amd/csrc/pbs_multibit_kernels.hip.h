@@ -176,20 +176,35 @@ struct MultiBitCombineGenericArgs {
     uint32_t n, logN, P, ggsw_elems, count;
 };
 
+// Launch shape of multibit_combine_generic_kernel: grid (n/G, ceil(ggsw_elems / ELEMS_PER_WG), ceil(count / CHUNK)); the
+// kernel body and the variant registry (blind_rotate.hip) both read it from here.
+struct MultiBitCombineGenericCfg {
+    static constexpr int THREADS = 256;
+    static constexpr int EPT = 2;                        // GGSW elements per thread
+    static constexpr int ELEMS_PER_WG = EPT * THREADS;
+    static constexpr int CHUNK = 8;                      // LWEs one workgroup walks with the key GGSWs in registers
+    // two-level root table of e^{i pi m / N}, m < 2N, split as in BrMultiBitCfg::LDS_ROOTS
+    static constexpr uint32_t root_lo_bits(uint32_t logN) { return (logN + 1) / 2; }
+    static constexpr size_t lds_bytes(uint32_t logN) {
+        return ((size_t)(1u << root_lo_bits(logN)) + (size_t)(1u << (logN + 1 - root_lo_bits(logN)))) * 16;
+    }
+};
+
 template <int G>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(MultiBitCombineGenericCfg::THREADS)
 multibit_combine_generic_kernel(MultiBitCombineGenericArgs a) {
-    constexpr int SEL = (1 << G) - 1, EPT = 2, CHUNK = 8;
+    using CFG = MultiBitCombineGenericCfg;
+    constexpr int SEL = (1 << G) - 1, EPT = CFG::EPT, CHUNK = CFG::CHUNK;
     extern __shared__ __align__(16) unsigned char smem[];
-    const uint32_t lo_bits = (a.logN + 1) / 2, hi_bits = a.logN + 1 - lo_bits, N = 1u << a.logN;
+    const uint32_t lo_bits = CFG::root_lo_bits(a.logN), hi_bits = a.logN + 1 - lo_bits, N = 1u << a.logN;
     double2* root_lo = reinterpret_cast<double2*>(smem);
     double2* root_hi = root_lo + (1u << lo_bits);
-    for (uint32_t e = threadIdx.x; e < (1u << lo_bits); e += 256) {
+    for (uint32_t e = threadIdx.x; e < (1u << lo_bits); e += CFG::THREADS) {
         double sn, cs;
         sincospi((double)e / (double)N, &sn, &cs);
         root_lo[e] = make_double2(cs, sn);
     }
-    for (uint32_t e = threadIdx.x; e < (1u << hi_bits); e += 256) {
+    for (uint32_t e = threadIdx.x; e < (1u << hi_bits); e += CFG::THREADS) {
         double sn, cs;
         sincospi((double)((size_t)e << lo_bits) / (double)N, &sn, &cs);
         root_hi[e] = make_double2(cs, sn);
@@ -200,7 +215,7 @@ multibit_combine_generic_kernel(MultiBitCombineGenericArgs a) {
     double2 gv[SEL + 1][EPT];
 #pragma unroll
     for (int k = 0; k < EPT; k++) {
-        elem[k] = (blockIdx.y * EPT + k) * 256 + threadIdx.x;
+        elem[k] = (blockIdx.y * EPT + k) * CFG::THREADS + threadIdx.x;
         const bool live = elem[k] < a.ggsw_elems;
         expo[k] = live ? a.slot_exp[elem[k] % a.P] : 0;
 #pragma unroll

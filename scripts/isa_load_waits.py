@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static check of the blind-rotation kernels' main loops for serialised memory loads (no GPU needed).
 
-Compiles csrc/engine.hip to gfx950 assembly and, for every blind_rotate_* kernel, finds its largest loop and counts global /
+Compiles csrc/blind_rotate.hip to gfx950 assembly and, for every blind_rotate_* kernel, finds its largest loop and counts global /
 buffer loads, scratch (spill) loads, `s_waitcnt vmcnt` instructions, and how many of those waits drain a queue of at most two
 loads -- the signature of "load, wait, use" chains that pay the L2 latency once per load.  Round 4 found an N = 1024 build whose
 36 key loads per step had come out that way (2x slower); the largest loop of the multi-CU kernels is their per-LWE loop, whose
@@ -13,7 +13,7 @@ import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = os.path.join(tempfile.mkdtemp(), "engine.s")
 subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-S",
-                "-o", out, os.path.join(ROOT, "fhe-string-bounty_amd", "csrc", "engine.hip")] + sys.argv[1:], check=True, stderr=subprocess.DEVNULL)
+                "-o", out, os.path.join(ROOT, "fhe-string-bounty_amd", "csrc", "blind_rotate.hip")] + sys.argv[1:], check=True, stderr=subprocess.DEVNULL)
 kern, cur = {}, None
 for l in open(out):
     l = l.rstrip("\n")

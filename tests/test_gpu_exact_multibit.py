@@ -1,7 +1,7 @@
 """Multi-bit blind rotation against exact integers at every batch regime (tier 1 of tests/test_gpu_exact_rotation.py:
 the whole output ciphertext, mask and body, equals multi_bit_pbs_exact_batch bit for bit under a structured key).
 
-What the batch size changes (choose_rotate_path, rotate_multibit_combined, rotate_multibit_two_kernel in csrc/engine.hip):
+What the batch size changes (choose_rotate_path, rotate_multibit_combined, rotate_multibit_two_kernel in csrc/blind_rotate.hip):
     N = 2048, B <= multibit_combine_max = 64   multibit_combine_kernel walks chunks of 8 LWEs (grid z = ceil(B / 8)), then the
                                                PRE rotation reads [B][n/G] prepared GGSWs: B = 1, 7, 8, 9, 17, 64
     N = 2048, B > 64                           the fused kernel, one workgroup per LWE and no two-per-CU twin: 65, 256 (the

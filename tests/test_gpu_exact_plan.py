@@ -253,7 +253,7 @@ def test_two_operand_entry_points(p):
 
 def _crossing_count(plan, limit=None):
     """Smallest instance count for which jobs x instances of the plan's widest level exceeds `limit`; by default the
-    device's compute units (256 on an MI355X): choose_rotate_path (csrc/engine.hip) then takes the variant that shares a
+    device's compute units (256 on an MI355X): choose_rotate_path (csrc/blind_rotate.hip) then takes the variant that shares a
     CU between two LWEs.  The count follows the device, so the case cannot go stale against that threshold."""
     import torch
     cus = torch.cuda.get_device_properties(0).multi_processor_count

@@ -4,7 +4,7 @@ Tier 1, bit exact: under a structured bootstrapping key (every word c << t, |c| 
 every value of a correct f64 PBS lies on the engine's from_torus grid with a wide margin (tests/test_exact_pbs.py pins
 that premise on the CPU oracle), so the whole output ciphertext -- mask and body -- must equal the exact integer PBS bit
 for bit.  A transform that lost precision, a wrong twiddle, a swapped GGSW block, level or sign shows as a mismatch.
-Each path is reached through the public setters and batch sizes only (choose_rotate_path in csrc/engine.hip is
+Each path is reached through the public setters and batch sizes only (choose_rotate_path in csrc/blind_rotate.hip is
 the map; an MI355X has 256 CUs).  Multi-bit here runs B = 5 on every shape; its batch regimes -- the combined prepass's chunks
 of 8 up to multibit_combine_max = 64, the fused kernel from 65 on and beyond the CU count, the two-kernel path's sub-batch
 loop (reached through the environment switch FHESTR_MULTIBIT_WS_CAP, bytes, read when an engine is created) and real n --

@@ -74,7 +74,7 @@ def test_reference_parameter_set_decrypts(name):
         eng.close()
 
 
-# One parameter set per blind-rotation kernel family (csrc/engine.hip, variants()): N = 256 (k = 5), 512 (k = 3 and k = 2 with
+# One parameter set per blind-rotation kernel family (csrc/blind_rotate.hip, variants()): N = 256 (k = 5), 512 (k = 3 and k = 2 with
 # two levels), 1024 (k = 2), 2048, 4096 (one and two levels), 8192 (seq kernel, one and two levels), 16384 and 32768 (cluster
 # kernel, two and three levels).
 FAMILIES = ["PARAM_MESSAGE_1_CARRY_0_KS_PBS", "PARAM_MESSAGE_1_CARRY_1_KS_PBS", "PARAM_MESSAGE_2_CARRY_0_KS_PBS",

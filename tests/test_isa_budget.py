@@ -1,6 +1,6 @@
 """Instruction budget of the P22 CMUX step (no GPU needed).
 
-Compiles csrc/engine.hip to gfx950 assembly the way scripts/isa_load_waits.py does, takes the main loop of
+Compiles csrc/blind_rotate.hip to gfx950 assembly the way scripts/isa_load_waits.py does, takes the main loop of
 blind_rotate_wide_kernel<11,2,2,1,false> (PARAM_MESSAGE_2_CARRY_2's kernel, the one bench.py's headline spends its
 time in) and checks its per-wave-step instruction counts against the budget of kernel revision r04.2, so that a
 register-allocation or scheduling change that quietly brings back instructions is seen here:
@@ -36,7 +36,7 @@ def asm(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("isa") / "engine.s")
     subprocess.run([HIPCC if os.path.exists(HIPCC) else "hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950",
                     "-ffp-contract=off", "--cuda-device-only", "-S", "-o", out,
-                    os.path.join(ROOT, "fhe-string-bounty_amd", "csrc", "engine.hip")],
+                    os.path.join(ROOT, "fhe-string-bounty_amd", "csrc", "blind_rotate.hip")],
                    check=True, stderr=subprocess.DEVNULL)
     return open(out).read()
 
