@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "det_math.h"
 #include "engine.h"
 
 using fhe::fail;
@@ -153,6 +154,32 @@ int fhe_debug_pipeline_calls(fhe_engine* eng) {
     if (!eng) return -1;
     LOCK_ENGINE(eng);
     return (int)eng->impl->pipe.calls;
+}
+
+// Not part of include/fhestr.h (tests only): the parts of the noise sampler (det_math.h) as the host compiles them, so the
+// tests can hold them against a real logarithm and a real normal distribution (tests/test_exact_keys.py).
+int fhe_debug_det_log(const double* x, size_t n, double* out) {
+    if (n && (!x || !out)) return fail("null pointer");
+    for (size_t i = 0; i < n; i++) out[i] = fhe::det_log(x[i]);
+    return 0;
+}
+
+// `count` consecutive gaussian_torus values of one Rng (seed, stream)
+int fhe_debug_noise_samples(const uint8_t seed[32], uint64_t stream, double std_dev, size_t count, uint64_t* out) {
+    if (!seed || (count && !out)) return fail("null pointer");
+    fhe::Rng r(fhe::seed_from_bytes(seed), stream);
+    for (size_t i = 0; i < count; i++) out[i] = fhe::gaussian_torus(r, std_dev);
+    return 0;
+}
+
+// round_half_away and from_torus_exact of every x
+int fhe_debug_round_torus(const double* x, size_t n, double* rounded, uint64_t* torus) {
+    if (n && (!x || !rounded || !torus)) return fail("null pointer");
+    for (size_t i = 0; i < n; i++) {
+        rounded[i] = fhe::round_half_away(x[i]);
+        torus[i] = fhe::from_torus_exact(x[i]);
+    }
+    return 0;
 }
 
 int fhe_engine_set_multibit_combine_max(fhe_engine* eng, uint32_t max_batch) {

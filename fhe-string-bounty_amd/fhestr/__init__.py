@@ -211,6 +211,9 @@ def lib() -> C.CDLL:
     sig("fhe_engine_generate_keys", vp, vp, vp, vp, vp, vp)
     sig("fhe_random_seed", vp)
     sig("fhe_chacha20_block", vp, C.c_uint64, C.c_uint64, vp)
+    sig("fhe_debug_det_log", vp, C.c_size_t, vp)
+    sig("fhe_debug_noise_samples", vp, C.c_uint64, C.c_double, C.c_size_t, vp)
+    sig("fhe_debug_round_torus", vp, C.c_size_t, vp, vp)
     sig("fhe_engine_synchronize", vp)
     sig("fhe_engine_set_variant", vp, i32)
     sig("fhe_engine_set_multibit_combine_max", vp, u32)
@@ -352,6 +355,31 @@ def chacha20_block(key: bytes, counter: int, stream: int) -> np.ndarray:
     kb = (C.c_uint8 * 32)(*seed_bytes(key))
     _check(lib().fhe_chacha20_block(kb, C.c_uint64(counter), C.c_uint64(stream), _ptr(out)))
     return out
+
+
+def debug_det_log(x) -> np.ndarray:
+    """det_log (csrc/det_math.h, the sampler's libm-free logarithm) of every x, as the host computes it.  Tests only."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.zeros(x.shape, dtype=np.float64)
+    _check(lib().fhe_debug_det_log(_ptr(x), x.size, _ptr(out)))
+    return out
+
+
+def debug_noise_samples(seed, stream: int, std_dev: float, count: int) -> np.ndarray:
+    """`count` consecutive gaussian_torus values (csrc/det_math.h) of one ChaCha20 stream, as torus words.  Tests only."""
+    out = np.zeros(count, dtype=np.uint64)
+    sb = (C.c_uint8 * 32)(*seed_bytes(seed))
+    _check(lib().fhe_debug_noise_samples(sb, C.c_uint64(stream), float(std_dev), count, _ptr(out)))
+    return out
+
+
+def debug_round_torus(x):
+    """(round_half_away(x), from_torus_exact(x)) of every x (csrc/det_math.h).  Tests only."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    rounded = np.zeros(x.shape, dtype=np.float64)
+    torus = np.zeros(x.shape, dtype=np.uint64)
+    _check(lib().fhe_debug_round_torus(_ptr(x), x.size, _ptr(rounded), _ptr(torus)))
+    return rounded, torus
 
 
 def pinned_empty(shape, dtype=np.uint64):
