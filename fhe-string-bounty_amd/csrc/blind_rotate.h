@@ -7,10 +7,13 @@
 #include <stdint.h>
 
 #include "../../include/fhestr.h"
+#include "device_buffer.h"
 
 namespace fhe {
 
 struct Engine;
+struct ClusterCtl;      // pbs_cluster_kernels.hip.h
+struct ClusterStatus;
 
 // A kernel and its launch shape, filled in from the kernel's own config struct where the kernel is instantiated.
 struct KernelRef {
@@ -70,6 +73,31 @@ const BrVariant* find_variant(const fhe_params_t& p, int selector);
 // twin of the default (same points per thread => same key layout) serves the big batches.
 struct BrVariantPair { const BrVariant *small, *large; };
 BrVariantPair find_variant_pair(const fhe_params_t& p, int selector);
+
+// ---- what the multi-CU rotation paths keep between launches (the 8-CU clusters and the whole-XCD kernel) ---------------------
+// One device block holds the ClusterCtl (tickets, flags: zeroed per launch) and, right behind it, the ClusterStatus (sticky
+// until the host has read an error out of it).  Defined in blind_rotate.hip.
+struct MultiCuRuntime {
+    DeviceBuffer<unsigned char> ws;   // exchange matrices: 1.5 MB per cluster (L2-resident by design)
+    DeviceBuffer<void> block;         // ClusterCtl + ClusterStatus
+    bool unchecked = false;           // a launch whose status words have not been read yet (cfg.cluster_fallback off)
+    uint32_t last = 0;                // clusters the last checked launch formed
+    uint32_t n_fallbacks = 0;         // launches that gave up and were re-run on the one-workgroup kernel
+    uint32_t last_error = 0;          // the status code of the latest of them
+    int xcd_per_cu = -1;              // workgroups of the whole-XCD kernel a CU holds (occupancy query, cached)
+
+    // Before a launch, on its stream: room for max_clusters workspaces, the block (allocated and zeroed whole on first use),
+    // the control part zeroed.
+    int prepare(hipStream_t stream, uint32_t max_clusters, size_t ws_per_cluster);
+    ClusterCtl* ctl() const;
+    ClusterStatus* status() const;
+    // After a launch of `count` LWEs on e.stream: wait, read the status and, where the launch gave up, run the batch again on
+    // the one-workgroup kernel.  With cfg.cluster_fallback off: leave it to the next check().
+    int settle(Engine& e, const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big, uint32_t count);
+    int check();                      // after a synchronisation: did an unsettled launch give up on a hand-over?
+    uint32_t last_clusters() const { return last; }   // fhe_engine_cluster_info
+    uint32_t fallbacks() const { return n_fallbacks; }   // fhe_engine_cluster_fallbacks
+};
 
 // May a call take throughput mode 2 (whole calls overlapped on several streams) / mode 1 (its keyswitch in the shadow of the
 // previous call's blind rotation)?  Asked by Engine::ks_pbs_dev.

@@ -280,16 +280,17 @@ int Engine::convert_dense_key(const uint64_t* d_std, uint32_t n_polys) {
 enum class BrPath { Overlapped, MultiBitCombined, MultiBitTwoKernel, WholeXcd, Cluster, Large, Dense, Plain };
 
 // Which path serves a batch, and (`v`) on which of the engine's two variants.  Reads cu_count and the dispatch settings
-// (cluster_mode, cluster_max_batch, xcd_auto_max, multibit_combine_max, dense_per_cu, whether d_fbsk_dense exists); calls no HIP
-// function.  The order of the tests matters.  one_workgroup_only: the re-run of Engine::cluster_settle, never a multi-CU kernel.
+// of e.cfg (cluster_mode, cluster_max_batch, xcd_auto_max, multibit_combine_max, dense_per_cu) and whether d_fbsk_dense exists; calls
+// no HIP function.  The order of the tests matters.  one_workgroup_only: the re-run of MultiCuRuntime::settle, never a multi-CU kernel.
 static BrPath choose_rotate_path(const Engine& e, uint32_t count, bool two_per_cu, bool one_workgroup_only, const BrVariant*& v) {
+    const EngineSettings& cfg = e.cfg;
     const uint32_t cus = (uint32_t)e.cu_count;
     // one LWE per CU or fewer: spread it over more threads; above that: the compact layout that lets two LWEs share a CU
     v = two_per_cu || count > cus ? e.variant_large : e.variant;
     if (two_per_cu) return BrPath::Overlapped;      // overlapped throughput mode: the compact layout whatever the batch size, on the given stream
     // far fewer LWEs than CUs: the idle CUs prepare the groups' GGSWs (lwe_multi_bit_programmable_bootstrapping.rs
     // splits the same way over CPU threads), the rotation then runs n/G plain external products
-    if (v->combine && count <= e.multibit_combine_max) return BrPath::MultiBitCombined;
+    if (v->combine && count <= cfg.multibit_combine_max) return BrPath::MultiBitCombined;
     // multi-bit PBS on a shape without a fused kernel: prepare the (LWE, group) GGSWs, then n/G external products per LWE
     if (v->rotate_is_extprod) return BrPath::MultiBitTwoKernel;
     // automatic mode: the whole-XCD kernel up to two LWEs per XCD (one LWE 12.3 ms, 16 LWEs 18.4 ms; the 8-CU clusters: 20.9 /
@@ -297,15 +298,15 @@ static BrPath choose_rotate_path(const Engine& e, uint32_t count, bool two_per_c
     // hand-over latency better than two; profiles/r04_xcd_history.txt).  Mode 2: clusters, never the whole-XCD kernel.
     // (a device with fewer than 8 * C compute units -- e.g. one XCD of a partitioned GPU -- cannot host a grid of either
     // kernel: it takes the one-workgroup kernel below)
-    const int mode = one_workgroup_only ? 0 : e.cluster_mode;
-    if (v->xcd && mode != 0 && mode != 2 && (mode == 1 || count <= std::min(e.cluster_max_batch, e.xcd_auto_max)) &&
+    const int mode = one_workgroup_only ? 0 : cfg.cluster_mode;
+    if (v->xcd && mode != 0 && mode != 2 && (mode == 1 || count <= std::min(cfg.cluster_max_batch, cfg.xcd_auto_max)) &&
         cus >= 8u * (uint32_t)v->xcd_size)
         return BrPath::WholeXcd;
-    if (v->cluster && mode != 0 && (mode >= 1 || count <= e.cluster_max_batch) && cus >= 8u * (uint32_t)v->cluster_size)
+    if (v->cluster && mode != 0 && (mode >= 1 || count <= cfg.cluster_max_batch) && cus >= 8u * (uint32_t)v->cluster_size)
         return BrPath::Cluster;
     if (v->large) return BrPath::Large;      // polynomial beyond the LDS: one workgroup per LWE with an HBM workspace
     // more than two LWEs per CU: the variant that puts four on one
-    if (v->dense && e.d_fbsk_dense && e.dense_per_cu && count > e.dense_per_cu * cus) return BrPath::Dense;
+    if (v->dense && e.d_fbsk_dense && cfg.dense_per_cu && count > cfg.dense_per_cu * cus) return BrPath::Dense;
     return BrPath::Plain;
 }
 
@@ -322,7 +323,7 @@ bool shadow_mode_eligible(const Engine& e, uint32_t count) {
 }
 
 static int rotate_overlapped(Engine& e, const BrVariant* w, BlindRotateArgs a, hipStream_t on) {
-    a.fair_shift = e.wide_fair_shift;      // the two launches that share the GPU progress at the same rate (110 k -> 122 k PBS/s)
+    a.fair_shift = e.cfg.wide_fair_shift;      // the two launches that share the GPU progress at the same rate (110 k -> 122 k PBS/s)
     void* args[] = {(void*)&a};
     HIP_TRY(launch(w->rotate, dim3(a.batch), args, e.p.n, on));
     return 0;
@@ -348,7 +349,7 @@ static int rotate_multibit_two_kernel(Engine& e, const BrVariant* v, const Blind
     const uint32_t count = a.batch;
     const size_t groups = p.n / p.grouping_factor, per_lwe = groups * v->combined_bytes;
     const size_t rot_ws = v->large ? v->ws_bytes : 0;
-    size_t cap = e.multibit_workspace_cap;
+    size_t cap = e.cfg.multibit_workspace_cap;
     if (cap == 0) {       // automatic: half of what is free now (plus what the workspace already holds), at most 64 GB
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
@@ -384,31 +385,25 @@ static int rotate_multi_cu(Engine& e, const BlindRotateArgs& a, const KernelRef&
     const uint32_t max_clusters = std::min<uint32_t>((uint32_t)CLUSTER_MAX, ((uint32_t)e.cu_count / quantum) * 8 * rounds);
     const uint32_t grid = (std::min(a.batch, max_clusters) + 7) / 8 * quantum;
     const size_t lds = grid <= (uint32_t)e.cu_count ? std::max(k.lds(e.p.n), lds_one_per_cu) : k.lds(e.p.n);
-    if (e.d_cluster_ws.reserve((size_t)max_clusters * ws_per_cluster)) return 1;
-    if (!e.d_cluster_ctl) {
-        if (e.d_cluster_ctl.alloc(sizeof(ClusterCtl) + sizeof(ClusterStatus))) return 1;
-        HIP_TRY(hipMemsetAsync(e.d_cluster_ctl, 0, sizeof(ClusterCtl) + sizeof(ClusterStatus), e.stream));
-    }
-    // tickets and flags start from zero; the status words behind them are sticky (read by cluster_status())
-    HIP_TRY(hipMemsetAsync(e.d_cluster_ctl, 0, sizeof(ClusterCtl), e.stream));
-    ClusterCtl* ctl = static_cast<ClusterCtl*>(e.d_cluster_ctl.ptr);
-    BlindRotateClusterArgs ka{a, e.d_cluster_ws, ctl, reinterpret_cast<ClusterStatus*>(ctl + 1),
-                              e.cluster_spin_limit, e.cluster_test_fault};
+    MultiCuRuntime& rt = e.multi_cu;
+    if (rt.prepare(e.stream, max_clusters, ws_per_cluster)) return 1;
+    BlindRotateClusterArgs ka{a, rt.ws, rt.ctl(), rt.status(), e.cfg.cluster_spin_limit, e.cfg.cluster_test_fault};
     void* kargs[] = {(void*)&ka};
     HIP_TRY(launch(k, dim3(grid), kargs, e.p.n, e.stream, lds));
-    return e.cluster_settle(a.lwe_small, a.lut_idx, a.lwe_out, a.batch);
+    return rt.settle(e, a.lwe_small, a.lut_idx, a.lwe_out, a.batch);
 }
 
 // All CUs of an XCD per LWE (pbs_xcd_kernels.hip.h).  Up to 8 LWEs: one cluster per XCD, one 256-thread workgroup
 // per CU (the dynamic LDS request is padded past half a CU's LDS so that no CU takes two).  More: two clusters per
 // XCD, i.e. two workgroups on every CU -- the grid is exactly what the device holds.
 static int rotate_whole_xcd(Engine& e, const BrVariant* v, const BlindRotateArgs& a) {
-    if (e.xcd_per_cu < 0) {       // once per engine: do two of its workgroups fit a CU?  (registers, LDS: asked, not assumed)
+    int& xcd_per_cu = e.multi_cu.xcd_per_cu;
+    if (xcd_per_cu < 0) {       // once per engine: do two of its workgroups fit a CU?  (registers, LDS: asked, not assumed)
         int per_cu = 0;
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->xcd.fn, v->xcd.threads, v->xcd.lds(e.p.n)));
-        e.xcd_per_cu = per_cu;
+        xcd_per_cu = per_cu;
     }
-    const uint32_t rounds = (a.batch > 8 && e.xcd_per_cu >= 2) ? 2u : 1u;
+    const uint32_t rounds = (a.batch > 8 && xcd_per_cu >= 2) ? 2u : 1u;
     return rotate_multi_cu(e, a, v->xcd, (uint32_t)v->xcd_size, v->xcd_lds_one_per_cu, v->xcd_ws, rounds);
 }
 
@@ -433,7 +428,7 @@ static int rotate_plain(Engine& e, const BrVariant* v, BlindRotateArgs a) {
     // keep-busy mode (fhe_engine_set_keep_busy): a launch that would leave more than half of the CUs idle carries replicas of
     // its workgroups on them (they recompute and store nothing) -- the part then keeps its clock for the large launch that
     // follows (2.22 -> 2.39 GHz over 14 ms otherwise, profiles/r03_after_idle.txt), at the price of the energy
-    if (e.keep_busy && !v->wide && !v->large && a.batch * 2 <= (uint32_t)e.cu_count) grid = a.batch * ((uint32_t)e.cu_count / a.batch);
+    if (e.cfg.keep_busy && !v->wide && !v->large && a.batch * 2 <= (uint32_t)e.cu_count) grid = a.batch * ((uint32_t)e.cu_count / a.batch);
     void* args[] = {(void*)&a};
     HIP_TRY(launch(v->rotate_keypf && v->wide ? v->rotate_keypf : v->rotate, dim3(grid), args, e.p.n, e.stream));
     return 0;
@@ -447,7 +442,7 @@ int Engine::launch_blind_rotate(const uint64_t* d_sm, const uint32_t* d_lut_idx,
     a.grouping = 0;
     // two-LWEs-per-CU kernel: fair time-sliced priorities when every CU gets an even number of workgroups (pbs_kernels.hip.h)
     const uint32_t cus = (uint32_t)cu_count;
-    a.fair_shift = (count > cus && (((count + cus - 1) / cus) & 1u) == 0) ? wide_fair_shift : 0u;
+    a.fair_shift = (count > cus && (((count + cus - 1) / cus) & 1u) == 0) ? cfg.wide_fair_shift : 0u;
     const BrVariant* v = nullptr;
     switch (choose_rotate_path(*this, count, two_per_cu, one_workgroup_only, v)) {
         case BrPath::Overlapped: return rotate_overlapped(*this, v, a, on ? on : stream);
@@ -483,6 +478,21 @@ uint32_t Engine::rotate_registers() const {
     return variant && hipFuncGetAttributes(&fa, variant->rotate.fn) == hipSuccess ? (uint32_t)fa.numRegs : 0u;
 }
 
+// ---- MultiCuRuntime ---------------------------------------------------------------------------------------------------
+int MultiCuRuntime::prepare(hipStream_t stream, uint32_t max_clusters, size_t ws_per_cluster) {
+    if (ws.reserve((size_t)max_clusters * ws_per_cluster)) return 1;
+    if (!block) {
+        if (block.alloc(sizeof(ClusterCtl) + sizeof(ClusterStatus))) return 1;
+        HIP_TRY(hipMemsetAsync(block, 0, sizeof(ClusterCtl) + sizeof(ClusterStatus), stream));
+    }
+    // tickets and flags start from zero; the status words behind them are sticky (read by settle() / check())
+    HIP_TRY(hipMemsetAsync(block, 0, sizeof(ClusterCtl), stream));
+    return 0;
+}
+
+ClusterCtl* MultiCuRuntime::ctl() const { return static_cast<ClusterCtl*>(block.ptr); }
+ClusterStatus* MultiCuRuntime::status() const { return reinterpret_cast<ClusterStatus*>(ctl() + 1); }
+
 // The cluster kernel never hangs on a hand-over that does not arrive: it gives up, finishes with garbage and says so
 // in its status words.  Every host-visible completion point asks here.
 // A launch of one of the multi-CU kernels is settled before the call returns: the host waits for it, reads the
@@ -490,28 +500,27 @@ uint32_t Engine::rotate_registers() const {
 // the kernel drained with invalid results instead of hanging -- runs the same batch on the one-workgroup kernel, which
 // needs nothing resident but itself.  These kernels take 10 ms and more per launch: the synchronisation costs nothing
 // measurable.  FHESTR_CLUSTER_FALLBACK=0: the round-3 behaviour (checked at the next completion point, reported as an error).
-int Engine::cluster_settle(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big, uint32_t count) {
-    if (!cluster_fallback) { cluster_unchecked = true; return 0; }
+int MultiCuRuntime::settle(Engine& e, const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big, uint32_t count) {
+    if (!e.cfg.cluster_fallback) { unchecked = true; return 0; }
     ClusterStatus st{};
-    ClusterStatus* d_st = reinterpret_cast<ClusterStatus*>(static_cast<ClusterCtl*>(d_cluster_ctl.ptr) + 1);
-    HIP_TRY(hipMemcpyAsync(&st, d_st, sizeof(st), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    cluster_last = st.clusters;
+    HIP_TRY(hipMemcpyAsync(&st, status(), sizeof(st), hipMemcpyDeviceToHost, e.stream));
+    HIP_TRY(hipStreamSynchronize(e.stream));
+    last = st.clusters;
     if (!st.error) return 0;
-    HIP_TRY(hipMemsetAsync(d_st, 0, sizeof(st), stream));
-    cluster_fallbacks++;
-    cluster_last_error = st.error;
-    return launch_blind_rotate(d_sm, d_lut_idx, d_big, count, nullptr, false, /*one_workgroup_only=*/true);
+    HIP_TRY(hipMemsetAsync(status(), 0, sizeof(st), e.stream));
+    n_fallbacks++;
+    last_error = st.error;
+    return e.launch_blind_rotate(d_sm, d_lut_idx, d_big, count, nullptr, false, /*one_workgroup_only=*/true);
 }
 
-int Engine::cluster_check() {
-    if (!cluster_unchecked || !d_cluster_ctl) return 0;
+int MultiCuRuntime::check() {
+    if (!unchecked || !block) return 0;
     ClusterStatus st{};
-    HIP_TRY(hipMemcpy(&st, static_cast<ClusterCtl*>(d_cluster_ctl.ptr) + 1, sizeof(st), hipMemcpyDeviceToHost));
-    cluster_unchecked = false;
-    cluster_last = st.clusters;
+    HIP_TRY(hipMemcpy(&st, status(), sizeof(st), hipMemcpyDeviceToHost));
+    unchecked = false;
+    last = st.clusters;
     if (st.error) {
-        HIP_TRY(hipMemset(static_cast<ClusterCtl*>(d_cluster_ctl.ptr) + 1, 0, sizeof(st)));
+        HIP_TRY(hipMemset(status(), 0, sizeof(st)));
         return fail("blind_rotate_cluster_kernel: a cluster hand-over timed out (code " + std::to_string(st.error) +
                     "); results of that launch are invalid");
     }

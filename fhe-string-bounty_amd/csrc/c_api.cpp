@@ -28,6 +28,8 @@ using fhe::fail;
 #define LOCK_PLAN(p) \
     std::unique_lock<std::recursive_mutex> _plan_lock; \
     if ((p)->c->engine()) _plan_lock = std::unique_lock<std::recursive_mutex>((p)->c->engine()->mu)
+// what an EngineSettings setter answered: nullptr (accepted), or why it refused the value and changed nothing
+static int refused(const char* why) { return why ? fail(why) : 0; }
 
 extern "C" {
 
@@ -185,26 +187,21 @@ int fhe_debug_round_torus(const double* x, size_t n, double* rounded, uint64_t* 
 int fhe_engine_set_multibit_combine_max(fhe_engine* eng, uint32_t max_batch) {
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng);
-    if (max_batch > 1024) return fhe::fail("multibit_combine_max: at most 1024 (workspace grows by 16 MB per LWE at N = 2048)");
-    eng->impl->multibit_combine_max = max_batch;
-    return 0;
+    return refused(eng->impl->cfg.set_multibit_combine_max(max_batch));
     API_END
 }
 
 int fhe_engine_set_cluster_mode(fhe_engine* eng, int mode, uint32_t max_batch) {
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng);
-    if (mode < -1 || mode > 2) return fhe::fail("cluster mode: -1 (automatic), 0 (never), 1 (always) or 2 (always, the 8-CU clusters of round 3)");
-    eng->impl->cluster_mode = mode;
-    eng->impl->cluster_max_batch = max_batch;
-    return 0;
+    return refused(eng->impl->cfg.set_cluster_mode(mode, max_batch));
     API_END
 }
 
 int fhe_engine_set_keep_busy(fhe_engine* eng, int on) {
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng);
-    eng->impl->keep_busy = on != 0;
+    eng->impl->cfg.set_keep_busy(on);
     return 0;
     API_END
 }
@@ -213,7 +210,7 @@ int fhe_engine_cluster_info(fhe_engine* eng, uint32_t* clusters) {
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(clusters);
     if (eng->impl->synchronize()) return 1;
-    *clusters = eng->impl->cluster_last;
+    *clusters = eng->impl->multi_cu.last_clusters();
     return 0;
     API_END
 }
@@ -253,7 +250,7 @@ int fhe_engine_pack_lwes_dev(fhe_engine* eng, const uint64_t* d_cts, uint32_t co
 int fhe_engine_packing_info(fhe_engine* eng, uint32_t info[5]) {
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(info);
-    for (int q = 0; q < 5; q++) info[q] = eng->impl->pack_last[q];
+    eng->impl->packing.pack_info(info);
     return 0;
     API_END
 }
@@ -277,7 +274,7 @@ int fhe_engine_unpack_glwes_dev(fhe_engine* eng, const uint64_t* d_glwes, uint32
 int fhe_engine_unpack_info(fhe_engine* eng, uint32_t info[4]) {
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(info);
-    for (int q = 0; q < 4; q++) info[q] = eng->impl->unpack_last[q];
+    eng->impl->packing.unpack_info(info);
     return 0;
     API_END
 }
@@ -285,7 +282,7 @@ int fhe_engine_unpack_info(fhe_engine* eng, uint32_t info[4]) {
 int fhe_engine_cluster_fallbacks(fhe_engine* eng, uint32_t* count) {
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(count);
-    *count = eng->impl->cluster_fallbacks;
+    *count = eng->impl->multi_cu.fallbacks();
     return 0;
     API_END
 }

@@ -436,7 +436,7 @@ int Circuit::run_host_parts(const uint64_t* const* parts, const uint32_t* counts
     if (gather_outputs(d_own_pool_, d_own_out_)) return 1;
     HIP_TRY(hipMemcpyAsync(outputs, d_own_out_, (size_t)n_outputs() * big * 8, hipMemcpyDeviceToHost, eng_->stream));
     HIP_TRY(hipStreamSynchronize(eng_->stream));
-    return eng_->cluster_check();
+    return eng_->multi_cu.check();
 }
 
 // ---- many instances of a plan in one pass ----
@@ -505,7 +505,7 @@ int Circuit::run_batch_host(const uint64_t* rows, uint32_t row_count, const uint
     if (batch_execute(d_out, instances)) return 1;
     HIP_TRY(hipMemcpyAsync(outputs, d_out, out_words * 8, hipMemcpyDeviceToHost, eng_->stream));
     HIP_TRY(hipStreamSynchronize(eng_->stream));
-    return eng_->cluster_check();
+    return eng_->multi_cu.check();
 }
 
 Circuit::~Circuit() {

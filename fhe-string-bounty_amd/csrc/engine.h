@@ -11,7 +11,9 @@
 #include <vector>
 
 #include "../../include/fhestr.h"
+#include "blind_rotate.h"
 #include "device_buffer.h"
+#include "engine_settings.h"
 
 // bumped whenever a device kernel changes; profiles/r03_counters.json records the revision its
 // rocprofv3 counters were taken on and bench.py only attaches them to a matching build
@@ -39,30 +41,10 @@ extern thread_local std::string g_last_error;
 inline int under(const char* who, hipError_t e) { return e == hipSuccess ? 0 : fail(std::string(who) + ": " + hipGetErrorString(e)); }
 inline int under(const char* who, int rc) { return rc ? fail(std::string(who) + ": " + g_last_error) : 0; }
 
-struct BrVariant;   // blind_rotate.h
-
 // fill_accumulator: shortint/engine/mod.rs:72-128 (host side, no device needed)
 uint64_t fill_accumulator(const fhe_params_t& p, const uint64_t* table, std::vector<uint64_t>& acc);
 // the same from torus values per box (tables whose entries are not multiples of delta: Circuit::pbs_full_box)
 void fill_accumulator_torus(const fhe_params_t& p, const uint64_t* box_values, std::vector<uint64_t>& acc);
-
-// Environment switches (diagnostics / A/B measurements only; -1 or -2 = not set).  Read once per engine, engine.hip: EngineEnv::read.
-struct EngineEnv {
-    int log2_points = 0;              // FHESTR_LOG2_POINTS          blind-rotation variant selector (fhe_engine_set_variant)
-    int wide_fair = -1;               // FHESTR_WIDE_FAIR            log2 ticks of the two-LWEs-per-CU kernel's priority slices, 0 = off
-    int keep_busy = -1;               // FHESTR_KEEP_BUSY            fhe_engine_set_keep_busy at creation
-    int overlap_streams = -1;         // FHESTR_OVERLAP_STREAMS      streams of throughput mode 2 (2 .. 4)
-    int ks_mfma = -1;                 // FHESTR_KS_MFMA              0: byte-plane keyswitch kernel everywhere
-    int ks_chunks = -1;               // FHESTR_KS_CHUNKS            K chunks of the matrix-core keyswitch
-    int cluster_mode = -2;            // FHESTR_CLUSTER              fhe_engine_set_cluster_mode at creation (-1 .. 2)
-    int cluster_spin_limit = -1;      // FHESTR_CLUSTER_SPIN_LIMIT   polls before a hand-over wait gives up
-    int multibit_combine_max = -1;    // FHESTR_MULTIBIT_COMBINE_MAX fhe_engine_set_multibit_combine_max at creation
-    int multibit_ws_cap = -1;         // FHESTR_MULTIBIT_WS_CAP      bytes of prepared GGSWs (+ rotation workspace) the two-kernel multi-bit path keeps at once
-    int cluster_test_fault = -1;      // FHESTR_CLUSTER_TEST_FAULT   honoured by the -DFHESTR_TEST_HOOKS build only
-    int dense_per_cu = -1;            // FHESTR_DENSE_PER_CU         LWEs per CU beyond which the dense wide kernel runs (0 = never)
-    int cluster_fallback = -1;        // FHESTR_CLUSTER_FALLBACK     0: a multi-CU launch that gave up is an error, not re-run
-    static EngineEnv read();
-};
 
 // ---- the ks_pbs throughput modes (Engine::ks_pbs_dev): their streams, events, buffers and hazard records -----------------
 struct ByteRange { const char* lo; const char* hi; };
@@ -101,7 +83,7 @@ struct Pipeline {
     static constexpr int MAX_LANES = 4;
     PipeLane lane[MAX_LANES];
     int ready = 0;                      // lanes ensure() has set up
-    int width = 2;                      // lanes the calls of mode 2 rotate over (FHESTR_OVERLAP_STREAMS)
+    int width = 2;                      // lanes the calls of mode 2 rotate over (EngineSettings::overlap_width)
     uint64_t calls = 0;                 // pipelined calls of the current run
     hipEvent_t input_ready = nullptr;   // caller's event the next pipelined keyswitch waits for (one shot)
     // mode 1 hands its two small buffers between the keyswitch stream and the engine's: keyswitch done [slot], blind rotation done [slot]
@@ -122,6 +104,22 @@ struct Pipeline {
     void destroy(int keep = 0);         // after the waits: the streams of lanes keep .. 3 and, with keep = 0, the events
     ~Pipeline() { destroy(); }
 };
+static_assert(EngineSettings::OVERLAP_MAX == Pipeline::MAX_LANES, "every width the settings accept has its lane");
+
+// The packing keyswitch (packing_ks_kernels.hip.h) and the packed inputs (glwe_extract_kernels.hip.h): the resident key,
+// the staging of the host entry points and what the last launch of each did.
+struct PackingState {
+    DeviceBuffer<int8_t> key;            // the packing key's balanced base-256 digit planes in MFMA B-fragment order
+    fhe_packing_params_t pp{0, 0};       // its decomposition
+    DeviceBuffer<int8_t> digits;         // the batch's digit fragments; same reuse rules as PipeLane::digits: zeroed at allocation, grown, rows past the batch never read
+    DeviceBuffer<uint64_t> pack_in, pack_out;       // staging of fhe_engine_pack_lwes (host ciphertexts)
+    uint32_t pack_last[5] = {0, 0, 0, 0, 0};        // fhe_engine_packing_info: ran, MT, K chunks, K steps per chunk, K steps
+    DeviceBuffer<uint64_t> unpack_in, unpack_out;   // staging of fhe_engine_unpack_glwes
+    DeviceBuffer<uint32_t> unpack_idx;              // the refresh's table indices: the identity table's id, once per block of the largest refresh so far
+    uint32_t unpack_last[4] = {0, 0, 0, 0};         // fhe_engine_unpack_info: ran, rows, workgroups, refreshed
+    void pack_info(uint32_t out[5]) const { std::copy(pack_last, pack_last + 5, out); }
+    void unpack_info(uint32_t out[4]) const { std::copy(unpack_last, unpack_last + 4, out); }
+};
 
 struct Engine {
     std::recursive_mutex mu;      // taken by every C ABI entry point that touches this engine (c_api.cpp, LOCK_ENGINE)
@@ -135,12 +133,18 @@ struct Engine {
     const BrVariant* variant = nullptr;       // layout used up to one LWE per CU
     const BrVariant* variant_large = nullptr; // same Fourier-key layout, used for larger batches (may equal variant)
     int cu_count = 256;
+    EngineSettings cfg;                       // defaults, environment (Engine::create) and the fhe_engine_set_* setters: engine_settings.h
     int pipeline = 0;                         // ks_pbs_dev throughput modes: 1 = keyswitch of call k+1 in the shadow of the blind rotation of call k; 2 = whole calls overlapped on pipe.width lanes
-    uint32_t wide_fair_shift = 13;           // two-LWEs-per-CU kernel: log2 ticks (100 MHz) of the priority time slice, 0 = off (FHESTR_WIDE_FAIR)
-    uint32_t dense_per_cu = 2;               // N = 1024, k = 2: the four-workgroups-per-CU kernel beyond this many LWEs per CU (0 = never)
-    bool keep_busy = false;                  // small launches carry replicas on the idle CUs (fhe_engine_set_keep_busy, FHESTR_KEEP_BUSY)
     Pipeline pipe;                           // streams, events, buffers and hazard records of the throughput modes; lane 0's buffers serve every serial call
     int sync_all_streams() { return pipe.wait_all(stream); }
+    // A call outside the throughput modes whose buffers their calls may still touch on other streams: wait for every stream
+    // and end the pipelined run, like any serial call.
+    int leave_pipelined_run() {
+        if (!pipeline) return 0;
+        if (sync_all_streams()) return 1;
+        pipe.end_run();
+        return 0;
+    }
     // Grow a buffer that launches in flight on any of the engine's streams may still read: they finish before the old
     // allocation goes.  Nothing can be reading an empty buffer, so a first allocation does not wait.
     template <class T>
@@ -150,13 +154,11 @@ struct Engine {
         return b.reserve(need);
     }
     int shadow_fit = -1;                      // -1 unknown, else whether a 64-VGPR wave fits next to the rotation's
-    uint32_t multibit_combine_max = 64;       // multi-bit PBS: batches up to this size prepare their GGSWs on the whole GPU first
 
     // resident keys / tables
     DeviceBuffer<uint32_t> d_ksk_packed; // [rows/4][8][n+1] byte planes for keyswitch_dot4_kernel
     DeviceBuffer<uint64_t> d_ksk_rowsum; // [kN / KS_IC][n+1] sums of every tile's key rows (bias removal)
     DeviceBuffer<int8_t> d_ksk_mfma;  // balanced base-256 digit planes of the KSK in MFMA B-fragment order (ks_mfma_kernels.hip.h)
-    bool ks_mfma_enabled = true;      // FHESTR_KS_MFMA=0: byte-plane dot4 kernel everywhere
     DeviceBuffer<double> d_fbsk;
     DeviceBuffer<double> d_fbsk_dense;       // the same key in the dense wide kernel's Fourier order (N = 1024, k = 2 only)
     DeviceBuffer<uint64_t> d_luts;
@@ -165,39 +167,21 @@ struct Engine {
     // staging / scratch (grown on demand)
     DeviceBuffer<uint64_t> d_in, d_out, d_pool;   // the small ciphertexts between keyswitch and rotation: pipe.lane[q].small
     DeviceBuffer<uint32_t> d_idx;
-    DeviceBuffer<uint32_t> d_slot_exp;   // multi-bit two-kernel path: exponent of w = e^{i pi / N} each Fourier slot evaluates at
-    size_t multibit_workspace_cap = 0;   // bytes of prepared GGSWs kept at once, larger batches run in sub-batches (0 = from free memory; FHESTR_MULTIBIT_WS_CAP)
     DeviceBuffer<unsigned char> d_meta;
     DeviceBuffer<uint64_t> d_compact;   // a compact ciphertext list on its way to compact_expand_kernel
-    DeviceBuffer<unsigned char> d_ws;   // per-LWE HBM workspace of the large-N blind rotation
-    DeviceBuffer<unsigned char> d_cluster_ws;   // cluster kernel: 1.5 MB of exchange matrices per cluster (L2-resident by design)
-    DeviceBuffer<void> d_cluster_ctl;   // ClusterCtl (tickets, flags; zeroed per launch) + ClusterStatus (sticky)
-    bool cluster_unchecked = false; // a cluster launch whose status words have not been read yet
-    uint32_t cluster_last = 0;      // clusters the last checked launch formed
-    bool cluster_fallback = true;   // a multi-CU launch that gave up is re-run on the one-workgroup kernel (cluster_settle)
-    uint32_t cluster_fallbacks = 0; // how often that happened
-    uint32_t cluster_last_error = 0;
-    int cluster_mode = -1;          // -1 automatic (by batch size), 0 never, 1 always (FHESTR_CLUSTER)
-    uint32_t cluster_max_batch = 0xFFFFFFFFu;
-    uint32_t ks_chunks_override = 0; // FHESTR_KS_CHUNKS: K chunks of the matrix-core keyswitch (0 = automatic)
+    // Blind-rotation workspace, shared by three paths of blind_rotate.hip: the large-N kernel's per-LWE HBM workspace
+    // (rotate_large), the prepared GGSWs of the multi-bit combined path (rotate_multibit_combined), and the prepared GGSWs
+    // followed by the rotation workspace of the multi-bit two-kernel path (rotate_multibit_two_kernel, at most
+    // cfg.multibit_workspace_cap bytes).  Contract: one launch sequence at a time, on the engine's stream -- a path reserves
+    // it, launches everything that reads or writes it on `stream`, and returns; stream order then separates it from the
+    // next user.  No launch on a pipeline lane's own stream may touch it (the overlapped path takes none of the three).
+    DeviceBuffer<unsigned char> d_ws;
+    DeviceBuffer<uint32_t> d_slot_exp;   // multi-bit two-kernel path: exponent of w = e^{i pi / N} each Fourier slot evaluates at
+    MultiCuRuntime multi_cu;            // the 8-CU clusters and the whole-XCD kernel: their workspace, control block and status checks (blind_rotate.h)
     // what the last launch_keyswitch launched (fhe_engine_keyswitch_info; recorded only, read by no decision): kernel
     // (FHE_KS_KERNEL_*), row tiles / samples per workgroup, K chunks (grid.z), K steps / input coefficients per chunk, K steps / in_dim
     uint32_t ks_last[5] = {0, 0, 0, 0, 0};
-    // packing keyswitch (packing_ks_kernels.hip.h): the key's digit planes, its decomposition, and the batch's digit fragments
-    DeviceBuffer<int8_t> d_pksk_mfma;
-    fhe_packing_params_t pack_pp{0, 0};
-    DeviceBuffer<int8_t> d_pack_digits;  // same reuse rules as PipeLane::digits: zeroed at allocation, grown, rows past the batch never read
-    DeviceBuffer<uint64_t> d_pack_in, d_pack_out;   // staging of fhe_engine_pack_lwes (host ciphertexts)
-    uint32_t pack_last[5] = {0, 0, 0, 0, 0};   // fhe_engine_packing_info: ran, MT, K chunks, K steps per chunk, K steps
-    // packed inputs (glwe_extract_kernels.hip.h): staging of fhe_engine_unpack_glwes, the refresh's table indices
-    DeviceBuffer<uint64_t> d_unpack_in, d_unpack_out;
-    DeviceBuffer<uint32_t> d_unpack_idx;       // the identity table's id, once per block of the largest refresh so far
-    uint32_t unpack_last[4] = {0, 0, 0, 0};    // fhe_engine_unpack_info: ran, rows, workgroups, refreshed
-    int xcd_per_cu = -1;             // workgroups of the whole-XCD kernel a CU holds (occupancy query, cached)
-    uint32_t xcd_auto_max = 16;     // automatic mode: batches up to this size take the whole-XCD kernel (two LWEs per XCD in flight)
-    uint32_t cluster_spin_limit = 1u << 22;   // polls before a hand-over wait gives up (FHESTR_CLUSTER_SPIN_LIMIT)
-    uint32_t cluster_test_fault = 0;          // tests only (FHESTR_CLUSTER_TEST_FAULT): epoch one workgroup stays silent at
-    int cluster_check();            // after a synchronisation: did a cluster launch give up on a hand-over?  (blind_rotate.hip)
+    PackingState packing;
 
     static int create(const fhe_params_t& p, int device, Engine** out);
     ~Engine();
@@ -215,7 +199,6 @@ struct Engine {
     int install_keys(DeviceBuffer<uint64_t>&& d_ksk_std, DeviceBuffer<uint64_t>&& d_bsk_std);
     int convert_polys(const uint64_t* d_std, double* d_out, uint32_t n_polys);
     int convert_dense_key(const uint64_t* d_std, uint32_t n_polys);   // d_fbsk_dense, where variant_large has a dense kernel
-    int cluster_settle(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big, uint32_t count);
     int probe_slot_exponents();
     uint64_t fill_accumulator(const uint64_t* table, std::vector<uint64_t>& acc) const { return fhe::fill_accumulator(p, table, acc); }
     int lut_upload_dedup(const std::vector<uint64_t>& acc, uint32_t* id);   // same contents -> same id
@@ -228,7 +211,7 @@ struct Engine {
 
     int launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t count, DeviceBuffer<int8_t>& digits, hipStream_t on = nullptr, bool shadow = false);
     int launch_blind_rotate(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big, uint32_t count, hipStream_t on = nullptr, bool two_per_cu = false,
-                            bool one_workgroup_only = false);   // never a kernel that needs several workgroups resident at once (cluster_settle's re-run)
+                            bool one_workgroup_only = false);   // never a kernel that needs several workgroups resident at once (MultiCuRuntime::settle's re-run)
     bool shadow_keyswitch_fits();
     int load_packing_key(const fhe_packing_params_t& pp, const uint64_t* pksk);
     int pack_lwes_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_glwes);

@@ -55,31 +55,9 @@ int params_supported(const fhe_params_t& p, int selector) {
 }
 int params_supported(const fhe_params_t& p) { return params_supported(p, 0); }
 
-// Every environment switch of the library in one place, read when an engine is created.  They exist for diagnostics and A/B
-// measurements (scripts/); the product interface is the API: fhe_engine_set_variant / _set_pipeline / _set_keep_busy /
-// _set_cluster_mode / _set_multibit_combine_max.
-EngineEnv EngineEnv::read() {
-    EngineEnv v;
-    auto num = [](const char* name, int& out) { if (const char* t = getenv(name)) out = atoi(t); };
-    num("FHESTR_LOG2_POINTS", v.log2_points);
-    num("FHESTR_WIDE_FAIR", v.wide_fair);
-    num("FHESTR_DENSE_PER_CU", v.dense_per_cu);
-    num("FHESTR_CLUSTER_FALLBACK", v.cluster_fallback);
-    num("FHESTR_KEEP_BUSY", v.keep_busy);
-    num("FHESTR_OVERLAP_STREAMS", v.overlap_streams);
-    num("FHESTR_KS_MFMA", v.ks_mfma);
-    num("FHESTR_KS_CHUNKS", v.ks_chunks);
-    num("FHESTR_CLUSTER", v.cluster_mode);
-    num("FHESTR_CLUSTER_SPIN_LIMIT", v.cluster_spin_limit);
-    num("FHESTR_MULTIBIT_COMBINE_MAX", v.multibit_combine_max);
-    num("FHESTR_MULTIBIT_WS_CAP", v.multibit_ws_cap);
-    num("FHESTR_CLUSTER_TEST_FAULT", v.cluster_test_fault);
-    return v;
-}
-
 int Engine::create(const fhe_params_t& p, int device, Engine** out) {
-    const EngineEnv env = EngineEnv::read();
-    if (params_supported(p, env.log2_points)) return 1;
+    const EngineSettings cfg = EngineSettings::from_env();   // defaults, ranges and environment names: engine_settings.h
+    if (params_supported(p, cfg.variant_selector)) return 1;
     int count = 0;
     HIP_TRY(hipGetDeviceCount(&count));
     if (count <= 0) return fail("no HIP device: libfhestr has no CPU fallback");
@@ -88,24 +66,11 @@ int Engine::create(const fhe_params_t& p, int device, Engine** out) {
     std::unique_ptr<Engine> e(new Engine());   // freed by every early return below
     e->p = p;
     e->device = device;
-    const BrVariantPair vp = find_variant_pair(p, env.log2_points);
+    const BrVariantPair vp = find_variant_pair(p, cfg.variant_selector);
     e->variant = vp.small;
     e->variant_large = vp.large;
-    if (env.wide_fair >= 0) e->wide_fair_shift = (uint32_t)std::min(20, env.wide_fair);
-    if (env.dense_per_cu >= 0) e->dense_per_cu = (uint32_t)env.dense_per_cu;
-    if (env.cluster_fallback >= 0) e->cluster_fallback = env.cluster_fallback != 0;
-    if (env.keep_busy >= 0) e->keep_busy = env.keep_busy != 0;
-    if (env.overlap_streams >= 0) e->pipe.width = std::min((int)Pipeline::MAX_LANES, std::max(2, env.overlap_streams));
-    if (env.ks_mfma >= 0) e->ks_mfma_enabled = env.ks_mfma != 0;
-    if (env.ks_chunks >= 0) e->ks_chunks_override = (uint32_t)env.ks_chunks;
-    if (env.cluster_spin_limit >= 0) e->cluster_spin_limit = (uint32_t)std::max(64, env.cluster_spin_limit);
-    if (env.cluster_mode > -2) e->cluster_mode = std::min(2, std::max(-1, env.cluster_mode));
-    if (env.multibit_combine_max >= 0) e->multibit_combine_max = (uint32_t)std::min(1024, env.multibit_combine_max);
-    // in bytes (an int: up to 2 GB, enough to split the toy shapes of the tests); 0 or unset: the automatic cap from free memory
-    if (env.multibit_ws_cap > 0) e->multibit_workspace_cap = (size_t)env.multibit_ws_cap;
-#ifdef FHESTR_TEST_HOOKS      // fault injection exists only in the test build (make testhooks), never in the product library
-    if (env.cluster_test_fault >= 0) e->cluster_test_fault = (uint32_t)env.cluster_test_fault;
-#endif
+    e->cfg = cfg;
+    e->pipe.width = cfg.overlap_width;
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     e->cu_count = prop.multiProcessorCount;
@@ -310,7 +275,7 @@ int Engine::install_keys(DeviceBuffer<uint64_t>&& ksk_std, DeviceBuffer<uint64_t
     // balanced base-256 digit planes in MFMA fragment order (ks_mfma_kernels.hip.h); a 16-slot group holds whole mask
     // elements with all their levels, so more than 16 levels (PARAM_MESSAGE_3_CARRY_4_COMPACT_PK_PBS_KS: 22) stay on the
     // byte-plane dot4 kernel
-    if (ks_mfma_enabled && ks_mfma_supported(p.ks_level)) {
+    if (cfg.ks_mfma_enabled && ks_mfma_supported(p.ks_level)) {
         const KsMfmaGeom g = ks_mfma_geom(p.k * p.N, p.n + 1, p.ks_level, p.ks_base_log);
         const size_t bytes = (size_t)g.col_groups * g.steps * 8 * 1024;
         if (d_ksk_mfma.alloc(bytes)) return 1;
@@ -434,7 +399,7 @@ int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t cou
     HIP_TRY(hipMemsetAsync(d_sm, 0, (size_t)count * out_size * 8, s));
     if (d_ksk_mfma && !shadow) {
         const KsMfmaGeom g = ks_mfma_geom(in_dim, out_size, p.ks_level, p.ks_base_log);
-        const KsMfmaLaunch l = ks_mfma_plan(g, count, p.ks_base_log, cu_count, ks_chunks_override);
+        const KsMfmaLaunch l = ks_mfma_plan(g, count, p.ks_base_log, cu_count, cfg.ks_chunks_override);
         if (ks_mfma_digits(*this, digits, l, g, d_big, count, s)) return 1;
         KsMfmaArgs ma{d_big, d_ksk_mfma, digits, d_sm, g, count, l.row_tiles, l.spc};
         switch (l.mt) {
@@ -471,9 +436,9 @@ int Engine::load_packing_key(const fhe_packing_params_t& pp, const uint64_t* pks
     if (packing_params_check(p, pp)) return 1;
     if (sync_all_streams()) return 1;                       // a launch in flight may still read the previous key or its digits
     const char* const who = "load_packing_key";
-    d_pksk_mfma.release();
-    d_pack_digits.release();      // the pad slots depend on the level count
-    for (auto& w : pack_last) w = 0;
+    packing.key.release();
+    packing.digits.release();      // the pad slots depend on the level count
+    for (auto& w : packing.pack_last) w = 0;
     const KsMfmaGeom g = ks_mfma_geom(p.k * p.N, (p.k + 1) * p.N, pp.level, pp.base_log);
     const size_t words = (size_t)g.in_dim * pp.level * g.out_size;
     DeviceBuffer<uint64_t> d_std;
@@ -485,8 +450,8 @@ int Engine::load_packing_key(const fhe_packing_params_t& pp, const uint64_t* pks
     hipLaunchKernelGGL(ksk_repack_mfma_kernel, dim3(g.col_groups, g.steps), dim3(64), 0, stream, d_std.ptr, planes.ptr, g);
     if (under(who, hipGetLastError()) || under(who, hipStreamSynchronize(stream))) return 1;
     d_std.release();      // the 64-bit layout (3.2 GB at N = 8192) goes as soon as the repack is done
-    d_pksk_mfma = std::move(planes);
-    pack_pp = pp;
+    packing.key = std::move(planes);
+    packing.pp = pp;
     return 0;
 }
 
@@ -496,40 +461,37 @@ int Engine::load_packing_key(const fhe_packing_params_t& pp, const uint64_t* pks
 // stream and ends the pipelined run, like any serial call (include/fhestr.h says so).
 int Engine::pack_lwes_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_glwes) {
     if (use()) return 1;
-    if (!d_pksk_mfma) return fail("packing key not loaded");
+    if (!packing.key) return fail("packing key not loaded");
     if (count == 0) return 0;
     if (count > 65535u) return fail("batch too large for one packing launch (max 65535 LWEs)");   // grid.y of the digit kernel
-    if (pipeline) {                                         // pipelined calls may still write the input on another stream
-        if (sync_all_streams()) return 1;
-        pipe.end_run();
-    }
+    if (leave_pipelined_run()) return 1;                    // pipelined calls may still write the input on another stream
     const uint32_t in_dim = p.k * p.N, out_size = (p.k + 1) * p.N;
-    const KsMfmaGeom g = ks_mfma_geom(in_dim, out_size, pack_pp.level, pack_pp.base_log);
+    const KsMfmaGeom g = ks_mfma_geom(in_dim, out_size, packing.pp.level, packing.pp.base_log);
     const uint32_t n_glwe = (count + p.N - 1) / p.N;
     HIP_TRY(hipMemsetAsync(d_glwes, 0, (size_t)n_glwe * out_size * 8, stream));
-    const KsMfmaLaunch l = ks_mfma_plan(g, count, pack_pp.base_log, cu_count, ks_chunks_override);
-    if (ks_mfma_digits(*this, d_pack_digits, l, g, d_cts, count, stream)) return 1;
-    PackKsArgs pa{d_cts, d_pksk_mfma, d_pack_digits, d_glwes, g, count, l.row_tiles, l.spc, p.N, p.k * p.N / 32};
+    const KsMfmaLaunch l = ks_mfma_plan(g, count, packing.pp.base_log, cu_count, cfg.ks_chunks_override);
+    if (ks_mfma_digits(*this, packing.digits, l, g, d_cts, count, stream)) return 1;
+    PackKsArgs pa{d_cts, packing.key, packing.digits, d_glwes, g, count, l.row_tiles, l.spc, p.N, p.k * p.N / 32};
     switch (l.mt) {
         case 1: hipLaunchKernelGGL(packing_ks_mfma_kernel<1>, l.grid(g), dim3(64), 0, stream, pa); break;
         case 2: hipLaunchKernelGGL(packing_ks_mfma_kernel<2>, l.grid(g), dim3(128), 0, stream, pa); break;
         case 4: hipLaunchKernelGGL(packing_ks_mfma_kernel<4>, l.grid(g), dim3(256), 0, stream, pa); break;
         default: hipLaunchKernelGGL(packing_ks_mfma_kernel<8>, l.grid(g), dim3(512), 0, stream, pa); break;
     }
-    l.info(pack_last, 1, g);
+    l.info(packing.pack_last, 1, g);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
 int Engine::pack_lwes_host(const uint64_t* cts, uint32_t count, uint64_t* glwes) {
     if (use()) return 1;
-    if (!d_pksk_mfma) return fail("packing key not loaded");
+    if (!packing.key) return fail("packing key not loaded");
     if (count == 0) return 0;
     const size_t big = (size_t)p.k * p.N + 1, out_words = (size_t)((count + p.N - 1) / p.N) * (p.k + 1) * p.N;
-    if (reserve_idle(d_pack_in, count * big * 8) || reserve_idle(d_pack_out, out_words * 8)) return 1;
-    HIP_TRY(hipMemcpyAsync(d_pack_in, cts, count * big * 8, hipMemcpyHostToDevice, stream));
-    if (pack_lwes_dev(d_pack_in, count, d_pack_out)) return 1;
-    HIP_TRY(hipMemcpyAsync(glwes, d_pack_out, out_words * 8, hipMemcpyDeviceToHost, stream));
+    if (reserve_idle(packing.pack_in, count * big * 8) || reserve_idle(packing.pack_out, out_words * 8)) return 1;
+    HIP_TRY(hipMemcpyAsync(packing.pack_in, cts, count * big * 8, hipMemcpyHostToDevice, stream));
+    if (pack_lwes_dev(packing.pack_in, count, packing.pack_out)) return 1;
+    HIP_TRY(hipMemcpyAsync(glwes, packing.pack_out, out_words * 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
 }
@@ -547,21 +509,18 @@ int Engine::unpack_glwes_dev(const uint64_t* d_glwes, uint32_t first, uint32_t c
     const uint32_t kN = p.k * p.N;
     if (p.N < 2 || (p.N & (p.N - 1))) return fail("unpack_glwes: polynomial size must be a power of two");
     if (refresh) {
-        if (!d_pksk_mfma) return fail("unpack_glwes: the refresh needs the loaded packing key's decomposition to judge the blocks' noise; none is loaded");
+        if (!packing.key) return fail("unpack_glwes: the refresh needs the loaded packing key's decomposition to judge the blocks' noise; none is loaded");
         double v[2];
-        packing_unpack_noise(p, pack_pp, v);
+        packing_unpack_noise(p, packing.pp, v);
         if (!(v[0] <= v[1]))
             return fail("unpack_glwes: refresh refused, a raw extracted block carries " + std::to_string(v[0]) +
                         " nominal variances, the PBS-input budget is " + std::to_string(v[1]));
     }
-    if (pipeline) {                                         // pipelined calls may still read or write these buffers on other streams
-        if (sync_all_streams()) return 1;
-        pipe.end_run();
-    }
+    if (leave_pipelined_run()) return 1;                    // pipelined calls may still read or write these buffers on other streams
     const uint32_t chunks = (kN / 2 + GLWE_EXTRACT_PAIRS_PER_WG - 1) / GLWE_EXTRACT_PAIRS_PER_WG;
     if ((uint64_t)count * chunks > 0x7FFFFFFFull) return fail("unpack_glwes: too many ciphertexts for one launch");
     hipLaunchKernelGGL(glwe_sample_extract_kernel, dim3(count * chunks), dim3(256), 0, stream, d_glwes, d_cts, p.N, kN, first, count, chunks);
-    unpack_last[0] = 1; unpack_last[1] = count; unpack_last[2] = count * chunks; unpack_last[3] = 0;
+    packing.unpack_last[0] = 1; packing.unpack_last[1] = count; packing.unpack_last[2] = count * chunks; packing.unpack_last[3] = 0;
     HIP_TRY(hipGetLastError());
     if (!refresh) return 0;
     const uint32_t M = p.msg_mod * p.carry_mod;
@@ -570,10 +529,10 @@ int Engine::unpack_glwes_dev(const uint64_t* d_glwes, uint32_t first, uint32_t c
     fill_accumulator(table.data(), acc);
     uint32_t id = 0;
     if (lut_upload_dedup(acc, &id)) return 1;
-    if (reserve_idle(d_unpack_idx, (size_t)count * 4)) return 1;   // an earlier refresh may still read the smaller array
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_unpack_idx.ptr, (int)id, count, stream));
-    if (ks_pbs_dev(d_cts, d_unpack_idx, d_cts, count)) return 1;   // the keyswitch has read every row before the rotation writes one
-    unpack_last[3] = 1;
+    if (reserve_idle(packing.unpack_idx, (size_t)count * 4)) return 1;   // an earlier refresh may still read the smaller array
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)packing.unpack_idx.ptr, (int)id, count, stream));
+    if (ks_pbs_dev(d_cts, packing.unpack_idx, d_cts, count)) return 1;   // the keyswitch has read every row before the rotation writes one
+    packing.unpack_last[3] = 1;
     return 0;
 }
 
@@ -583,12 +542,12 @@ int Engine::unpack_glwes_host(const uint64_t* glwes, uint32_t first, uint32_t co
     const size_t big = (size_t)p.k * p.N + 1, glwe_len = (size_t)(p.k + 1) * p.N;
     const uint64_t g_lo = first / p.N, g_hi = ((uint64_t)first + count - 1) / p.N;      // only the GLWEs the range touches go up
     const size_t in_words = (size_t)(g_hi - g_lo + 1) * glwe_len;
-    if (reserve_idle(d_unpack_in, in_words * 8) || reserve_idle(d_unpack_out, count * big * 8)) return 1;
-    HIP_TRY(hipMemcpyAsync(d_unpack_in, glwes + (size_t)g_lo * glwe_len, in_words * 8, hipMemcpyHostToDevice, stream));
-    if (unpack_glwes_dev(d_unpack_in, first % p.N, count, refresh, d_unpack_out)) return 1;
-    HIP_TRY(hipMemcpyAsync(cts, d_unpack_out, count * big * 8, hipMemcpyDeviceToHost, stream));
+    if (reserve_idle(packing.unpack_in, in_words * 8) || reserve_idle(packing.unpack_out, count * big * 8)) return 1;
+    HIP_TRY(hipMemcpyAsync(packing.unpack_in, glwes + (size_t)g_lo * glwe_len, in_words * 8, hipMemcpyHostToDevice, stream));
+    if (unpack_glwes_dev(packing.unpack_in, first % p.N, count, refresh, packing.unpack_out)) return 1;
+    HIP_TRY(hipMemcpyAsync(cts, packing.unpack_out, count * big * 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    return refresh ? cluster_check() : 0;
+    return refresh ? multi_cu.check() : 0;
 }
 
 void Engine::keyswitch_info(uint32_t info[6]) const {
@@ -733,7 +692,7 @@ int Engine::ks_pbs_host(const uint64_t* in, const uint32_t* lut_idx, uint64_t* o
     if (ks_pbs_dev(d_in, lut_idx ? d_idx : nullptr, d_out, count)) return 1;
     HIP_TRY(hipMemcpyAsync(out, d_out, count * big * 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    return cluster_check();
+    return multi_cu.check();
 }
 
 int Engine::keyswitch_host(const uint64_t* in, uint64_t* out_small, uint32_t count) {
@@ -761,7 +720,7 @@ int Engine::pbs_host(const uint64_t* in_small, const uint32_t* lut_idx, uint64_t
     if (launch_blind_rotate(d_small, lut_idx ? d_idx : nullptr, d_out, count)) return 1;
     HIP_TRY(hipMemcpyAsync(out, d_out, count * big * 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    return cluster_check();
+    return multi_cu.check();
 }
 
 // Small-key order (programmable_bootstrap_keyswitch_assign, shortint/server_key/mod.rs:859-932):
@@ -782,7 +741,7 @@ int Engine::pbs_ks_host(const uint64_t* in_small, const uint32_t* lut_idx, uint6
     if (launch_keyswitch(d_out, d_small2, count, pipe.lane[0].digits)) return 1;
     HIP_TRY(hipMemcpyAsync(out_small, d_small2, count * small * 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    return cluster_check();
+    return multi_cu.check();
 }
 
 int Engine::lincomb_dev(const uint64_t* d_pool_, const uint32_t* d_off, const uint32_t* d_src,
@@ -879,7 +838,7 @@ int Engine::synchronize() {
     if (use()) return 1;
     if (sync_all_streams()) return 1;
     pipe.end_run();                       // every stream is idle: the next pipelined call starts a new run
-    return cluster_check();
+    return multi_cu.check();
 }
 
 int Pipeline::ensure(int n) {
