@@ -301,3 +301,110 @@ def pbs_exact_batch_parallel(params, terms, cts, luts, lut_idx, workers=12):
     parts = [p for p in np.array_split(np.arange(len(cts)), workers) if len(p)]
     with ProcessPoolExecutor(len(parts), mp_context=multiprocessing.get_context("spawn")) as pool:
         return np.concatenate(list(pool.map(_pbs_rows, [(params, terms, cts[p], luts, idx[p]) for p in parts])))
+
+
+# ---- f64 transform precision at full scale -----------------------------------------------------------------------------
+#
+# Under a uniformly random full-range key nothing is bit exact between two f64 implementations, but the per-coefficient
+# error against the exact integers is a sample of the transform's rounding noise.  One external product per LWE (one
+# non-zero mask word, or one multi-bit group) keeps every decomposition digit the same in both, so the error is that
+# noise alone and an implementation's spread can be held against the oracle's f64 path.  The rig of
+# tests/test_gpu_rotation_precision.py; tests/test_exact_pbs.py pins its bounds on the oracle itself.
+
+ORACLE_ROWS = 16               # the reference spread comes from at most this many LWEs: the error's distribution is the same for every one
+
+
+def twin(p, n, name=None):
+    """The shape p with another small dimension n."""
+    import dataclasses
+    return dataclasses.replace(p, n=n, name=name or f"{p.name}_n{n}")
+
+
+def signed_errors(got, want):
+    """got - want on the u64 torus as signed f64, flat."""
+    with np.errstate(over="ignore"):
+        return (np.asarray(got, dtype=U64) - want).astype(np.int64).astype(np.float64).reshape(-1)
+
+
+def one_cmux_inputs(p, rng, B):
+    """Small-key LWEs with a random body and exactly one non-zero mask word: one CMUX each."""
+    cts = np.zeros((B, p.n + 1), dtype=U64)
+    cts[:, p.n] = rng.integers(0, 2**64, size=B, dtype=U64)
+    pos = rng.integers(0, p.n, size=B)
+    cts[np.arange(B), pos] = rng.integers(1, 2**64, size=B, dtype=U64)
+    return cts
+
+
+class PrecisionCase:
+    """A full-range key, one table, `count` distinct LWEs of one external product each, their exact outputs, and the
+    error of the oracle's f64 path on the first ORACLE_ROWS of them (e_orc [rows, big_size], s_orc its pooled std).
+    grouping = 0: classic PBS, one_cmux_inputs; grouping = G: multi-bit on a shape with n = G, uniformly random LWEs."""
+
+    def __init__(self, p, grouping, count, seed=0):
+        import oracle as O
+        assert not grouping or p.n == grouping
+        self.p, self.G, self.count = p, grouping, count
+        rng = np.random.default_rng([p.N, p.k, p.pbs_level, p.n, grouping, count, seed])
+        n_ggsw = p.n // grouping * (1 << grouping) if grouping else p.n
+        self.bsk = rng.integers(0, 2**64, size=(n_ggsw, p.pbs_level, p.k + 1, p.k + 1, p.N), dtype=U64)
+        self.lut = rng.integers(0, 2**64, size=p.glwe_len, dtype=U64)
+        terms = limb_terms(self.bsk)
+        if grouping:
+            self.cts = rng.integers(0, 2**64, size=(count, p.n + 1), dtype=U64)
+            self.want = multi_bit_pbs_exact_batch(p, grouping, terms, self.cts, self.lut)
+            sk = O.MultiBitServerKey.from_keys(p, grouping, self.bsk, threads=4)
+        else:
+            self.cts = self._live_one_cmux_inputs(p, rng, count)
+            self.want = np.zeros((count, p.big_size), dtype=U64)
+            pos = (self.cts[:, :p.n] != 0).argmax(axis=1)
+            for i in np.unique(pos):                       # pbs_exact_batch skips a step no row of which is live: n times less work
+                self.want[pos == i] = pbs_exact_batch(p, terms, self.cts[pos == i], self.lut)
+            ksk = np.zeros(p.big_dim * p.ks_level * p.small_size, dtype=U64)
+            sk = O.ServerKey.from_keys(p, self.bsk, ksk, threads=4)
+        rows = min(count, ORACLE_ROWS)
+        self.orc = np.stack([sk.pbs(c, self.lut) for c in self.cts[:rows]])
+        self.e_orc = signed_errors(self.orc, self.want[:rows]).reshape(rows, -1)
+        self.s_orc = self.e_orc.std()
+
+    @staticmethod
+    def _live_one_cmux_inputs(p, rng, count):
+        """one_cmux_inputs whose mask word does not switch to X^0: there the CMUX multiplies by zero and the LWE would carry
+        no error at all (one draw in 2N: one in 256 at N = 128)."""
+        logN = p.N.bit_length() - 1
+        while True:
+            cts = one_cmux_inputs(p, rng, count)
+            if all(modulus_switch(a, logN) % (2 * p.N) for a in cts[:, :p.n].max(axis=1)):
+                return cts
+
+
+def f64_precision_figures(errors, s_orc, distinct):
+    """errors [slots, big_size]: an f64 implementation's signed error against exact on a PrecisionCase, slot by slot (slots
+    beyond `distinct` repeat earlier inputs); s_orc: the oracle's spread on it.  Returns a dict of the figures the bounds read."""
+    errors = np.asarray(errors, dtype=np.float64)
+    m = errors.shape[1]
+    s = errors.std()
+    per_slot = errors.std(axis=1)
+    # repeated slots repeat their values on a deterministic implementation: the mean has the spread of distinct * m samples
+    n_eff = distinct * m
+    return {"s": s, "s_orc": s_orc, "ratio": s / s_orc, "max": np.abs(errors).max(),
+            "bias_sigmas": abs(errors.mean()) * np.sqrt(n_eff) / s if s else 0.0,
+            "worst_slot": int(per_slot.argmax()), "worst_slot_ratio": per_slot.max() / s_orc,
+            "slot_bound": 1.6 * (1 + 4 / np.sqrt(2 * m))}
+
+
+def assert_f64_precision(name, errors, s_orc, distinct):
+    """The three bounds an f64 blind rotation is held to, with one printed line of figures.
+      * pooled: 0.25 s_orc < std <= 1.6 s_orc and max |e| < 8 s_orc -- its transforms are no noisier than the reference algorithm's;
+      * per slot: the std over a slot's m = big_size coefficients <= 1.6 s_orc (1 + 4 / sqrt(2 m)): a std of m samples has
+        relative sampling error 1 / sqrt(2 m), four of them allowed -- a loss on one of the workgroups sharing a CU, or on one
+        round of a tiled batch, shows here and is diluted in the pool;
+      * no bias: |mean| <= 5 std / sqrt(n) over the n independent coefficients -- a truncating from_torus or a dropped rounding."""
+    f = f64_precision_figures(errors, s_orc, distinct)
+    print(f"{name}: error std 2^{np.log2(f['s']):.2f}, oracle f64 2^{np.log2(s_orc):.2f} (ratio {f['ratio']:.3f}); max 2^{np.log2(f['max']):.2f} "
+          f"({f['max'] / s_orc:.2f} s_orc); bias {f['bias_sigmas']:.2f} sigma/sqrt(n); worst slot {f['worst_slot']} of {len(errors)} at "
+          f"{f['worst_slot_ratio']:.3f} s_orc (bound {f['slot_bound']:.3f})")
+    assert 0.25 * s_orc < f["s"] <= 1.6 * s_orc
+    assert f["max"] < 8 * s_orc
+    assert f["worst_slot_ratio"] <= f["slot_bound"]
+    assert f["bias_sigmas"] <= 5
+    return f

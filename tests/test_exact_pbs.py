@@ -136,3 +136,38 @@ def test_oracle_f64_multi_bit_pbs_is_bit_exact_under_structured_keys(params, G):
     want = multi_bit_pbs_exact_batch(params, G, terms, cts, luts, idx)
     got = np.stack([sk.pbs(c, luts[i]) for c, i in zip(cts, idx)])
     _assert_on_grid(got, want, params)
+
+
+# ---- full-range keys: the oracle's f64 path stays inside the precision bounds (the premise of tests/test_gpu_rotation_precision.py) ---
+
+from exact_pbs import ORACLE_ROWS, PrecisionCase, assert_f64_precision, f64_precision_figures, twin   # noqa: E402
+
+PRECISION_SHAPES = [twin(O.PARAM_MESSAGE_2_CARRY_2_KS_PBS, 8, "TOY_N2048_K1"), twin(O.PARAM_MESSAGE_2_CARRY_1_KS_PBS, 8, "TOY_N1024_K2_n8"),
+                    O.TOY_K2, next(p for p in O.TOY_SHAPES if p.name == "TOY_N4096_L2")]
+
+
+@pytest.mark.parametrize("params", PRECISION_SHAPES, ids=lambda p: p.name)
+def test_oracle_f64_pbs_meets_the_precision_bounds(params):
+    """The three bounds of assert_f64_precision with the oracle's f64 output in the GPU's place: 16 one-CMUX LWEs under one
+    full-range key, held against the oracle's spread on 16 others under another key (a second seed).  A correct f64
+    implementation reaches the bounds, and every coefficient carries an error: none of the measurement is vacuous."""
+    ref, other = PrecisionCase(params, 0, ORACLE_ROWS, seed=0), PrecisionCase(params, 0, ORACLE_ROWS, seed=1)
+    assert (other.e_orc != 0).mean() > 0.99
+    f = assert_f64_precision(params.name, other.e_orc, ref.s_orc, ORACLE_ROWS)
+    assert 0.8 < f["ratio"] < 1.25                     # the spread varies a little from LWE to LWE (digits, table); 16 of them pooled agree well within a quarter
+
+
+def test_precision_bounds_catch_a_lost_bit_a_truncation_and_one_bad_slot():
+    """Negative controls on the oracle's own error: twice the spread, an offset of half a sigma, one slot of 16 at 2.5 times the noise."""
+    case = PrecisionCase(O.TOY_K2, 0, ORACLE_ROWS)
+    e, s = case.e_orc, case.s_orc
+    f64_precision_figures(e, s, ORACLE_ROWS)
+    with pytest.raises(AssertionError):
+        assert_f64_precision("doubled", 2 * e, s, ORACLE_ROWS)
+    with pytest.raises(AssertionError):
+        assert_f64_precision("offset", e - 0.5 * s, s, ORACLE_ROWS)
+    one = e.copy()
+    one[5] *= 2.5
+    assert one.std() <= 1.6 * s                       # diluted in the pool: only the per-slot bound sees it
+    with pytest.raises(AssertionError):
+        assert_f64_precision("one slot", one, s, ORACLE_ROWS)

@@ -11,7 +11,8 @@ loop (reached through the environment switch FHESTR_MULTIBIT_WS_CAP, bytes, read
 are in tests/test_gpu_exact_multibit.py, on this file's rig.
 
 Tier 2, full scale: uniformly random keys and LWEs with exactly one non-zero mask element (one CMUX, no decomposition
-digit can differ): the engine's per-coefficient error against exact must have the spread of the oracle's f64 path."""
+digit can differ): the engine's per-coefficient error against exact must have the spread of the oracle's f64 path.  Here on the
+default path at B = 8; path by path, where tier 1's grid margin hides a loss of up to a dozen bits, in tests/test_gpu_rotation_precision.py."""
 import numpy as np
 import pytest
 
@@ -19,16 +20,12 @@ import oracle as O
 from conftest import torus_distance
 from exact_keyswitch import ExactKeyswitch, edge_big_cts
 from exact_pbs import (edge_small_cts, limb_terms, multi_bit_pbs_exact_batch, pbs_exact_batch, structured_bsk)
+from exact_pbs import one_cmux_inputs as _one_cmux_inputs, signed_errors as _errors, twin as _twin      # shared with the CPU tests
 
 pytestmark = pytest.mark.gpu
 
 DISTINCT = 64            # large batches tile this many distinct (ciphertext, table) pairs, adjacent slots distinct
 N_LUTS = 3
-
-
-def _twin(p, n, name=None):
-    return O.Params(n, p.k, p.N, p.pbs_base_log, p.pbs_level, p.ks_base_log, p.ks_level, p.msg_mod, p.carry_mod,
-                    p.lwe_std, p.glwe_std, name or f"{p.name}_n{n}")
 
 
 def _shape(name):
@@ -259,11 +256,6 @@ FULL_MB = [(_twin(O.TOY_MULTI_BIT_N2048, 2, "TOY_MULTI_BIT_N2048_G2_n2"), 2),
            (_twin(O.TOY_MULTI_BIT_N8192_G3, 3, "TOY_MULTI_BIT_N8192_G3_n3"), 3)]
 
 
-def _errors(got, want):
-    with np.errstate(over="ignore"):
-        return (np.asarray(got, dtype=np.uint64) - want).astype(np.int64).astype(np.float64).reshape(-1)
-
-
 def _precision(name, eng_out, orc_out, want):
     e_gpu, e_orc = _errors(eng_out, want), _errors(orc_out, want)
     s_gpu, s_orc = e_gpu.std(), e_orc.std()
@@ -271,14 +263,6 @@ def _precision(name, eng_out, orc_out, want):
           f"GPU max 2^{np.log2(np.abs(e_gpu).max()):.2f}")
     assert 0.25 * s_orc < s_gpu <= 1.6 * s_orc
     assert np.abs(e_gpu).max() < 8 * s_orc
-
-
-def _one_cmux_inputs(p, rng, B):
-    cts = np.zeros((B, p.n + 1), dtype=np.uint64)
-    cts[:, p.n] = rng.integers(0, 2**64, size=B, dtype=np.uint64)
-    pos = rng.integers(0, p.n, size=B)
-    cts[np.arange(B), pos] = rng.integers(1, 2**64, size=B, dtype=np.uint64)
-    return cts
 
 
 @pytest.mark.parametrize("p", FULL, ids=lambda p: p.name)
