@@ -895,6 +895,56 @@ int fhe_str_replace_clear_general(fhe_engine* eng, const uint64_t* a, uint32_t a
     return str_op(eng, op.c_str(), a, a_cap, nullptr, 0, both.data(), (uint32_t)both.size(), out);
 }
 
+int fhe_str_replacen(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint64_t* from, uint32_t from_cap,
+                     const uint64_t* to, uint32_t to_cap, uint32_t n, uint32_t out_cap, uint64_t* out) {
+    if (!a) return fail("null pointer: a");
+    if (!from || from_cap == 0) return fail("replacen: `from` needs a capacity of at least one character");
+    if (to_cap && !to) return fail("null pointer: to");
+    const std::string op = "replacen:" + std::to_string(n) + ":" + std::to_string(from_cap) + ":" + std::to_string(out_cap);
+    const uint64_t* operands[3] = {a, from, to};
+    const uint32_t caps[3] = {a_cap, from_cap, to_cap};
+    return str_op_parts(eng, op, operands, caps, to_cap ? 3 : 2, nullptr, 0, out);
+}
+int fhe_str_replacen_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint8_t* from, uint32_t from_len,
+                           const uint8_t* to, uint32_t to_len, uint32_t n, uint32_t out_cap, uint64_t* out) {
+    if ((from_len && !from) || (to_len && !to)) return fail("null pointer: from / to");
+    std::vector<uint8_t> both(from, from + from_len);
+    both.insert(both.end(), to, to + to_len);
+    const std::string op = "replacen_clear:" + std::to_string(n) + ":" + std::to_string(from_len) + ":" + std::to_string(out_cap);
+    return str_op(eng, op.c_str(), a, a_cap, nullptr, 0, both.data(), (uint32_t)both.size(), out);
+}
+
+// the split family: one plan name per (operation, clear / encrypted pattern, max_parts, part capacity)
+int fhe_str_split(fhe_engine* eng, const char* op, const uint64_t* a, uint32_t a_cap, const uint64_t* pat, uint32_t pat_cap,
+                  const uint8_t* clear, uint32_t clear_len, uint32_t max_parts, uint32_t part_cap, uint64_t* out,
+                  uint32_t* n_outputs) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(op);
+    const std::string base(op);
+    static const char* const names[] = {"split", "rsplit", "split_terminator", "rsplit_terminator", "split_inclusive", "splitn",
+                                        "rsplitn", "split_once", "rsplit_once", "split_ascii_whitespace"};
+    if (std::find(std::begin(names), std::end(names), base) == std::end(names)) return fail("fhe_str_split: unknown operation: " + base);
+    if (pat && (clear || clear_len)) return fail("fhe_str_split: give an encrypted pattern or a clear one, not both");
+    if (pat && pat_cap == 0) return fail("fhe_str_split: the encrypted pattern needs a capacity of at least one character");
+    const bool takes_pattern = base != "split_ascii_whitespace";
+    if (!takes_pattern && (pat || clear || clear_len)) return fail("split_ascii_whitespace takes no pattern");
+    if (takes_pattern && !pat && !clear && clear_len) return fail("null clear pattern");
+    const bool is_clear = takes_pattern && !pat;        // (an empty clear pattern is refused by the builder)
+    std::string name = base + (is_clear ? "_clear" : "");
+    if (base != "split_once" && base != "rsplit_once") name += ":" + std::to_string(max_parts);
+    if (part_cap) name += ":" + std::to_string(part_cap);
+    fhe_plan* plan = nullptr;
+    if (cached_str_plan(eng, name, a_cap, pat ? pat_cap : 0, is_clear ? clear : nullptr, is_clear ? clear_len : 0, &plan)) return 1;
+    if (n_outputs) *n_outputs = plan->c->n_outputs();
+    if (!out && n_outputs) return 0;                    // query: how many output ciphertexts
+    CHECK_PTR(a); CHECK_PTR(out);
+    const uint32_t bpc = plan->c->n_inputs() / (a_cap + (pat ? pat_cap : 0));
+    const uint64_t* operands[2] = {a, pat};
+    const uint32_t counts[2] = {a_cap * bpc, pat ? pat_cap * bpc : 0};
+    return plan->c->run_host_parts(operands, counts, pat ? 2 : 1, out);
+    API_END
+}
+
 int fhe_str_repeat_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, uint32_t count, uint64_t* out) {
     if (count == 0 || count > 255) return fail("repeat: count must be in 1..255");
     const uint8_t c = (uint8_t)count;

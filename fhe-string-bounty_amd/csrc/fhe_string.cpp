@@ -998,18 +998,35 @@ public:
         }
         return true;
     }
+    // (offset, j) -> sel[offset] AND nzf[j]: the occurrence selected at `offset` still runs j characters on
+    using RunMemo = std::map<std::pair<uint32_t, uint32_t>, uint32_t>;
+    uint32_t running_bit(const std::vector<uint32_t>& sel, const std::vector<uint32_t>* nzf, uint32_t o, uint32_t j, RunMemo& running) {
+        if (!nzf || j == 0) return sel[o];
+        auto key = std::make_pair(o, j);
+        auto it = running.find(key);
+        if (it == running.end()) it = running.emplace(key, and_bits(sel[o], (*nzf)[j])).first;
+        return it->second;
+    }
+    // cover[i] = [character i lies inside a selected occurrence], forward from the selection whatever produced it (the
+    // recurrence below, a selection taken from the right, a selection cut after n occurrences)
+    std::vector<uint32_t> cover_from_sel(const std::vector<uint32_t>& sel, uint32_t m, uint32_t n_chars, const std::vector<uint32_t>* nzf,
+                                         RunMemo& running) {
+        std::vector<uint32_t> cover(n_chars);
+        for (uint32_t i = 0; i < n_chars; i++) {
+            std::vector<Term> terms;
+            for (uint32_t j = 0; j < m && j <= i; j++)
+                if (i - j < sel.size()) terms.push_back({running_bit(sel, nzf, i - j, j, running), 1});
+            cover[i] = c.lin(terms, 0, 1);                                     // at most one occurrence covers i
+            if (terms.size() > 8) cover[i] = c.pbs(cover[i], c.lut_fn([](uint64_t x) { return (uint64_t)(x != 0); }));
+        }
+        return cover;
+    }
     Occurrences occurrences(const std::vector<uint32_t>& match, uint32_t m, uint32_t n_chars, bool may_overlap,
                             const std::vector<uint32_t>* nzf) {
         Occurrences oc;
         if (may_overlap && occurrences_scan(match, m, n_chars, nzf, oc)) return oc;
-        std::map<std::pair<uint32_t, uint32_t>, uint32_t> running;   // (offset, j) -> sel[offset] AND nzf[j]
-        auto run_bit = [&](uint32_t o, uint32_t j) {
-            if (!nzf || j == 0) return oc.sel[o];
-            auto key = std::make_pair(o, j);
-            auto it = running.find(key);
-            if (it == running.end()) it = running.emplace(key, and_bits(oc.sel[o], (*nzf)[j])).first;
-            return it->second;
-        };
+        RunMemo running;
+        auto run_bit = [&](uint32_t o, uint32_t j) { return running_bit(oc.sel, nzf, o, j, running); };
         oc.sel.resize(match.size());
         const uint32_t l3 = c.lut_fn([](uint64_t x) { return (uint64_t)(x == 3); });
         // Two offsets per lookup level (default plans).  sel[o+1] needs sel[o], but sel[o] = match[o] AND NOT B with
@@ -1052,14 +1069,7 @@ public:
             oc.sel[o + 1] = c.pbs(c.lin(tt, 0, 11), l_second);
             o++;
         }
-        oc.cover.resize(n_chars);
-        for (uint32_t i = 0; i < n_chars; i++) {
-            std::vector<Term> terms;
-            for (uint32_t j = 0; j < m && j <= i; j++)
-                if (i - j < oc.sel.size()) terms.push_back({run_bit(i - j, j), 1});
-            oc.cover[i] = c.lin(terms, 0, 1);                                  // at most one occurrence covers i
-            if (terms.size() > 8) oc.cover[i] = c.pbs(oc.cover[i], c.lut_fn([](uint64_t x) { return (uint64_t)(x != 0); }));
-        }
+        oc.cover = cover_from_sel(oc.sel, m, n_chars, nzf, running);
         return oc;
     }
     // sel * (clear block v): one lookup on the selector (the linear form v * sel would cost v^2 in noise)
@@ -1186,6 +1196,255 @@ public:
         for (uint32_t b = 1; b < m; b++)
             if (std::memcmp(p, p + m - b, b) == 0) return true;
         return false;
+    }
+    // ---- split family and replacen ----
+    // prefix_or with the bits known at build time (leading / trailing zeros: offsets a clear pattern cannot start at) kept
+    // out of the lookups
+    std::vector<uint32_t> prefix_or_known(const std::vector<uint32_t>& bits) {
+        auto known_zero = [&](uint32_t b) { int64_t v = 0; return is_trivial(b, &v) && v == 0; };
+        size_t lo = 0, hi = bits.size();
+        while (lo < hi && known_zero(bits[lo])) lo++;
+        while (hi > lo && known_zero(bits[hi - 1])) hi--;
+        std::vector<uint32_t> out(bits.size(), c.trivial(0));
+        if (lo == hi) return out;
+        const std::vector<uint32_t> core = prefix_or(std::vector<uint32_t>(bits.begin() + lo, bits.begin() + hi));
+        std::copy(core.begin(), core.end(), out.begin() + lo);
+        for (size_t j = hi; j < bits.size(); j++) out[j] = core.back();
+        return out;
+    }
+    // Counting marks without an integer wider than a bit: ge[q - 1][i] = [at least q of marks[0..i] are set], q = 1..Q.
+    // ge_1 = prefix_or(marks), ge_{q+1} = prefix_or(marks[i] AND ge_q[i - 1]); "exactly q" is the linear difference
+    // ge_q - ge_{q+1}.
+    std::vector<std::vector<uint32_t>> count_ge(const std::vector<uint32_t>& marks, uint32_t Q) {
+        std::vector<std::vector<uint32_t>> ge;
+        if (Q == 0) return ge;
+        const uint32_t n = (uint32_t)marks.size();
+        std::vector<uint32_t> cur = prefix_or_known(marks);
+        for (uint32_t q = 1;; q++) {
+            ge.push_back(cur);
+            if (q == Q) break;
+            std::vector<uint32_t> nxt(n, c.trivial(0));
+            for (uint32_t i = 1; i < n; i++) {
+                Scope sc(c, owner_for(i, n));
+                nxt[i] = and_bits(marks[i], cur[i - 1]);
+            }
+            cur = prefix_or_known(nxt);
+        }
+        return ge;
+    }
+    // "mask, then left-justify": the characters of s where in[i] is set (contiguous or absent), moved to the front.  The
+    // lead indicator NOT prefix_or(in) is monotone by construction; an empty part shifts zeros.
+    Str extract_part(const Str& s, const std::vector<uint32_t>& in, uint32_t part_cap) {
+        Str g;
+        g.cap = s.cap;
+        g.ch.resize(s.cap);
+        for (uint32_t i = 0; i < s.cap; i++)
+            for (uint32_t k = 0; k < bpc; k++) g.ch[i].push_back(gate_block(s.ch[i][k], in[i], true));
+        const std::vector<uint32_t> seen = prefix_or_known(in);
+        std::vector<uint32_t> lead(s.cap);
+        for (uint32_t i = 0; i < s.cap; i++) lead[i] = not_bit(seen[i]);
+        return fit(shift_left_by_leading(g, lead), part_cap);
+    }
+    // The count of parts as little-endian base-M digits, from its unary code g_1 >= g_2 >= ... (count = sum g_v):
+    // digit d = sum_v g_v (digit_d(v) - digit_d(v - 1)), a value in [0, M) by construction; as many digits as max_value needs.
+    void emit_count(const std::vector<uint32_t>& unary, uint32_t max_value) {
+        uint32_t n_digits = 1;
+        while ((1ull << (n_digits * bits_per_block)) <= max_value) n_digits++;
+        const uint32_t mm = M;
+        const uint32_t idm = c.lut_fn([mm](uint64_t x) { return x % mm; });
+        for (uint32_t d = 0; d < n_digits; d++) {
+            auto dig = [&](uint32_t v) { return (int32_t)((v >> (d * bits_per_block)) & (M - 1)); };
+            std::vector<Term> terms;
+            for (uint32_t v = 1; v <= unary.size(); v++)
+                if (dig(v) != dig(v - 1)) terms.push_back({unary[v - 1], dig(v) - dig(v - 1)});
+            uint32_t digit = c.lin(terms, 0, (int64_t)M - 1);
+            if (c.node(digit).noise > budget()) {
+                // the differences cost their squares in noise: take the one-hot form instead, sum_v digit_d(v) [count == v],
+                // every product by its own lookup (a max_parts whose sum still does not fit fails below, with the budget's message)
+                terms.clear();
+                for (uint32_t v = 1; v <= unary.size(); v++) {
+                    if (dig(v) == 0) continue;
+                    const uint32_t is_v = v < unary.size() ? c.lin({{unary[v - 1], 1}, {unary[v], -1}}, 0, 1) : unary[v - 1];
+                    terms.push_back({scale_bit(is_v, (uint32_t)dig(v)), 1});
+                }
+                digit = c.lin(terms, 0, (int64_t)M - 1);
+            }
+            if (c.node(digit).noise > 2.0) digit = c.pbs(digit, idm);
+            c.output(digit);
+        }
+    }
+    // Which operation of the family: see include/fhestr.h for the semantics of each.
+    struct SplitKind {
+        bool reverse = false, terminator = false, inclusive = false, limited = false, once = false, whitespace = false;
+    };
+    static bool split_kind(const std::string& base, SplitKind& k) {
+        k = SplitKind();
+        if (base == "split") return true;
+        if (base == "rsplit") { k.reverse = true; return true; }
+        if (base == "split_terminator") { k.terminator = true; return true; }
+        if (base == "rsplit_terminator") { k.reverse = k.terminator = true; return true; }
+        if (base == "split_inclusive") { k.inclusive = true; return true; }
+        if (base == "splitn") { k.limited = true; return true; }
+        if (base == "rsplitn") { k.reverse = k.limited = true; return true; }
+        if (base == "split_once") { k.once = true; return true; }
+        if (base == "rsplit_once") { k.reverse = k.once = true; return true; }
+        if (base == "split_ascii_whitespace") { k.whitespace = true; return true; }
+        return false;
+    }
+    // (like the split names, a name that does not build without its parameters)
+    static bool is_replacen(const std::string& base) { return base == "replacen"; }
+    // Selected occurrences of the pattern in s and the characters they cover: leftmost first (as replace), or rightmost
+    // first -- two occurrences of one length L do not overlap iff their offsets differ by at least L, so that is the same
+    // recurrence over the reversed match vector, hidden lengths included; cover is then rebuilt forward from sel.
+    // sel has s.cap entries (offsets the pattern cannot start at: known zeros).
+    Occurrences select_occurrences(const Str& s, const Str* pat, const uint8_t* clear, uint32_t clear_len, bool from_right) {
+        const uint32_t n = s.cap, zero = c.trivial(0);
+        std::vector<uint32_t> match, nzf;
+        uint32_t m;
+        bool may_overlap = true;
+        if (pat) {
+            m = pat->cap;
+            for (uint32_t j = 0; j < m; j++) nzf.push_back(not_bit(char_is_zero(pat->ch[j])));
+            match = window_matches(s, *pat, n, true);
+            for (uint32_t o = 0; o < n; o++) {          // a pattern that decrypts to the empty string matches nowhere
+                Scope sc(c, owner_for(o, n));
+                match[o] = and_bits(match[o], nzf[0]);
+            }
+        } else {
+            m = clear_len;
+            may_overlap = has_border(clear, m);
+            if (m <= n) match = window_matches_clear(s, clear, m, n - m + 1);
+        }
+        Occurrences oc;
+        if (match.empty()) {
+            oc.sel.assign(n, zero);
+            oc.cover.assign(n, zero);
+            return oc;
+        }
+        if (from_right) std::reverse(match.begin(), match.end());
+        oc = occurrences(match, m, n, may_overlap, pat ? &nzf : nullptr);
+        if (from_right) {
+            std::reverse(oc.sel.begin(), oc.sel.end());
+            RunMemo running;
+            oc.cover = cover_from_sel(oc.sel, m, n, pat ? &nzf : nullptr, running);
+        }
+        oc.sel.resize(n, zero);
+        return oc;
+    }
+    // outputs: the count digits (split_once / rsplit_once: the found bit), then P parts of part_cap characters
+    void split(const Str& s, const SplitKind& kind, const Str* pat, const uint8_t* clear, uint32_t clear_len, uint32_t P,
+               uint32_t part_cap) {
+        const uint32_t n = s.cap, zero = c.trivial(0), one = c.trivial(1);
+        const uint32_t l2 = c.lut_fn([](uint64_t x) { return (uint64_t)(x == 2); });
+        std::vector<std::vector<uint32_t>> in(P, std::vector<uint32_t>(n, zero));    // in[p][i]: character i belongs to part p
+        std::vector<uint32_t> unary;                                                 // of the count
+        if (kind.whitespace) {
+            // word characters w = NOT (whitespace or null); a word starts where w rises; in_p = w AND [starts so far == p + 1]
+            const std::vector<uint32_t> wz = whitespace_bits(s, true);
+            std::vector<uint32_t> w(n), start(n);
+            for (uint32_t i = 0; i < n; i++) w[i] = not_bit(wz[i]);
+            for (uint32_t i = 0; i < n; i++) {
+                Scope sc(c, owner_for(i, n));
+                start[i] = i == 0 ? w[0] : c.pbs(c.lin({{w[i], 1}, {wz[i - 1], 1}}), l2);
+            }
+            const auto ge = count_ge(start, P + 1);
+            for (uint32_t p = 0; p < P; p++)
+                for (uint32_t i = 0; i < n; i++) {
+                    Scope sc(c, owner_for(i, n));
+                    in[p][i] = and_bits(w[i], c.lin({{ge[p][i], 1}, {ge[p + 1][i], -1}}, 0, 1));
+                }
+            for (uint32_t v = 1; v <= P + 1; v++) unary.push_back(ge[v - 1][n - 1]);
+            emit_count(unary, P + 1);
+        } else {
+            std::vector<uint32_t> nz(n), keep(n);
+            for (uint32_t i = 0; i < n; i++) {
+                Scope sc(c, owner_for(i, n));
+                nz[i] = not_bit(char_is_zero(s.ch[i]));
+            }
+            const Occurrences oc = select_occurrences(s, pat, clear, clear_len, kind.reverse);
+            for (uint32_t i = 0; i < n; i++) keep[i] = c.lin({{nz[i], 1}, {oc.cover[i], -1}}, 0, 1);     // a character outside every occurrence
+            // how many selected occurrences the operation has to tell apart
+            const bool drops_empty_end = kind.terminator || kind.inclusive;
+            uint32_t Q = kind.once ? (kind.reverse ? 1 : 2) : kind.limited ? (kind.reverse ? P - 1 : P) : drops_empty_end ? P + 1 : P;
+            Q = std::min(Q, n);                                               // (more occurrences than characters cannot be)
+            std::vector<uint32_t> marks(oc.sel);
+            if (kind.reverse) std::reverse(marks.begin(), marks.end());
+            const auto ge = count_ge(marks, Q);
+            // G(q, i) = [cF[i] >= q] (occurrences selected at offsets <= i), reverse operations: [cR[i] >= q] (offsets > i)
+            auto G = [&](uint32_t q, uint32_t i) {
+                if (q == 0) return one;
+                if (q > Q) return zero;
+                if (!kind.reverse) return ge[q - 1][i];
+                return i + 1 < n ? ge[q - 1][n - 2 - i] : zero;
+            };
+            auto total = [&](uint32_t q) { return q == 0 ? one : q > Q ? zero : ge[q - 1][n - 1]; };   // [K >= q]
+            auto exactly = [&](uint32_t q, uint32_t i) { return c.lin({{G(q, i), 1}, {G(q + 1, i), -1}}, 0, 1); };
+            // e = [the string is empty, or it ends inside a selected occurrence]: the operations that drop an empty last piece
+            uint32_t e = zero;
+            if (drops_empty_end) {
+                std::vector<uint32_t> bits{not_bit(nz[0])};
+                for (uint32_t i = 0; i < n; i++) {
+                    int64_t v = 0;
+                    if (is_trivial(oc.cover[i], &v) && v == 0) continue;
+                    Scope sc(c, owner_for(i, n));
+                    bits.push_back(i + 1 < n ? c.pbs(c.lin({{oc.cover[i], 1}, {nz[i + 1], -1}}, 1), l2) : oc.cover[i]);
+                }
+                e = any_true(bits);
+            }
+            // the last piece of splitn / the second of split_once: everything from the end of occurrence number `q` on,
+            // nz AND (cF >= q + 1 OR (cF == q AND NOT cover)), one lookup on (keep + 2 cover) + 3 (ge_q + ge_{q+1})
+            const uint32_t l_rest = c.lut_fn([](uint64_t x) { const uint64_t u = x % 3, v = x / 3; return (uint64_t)((u == 1 && v >= 1) || (u == 2 && v == 2)); });
+            auto rest_after = [&](uint32_t q, uint32_t i) {
+                return c.pbs(c.lin({{nz[i], 1}, {oc.cover[i], 1}, {G(q, i), 3}, {G(q + 1, i), 3}}, 0, 8), l_rest);
+            };
+            const uint32_t l_incl = c.lut_fn([](uint64_t x) { const uint64_t u = x % 3, v = x / 3; return (uint64_t)(u != 0 && u == v); });
+            const uint32_t l_shift = c.lut_fn([](uint64_t x) { return (uint64_t)(x == 1 || x == 5); });
+            for (uint32_t p = 0; p < P; p++)
+                for (uint32_t i = 0; i < n; i++) {
+                    Scope sc(c, owner_for(i, n));
+                    uint32_t bit;
+                    if (kind.once && kind.reverse) bit = p == 0 ? and_bits(nz[i], G(1, i)) : and_bits(keep[i], exactly(0, i));
+                    else if (kind.once) bit = p == 0 ? and_bits(keep[i], exactly(0, i)) : rest_after(1, i);
+                    else if (kind.limited && p == P - 1) bit = kind.reverse ? and_bits(nz[i], G(P - 1, i)) : rest_after(P - 1, i);
+                    else if (kind.inclusive) {    // (NOT cover AND cF == p) OR (cover AND cF == p + 1), on (keep + 2 cover) + 3 (eq_p + 2 eq_{p+1})
+                        const uint32_t x = c.lin({{nz[i], 1}, {oc.cover[i], 1}, {G(p, i), 3}, {G(p + 1, i), 3}, {G(p + 2, i), -6}}, 0, 8);
+                        bit = c.node(x).noise <= budget() ? c.pbs(x, l_incl)      // (54 nominal variances and more; else the two terms apart)
+                                                          : c.lin({{and_bits(keep[i], exactly(p, i)), 1}, {and_bits(oc.cover[i], exactly(p + 1, i)), 1}}, 0, 1);
+                    }
+                    else if (kind.terminator && kind.reverse)      // cR == p + e: e picks between "exactly p" and "exactly p + 1"
+                        bit = and_bits(keep[i], c.pbs(c.lin({{G(p, i), 1}, {G(p + 1, i), 1}, {G(p + 2, i), -2}, {e, 3}}, 0, 5), l_shift));
+                    else bit = and_bits(keep[i], exactly(p, i));
+                    in[p][i] = bit;
+                }
+            if (kind.once) {
+                c.output(total(1));                                           // found
+            } else {
+                if (drops_empty_end) {
+                    // piece p exists iff K >= p + 1, or K == p and the last piece is not empty: on (ge_p + ge_{p+1}) + 3 e
+                    const uint32_t l_ex = c.lut_fn([](uint64_t x) { return (uint64_t)(x == 1 || x == 2 || x == 5); });
+                    for (uint32_t p = 0; p <= P; p++)
+                        unary.push_back(c.pbs(c.lin({{total(p), 1}, {total(p + 1), 1}, {e, 3}}, 0, 5), l_ex));
+                } else {
+                    for (uint32_t v = 1; v <= (kind.limited ? P : P + 1); v++) unary.push_back(total(v - 1));   // 1 + K, capped
+                }
+                emit_count(unary, P + 1);
+            }
+        }
+        for (uint32_t p = 0; p < P; p++) {
+            Scope sc(c, owner_for(p, P));                                     // one rank per part
+            emit(extract_part(s, in[p], part_cap));
+        }
+    }
+    // replacen: only the first n selected occurrences stay selected (cF[o] <= n); cover follows the cut selection
+    void keep_first_occurrences(Occurrences& oc, uint32_t n, uint32_t m, uint32_t n_chars, const std::vector<uint32_t>* nzf) {
+        if (n >= oc.sel.size()) return;
+        const auto ge = count_ge(oc.sel, n + 1);
+        for (uint32_t o = 0; o < oc.sel.size(); o++) {
+            Scope sc(c, owner_for(o, (uint32_t)oc.sel.size()));
+            oc.sel[o] = and_bits(oc.sel[o], not_bit(ge[n][o]));
+        }
+        RunMemo running;
+        oc.cover = cover_from_sel(oc.sel, m, n_chars, nzf, running);
     }
     // ---- length, emptiness, case-insensitive equality, prefix / suffix stripping ----
     uint32_t is_empty(const Str& s) { return char_is_zero(s.ch[0]); }
@@ -1376,9 +1635,20 @@ int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t 
     if (is_clear && !clear && clear_len) return fail("null clear pattern");
     Str a = s.input_string(a_cap);
     Str b;
+    StrOps::SplitKind split_kind;
+    const bool is_split = StrOps::split_kind(base, split_kind);
+    if (is_split && split_kind.whitespace && (is_clear || clear_len)) return fail("split_ascii_whitespace takes no pattern");
     const bool unary = base == "to_upper" || base == "to_lower" || base == "trim_start" || base == "trim_end" ||
-                       base == "strip" || base == "trim" || base == "len" || base == "is_empty";
-    const bool is_replace = base == "replace";
+                       base == "strip" || base == "trim" || base == "len" || base == "is_empty" || (is_split && split_kind.whitespace);
+    // replacen[_clear]:n:F:C = the general replace[_clear]:F:C cut after the first n occurrences
+    const bool is_replacen = StrOps::is_replacen(base);
+    uint32_t replacen_n = 0;
+    if (is_replacen) {
+        if (op_params.size() != 3) return fail("replacen takes three parameters: the count, the pattern capacity and the output capacity");
+        replacen_n = op_params[0];
+        op_params.erase(op_params.begin());
+    }
+    const bool is_replace = base == "replace" || is_replacen;
     if (!is_clear && !unary) {
         if (b_cap == 0) return fail("pattern capacity must be > 0");
         b = s.input_string(b_cap);
@@ -1467,6 +1737,22 @@ int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t 
         s.emit(s.trim_start(a));
     } else if (base == "strip" || base == "trim") {
         s.emit(s.trim_start(s.trim_end(a)));
+    } else if (is_split) {
+        // name[_clear]:P[:C]   P = max_parts (splitn / rsplitn: n), C = capacity of every part (default a_cap)
+        // split_once[_clear][:C], rsplit_once[_clear][:C]: two parts
+        const bool once = split_kind.once;
+        if (op_params.size() > (once ? 1u : 2u) || (!once && op_params.empty()))
+            return fail(once ? "split_once takes at most one parameter: the part capacity"
+                             : "split takes one or two parameters: max_parts and the part capacity");
+        const uint32_t P = once ? 2 : op_params[0];
+        const bool has_cap = op_params.size() > (once ? 0u : 1u);
+        const uint32_t part_cap = has_cap ? op_params.back() : a_cap;
+        if (P == 0) return fail(split_kind.limited ? "splitn: n must be at least 1" : "split: max_parts must be at least 1");
+        if (part_cap == 0) return fail("split: the part capacity must be > 0");
+        if (is_clear && clear_len == 0)
+            return fail("split: a clear pattern must not be empty (the per-character split of an empty pattern is not supported)");
+        if (s.T < 16) return fail("split needs a message * carry space of at least 16 values");
+        s.split(a, split_kind, is_clear || split_kind.whitespace ? nullptr : &b, clear, clear_len, P, part_cap);
     } else if (is_replace) {
         // replace_clear[:F:C]  clear = from (F bytes; default: half) || to,   output capacity C (default a_cap)
         // replace[:F:C]        b = encrypted from (capacity F; default: half) || to
@@ -1482,11 +1768,13 @@ int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t 
             if (m > clear_len) return fail("replace_clear: pattern length beyond the clear buffer");
             const uint32_t t = clear_len - m;
             const uint8_t* to = clear + m;
+            if (m == 0 && is_replacen) return fail("replacen: a clear pattern must not be empty");
             if (m == 0) s.emit(general ? s.replace_empty_pattern(a, to, t, out_cap) : a);
-            else if (m > a_cap) s.emit(s.fit(a, out_cap));
+            else if (m > a_cap || (is_replacen && replacen_n == 0)) s.emit(s.fit(a, out_cap));
             else {
                 std::vector<uint32_t> match = s.window_matches_clear(a, clear, m, a_cap - m + 1);
                 StrOps::Occurrences oc = s.occurrences(match, m, a_cap, StrOps::has_border(clear, m), nullptr);
+                if (is_replacen) s.keep_first_occurrences(oc, replacen_n, m, a_cap, nullptr);
                 s.emit(m == t && out_cap == a_cap ? s.replace_in_place(a, oc, m, to, nullptr)
                                                   : s.replace_general(a, oc, to, t, nullptr, out_cap));
             }
@@ -1506,6 +1794,8 @@ int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t 
                     StrOps::Occurrences oc = s.occurrences(match, m, a_cap, true, nullptr);
                     s.emit(s.replace_in_place(a, oc, m, nullptr, &to));
                 }
+            } else if (is_replacen && replacen_n == 0) {
+                s.emit(s.fit(a, out_cap));
             } else {
                 // padded pattern: its zero tail matches anything; an occurrence runs over from[j] != 0 only.
                 // A pattern that decrypts to the empty string selects nothing (nzf[0] = 0).
@@ -1517,6 +1807,7 @@ int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t 
                     match[o] = s.and_bits(match[o], nzf[0]);
                 }
                 StrOps::Occurrences oc = s.occurrences(match, m, a_cap, true, &nzf);
+                if (is_replacen) s.keep_first_occurrences(oc, replacen_n, m, a_cap, &nzf);
                 s.emit(s.replace_general(a, oc, nullptr, 0, to.cap ? &to : nullptr, out_cap));
             }
         }

@@ -169,7 +169,7 @@ EXPORTS = [
     "fhe_glwe_sample_extract_host", "fhe_packing_unpack_noise", "fhe_engine_unpack_glwes", "fhe_engine_unpack_glwes_dev",
     "fhe_engine_unpack_info",
 ] + [f"fhe_str_{n}{s}" for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat")
-     for s in ("", "_clear")] + ["fhe_str_repeat_clear"]
+     for s in ("", "_clear")] + ["fhe_str_repeat_clear", "fhe_str_split", "fhe_str_replacen", "fhe_str_replacen_clear"]
 
 
 def lib() -> C.CDLL:
@@ -299,6 +299,9 @@ def lib() -> C.CDLL:
     sig("fhe_str_strip_suffix", vp, vp, u32, vp, u32, vp)
     sig("fhe_str_replace_general", vp, vp, u32, vp, u32, vp, u32, u32, vp)
     sig("fhe_str_replace_clear_general", vp, vp, u32, vp, u32, vp, u32, u32, vp)
+    sig("fhe_str_replacen", vp, vp, u32, vp, u32, vp, u32, u32, u32, vp)
+    sig("fhe_str_replacen_clear", vp, vp, u32, vp, u32, vp, u32, u32, u32, vp)
+    sig("fhe_str_split", vp, C.c_char_p, vp, u32, vp, u32, vp, u32, u32, u32, vp, C.POINTER(u32))
     for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat"):
         sig(f"fhe_str_{n}", vp, vp, u32, vp, u32, vp)
         sig(f"fhe_str_{n}_clear", vp, vp, u32, vp, u32, vp)
@@ -1227,9 +1230,34 @@ def blocks_to_string(params: Params, blocks) -> bytes:
     return bytes(int(v) for v in vals).rstrip(b"\0")
 
 
+def decode_count(params: Params, msgs) -> int:
+    """The count of a split result from its decrypted digit blocks (little-endian base msg_mod).  The value max_parts + 1
+    says that parts were cut off."""
+    return sum((int(d) % params.msg_mod) * params.msg_mod ** i for i, d in enumerate(np.asarray(msgs).reshape(-1)))
+
+
+class SplitResult:
+    """What the operations that return several strings give back: `count` -- the digit ciphertexts of min(number of
+    parts, max_parts + 1) (decode_count); for split_once / rsplit_once the one 0/1 block `found` -- and `parts`, a list
+    of max_parts strings of part_cap characters each, left-justified and zero padded (parts that do not exist are all
+    zero).  Expanded: arrays (n, kN+1); packed=True: every member is a PackedString of its own, so each part is an
+    operand of the next operation."""
+    __slots__ = ("count", "parts")
+
+    def __init__(self, count, parts):
+        self.count, self.parts = count, list(parts)
+
+    @property
+    def found(self):
+        return self.count
+
+    def __iter__(self):
+        return iter((self.count, self.parts))
+
+
 class FheStringOps:
     """FheString operator surface over one engine (eq/ne/starts_with/ends_with/contains/find/
-    to_upper/to_lower).  Strings are (cap*blocks, kN+1) arrays of big-key LWEs (see string_to_blocks)."""
+    to_upper/to_lower, ..., replace / replacen, the split family).  Strings are (cap*blocks, kN+1) arrays of big-key LWEs (see string_to_blocks)."""
 
     def __init__(self, engine: Engine, out_alloc=None):
         """out_alloc(shape) -> uint64 array the results are written into (default: np.zeros; pass fhestr.pinned_empty --
@@ -1288,6 +1316,12 @@ class FheStringOps:
         back, as a PackedString: (n_glwe, k+1, N), output block j at coefficient j % N of GLWE j // N; decrypt with
         ClientKey.decrypt_packed, or pass it to the next operation.  Otherwise the output LWEs are downloaded.
         Plans are kept per (operation, capacities, clear pattern)."""
+        d_out, n_out, keep = self._run_device(op, a_cap, b_cap, clear, operands)
+        return self._finish(d_out, n_out, packed)
+
+    def _run_device(self, op, a_cap, b_cap, clear, operands):
+        """The operation's plan on device buffers (see _packed): (output tensor, its rows, what must stay alive until the
+        engine has been synchronised)."""
         import torch
         big = self.engine.params.big_size
         plan = self._plan(op, a_cap, b_cap, clear)
@@ -1300,7 +1334,7 @@ class FheStringOps:
         d_out = torch.empty((info["n_outputs"], big), dtype=torch.int64, device=dev)
         keep = self._stage(d_in, list(zip(np.cumsum([0] + sizes[:-1]).tolist(), operands)))
         plan.run_dev(d_in.data_ptr(), d_out.data_ptr())
-        return self._finish(d_out, info["n_outputs"], packed)
+        return d_out, info["n_outputs"], (keep, d_in)
 
     def _cap(self, ct):
         if isinstance(ct, PackedString):
@@ -1336,12 +1370,14 @@ class FheStringOps:
     def op_many(self, op, rows, b=None, packed=False):
         """`op` on every row against ONE second operand in a single pass (fhe_str_op_many): rows (count, cap*blocks, kN+1),
         or a sequence of PackedString of one capacity (one per row); b: an encrypted (zero padded) string -- expanded or a
-        PackedString --, clear bytes, or None for unary operations.  Returns (count, n_outputs, kN+1); with packed=True
-        one PackedString, output o of row r at block r * n_outputs + o."""
+        PackedString --, clear bytes, or None for unary operations.  `op` may be any plan name, parameters included
+        ("split:3" -- with clear bytes "split_clear:3" is meant, and may be written).  Returns (count, n_outputs, kN+1); with
+        packed=True one PackedString, output o of row r at block r * n_outputs + o."""
         big = self.engine.params.big_size
         clear = b if isinstance(b, (bytes, bytearray)) else None
         enc = None if (b is None or clear is not None) else self._cap(b)
-        name = op + ("_clear" if clear is not None else "")
+        base, colon, op_params = op.partition(":")          # a parametrised plan name ("split:3", "split_clear:3") keeps its parameters last
+        name = base + ("_clear" if clear is not None and not base.endswith("_clear") else "") + colon + op_params
         if isinstance(rows, (list, tuple)) and any(isinstance(r, PackedString) for r in rows):
             rows = [self._cap(r)[0] for r in rows]
             sizes = {r.count if isinstance(r, PackedString) else r.shape[0] for r in rows}
@@ -1516,6 +1552,90 @@ class FheStringOps:
             _check(lib().fhe_str_replace_general(self.engine.handle, _ptr(a), a_cap, _ptr(frm), f_cap,
                                                  _ptr(to) if t_cap else None, t_cap, out_cap, _ptr(out)))
         return out
+
+    def replacen(self, a, frm, to, n: int, out_cap: int | None = None, packed=False):
+        """Replace the first n leftmost non-overlapping occurrences of frm by to (bytes.replace(frm, to, n), Rust's
+        str::replacen).  frm / to: both clear bytes, or both encrypted strings (may be zero padded); any lengths; the
+        result has out_cap characters (default: the capacity of a) and is cut there.  A clear empty frm is refused."""
+        a, a_cap = self._cap(a)
+        big = self.engine.params.big_size
+        out_cap = a_cap if out_cap is None else out_cap
+        clear = isinstance(frm, (bytes, bytearray))
+        if self._dev(packed, a, frm, to):
+            if clear:
+                return self._packed(f"replacen_clear:{n}:{len(frm)}:{out_cap}", a_cap, 0, bytes(frm) + bytes(to), [a], packed)
+            frm, f_cap = self._cap(frm)
+            to, t_cap = self._cap(to)
+            return self._packed(f"replacen:{n}:{f_cap}:{out_cap}", a_cap, f_cap + t_cap, None, [a, frm, to], packed)
+        out = self._alloc((out_cap * self.bpc, big))
+        if clear:
+            fb = (C.c_uint8 * max(1, len(frm)))(*frm)
+            tb = (C.c_uint8 * max(1, len(to)))(*to)
+            _check(lib().fhe_str_replacen_clear(self.engine.handle, _ptr(a), a_cap, fb, len(frm), tb, len(to), n, out_cap, _ptr(out)))
+        else:
+            frm, f_cap = self._cap(frm)
+            to, t_cap = self._cap(to)
+            _check(lib().fhe_str_replacen(self.engine.handle, _ptr(a), a_cap, _ptr(frm), f_cap, _ptr(to) if t_cap else None, t_cap,
+                                          n, out_cap, _ptr(out)))
+        return out
+
+    def _count_digits(self, max_parts):
+        n = 1
+        while self.engine.params.msg_mod ** n <= max_parts + 1:
+            n += 1
+        return n
+
+    def _split(self, op, a, pat, max_parts, part_cap=None, packed=False):
+        """The split family (include/fhestr.h, fhe_str_split).  pat: clear bytes, an expanded encrypted (zero padded)
+        pattern, a PackedString, or None (split_ascii_whitespace).  Returns a SplitResult."""
+        a, a_cap = self._cap(a)
+        big = self.engine.params.big_size
+        once = op in ("split_once", "rsplit_once")
+        P = 2 if once else int(max_parts)
+        if part_cap is not None and int(part_cap) <= 0:
+            raise FheError("split: the part capacity must be > 0")
+        cap = a_cap if part_cap is None else int(part_cap)
+        n_head = 1 if once else self._count_digits(P)
+        n_part = cap * self.bpc
+        clear = bytes(pat) if isinstance(pat, (bytes, bytearray)) else None
+        enc = None if (pat is None or clear is not None) else self._cap(pat)
+        if self._dev(packed, a, pat):
+            name = op + ("_clear" if clear is not None else "") + ("" if once else f":{P}") + (f":{cap}" if part_cap is not None else "")
+            d_out, n_out, keep = self._run_device(name, a_cap, enc[1] if enc else 0, clear, [a] + ([enc[0]] if enc else []))
+            if n_out != n_head + P * n_part:
+                raise FheError(f"{name}: the plan has {n_out} outputs, expected {n_head + P * n_part}")
+            if not packed:
+                self.engine.synchronize()
+                out = d_out.cpu().numpy().view(np.uint64)
+            else:
+                # the count blocks and every part packed on their own, where they lie: a part is the next operation's operand
+                count = PackedString(self.engine.pack(d_out[:n_head], count=n_head), n_head, 0)
+                parts = [PackedString(self.engine.pack(d_out[n_head + p * n_part: n_head + (p + 1) * n_part], count=n_part), n_part, cap)
+                         for p in range(P)]
+                return SplitResult(count, parts)
+        else:
+            buf = (C.c_uint8 * max(1, len(clear)))(*clear) if clear is not None else None
+            args = (self.engine.handle, op.encode(), _ptr(a), a_cap, _ptr(enc[0]) if enc else None, enc[1] if enc else 0,
+                    buf, len(clear) if clear is not None else 0, P, 0 if part_cap is None else cap)
+            n_out = C.c_uint32(0)
+            _check(lib().fhe_str_split(*args, None, C.byref(n_out)))        # builds and caches the plan
+            if n_out.value != n_head + P * n_part:
+                raise FheError(f"{op}: the plan has {n_out.value} outputs, expected {n_head + P * n_part}")
+            out = self._alloc((n_out.value, big))
+            _check(lib().fhe_str_split(*args, _ptr(out), C.byref(n_out)))
+        head = out[0] if once else out[:n_head]
+        return SplitResult(head, [out[n_head + p * n_part: n_head + (p + 1) * n_part] for p in range(P)])
+
+    def split(self, a, pat, max_parts, part_cap=None, packed=False): return self._split("split", a, pat, max_parts, part_cap, packed)
+    def rsplit(self, a, pat, max_parts, part_cap=None, packed=False): return self._split("rsplit", a, pat, max_parts, part_cap, packed)
+    def split_terminator(self, a, pat, max_parts, part_cap=None, packed=False): return self._split("split_terminator", a, pat, max_parts, part_cap, packed)
+    def rsplit_terminator(self, a, pat, max_parts, part_cap=None, packed=False): return self._split("rsplit_terminator", a, pat, max_parts, part_cap, packed)
+    def split_inclusive(self, a, pat, max_parts, part_cap=None, packed=False): return self._split("split_inclusive", a, pat, max_parts, part_cap, packed)
+    def splitn(self, a, pat, n, part_cap=None, packed=False): return self._split("splitn", a, pat, n, part_cap, packed)
+    def rsplitn(self, a, pat, n, part_cap=None, packed=False): return self._split("rsplitn", a, pat, n, part_cap, packed)
+    def split_once(self, a, pat, part_cap=None, packed=False): return self._split("split_once", a, pat, 2, part_cap, packed)
+    def rsplit_once(self, a, pat, part_cap=None, packed=False): return self._split("rsplit_once", a, pat, 2, part_cap, packed)
+    def split_ascii_whitespace(self, a, max_parts, part_cap=None, packed=False): return self._split("split_ascii_whitespace", a, None, max_parts, part_cap, packed)
 
     def concat(self, a, b, packed=False):
         """a ++ b (padding of a removed); b encrypted (any capacity) or clear bytes."""

@@ -311,7 +311,7 @@ int fhe_int_plan_create_offline(const fhe_params_t *params, const char *op, uint
  * after the text and nowhere else (the searches with an encrypted pattern rely on it: csrc/fhe_string.cpp, group_match).
  * op in {"eq","ne","starts_with","ends_with","contains","find"} (+ "_clear" suffix for a clear
  * pattern) or {"to_upper","to_lower","trim_start","trim_end","strip","replace","replace_clear","concat",
- * "concat_clear","repeat_clear"}.  Outputs: one 0/1 block; find: found block then
+ * "concat_clear","repeat_clear"}, or a name of the split family / replacen (see fhe_str_split below).  Outputs: one 0/1 block; find: found block then
  * ceil(log_msg_mod(cap+1)) index digits (little endian); case ops: the whole string. */
 int fhe_str_plan_create(fhe_engine *eng, const char *op, uint32_t a_cap, uint32_t b_cap,
                         const uint8_t *clear, uint32_t clear_len, uint32_t world, fhe_plan **out);
@@ -366,6 +366,45 @@ int fhe_str_replace(fhe_engine *eng, const uint64_t *a, uint32_t a_cap, const ui
                     uint32_t pat_cap, uint64_t *out);
 int fhe_str_replace_clear(fhe_engine *eng, const uint64_t *a, uint32_t a_cap, const uint8_t *from,
                           const uint8_t *to, uint32_t pat_len, uint64_t *out);
+/* replacen: replace the first `n` (clear, >= 0) leftmost non-overlapping occurrences (Rust's str::replacen / Python's
+ * bytes.replace(from, to, n)); every other argument, the output and the conventions are those of the general replace
+ * above (n = 0 returns the string, fitted to out_cap).  A clear empty `from` is refused.  Plan op names
+ * "replacen:<n>:<from_cap>:<out_cap>" (b = from || to) and "replacen_clear:<n>:<from_len>:<out_cap>" (clear = from || to). */
+int fhe_str_replacen(fhe_engine *eng, const uint64_t *a, uint32_t a_cap, const uint64_t *from, uint32_t from_cap,
+                     const uint64_t *to, uint32_t to_cap, uint32_t n, uint32_t out_cap, uint64_t *out);
+int fhe_str_replacen_clear(fhe_engine *eng, const uint64_t *a, uint32_t a_cap, const uint8_t *from, uint32_t from_len,
+                           const uint8_t *to, uint32_t to_len, uint32_t n, uint32_t out_cap, uint64_t *out);
+/* The operations that return SEVERAL strings.  `op` is one of the names below, without "_clear" and without parameters;
+ * the result is Rust's str method of that name, stated here with Python bytes (`sep` non-empty):
+ *   "split"                   s.split(sep)
+ *   "rsplit"                  s.rsplit(sep)[::-1]       from the right, as Rust yields them; with a self-overlapping
+ *                                                       separator the pieces are cut elsewhere than split's
+ *   "split_terminator"        split, the last part dropped if it is empty
+ *   "rsplit_terminator"       rsplit as above, the first part dropped if it is empty
+ *   "split_inclusive"         every part keeps its separator; no empty last part
+ *   "splitn" / "rsplitn"      s.split(sep, n - 1) / s.rsplit(sep, n - 1)[::-1]; max_parts IS n (>= 1)
+ *   "split_once"              s.partition(sep): (before, after); not found: (s, "")
+ *   "rsplit_once"             s.rpartition(sep): (before, after); not found: ("", s)
+ *   "split_ascii_whitespace"  s.split(); takes no pattern.  Whitespace = ASCII 9..13 and 32, the set of trim_start /
+ *                             trim_end: Rust's is_ascii_whitespace lacks 0x0B (vertical tab), this one has it.
+ * The pattern is encrypted (pat, pat_cap characters, may be zero padded: hidden length) or clear (clear, clear_len
+ * bytes); give one of them, none for split_ascii_whitespace.  An encrypted pattern that decrypts to the empty string
+ * separates nothing -- the convention of replace above, and a deviation from Rust, which splits between all characters.
+ * A clear empty pattern is refused when the plan is built (the per-character split is not provided), and so are
+ * max_parts == 0 (splitn: n == 0), a part capacity of 0 in a plan name, and a pattern given to split_ascii_whitespace.
+ * The number of parts is hidden, so the caller gives max_parts = P (split_once / rsplit_once: ignored, P = 2) and the
+ * capacity of every part, part_cap (0 = a_cap).  Outputs, in this order:
+ *   1. count = min(number of parts, P + 1) as little-endian base-msg_mod digits, as many as the value P + 1 needs; the
+ *      value P + 1 says that parts were cut off.  split_once / rsplit_once: ONE 0/1 block `found` instead.
+ *   2. the P parts in the order above, each part_cap characters, left-justified and zero padded (part_cap * blocks
+ *      LWEs).  Parts that do not exist are all zero, a part longer than part_cap is cut as replace cuts at out_cap,
+ *      parts beyond P are dropped.
+ * *n_outputs (optional) = the number of output ciphertexts; with out == NULL the call only builds the plan and returns
+ * that number.  Plan op names: "<op>[_clear]:<max_parts>[:<part_cap>]", "split_once[_clear][:<part_cap>]",
+ * "rsplit_once[_clear][:<part_cap>]", "split_ascii_whitespace:<max_parts>[:<part_cap>]".  They need msg_mod * carry_mod >= 16. */
+int fhe_str_split(fhe_engine *eng, const char *op, const uint64_t *a, uint32_t a_cap, const uint64_t *pat, uint32_t pat_cap,
+                  const uint8_t *clear, uint32_t clear_len, uint32_t max_parts, uint32_t part_cap, uint64_t *out,
+                  uint32_t *n_outputs);
 /* Many strings against ONE second operand in one pass (fhe_plan_run_batch on the operation's cached plan): `op` is an
  * operation name of fhe_str_plan_create ("eq", "ne", "contains", "find", "starts_with", "to_lower", ...; "<op>_clear" with
  * a clear pattern), rows = [count][a_cap * blocks] ciphertexts, b = the shared encrypted operand ([b_cap * blocks]

@@ -6,8 +6,10 @@ import os
 import sys
 import numpy as np
 sys.path.insert(0, "."); sys.path.insert(0, "fhe-string-bounty_amd")
+sys.path.insert(0, "tests")
 import oracle as O
 import fhestr
+from split_ref import ONCE, SPLIT_OPS, decode_split, split_ref        # the clear-text definitions of the split family
 
 N_CASES = int(sys.argv[1]) if len(sys.argv) > 1 else 150
 SEED = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -59,7 +61,7 @@ for case in range(N_CASES):
     ea, eb = enc(a, cap), enc(b, b_cap)
     op = str(rng.choice(["eq", "ne", "lt", "le", "gt", "ge", "eqic", "starts", "ends", "contains", "find", "rfind",
                          "upper", "lower", "trim_start", "trim_end", "strip", "replace", "len", "is_empty",
-                         "strip_prefix", "strip_suffix", "concat", "repeat", "replace_general"]))
+                         "strip_prefix", "strip_suffix", "concat", "repeat", "replace_general", "split", "split_ws", "replacen"]))
     clear = bool(rng.random() < 0.5)
     rhs = b if clear else eb
     ctx = (op, a, b, cap, b_cap, clear)
@@ -130,5 +132,34 @@ for case in range(N_CASES):
         want = (a[len(b):] if op == "strip_prefix" else a[:len(a) - len(b)]) if had else a
         check(op + ".bit", int(dec(bit)[0]), int(had), ctx)
         check(op + ".str", dec_str(out), want, ctx)
+    elif op == "split":
+        # one operation of the family; clear or encrypted (zero padded) separator, often a part capacity that cuts
+        name = str(rng.choice(SPLIT_OPS))
+        if len(b) == 0:
+            continue        # a clear empty separator is refused, an encrypted one separates nothing (fhestr.h)
+        max_parts = int(rng.integers(1, 5))
+        part_cap = int(rng.integers(1, cap + 1)) if rng.random() < 0.4 else None
+        res = getattr(ops, name)(ea, rhs, part_cap) if name in ONCE else getattr(ops, name)(ea, rhs, max_parts, part_cap)
+        flat = np.concatenate([np.asarray(res.count).reshape(-1, p.big_size)] + list(res.parts))
+        got = decode_split(name, dec(flat), p.msg_mod, max_parts, part_cap or cap)
+        check(name, got, split_ref(name, a, b, max_parts, part_cap=part_cap), ctx + (max_parts, part_cap))
+    elif op == "split_ws":
+        max_parts = int(rng.integers(1, 5))
+        res = ops.split_ascii_whitespace(ea, max_parts)
+        flat = np.concatenate([np.asarray(res.count).reshape(-1, p.big_size)] + list(res.parts))
+        check(op, decode_split("split_ascii_whitespace", dec(flat), p.msg_mod, max_parts, cap),
+              split_ref("split_ascii_whitespace", a, None, max_parts), ctx + (max_parts,))
+    elif op == "replacen":
+        if len(b) == 0:
+            continue
+        to = bytes(ALPHA[int(i)] for i in rng.integers(0, len(ALPHA), size=int(rng.integers(0, 4))))
+        n = int(rng.integers(0, 4))
+        want = a.replace(b, to, n)
+        out_cap = max(1, len(want) + int(rng.integers(0, 2)))
+        if clear:
+            got = dec_str(ops.replacen(ea, b, to, n, out_cap=out_cap))
+        else:
+            got = dec_str(ops.replacen(ea, eb, enc(to, max(1, len(to) + int(rng.integers(0, 2)))), n, out_cap=out_cap))
+        check(op, got, want, ctx + (to, n, out_cap))
 print(f"fuzz: {N_CASES} cases, {fails} mismatches")
 sys.exit(1 if fails else 0)
