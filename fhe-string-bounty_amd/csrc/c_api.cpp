@@ -799,6 +799,12 @@ static int cached_str_plan(fhe_engine* eng, const std::string& op, uint32_t a_ca
     return 0;
 }
 
+static uint32_t blocks_per_char(const fhe_plan* plan) {
+    uint32_t bits = 0;
+    while ((1u << bits) < plan->c->msg_modulus()) bits++;
+    return bits ? 8 / bits : 8;
+}
+
 // one-call FheString operations (host buffers): up to three encrypted operands, each `caps[i]` characters
 static int str_op_parts(fhe_engine* eng, const std::string& op, const uint64_t* const* operands, const uint32_t* caps,
                         uint32_t n_operands, const uint8_t* clear, uint32_t clear_len, uint64_t* out) {
@@ -838,8 +844,11 @@ int fhe_str_op_many(fhe_engine* eng, const char* op, const uint64_t* rows, uint3
     CHECK_PTR(rows); CHECK_PTR(out);
     if (b_cap && !b) return fail("null pointer: b");
     if (a_cap + b_cap == 0) return fail("fhe_str_op_many: empty operands");
-    const uint32_t bpc = plan->c->n_inputs() / (a_cap + b_cap);
-    return plan->c->run_batch_host(rows, a_cap * bpc, b_cap ? b : nullptr, out, count);
+    const uint32_t bpc = blocks_per_char(plan);
+    // what the rows do not bring is shared: the second operand, then the digits of an encrypted count
+    const bool shares = plan->c->n_inputs() > a_cap * bpc;
+    if (shares && !b) return fail("null pointer: b (the shared operand: the pattern, then the digits of an encrypted count)");
+    return plan->c->run_batch_host(rows, a_cap * bpc, shares ? b : nullptr, out, count);
     API_END
 }
 
@@ -943,6 +952,75 @@ int fhe_str_split(fhe_engine* eng, const char* op, const uint64_t* a, uint32_t a
     const uint32_t counts[2] = {a_cap * bpc, pat ? pat_cap * bpc : 0};
     return plan->c->run_host_parts(operands, counts, pat ? 2 : 1, out);
     API_END
+}
+
+// ---- encrypted counts: the D digits of n are the plan's last inputs (include/fhestr.h) ----
+static int str_op_counted(fhe_engine* eng, const std::string& op, const uint64_t* const* operands, const uint32_t* caps,
+                          uint32_t n_operands, const uint64_t* n_digits, const uint8_t* clear, uint32_t clear_len, uint64_t* out,
+                          uint32_t* n_outputs) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    uint32_t b_cap = 0;
+    for (uint32_t i = 1; i < n_operands; i++) b_cap += caps[i];
+    fhe_plan* plan = nullptr;
+    if (cached_str_plan(eng, op, caps[0], b_cap, clear, clear_len, &plan)) return 1;
+    if (n_outputs) *n_outputs = plan->c->n_outputs();
+    if (!out && n_outputs) return 0;                    // query: how many output ciphertexts
+    CHECK_PTR(out); CHECK_PTR(n_digits);
+    const uint32_t bpc = blocks_per_char(plan);
+    const uint64_t* parts[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t counts[4] = {0, 0, 0, 0}, placed = 0;
+    for (uint32_t i = 0; i < n_operands; i++) {
+        CHECK_PTR(operands[i]);
+        parts[i] = operands[i];
+        counts[i] = caps[i] * bpc;
+        placed += counts[i];
+    }
+    if (placed >= plan->c->n_inputs()) return fail(op + ": the plan has no input left for the count's digits");
+    parts[n_operands] = n_digits;
+    counts[n_operands] = plan->c->n_inputs() - placed;
+    return plan->c->run_host_parts(parts, counts, n_operands + 1, out);
+    API_END
+}
+
+int fhe_str_repeat(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint64_t* n_digits, uint32_t max_count, uint64_t* out) {
+    if (max_count == 0 || max_count > 255) return fail("repeat: max_count must be in 1..255");
+    const uint64_t* operands[1] = {a};
+    return str_op_counted(eng, "repeat:" + std::to_string(max_count), operands, &a_cap, 1, n_digits, nullptr, 0, out, nullptr);
+}
+int fhe_str_replacen_encn(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint64_t* from, uint32_t from_cap,
+                          const uint64_t* to, uint32_t to_cap, const uint64_t* n_digits, uint32_t n_max, uint32_t out_cap, uint64_t* out) {
+    if (!from || from_cap == 0) return fail("replacen: `from` needs a capacity of at least one character");
+    if (to_cap && !to) return fail("null pointer: to");
+    const std::string op = "replacen_encn:" + std::to_string(n_max) + ":" + std::to_string(from_cap) + ":" + std::to_string(out_cap);
+    const uint64_t* operands[3] = {a, from, to};
+    const uint32_t caps[3] = {a_cap, from_cap, to_cap};
+    return str_op_counted(eng, op, operands, caps, to_cap ? 3 : 2, n_digits, nullptr, 0, out, nullptr);
+}
+int fhe_str_replacen_encn_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint8_t* from, uint32_t from_len,
+                                const uint8_t* to, uint32_t to_len, const uint64_t* n_digits, uint32_t n_max, uint32_t out_cap,
+                                uint64_t* out) {
+    if ((from_len && !from) || (to_len && !to)) return fail("null pointer: from / to");
+    std::vector<uint8_t> both(from, from + from_len);
+    both.insert(both.end(), to, to + to_len);
+    const std::string op = "replacen_encn_clear:" + std::to_string(n_max) + ":" + std::to_string(from_len) + ":" + std::to_string(out_cap);
+    const uint64_t* operands[1] = {a};
+    return str_op_counted(eng, op, operands, &a_cap, 1, n_digits, both.data(), (uint32_t)both.size(), out, nullptr);
+}
+int fhe_str_splitn_encn(fhe_engine* eng, const char* op, const uint64_t* a, uint32_t a_cap, const uint64_t* pat, uint32_t pat_cap,
+                        const uint8_t* clear, uint32_t clear_len, const uint64_t* n_digits, uint32_t max_parts, uint32_t part_cap,
+                        uint64_t* out, uint32_t* n_outputs) {
+    if (!op) return fail("null pointer: op");
+    const std::string base(op);
+    if (base != "splitn" && base != "rsplitn") return fail("fhe_str_splitn_encn: op must be \"splitn\" or \"rsplitn\", got: " + base);
+    if (pat && (clear || clear_len)) return fail("fhe_str_splitn_encn: give an encrypted pattern or a clear one, not both");
+    if (pat && pat_cap == 0) return fail("fhe_str_splitn_encn: the encrypted pattern needs a capacity of at least one character");
+    if (!pat && !clear && clear_len) return fail("null clear pattern");
+    std::string name = base + "_encn" + (pat ? "" : "_clear") + ":" + std::to_string(max_parts);
+    if (part_cap) name += ":" + std::to_string(part_cap);
+    const uint64_t* operands[2] = {a, pat};
+    const uint32_t caps[2] = {a_cap, pat ? pat_cap : 0};
+    return str_op_counted(eng, name, operands, caps, pat ? 2 : 1, n_digits, pat ? nullptr : clear, pat ? 0 : clear_len, out, n_outputs);
 }
 
 int fhe_str_repeat_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, uint32_t count, uint64_t* out) {

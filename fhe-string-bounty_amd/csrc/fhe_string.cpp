@@ -1276,6 +1276,7 @@ public:
     // Which operation of the family: see include/fhestr.h for the semantics of each.
     struct SplitKind {
         bool reverse = false, terminator = false, inclusive = false, limited = false, once = false, whitespace = false;
+        bool enc_count = false;        // splitn_encn / rsplitn_encn: n is encrypted, max_parts is its public bound
     };
     static bool split_kind(const std::string& base, SplitKind& k) {
         k = SplitKind();
@@ -1286,13 +1287,76 @@ public:
         if (base == "split_inclusive") { k.inclusive = true; return true; }
         if (base == "splitn") { k.limited = true; return true; }
         if (base == "rsplitn") { k.reverse = k.limited = true; return true; }
+        if (base == "splitn_encn") { k.limited = k.enc_count = true; return true; }
+        if (base == "rsplitn_encn") { k.reverse = k.limited = k.enc_count = true; return true; }
         if (base == "split_once") { k.once = true; return true; }
         if (base == "rsplit_once") { k.reverse = k.once = true; return true; }
         if (base == "split_ascii_whitespace") { k.whitespace = true; return true; }
         return false;
     }
     // (like the split names, a name that does not build without its parameters)
-    static bool is_replacen(const std::string& base) { return base == "replacen"; }
+    static bool is_replacen(const std::string& base) { return base == "replacen" || base == "replacen_encn"; }
+    static bool is_replacen_encn(const std::string& base) { return base == "replacen_encn"; }
+    // ---- encrypted counts ("Encrypted counts") ----
+    // n arrives as D little-endian base-M digits, D the smallest with M^D > n_max (the public bound); every consumer
+    // works from the thermometer g[q - 1] = [n >= q], q = 1 .. n_max, so a value above the bound acts as the bound.
+    static uint32_t count_input_digits(uint32_t M, uint32_t n_max) {
+        uint32_t d = 1;
+        for (uint64_t span = M; span <= n_max; span *= M) d++;
+        return d;
+    }
+    std::vector<uint32_t> count_inputs(uint32_t n_max) {
+        std::vector<uint32_t> digits;
+        for (uint32_t d = 0; d < count_input_digits(M, n_max); d++) digits.push_back(c.input(M - 1));
+        return digits;
+    }
+    // The integer layer's scalar comparison (fhe_integer.cpp, scalar_comparison.rs:104-138 / comparator.rs:240-268) for
+    // every q at once: the digits are packed in pairs hi * M + lo where that fits the box and the budget.  One packed
+    // unit (D <= 2): [unit >= q] is one lookup per q.  More: the sign of (unit - q's unit) per unit, the most
+    // significant non-equal one wins, and the last pick answers [sign != less] directly.
+    std::vector<uint32_t> count_thermometer(const std::vector<uint32_t>& digits, uint32_t n_max) {
+        const bool pack = (uint64_t)M * M <= (uint64_t)T && 1.0 + (double)M * M <= budget();
+        const uint32_t per = pack ? 2 : 1;
+        std::vector<uint32_t> units;
+        for (size_t i = 0; i < digits.size(); i += per)
+            units.push_back(pack && i + 1 < digits.size() ? c.lin({{digits[i], 1}, {digits[i + 1], (int32_t)M}}) : digits[i]);
+        const uint64_t unit_mod = pack ? (uint64_t)M * M : M;
+        const uint32_t sgn = c.lut_fn([](uint64_t x) { return (uint64_t)(x != 0); });      // odd: -1 below zero for free
+        const uint32_t pick = c.lut_fn([](uint64_t x) { const uint64_t msb = (x / 4) & 3, lsb = x & 3; return msb == 1 ? lsb : msb; });
+        const uint32_t pick_ge = c.lut_fn([](uint64_t x) { const uint64_t msb = (x / 4) & 3, lsb = x & 3; return (uint64_t)((msb == 1 ? lsb : msb) != 0); });
+        std::vector<uint32_t> g;
+        for (uint32_t q = 1; q <= n_max; q++) {
+            if (units.size() == 1) {
+                g.push_back(c.pbs(units[0], c.lut_fn([q](uint64_t x) { return (uint64_t)(x >= q); })));
+                continue;
+            }
+            std::vector<uint32_t> signs;       // least significant first, {0: <, 1: ==, 2: >}
+            uint64_t rest = q;
+            for (size_t u = 0; u < units.size(); u++, rest /= unit_mod)
+                signs.push_back(c.lin({{c.pbs(c.lin({{units[u], 1}}, -(int64_t)(rest % unit_mod)), sgn, /*signed_input=*/true), 1}}, 1, 2));
+            while (signs.size() > 2) {
+                std::vector<uint32_t> next;
+                for (size_t i = 0; i + 1 < signs.size(); i += 2) next.push_back(c.pbs(c.lin({{signs[i + 1], 4}, {signs[i], 1}}), pick));
+                if (signs.size() & 1) next.push_back(signs.back());
+                signs.swap(next);
+            }
+            g.push_back(c.pbs(c.lin({{signs[1], 4}, {signs[0], 1}}), pick_ge));
+        }
+        return g;
+    }
+    // AND of 0/1 blocks in one lookup (their sum against their number); bits known at build time drop out
+    uint32_t and_all(const std::vector<uint32_t>& bits) {
+        std::vector<Term> terms;
+        for (uint32_t b : bits) {
+            int64_t v = 0;
+            if (!is_trivial(b, &v)) terms.push_back({b, 1});
+            else if (v == 0) return c.trivial(0);
+        }
+        if (terms.empty()) return c.trivial(1);
+        if (terms.size() == 1) return terms[0].node;
+        const size_t k = terms.size();
+        return c.pbs(c.lin(terms), c.lut_fn([k](uint64_t x) { return (uint64_t)(x == k); }));
+    }
     // Selected occurrences of the pattern in s and the characters they cover: leftmost first (as replace), or rightmost
     // first -- two occurrences of one length L do not overlap iff their offsets differ by at least L, so that is the same
     // recurrence over the reversed match vector, hidden lengths included; cover is then rebuilt forward from sel.
@@ -1332,8 +1396,9 @@ public:
         return oc;
     }
     // outputs: the count digits (split_once / rsplit_once: the found bit), then P parts of part_cap characters
+    // g (splitn_encn / rsplitn_encn only): the thermometer of the encrypted n, P entries
     void split(const Str& s, const SplitKind& kind, const Str* pat, const uint8_t* clear, uint32_t clear_len, uint32_t P,
-               uint32_t part_cap) {
+               uint32_t part_cap, const std::vector<uint32_t>* g = nullptr) {
         const uint32_t n = s.cap, zero = c.trivial(0), one = c.trivial(1);
         const uint32_t l2 = c.lut_fn([](uint64_t x) { return (uint64_t)(x == 2); });
         std::vector<std::vector<uint32_t>> in(P, std::vector<uint32_t>(n, zero));    // in[p][i]: character i belongs to part p
@@ -1403,7 +1468,19 @@ public:
                 for (uint32_t i = 0; i < n; i++) {
                     Scope sc(c, owner_for(i, n));
                     uint32_t bit;
-                    if (kind.once && kind.reverse) bit = p == 0 ? and_bits(nz[i], G(1, i)) : and_bits(keep[i], exactly(0, i));
+                    if (g) {
+                        // slot q = p + 1 of an encrypted n: the ordinary piece while q < n, the rest of the string when
+                        // q == n, nothing beyond -- two disjoint products, the thermometer taken into the mask lookups:
+                        //   forward  keep AND [cF == q - 1] AND g_q      +  nz AND [cF >= q] AND (g_q - g_{q+1})
+                        //            (rest_after(q - 1) = the ordinary piece OR everything behind occurrence q)
+                        //   reverse  keep AND [cR == q - 1] AND g_{q+1}  +  nz AND [cR >= q - 1] AND (g_q - g_{q+1})
+                        const uint32_t q = p + 1, g_q = (*g)[p], g_next = q < P ? (*g)[q] : zero;
+                        const uint32_t is_last = c.lin({{g_q, 1}, {g_next, -1}}, 0, 1);
+                        const uint32_t ordinary = and_all({keep[i], exactly(q - 1, i), kind.reverse ? g_next : g_q});
+                        const uint32_t rest = and_all({nz[i], G(kind.reverse ? q - 1 : q, i), is_last});
+                        bit = c.lin({{ordinary, 1}, {rest, 1}}, 0, 1);
+                    }
+                    else if (kind.once && kind.reverse) bit = p == 0 ? and_bits(nz[i], G(1, i)) : and_bits(keep[i], exactly(0, i));
                     else if (kind.once) bit = p == 0 ? and_bits(keep[i], exactly(0, i)) : rest_after(1, i);
                     else if (kind.limited && p == P - 1) bit = kind.reverse ? and_bits(nz[i], G(P - 1, i)) : rest_after(P - 1, i);
                     else if (kind.inclusive) {    // (NOT cover AND cF == p) OR (cover AND cF == p + 1), on (keep + 2 cover) + 3 (eq_p + 2 eq_{p+1})
@@ -1424,6 +1501,8 @@ public:
                     const uint32_t l_ex = c.lut_fn([](uint64_t x) { return (uint64_t)(x == 1 || x == 2 || x == 5); });
                     for (uint32_t p = 0; p <= P; p++)
                         unary.push_back(c.pbs(c.lin({{total(p), 1}, {total(p + 1), 1}, {e, 3}}, 0, 5), l_ex));
+                } else if (g) {
+                    for (uint32_t v = 1; v <= P; v++) unary.push_back(and_bits((*g)[v - 1], total(v - 1)));    // min(1 + K, n)
                 } else {
                     for (uint32_t v = 1; v <= (kind.limited ? P : P + 1); v++) unary.push_back(total(v - 1));   // 1 + K, capped
                 }
@@ -1442,6 +1521,34 @@ public:
         for (uint32_t o = 0; o < oc.sel.size(); o++) {
             Scope sc(c, owner_for(o, (uint32_t)oc.sel.size()));
             oc.sel[o] = and_bits(oc.sel[o], not_bit(ge[n][o]));
+        }
+        RunMemo running;
+        oc.cover = cover_from_sel(oc.sel, m, n_chars, nzf, running);
+    }
+    // replacen with an encrypted n (thermometer g, n_max entries): a selected occurrence stays iff its running count q
+    // (1-based) has g_q set -- [cF[o] == q] = ge_q - ge_{q+1}, exactly one q for a selected o, none beyond n_max
+    void keep_counted_occurrences(Occurrences& oc, const std::vector<uint32_t>& g, uint32_t m, uint32_t n_chars, const std::vector<uint32_t>* nzf) {
+        const uint32_t n_max = (uint32_t)g.size();
+        const auto ge = count_ge(oc.sel, n_max + 1);
+        const uint32_t l2 = c.lut_fn([](uint64_t x) { return (uint64_t)(x == 2); });
+        for (uint32_t o = 0; o < oc.sel.size(); o++) {
+            Scope sc(c, owner_for(o, (uint32_t)oc.sel.size()));
+            int64_t v = 0;
+            if (is_trivial(oc.sel[o], &v) && v == 0) continue;
+            std::vector<Term> allowed;
+            for (uint32_t q = 1; q <= n_max; q++) {
+                const uint32_t hit = and_bits(c.lin({{ge[q - 1][o], 1}, {ge[q][o], -1}}, 0, 1), g[q - 1]);
+                if (!(is_trivial(hit, &v) && v == 0)) allowed.push_back({hit, 1});
+            }
+            if (allowed.empty()) { oc.sel[o] = c.trivial(0); continue; }
+            // sel + (at most one product set) == 2; a sum too noisy for one lookup is OR-ed first
+            std::vector<Term> both(allowed);
+            both.push_back({oc.sel[o], 1});
+            const uint32_t x = c.lin(both, 0, 2);
+            if (c.node(x).noise <= budget()) { oc.sel[o] = c.pbs(x, l2); continue; }
+            std::vector<uint32_t> bits;
+            for (const Term& t : allowed) bits.push_back(t.node);
+            oc.sel[o] = and_bits(oc.sel[o], reduce_local(bits, false));
         }
         RunMemo running;
         oc.cover = cover_from_sel(oc.sel, m, n_chars, nzf, running);
@@ -1641,18 +1748,27 @@ int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t 
     const bool unary = base == "to_upper" || base == "to_lower" || base == "trim_start" || base == "trim_end" ||
                        base == "strip" || base == "trim" || base == "len" || base == "is_empty" || (is_split && split_kind.whitespace);
     // replacen[_clear]:n:F:C = the general replace[_clear]:F:C cut after the first n occurrences
-    const bool is_replacen = StrOps::is_replacen(base);
+    const bool is_replacen = StrOps::is_replacen(base), is_replacen_encn = StrOps::is_replacen_encn(base);
     uint32_t replacen_n = 0;
     if (is_replacen) {
-        if (op_params.size() != 3) return fail("replacen takes three parameters: the count, the pattern capacity and the output capacity");
+        if (op_params.size() != 3)
+            return fail(is_replacen_encn ? "replacen_encn takes three parameters: the count's bound n_max, the pattern capacity and the output capacity"
+                                         : "replacen takes three parameters: the count, the pattern capacity and the output capacity");
         replacen_n = op_params[0];
         op_params.erase(op_params.begin());
+        if (is_replacen_encn && replacen_n == 0) return fail("replacen_encn: n_max must be at least 1");
     }
     const bool is_replace = base == "replace" || is_replacen;
-    if (!is_clear && !unary) {
+    // repeat:<n_max>: the encrypted-count form of repeat_clear (a bare `repeat` stays refused below)
+    const bool counted_repeat = base == "repeat" && !is_clear && !op_params.empty();
+    if (counted_repeat && b_cap) return fail("repeat takes no second string: its inputs are the string and the count's digits");
+    if (!is_clear && !unary && !counted_repeat) {
         if (b_cap == 0) return fail("pattern capacity must be > 0");
         b = s.input_string(b_cap);
     }
+    // an encrypted count: its digits are the plan's last inputs, after the string and the encrypted pattern operand(s)
+    std::vector<uint32_t> count_g;
+    auto take_count = [&](uint32_t n_max) { count_g = s.count_thermometer(s.count_inputs(n_max), n_max); };
     uint32_t n_digits = 0;
     while ((1ull << (n_digits * s.bits_per_block)) < (uint64_t)a_cap + 1) n_digits++;
     if (base == "eq" || base == "ne") {
@@ -1723,10 +1839,30 @@ int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t 
         else s.emit(s.concat(a, is_clear ? s.clear_string(clear, clear_len) : b));
     } else if (base == "repeat") {
         // clear repetition count in clear[0] (>= 1): out capacity = count * a_cap
-        if (!is_clear || clear_len != 1 || clear[0] == 0) return fail("repeat_clear takes one clear byte: the count (>= 1)");
-        Str r = a;
-        for (uint32_t i = 1; i < clear[0]; i++) r = s.concat(r, a);
-        s.emit(r);
+        if (counted_repeat) {
+            // copy i is masked by [n >= i + 1] before it is appended: zeroing the tail copies leaves a left-justified result
+            if (op_params.size() != 1) return fail("repeat takes one parameter: the count's bound n_max");
+            const uint32_t n_max = op_params[0];
+            if (n_max == 0 || n_max > 255) return fail("repeat: n_max must be in 1..255");
+            take_count(n_max);
+            Str r;
+            for (uint32_t i = 0; i < n_max; i++) {
+                Str copy;
+                copy.cap = a_cap;
+                copy.ch.resize(a_cap);
+                for (uint32_t j = 0; j < a_cap; j++) {
+                    StrOps::Scope sc(c, s.owner_for(j, a_cap));
+                    for (uint32_t k = 0; k < s.bpc; k++) copy.ch[j].push_back(s.gate_block(a.ch[j][k], count_g[i], true));
+                }
+                r = i ? s.concat(r, copy) : copy;
+            }
+            s.emit(r);
+        } else {
+            if (!is_clear || clear_len != 1 || clear[0] == 0) return fail("repeat_clear takes one clear byte: the count (>= 1)");
+            Str r = a;
+            for (uint32_t i = 1; i < clear[0]; i++) r = s.concat(r, a);
+            s.emit(r);
+        }
     } else if (base == "to_upper" || base == "to_lower") {
         std::vector<uint32_t> outs;
         s.change_case(a, base == "to_lower", outs);
@@ -1752,7 +1888,9 @@ int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t 
         if (is_clear && clear_len == 0)
             return fail("split: a clear pattern must not be empty (the per-character split of an empty pattern is not supported)");
         if (s.T < 16) return fail("split needs a message * carry space of at least 16 values");
-        s.split(a, split_kind, is_clear || split_kind.whitespace ? nullptr : &b, clear, clear_len, P, part_cap);
+        if (split_kind.enc_count) take_count(P);
+        s.split(a, split_kind, is_clear || split_kind.whitespace ? nullptr : &b, clear, clear_len, P, part_cap,
+                split_kind.enc_count ? &count_g : nullptr);
     } else if (is_replace) {
         // replace_clear[:F:C]  clear = from (F bytes; default: half) || to,   output capacity C (default a_cap)
         // replace[:F:C]        b = encrypted from (capacity F; default: half) || to
@@ -1762,6 +1900,7 @@ int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t 
         const bool general = !op_params.empty();
         const uint32_t out_cap = general ? op_params[1] : a_cap;
         if (out_cap == 0) return fail("output capacity must be > 0");
+        if (is_replacen_encn) take_count(replacen_n);
         if (is_clear) {
             if (!general && clear_len % 2) return fail("replace_clear expects `from` and `to` of equal length, concatenated");
             const uint32_t m = general ? op_params[0] : clear_len / 2;
@@ -1770,11 +1909,12 @@ int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t 
             const uint8_t* to = clear + m;
             if (m == 0 && is_replacen) return fail("replacen: a clear pattern must not be empty");
             if (m == 0) s.emit(general ? s.replace_empty_pattern(a, to, t, out_cap) : a);
-            else if (m > a_cap || (is_replacen && replacen_n == 0)) s.emit(s.fit(a, out_cap));
+            else if (m > a_cap || (is_replacen && replacen_n == 0)) s.emit(s.fit(a, out_cap));      // (replacen_encn: n_max >= 1)
             else {
                 std::vector<uint32_t> match = s.window_matches_clear(a, clear, m, a_cap - m + 1);
                 StrOps::Occurrences oc = s.occurrences(match, m, a_cap, StrOps::has_border(clear, m), nullptr);
-                if (is_replacen) s.keep_first_occurrences(oc, replacen_n, m, a_cap, nullptr);
+                if (is_replacen_encn) s.keep_counted_occurrences(oc, count_g, m, a_cap, nullptr);
+                else if (is_replacen) s.keep_first_occurrences(oc, replacen_n, m, a_cap, nullptr);
                 s.emit(m == t && out_cap == a_cap ? s.replace_in_place(a, oc, m, to, nullptr)
                                                   : s.replace_general(a, oc, to, t, nullptr, out_cap));
             }
@@ -1807,7 +1947,8 @@ int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t 
                     match[o] = s.and_bits(match[o], nzf[0]);
                 }
                 StrOps::Occurrences oc = s.occurrences(match, m, a_cap, true, &nzf);
-                if (is_replacen) s.keep_first_occurrences(oc, replacen_n, m, a_cap, &nzf);
+                if (is_replacen_encn) s.keep_counted_occurrences(oc, count_g, m, a_cap, &nzf);
+                else if (is_replacen) s.keep_first_occurrences(oc, replacen_n, m, a_cap, &nzf);
                 s.emit(s.replace_general(a, oc, nullptr, 0, to.cap ? &to : nullptr, out_cap));
             }
         }

@@ -169,7 +169,8 @@ EXPORTS = [
     "fhe_glwe_sample_extract_host", "fhe_packing_unpack_noise", "fhe_engine_unpack_glwes", "fhe_engine_unpack_glwes_dev",
     "fhe_engine_unpack_info",
 ] + [f"fhe_str_{n}{s}" for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat")
-     for s in ("", "_clear")] + ["fhe_str_repeat_clear", "fhe_str_split", "fhe_str_replacen", "fhe_str_replacen_clear"]
+     for s in ("", "_clear")] + ["fhe_str_repeat_clear", "fhe_str_split", "fhe_str_replacen", "fhe_str_replacen_clear",
+                                   "fhe_str_repeat", "fhe_str_replacen_encn", "fhe_str_replacen_encn_clear", "fhe_str_splitn_encn"]
 
 
 def lib() -> C.CDLL:
@@ -302,6 +303,10 @@ def lib() -> C.CDLL:
     sig("fhe_str_replacen", vp, vp, u32, vp, u32, vp, u32, u32, u32, vp)
     sig("fhe_str_replacen_clear", vp, vp, u32, vp, u32, vp, u32, u32, u32, vp)
     sig("fhe_str_split", vp, C.c_char_p, vp, u32, vp, u32, vp, u32, u32, u32, vp, C.POINTER(u32))
+    sig("fhe_str_repeat", vp, vp, u32, vp, u32, vp)
+    sig("fhe_str_replacen_encn", vp, vp, u32, vp, u32, vp, u32, vp, u32, u32, vp)
+    sig("fhe_str_replacen_encn_clear", vp, vp, u32, vp, u32, vp, u32, vp, u32, u32, vp)
+    sig("fhe_str_splitn_encn", vp, C.c_char_p, vp, u32, vp, u32, vp, u32, vp, u32, u32, vp, C.POINTER(u32))
     for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat"):
         sig(f"fhe_str_{n}", vp, vp, u32, vp, u32, vp)
         sig(f"fhe_str_{n}_clear", vp, vp, u32, vp, u32, vp)
@@ -1236,6 +1241,45 @@ def decode_count(params: Params, msgs) -> int:
     return sum((int(d) % params.msg_mod) * params.msg_mod ** i for i, d in enumerate(np.asarray(msgs).reshape(-1)))
 
 
+def count_input_digits(params: Params, n_max: int) -> int:
+    """D: how many base-msg_mod digits an encrypted count with the public bound n_max travels in (the smallest D with
+    msg_mod^D > n_max)."""
+    if int(n_max) < 1:
+        raise FheError("an encrypted count needs a bound n_max >= 1")
+    d = 1
+    while params.msg_mod ** d <= int(n_max):
+        d += 1
+    return d
+
+
+def encode_count(params: Params, n: int, n_max: int) -> np.ndarray:
+    """The D clear digits of the count n (little-endian base msg_mod) to encrypt for an operation with the public bound
+    n_max.  n may exceed n_max as long as D digits hold it: the operation then acts as for n_max."""
+    d = count_input_digits(params, n_max)
+    if not 0 <= int(n) < params.msg_mod ** d:
+        raise FheError(f"count {n} does not fit the {d} base-{params.msg_mod} digits of n_max = {n_max}")
+    return np.array([(int(n) // params.msg_mod ** i) % params.msg_mod for i in range(d)], dtype=np.uint64)
+
+
+class EncryptedCount:
+    """An encrypted count for FheStringOps.repeat / replacen / splitn / rsplitn: `digits`, the ciphertexts of its
+    little-endian base-msg_mod digits -- fresh encryptions of encode_count(...), or what len, find / rfind (without the
+    found block) or a split's count returned, expanded (D, kN+1) or a PackedString -- and the public bound `n_max` that
+    travels with them.  n_max=None: the largest value the digits hold, msg_mod^D - 1 (needs `params`)."""
+    __slots__ = ("digits", "n_max")
+
+    def __init__(self, digits, n_max: int | None = None, params: Params | None = None):
+        self.digits = digits
+        if n_max is None:
+            if params is None:
+                raise FheError("EncryptedCount: give n_max, or params to take the largest value the digits hold")
+            d = digits.count if isinstance(digits, PackedString) else int(np.asarray(digits).shape[0])
+            n_max = params.msg_mod ** d - 1
+        if int(n_max) < 1:
+            raise FheError("an encrypted count needs a bound n_max >= 1")
+        self.n_max = int(n_max)
+
+
 class SplitResult:
     """What the operations that return several strings give back: `count` -- the digit ciphertexts of min(number of
     parts, max_parts + 1) (decode_count); for split_once / rsplit_once the one 0/1 block `found` -- and `parts`, a list
@@ -1347,6 +1391,17 @@ class FheStringOps:
         """Does this call take the device route?  (packed output asked for, or a packed operand given)"""
         return bool(packed) or any(isinstance(x, PackedString) for x in operands)
 
+    def _count_operand(self, count: "EncryptedCount"):
+        """The digit ciphertexts of an encrypted count, checked against its bound."""
+        digits = count.digits
+        if not isinstance(digits, PackedString):
+            digits = _u64(digits).reshape(-1, self.engine.params.big_size)
+        have = digits.count if isinstance(digits, PackedString) else digits.shape[0]
+        want = count_input_digits(self.engine.params, count.n_max)
+        if have != want:
+            raise FheError(f"an encrypted count with n_max = {count.n_max} travels in {want} digits, got {have}")
+        return digits
+
     def _binary(self, op, a, b, packed=False):
         a, a_cap = self._cap(a)
         if self._dev(packed, a, b):
@@ -1367,13 +1422,16 @@ class FheStringOps:
             _check(getattr(lib(), f"fhe_str_{op}")(self.engine.handle, _ptr(a), a_cap, _ptr(b), b_cap, _ptr(out)))
         return out
 
-    def op_many(self, op, rows, b=None, packed=False):
+    def op_many(self, op, rows, b=None, packed=False, count: "EncryptedCount | None" = None):
         """`op` on every row against ONE second operand in a single pass (fhe_str_op_many): rows (count, cap*blocks, kN+1),
         or a sequence of PackedString of one capacity (one per row); b: an encrypted (zero padded) string -- expanded or a
         PackedString --, clear bytes, or None for unary operations.  `op` may be any plan name, parameters included
         ("split:3" -- with clear bytes "split_clear:3" is meant, and may be written).  Returns (count, n_outputs, kN+1); with
-        packed=True one PackedString, output o of row r at block r * n_outputs + o."""
+        packed=True one PackedString, output o of row r at block r * n_outputs + o.
+        count: the encrypted count of an encrypted-count plan name ("repeat:3", "splitn_encn:3", "replacen_encn:2:1:8"),
+        shared by all rows like b; its n_max must be the one in the name."""
         big = self.engine.params.big_size
+        digits = self._count_operand(count) if count is not None else None
         clear = b if isinstance(b, (bytes, bytearray)) else None
         enc = None if (b is None or clear is not None) else self._cap(b)
         base, colon, op_params = op.partition(":")          # a parametrised plan name ("split:3", "split_clear:3") keeps its parameters last
@@ -1383,45 +1441,55 @@ class FheStringOps:
             sizes = {r.count if isinstance(r, PackedString) else r.shape[0] for r in rows}
             if len(sizes) != 1:
                 raise FheError("op_many expects rows of one capacity")
-            return self._packed_many(name, rows, sizes.pop() // self.bpc, enc, clear, packed)
+            return self._packed_many(name, rows, sizes.pop() // self.bpc, enc, clear, packed, digits)
         rows = _u64(rows)
         if rows.ndim != 3 or rows.shape[2] != big:
             raise FheError(f"op_many expects rows of shape (count, cap*blocks, {big})")
-        count, a_cap = rows.shape[0], rows.shape[1] // self.bpc
-        if self._dev(packed, enc[0] if enc else None):
+        n_rows, a_cap = rows.shape[0], rows.shape[1] // self.bpc
+        if self._dev(packed, enc[0] if enc else None, digits):
             # every row's outputs after one another: output o of row r is packed block r * n_outputs + o
-            return self._packed_many(name, list(rows), a_cap, enc, clear, packed)
+            return self._packed_many(name, list(rows), a_cap, enc, clear, packed, digits)
         buf = (C.c_uint8 * max(1, len(clear)))(*clear) if clear is not None else None
-        args = (self.engine.handle, name.encode(), _ptr(rows), a_cap, count, _ptr(enc[0]) if enc else None, enc[1] if enc else 0,
+        shared = enc[0] if enc else None                    # the pattern operand, then the count's digits
+        if digits is not None:
+            shared = np.concatenate([shared, digits]) if enc else digits
+        args = (self.engine.handle, name.encode(), _ptr(rows), a_cap, n_rows, _ptr(shared) if shared is not None else None, enc[1] if enc else 0,
                 buf, len(clear) if clear is not None else 0)
         n_out = C.c_uint32(0)
         _check(lib().fhe_str_op_many(*args, None, C.byref(n_out)))          # outputs per row (builds and caches the plan)
-        out = self._alloc((count, n_out.value, big))
+        out = self._alloc((n_rows, n_out.value, big))
         _check(lib().fhe_str_op_many(*args, _ptr(out), C.byref(n_out)))
         return out
 
-    def _packed_many(self, name, rows, a_cap, enc, clear, packed=True):
-        """The device route of op_many (see _packed): rows is a list of expanded (cap*blocks, kN+1) arrays or PackedStrings."""
+    def _packed_many(self, name, rows, a_cap, enc, clear, packed=True, digits=None):
+        """The device route of op_many (see _packed): rows is a list of expanded (cap*blocks, kN+1) arrays or PackedStrings;
+        the shared operands (enc: the pattern, digits: an encrypted count) are placed once and copied to every row."""
         import torch
         big = self.engine.params.big_size
         plan = self._plan(name, a_cap, enc[1] if enc else 0, clear)
         info = plan.info()
         count, n_a = len(rows), a_cap * self.bpc
-        n_b = (enc[0].count if isinstance(enc[0], PackedString) else enc[0].shape[0]) if enc else 0
-        if n_a + n_b != info["n_inputs"]:
-            raise FheError(f"{name}: the plan takes {info['n_inputs']} input blocks per row, got {n_a + n_b}")
+        shared = ([enc[0]] if enc else []) + ([digits] if digits is not None else [])
+        sizes = [x.count if isinstance(x, PackedString) else x.shape[0] for x in shared]
+        if n_a + sum(sizes) != info["n_inputs"]:
+            raise FheError(f"{name}: the plan takes {info['n_inputs']} input blocks per row, got {n_a + sum(sizes)}")
         dev = f"cuda:{self.engine.device}"
         d_in = torch.empty((count, info["n_inputs"], big), dtype=torch.int64, device=dev)
         d_out = torch.empty((count, info["n_outputs"], big), dtype=torch.int64, device=dev)
         placed = [(r * info["n_inputs"], x) for r, x in enumerate(rows)]
-        if enc and isinstance(enc[0], PackedString):        # unpacked once, into row 0's slot, then copied on the device
-            placed.append((n_a, enc[0]))
-        elif enc:
-            d_in[:, n_a:].copy_(torch.from_numpy(enc[0].view(np.int64)).to(dev))
+        at, unpacked = n_a, []
+        for x, size in zip(shared, sizes):
+            if isinstance(x, PackedString):                 # unpacked once, into row 0's slot, then copied on the device
+                placed.append((at, x))
+                unpacked.append((at, size))
+            else:
+                d_in[:, at:at + size].copy_(torch.from_numpy(x.view(np.int64)).to(dev))
+            at += size
         keep = self._stage(d_in, placed)
-        if enc and isinstance(enc[0], PackedString) and count > 1:
+        if unpacked and count > 1:
             self.engine.synchronize()
-            d_in[1:, n_a:].copy_(d_in[0, n_a:])
+            for lo, size in unpacked:
+                d_in[1:, lo:lo + size].copy_(d_in[0, lo:lo + size])
             torch.cuda.synchronize()
         plan.run_batch_dev(d_in.data_ptr(), d_out.data_ptr(), count)
         out = self._finish(d_out, count * info["n_outputs"], packed)
@@ -1553,14 +1621,35 @@ class FheStringOps:
                                                  _ptr(to) if t_cap else None, t_cap, out_cap, _ptr(out)))
         return out
 
-    def replacen(self, a, frm, to, n: int, out_cap: int | None = None, packed=False):
+    def replacen(self, a, frm, to, n: "int | EncryptedCount", out_cap: int | None = None, packed=False):
         """Replace the first n leftmost non-overlapping occurrences of frm by to (bytes.replace(frm, to, n), Rust's
         str::replacen).  frm / to: both clear bytes, or both encrypted strings (may be zero padded); any lengths; the
-        result has out_cap characters (default: the capacity of a) and is cut there.  A clear empty frm is refused."""
+        result has out_cap characters (default: the capacity of a) and is cut there.  A clear empty frm is refused.
+        n: a clear int, or an EncryptedCount -- then min(n, n_max) occurrences are replaced, n = 0 returns a."""
         a, a_cap = self._cap(a)
         big = self.engine.params.big_size
         out_cap = a_cap if out_cap is None else out_cap
         clear = isinstance(frm, (bytes, bytearray))
+        if isinstance(n, EncryptedCount):
+            digits, n_max = self._count_operand(n), n.n_max
+            if self._dev(packed, a, frm, to, digits):
+                if clear:
+                    return self._packed(f"replacen_encn_clear:{n_max}:{len(frm)}:{out_cap}", a_cap, 0, bytes(frm) + bytes(to), [a, digits], packed)
+                frm, f_cap = self._cap(frm)
+                to, t_cap = self._cap(to)
+                return self._packed(f"replacen_encn:{n_max}:{f_cap}:{out_cap}", a_cap, f_cap + t_cap, None, [a, frm, to, digits], packed)
+            out = self._alloc((out_cap * self.bpc, big))
+            if clear:
+                fb = (C.c_uint8 * max(1, len(frm)))(*frm)
+                tb = (C.c_uint8 * max(1, len(to)))(*to)
+                _check(lib().fhe_str_replacen_encn_clear(self.engine.handle, _ptr(a), a_cap, fb, len(frm), tb, len(to), _ptr(digits),
+                                                         n_max, out_cap, _ptr(out)))
+            else:
+                frm, f_cap = self._cap(frm)
+                to, t_cap = self._cap(to)
+                _check(lib().fhe_str_replacen_encn(self.engine.handle, _ptr(a), a_cap, _ptr(frm), f_cap, _ptr(to) if t_cap else None,
+                                                   t_cap, _ptr(digits), n_max, out_cap, _ptr(out)))
+            return out
         if self._dev(packed, a, frm, to):
             if clear:
                 return self._packed(f"replacen_clear:{n}:{len(frm)}:{out_cap}", a_cap, 0, bytes(frm) + bytes(to), [a], packed)
@@ -1587,7 +1676,13 @@ class FheStringOps:
 
     def _split(self, op, a, pat, max_parts, part_cap=None, packed=False):
         """The split family (include/fhestr.h, fhe_str_split).  pat: clear bytes, an expanded encrypted (zero padded)
-        pattern, a PackedString, or None (split_ascii_whitespace).  Returns a SplitResult."""
+        pattern, a PackedString, or None (split_ascii_whitespace).  Returns a SplitResult.  max_parts may be an
+        EncryptedCount (splitn / rsplitn only): then its n_max is the number of parts returned."""
+        digits = None
+        if isinstance(max_parts, EncryptedCount):
+            if op not in ("splitn", "rsplitn"):
+                raise FheError(f"{op}: only splitn and rsplitn take an encrypted count")
+            digits, max_parts = self._count_operand(max_parts), max_parts.n_max
         a, a_cap = self._cap(a)
         big = self.engine.params.big_size
         once = op in ("split_once", "rsplit_once")
@@ -1599,9 +1694,11 @@ class FheStringOps:
         n_part = cap * self.bpc
         clear = bytes(pat) if isinstance(pat, (bytes, bytearray)) else None
         enc = None if (pat is None or clear is not None) else self._cap(pat)
-        if self._dev(packed, a, pat):
-            name = op + ("_clear" if clear is not None else "") + ("" if once else f":{P}") + (f":{cap}" if part_cap is not None else "")
-            d_out, n_out, keep = self._run_device(name, a_cap, enc[1] if enc else 0, clear, [a] + ([enc[0]] if enc else []))
+        if self._dev(packed, a, pat, digits):
+            name = (op + ("_encn" if digits is not None else "") + ("_clear" if clear is not None else "") + ("" if once else f":{P}") +
+                    (f":{cap}" if part_cap is not None else ""))
+            d_out, n_out, keep = self._run_device(name, a_cap, enc[1] if enc else 0, clear,
+                                                  [a] + ([enc[0]] if enc else []) + ([digits] if digits is not None else []))
             if n_out != n_head + P * n_part:
                 raise FheError(f"{name}: the plan has {n_out} outputs, expected {n_head + P * n_part}")
             if not packed:
@@ -1616,13 +1713,15 @@ class FheStringOps:
         else:
             buf = (C.c_uint8 * max(1, len(clear)))(*clear) if clear is not None else None
             args = (self.engine.handle, op.encode(), _ptr(a), a_cap, _ptr(enc[0]) if enc else None, enc[1] if enc else 0,
-                    buf, len(clear) if clear is not None else 0, P, 0 if part_cap is None else cap)
+                    buf, len(clear) if clear is not None else 0) + ((_ptr(digits),) if digits is not None else ()) + (
+                    P, 0 if part_cap is None else cap)
+            entry = lib().fhe_str_split if digits is None else lib().fhe_str_splitn_encn
             n_out = C.c_uint32(0)
-            _check(lib().fhe_str_split(*args, None, C.byref(n_out)))        # builds and caches the plan
+            _check(entry(*args, None, C.byref(n_out)))                      # builds and caches the plan
             if n_out.value != n_head + P * n_part:
                 raise FheError(f"{op}: the plan has {n_out.value} outputs, expected {n_head + P * n_part}")
             out = self._alloc((n_out.value, big))
-            _check(lib().fhe_str_split(*args, _ptr(out), C.byref(n_out)))
+            _check(entry(*args, _ptr(out), C.byref(n_out)))
         head = out[0] if once else out[:n_head]
         return SplitResult(head, [out[n_head + p * n_part: n_head + (p + 1) * n_part] for p in range(P)])
 
@@ -1655,8 +1754,17 @@ class FheStringOps:
             _check(lib().fhe_str_concat(self.engine.handle, _ptr(a), a_cap, _ptr(b), b_cap, _ptr(out)))
         return out
 
-    def repeat(self, a, count: int, packed=False):
+    def repeat(self, a, count: "int | EncryptedCount", packed=False):
+        """a repeated count times.  count: a clear int (1..255), or an EncryptedCount (n_max 1..255): the result then has
+        n_max * a_cap characters and holds min(n, n_max) copies -- none for n = 0."""
         a, a_cap = self._cap(a)
+        if isinstance(count, EncryptedCount):
+            digits = self._count_operand(count)
+            if self._dev(packed, a, digits):
+                return self._packed(f"repeat:{count.n_max}", a_cap, 0, None, [a, digits], packed)
+            out = self._alloc((count.n_max * a_cap * self.bpc, self.engine.params.big_size))
+            _check(lib().fhe_str_repeat(self.engine.handle, _ptr(a), a_cap, _ptr(digits), count.n_max, _ptr(out)))
+            return out
         if self._dev(packed, a):
             return self._packed("repeat_clear", a_cap, 0, bytes([count]), [a], packed)
         out = self._alloc((count * a_cap * self.bpc, self.engine.params.big_size))

@@ -311,7 +311,8 @@ int fhe_int_plan_create_offline(const fhe_params_t *params, const char *op, uint
  * after the text and nowhere else (the searches with an encrypted pattern rely on it: csrc/fhe_string.cpp, group_match).
  * op in {"eq","ne","starts_with","ends_with","contains","find"} (+ "_clear" suffix for a clear
  * pattern) or {"to_upper","to_lower","trim_start","trim_end","strip","replace","replace_clear","concat",
- * "concat_clear","repeat_clear"}, or a name of the split family / replacen (see fhe_str_split below).  Outputs: one 0/1 block; find: found block then
+ * "concat_clear","repeat_clear"}, or a name of the split family / replacen (see fhe_str_split below) or of an
+ * encrypted-count operation (see fhe_str_repeat below).  Outputs: one 0/1 block; find: found block then
  * ceil(log_msg_mod(cap+1)) index digits (little endian); case ops: the whole string. */
 int fhe_str_plan_create(fhe_engine *eng, const char *op, uint32_t a_cap, uint32_t b_cap,
                         const uint8_t *clear, uint32_t clear_len, uint32_t world, fhe_plan **out);
@@ -405,11 +406,46 @@ int fhe_str_replacen_clear(fhe_engine *eng, const uint64_t *a, uint32_t a_cap, c
 int fhe_str_split(fhe_engine *eng, const char *op, const uint64_t *a, uint32_t a_cap, const uint64_t *pat, uint32_t pat_cap,
                   const uint8_t *clear, uint32_t clear_len, uint32_t max_parts, uint32_t part_cap, uint64_t *out,
                   uint32_t *n_outputs);
+/* ---- encrypted counts ----
+ * repeat, replacen, splitn and rsplitn also take their count n ENCRYPTED.  n arrives as D big-key LWE blocks, its
+ * little-endian base-msg_mod digits, each in [0, msg_mod) with nominal noise: fresh encryptions, or the digit outputs of
+ * len, find / rfind or a split count.  The caller states a public bound n_max >= 1; D is the smallest number with
+ * msg_mod^D > n_max (feeding the D digits of another operation: n_max = msg_mod^D - 1).  A value above the bound acts as
+ * the bound: below, n* = min(n, n_max).  In a plan the digits are the LAST inputs: a, the encrypted pattern operand(s) if
+ * any, then the D digits.  Everything not said here is as for the clear-count operation above (an empty encrypted
+ * pattern selects / separates nothing, results are cut at out_cap / part_cap, the whitespace set).
+ *   fhe_str_repeat              a * n*, out = max_count * a_cap * blocks LWEs (n_max = max_count, 1..255); n = 0 gives the
+ *                               empty string.  Plan op name "repeat:<n_max>" (a bare "repeat" is refused).
+ *   fhe_str_replacen_encn       a.replace(from, to, n*); n = 0 returns a fitted to out_cap.  Plan op names
+ *   fhe_str_replacen_encn_clear "replacen_encn:<n_max>:<from_cap>:<out_cap>" (b = from || to) and
+ *                               "replacen_encn_clear:<n_max>:<from_len>:<out_cap>" (clear = from || to; an empty clear
+ *                               `from` is refused).
+ *   fhe_str_splitn_encn         op = "splitn": parts = [] if n* == 0 else a.split(sep, n* - 1); op = "rsplitn":
+ *                               parts = [] if n* == 0 else a.rsplit(sep, n* - 1)[::-1].  n_max = max_parts = P.  The
+ *                               outputs have exactly the layout of "splitn:<P>" (fhe_str_split): count = len(parts)
+ *                               (<= P) in as many digits as the value P + 1 needs, then P parts of part_cap characters
+ *                               (0 = a_cap), missing ones all zero.  Pattern arguments, out == NULL and *n_outputs as for
+ *                               fhe_str_split.  Plan op names "splitn_encn[_clear]:<P>[:<part_cap>]" and
+ *                               "rsplitn_encn[_clear]:<P>[:<part_cap>]"; they need msg_mod * carry_mod >= 16. */
+int fhe_str_repeat(fhe_engine *eng, const uint64_t *a, uint32_t a_cap, const uint64_t *n_digits, uint32_t max_count,
+                   uint64_t *out);
+int fhe_str_replacen_encn(fhe_engine *eng, const uint64_t *a, uint32_t a_cap, const uint64_t *from, uint32_t from_cap,
+                          const uint64_t *to, uint32_t to_cap, const uint64_t *n_digits, uint32_t n_max, uint32_t out_cap,
+                          uint64_t *out);
+int fhe_str_replacen_encn_clear(fhe_engine *eng, const uint64_t *a, uint32_t a_cap, const uint8_t *from, uint32_t from_len,
+                                const uint8_t *to, uint32_t to_len, const uint64_t *n_digits, uint32_t n_max,
+                                uint32_t out_cap, uint64_t *out);
+int fhe_str_splitn_encn(fhe_engine *eng, const char *op, const uint64_t *a, uint32_t a_cap, const uint64_t *pat,
+                        uint32_t pat_cap, const uint8_t *clear, uint32_t clear_len, const uint64_t *n_digits,
+                        uint32_t max_parts, uint32_t part_cap, uint64_t *out, uint32_t *n_outputs);
 /* Many strings against ONE second operand in one pass (fhe_plan_run_batch on the operation's cached plan): `op` is an
  * operation name of fhe_str_plan_create ("eq", "ne", "contains", "find", "starts_with", "to_lower", ...; "<op>_clear" with
  * a clear pattern), rows = [count][a_cap * blocks] ciphertexts, b = the shared encrypted operand ([b_cap * blocks]
  * ciphertexts, b_cap = 0 and NULL for unary operations and clear patterns), out = [count][n_outputs] ciphertexts,
- * *n_outputs (optional) = outputs per row; with out == NULL the call only builds the plan and returns that number.  One pattern against 32 rows: FheString::eq 12.8 ms alone, under 5 ms per row. */
+ * *n_outputs (optional) = outputs per row; with out == NULL the call only builds the plan and returns that number.
+ * Plan names with an encrypted count ("repeat:<n_max>", "replacen_encn:...", "splitn_encn:...") share the count as well: b =
+ * the pattern operand ([b_cap * blocks] ciphertexts) followed by the D digits, or the digits alone (b_cap = 0) for clear
+ * patterns and repeat.  One pattern against 32 rows: FheString::eq 12.8 ms alone, under 5 ms per row. */
 int fhe_str_op_many(fhe_engine *eng, const char *op, const uint64_t *rows, uint32_t a_cap, uint32_t count, const uint64_t *b,
                     uint32_t b_cap, const uint8_t *clear, uint32_t clear_len, uint64_t *out, uint32_t *n_outputs);
 /* len: ceil(log_msg_mod(cap+1)) little-endian digits; is_empty: one 0/1 block */

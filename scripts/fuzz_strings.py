@@ -10,6 +10,7 @@ sys.path.insert(0, "tests")
 import oracle as O
 import fhestr
 from split_ref import ONCE, SPLIT_OPS, decode_split, split_ref        # the clear-text definitions of the split family
+from count_ref import repeat_ref, replacen_ref, splitn_ref            # ... and of the operations with an encrypted count
 
 N_CASES = int(sys.argv[1]) if len(sys.argv) > 1 else 150
 SEED = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -61,7 +62,8 @@ for case in range(N_CASES):
     ea, eb = enc(a, cap), enc(b, b_cap)
     op = str(rng.choice(["eq", "ne", "lt", "le", "gt", "ge", "eqic", "starts", "ends", "contains", "find", "rfind",
                          "upper", "lower", "trim_start", "trim_end", "strip", "replace", "len", "is_empty",
-                         "strip_prefix", "strip_suffix", "concat", "repeat", "replace_general", "split", "split_ws", "replacen"]))
+                         "strip_prefix", "strip_suffix", "concat", "repeat", "replace_general", "split", "split_ws", "replacen",
+                         "repeat_encn", "replacen_encn", "splitn_encn", "rsplitn_encn"]))
     clear = bool(rng.random() < 0.5)
     rhs = b if clear else eb
     ctx = (op, a, b, cap, b_cap, clear)
@@ -161,5 +163,28 @@ for case in range(N_CASES):
         else:
             got = dec_str(ops.replacen(ea, eb, enc(to, max(1, len(to) + int(rng.integers(0, 2)))), n, out_cap=out_cap))
         check(op, got, want, ctx + (to, n, out_cap))
+    elif op.endswith("_encn"):
+        # an encrypted count: n in 0 .. n_max + 1 (what the digits of n_max cannot hold is left out)
+        n_max = int(rng.integers(1, 6))
+        n = min(int(rng.integers(0, n_max + 2)), p.msg_mod ** fhestr.count_input_digits(P, n_max) - 1)
+        count = fhestr.EncryptedCount(ck.encrypt_many(fhestr.encode_count(P, n, n_max)), n_max)
+        if op == "repeat_encn":
+            check(op, dec_str(ops.repeat(ea, count)), repeat_ref(a, n, n_max), ctx + (n, n_max))
+            continue
+        if clear and len(b) == 0:
+            continue        # a clear empty pattern is refused; an encrypted one selects / separates nothing
+        if op == "replacen_encn":
+            to = bytes(ALPHA[int(i)] for i in rng.integers(0, len(ALPHA), size=int(rng.integers(0, 4))))
+            want = replacen_ref(a, b, to, n, n_max)
+            out_cap = max(1, len(want) + int(rng.integers(0, 2)))
+            e_to = to if clear else enc(to, max(1, len(to) + int(rng.integers(0, 2))))
+            check(op, dec_str(ops.replacen(ea, rhs, e_to, count, out_cap=out_cap)), want, ctx + (to, n, n_max, out_cap))
+        else:
+            name = op[:-len("_encn")]
+            part_cap = int(rng.integers(1, cap + 1)) if rng.random() < 0.4 else None
+            res = getattr(ops, name)(ea, rhs, count, part_cap)
+            flat = np.concatenate([np.asarray(res.count).reshape(-1, p.big_size)] + list(res.parts))
+            check(op, decode_split("splitn", dec(flat), p.msg_mod, n_max, part_cap or cap),
+                  splitn_ref(name, a, b, n, n_max, part_cap=part_cap), ctx + (n, n_max, part_cap))
 print(f"fuzz: {N_CASES} cases, {fails} mismatches")
 sys.exit(1 if fails else 0)
