@@ -393,6 +393,7 @@ int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t 
 int build_integer_op(Circuit& c, const std::string& op, uint32_t n_blocks, uint64_t scalar);
 }
 #include "noise_model.h"
+#include "regex.h"
 
 struct fhe_plan {
     fhe::Circuit* c;
@@ -875,6 +876,23 @@ STR_BINARY(le)
 STR_BINARY(gt)
 STR_BINARY(ge)
 STR_BINARY(concat)
+
+/* a clear regular expression (the pattern text /.../ of regex.h): out = one 0/1 block */
+int fhe_str_matches_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint8_t* regex, uint32_t regex_len, uint64_t* out) {
+    if (regex_len && !regex) return fail("null pointer: regex");
+    return str_op(eng, "matches_clear", a, a_cap, nullptr, 0, regex, regex_len, out);
+}
+int fhe_regex_check(const uint8_t* regex, uint32_t len, uint32_t* n_positions, uint32_t* max_len) {
+    API_BEGIN
+    if (len && !regex) return fail("null pointer: regex");
+    fhe::regex::Automaton g;
+    std::string why;
+    if (fhe::regex::compile(regex, len, g, why)) return fail("regex: " + why);
+    if (n_positions) *n_positions = g.positions();
+    if (max_len) *max_len = g.max_len;
+    return 0;
+    API_END
+}
 
 /* encrypted (zero padded) pattern: out = 1 + a_cap * blocks LWEs, stripped bit first */
 int fhe_str_strip_prefix(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint64_t* pat, uint32_t pat_cap, uint64_t* out) {

@@ -170,7 +170,8 @@ EXPORTS = [
     "fhe_engine_unpack_info",
 ] + [f"fhe_str_{n}{s}" for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat")
      for s in ("", "_clear")] + ["fhe_str_repeat_clear", "fhe_str_split", "fhe_str_replacen", "fhe_str_replacen_clear",
-                                   "fhe_str_repeat", "fhe_str_replacen_encn", "fhe_str_replacen_encn_clear", "fhe_str_splitn_encn"]
+                                   "fhe_str_repeat", "fhe_str_replacen_encn", "fhe_str_replacen_encn_clear", "fhe_str_splitn_encn",
+                                   "fhe_str_matches_clear", "fhe_regex_check"]
 
 
 def lib() -> C.CDLL:
@@ -310,6 +311,8 @@ def lib() -> C.CDLL:
     for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat"):
         sig(f"fhe_str_{n}", vp, vp, u32, vp, u32, vp)
         sig(f"fhe_str_{n}_clear", vp, vp, u32, vp, u32, vp)
+    sig("fhe_str_matches_clear", vp, vp, u32, vp, u32, vp)
+    sig("fhe_regex_check", vp, u32, C.POINTER(u32), C.POINTER(u32))
     for n in ("trim_start", "trim_end", "strip"):
         sig(f"fhe_str_{n}", vp, vp, u32, vp)
     sig("fhe_str_replace", vp, vp, u32, vp, u32, vp)
@@ -422,6 +425,17 @@ def noise_model(params: "Params") -> dict:
     a = (C.c_double * 6)()
     _check(lib().fhe_noise_model(C.byref(params.c()), a))
     return dict(zip(("v_pbs", "v_ks", "v_ms", "half_box", "budget", "log2_pfail_at_budget"), map(float, a)))
+
+
+def regex_check(regex) -> dict:
+    """Parse a pattern of FheStringOps.matches without building anything: {"positions": character positions of the
+    expanded pattern, "max_len": the longest match in characters, None when unbounded}.  Raises FheError with the reason
+    (a malformed pattern: with the byte offset)."""
+    regex = regex.encode() if isinstance(regex, str) else bytes(regex)
+    buf = (C.c_uint8 * max(1, len(regex)))(*regex)
+    m, longest = C.c_uint32(0), C.c_uint32(0)
+    _check(lib().fhe_regex_check(buf, len(regex), C.byref(m), C.byref(longest)))
+    return {"positions": m.value, "max_len": None if longest.value == 0xFFFFFFFF else longest.value}
 
 
 def kernel_revision() -> str:
@@ -1501,6 +1515,7 @@ class FheStringOps:
     def starts_with_many(self, rows, b): return self.op_many("starts_with", rows, b)[:, 0]
     def ends_with_many(self, rows, b): return self.op_many("ends_with", rows, b)[:, 0]
     def find_many(self, rows, b): return self.op_many("find", rows, b)
+    def matches_many(self, rows, regex): return self.op_many("matches", rows, self._regex(regex))[:, 0]
 
     def eq(self, a, b, packed=False): return self._binary("eq", a, b, packed)[0]
     def ne(self, a, b, packed=False): return self._binary("ne", a, b, packed)[0]
@@ -1514,6 +1529,15 @@ class FheStringOps:
     def le(self, a, b, packed=False): return self._binary("le", a, b, packed)[0]
     def gt(self, a, b, packed=False): return self._binary("gt", a, b, packed)[0]
     def ge(self, a, b, packed=False): return self._binary("ge", a, b, packed)[0]
+
+    @staticmethod
+    def _regex(regex):
+        return regex.encode() if isinstance(regex, str) else bytes(regex)
+
+    def matches(self, a, regex, packed=False):
+        """One 0/1 block: does the clear regular expression match somewhere in the unpadded string?  regex: the pattern
+        text of the reference's regex engine, "/^[0-9]+$/", "/ab|cd/i" (grammar and deviations: include/fhestr.h)."""
+        return self._binary("matches", a, self._regex(regex), packed)[0]
 
     def _n_digits(self, cap):
         n = 0

@@ -311,7 +311,7 @@ int fhe_int_plan_create_offline(const fhe_params_t *params, const char *op, uint
  * after the text and nowhere else (the searches with an encrypted pattern rely on it: csrc/fhe_string.cpp, group_match).
  * op in {"eq","ne","starts_with","ends_with","contains","find"} (+ "_clear" suffix for a clear
  * pattern) or {"to_upper","to_lower","trim_start","trim_end","strip","replace","replace_clear","concat",
- * "concat_clear","repeat_clear"}, or a name of the split family / replacen (see fhe_str_split below) or of an
+ * "concat_clear","repeat_clear","matches_clear"}, or a name of the split family / replacen (see fhe_str_split below) or of an
  * encrypted-count operation (see fhe_str_repeat below).  Outputs: one 0/1 block; find: found block then
  * ceil(log_msg_mod(cap+1)) index digits (little endian); case ops: the whole string. */
 int fhe_str_plan_create(fhe_engine *eng, const char *op, uint32_t a_cap, uint32_t b_cap,
@@ -339,6 +339,33 @@ FHE_STR_BINARY_DECL(ge)
 /* concat: a followed by b (a's padding removed); out = (a_cap + b_cap) * blocks LWEs, resp. a_cap + pat_len
  * for the clear form.  Plan op names "concat" / "concat_clear". */
 FHE_STR_BINARY_DECL(concat)
+/* matches: does the clear regular expression `regex` match somewhere in the unpadded string?  out = one 0/1 block.
+ * Plan op name "matches_clear" with the pattern text as the clear operand; fhe_str_op_many takes it too.
+ * The pattern text is that of the reference's regex engine (tfhe/examples/regex_engine, `has_match`):
+ *   pattern = '/' '^'? regex '$'? '/' 'i'?     '^' and '$' exist only here, outermost, and bind looser than '|':
+ *                                              /^ab|cd$/ is ^(ab|cd)$
+ *   regex   = term ('|' regex)?                term = factor+
+ *   factor  = atom, then at most one of ? * + {n} {n,} {,m} {n,m}
+ *   atom    = .  |  \x (the byte x itself)  |  an alphanumeric  |  one of & ; : , ` ~ - _ ! @ # % ' "
+ *           |  ( regex )  |  [ class ]         class = ^ class | x-y (alphanumeric ends) | alphanumerics
+ * ASCII only; /i ignores ASCII case.  Four deviations from the reference's executor:
+ *   1. repeat counts mean what they say (the reference's /^a{,2}$/ accepts "aaa");
+ *   2. /i folds class members and range ends as well as literals;
+ *   3. //, an empty alternative or group, {} and {n,m} with n > m are refused with a message (the reference panics or
+ *      misparses);
+ *   4. a character never matches padding: . and [^...] match real characters only, and $ holds at the hidden end (the
+ *      position whose next character is zero, or a_cap).
+ * The answer equals Python's re.search(b"^?(?:body)\Z?", s, re.DOTALL [| re.I]) on the unpadded bytes, \x read as
+ * re.escape(x).  A plain literal builds the existing plan: /abc/ contains_clear, /^abc/ starts_with_clear, /abc$/
+ * ends_with_clear, /^abc$/ eq_clear.  Refused when the plan is built, the reason in fhe_last_error: a malformed pattern
+ * (with the byte offset), a non-ASCII byte, more than 256 automaton positions after the repeat counts are expanded,
+ * a_cap == 0.  It needs msg_mod * carry_mod >= 16. */
+int fhe_str_matches_clear(fhe_engine *eng, const uint64_t *a, uint32_t a_cap, const uint8_t *regex, uint32_t regex_len,
+                          uint64_t *out);
+/* Parses a pattern only (no engine): 0, or nonzero with the reason.  *n_positions: character positions of the expanded
+ * pattern (the automaton's states); *max_len: the longest match in characters, 0xFFFFFFFF when unbounded.  Both
+ * out-pointers are optional. */
+int fhe_regex_check(const uint8_t *regex, uint32_t len, uint32_t *n_positions, uint32_t *max_len);
 /* repeat: a repeated `count` (clear, 1..255) times; out = count * a_cap * blocks LWEs.  Plan op name
  * "repeat_clear" with the count as the one clear byte. */
 int fhe_str_repeat_clear(fhe_engine *eng, const uint64_t *a, uint32_t a_cap, uint32_t count, uint64_t *out);
