@@ -66,6 +66,21 @@ public:
                c.node(b[0]).noise + (double)M * M * c.node(b[1]).noise <= budget();
     }
     uint32_t whole_char(const std::vector<uint32_t>& b) { return c.lin({{b[1], (int32_t)M}, {b[0], 1}}); }
+    // The noise of sum_t coeff_t * node_t as Circuit::lin will build it: sources that several terms share add up by
+    // coefficient before they are squared (a LIN node is flattened onto inputs and lookup outputs).  It passes the terms'
+    // own noise added up where the terms are sums over the same lookup outputs: the bits `nz - cover` of a selection taken
+    // from the right with a clear pattern of 6 characters and more share up to 8 of them.
+    double sum_noise(const std::vector<Term>& terms) const {
+        std::map<uint32_t, int64_t> by_source;
+        for (const Term& t : terms) {
+            const Node& n = c.node(t.node);
+            if (n.kind == Node::LIN) for (const Term& u : n.terms) by_source[u.node] += (int64_t)t.coeff * u.coeff;
+            else by_source[t.node] += t.coeff;
+        }
+        double nu = 0;
+        for (const auto& kv : by_source) nu += (double)kv.second * kv.second * c.node(kv.first).noise;
+        return nu;
+    }
     std::vector<std::vector<Term>> term_groups(const std::vector<Term>& terms, size_t max_terms) const {
         std::vector<std::vector<Term>> out;
         double nu = 0;
@@ -549,11 +564,23 @@ public:
 
     // ---- find: (found, index digits) of the first match ----
     // prefix_any[o] = OR_{o' <= o} bits[o'] through a blocked scan (fan-in T-1 per PBS)
-    std::vector<uint32_t> prefix_or(const std::vector<uint32_t>& bits) {
+    std::vector<uint32_t> prefix_or(const std::vector<uint32_t>& bits_in) {
         const uint32_t F = full_box_reduce ? T : T - 1;        // a run of T bits: Circuit::pbs_full_box
         const uint32_t nz = c.lut_fn([](uint64_t x) { return (uint64_t)(x != 0); });
-        const size_t n = bits.size();
-        if (n <= 1) return bits;
+        const size_t n = bits_in.size();
+        if (n <= 1) return bits_in;
+        // a block whose bits are sums over shared lookup outputs may pass the noise budget as a run (sum_noise: rsplit,
+        // rsplitn and rsplit_once with a clear pattern of 6 characters and more reached 106 .. 122 nominal variances and
+        // were refused): its bits get a lookup of their own first.  A plan whose runs fit is built exactly as before.
+        std::vector<uint32_t> bits(bits_in);
+        for (size_t b = 0; b < n; b += F) {
+            std::vector<Term> block;
+            for (size_t j = b; j < std::min(n, b + F); j++) block.push_back({bits[j], 1});
+            if (sum_noise(block) <= budget()) continue;
+            const uint32_t is_one = c.lut_fn([](uint64_t x) { return (uint64_t)(x == 1); });
+            for (size_t j = b; j < std::min(n, b + F); j++)
+                if (c.node(bits[j]).noise > 1.0) bits[j] = c.pbs(bits[j], is_one);
+        }
         std::vector<uint32_t> within(n), block_tot;
         for (size_t b = 0; b < n; b += F) {
             std::vector<Term> run;

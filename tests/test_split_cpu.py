@@ -283,3 +283,33 @@ def test_every_operation_builds_on_other_parameter_sets(params):
                                ("replacen:2:4:32", 8, None)):
         noise = _plan(name, 32, b_cap, clear, params=params).noise_info()
         assert noise["max_pbs_input_noise"] <= noise["budget"], name
+
+
+LONG_SEP_CAP = 15
+
+
+@pytest.mark.parametrize("op", ["rsplit", "rsplitn", "rsplit_once"])
+def test_right_to_left_split_by_a_long_clear_separator(toy_k1, op):
+    """Regression, found by tests/test_plan_sweep_cpu.py: at 15 characters and more a clear separator of 6 characters and
+    more was refused for rsplit, rsplitn and rsplit_once (106 .. 122 nominal variances against TOY_K1's 99.6; from 7
+    characters on against PARAM_MESSAGE_2_CARRY_2's 138.2 as well).  A selection taken from the right rebuilds cover[i] as a
+    sum of up to 8 selection bits, the part masks `nz - cover` went unrefreshed into prefix_or, and a run of 16 of them
+    shares those bits: the run's noise as built is far above the 16 x 9 its terms add up to one by one.  prefix_or now gives
+    the bits of such a run a lookup of their own first.  The separators have no border and a border; one occurrence, two,
+    and none."""
+    import fhestr
+    from clear_plan import ClearBackend, run_clear
+    for sep in (b"ab, xy", b"aab,aa", b"ab, xyz"):
+        name = _name(op, True, 2)
+        plan = _plan(name, LONG_SEP_CAP, 0, sep)
+        assert plan.noise_info()["max_pbs_input_noise"] <= plan.noise_info()["budget"]
+        for s in (sep, b"x" + sep + b"yz" + sep[:5], sep + sep + b"q", b"ab, xab, x", b""):
+            s = s[:LONG_SEP_CAP]
+            out = toy_k1.ck.decrypt_many(run_with_oracle(plan, _enc(toy_k1, s, LONG_SEP_CAP), toy_k1.sk))
+            assert decode_split(op, out, M, 2, LONG_SEP_CAP) == split_ref(op, s, sep, 2), (op, s, sep)
+        p22 = _plan(name, LONG_SEP_CAP, 0, sep, params=O.PARAM_MESSAGE_2_CARRY_2_KS_PBS)
+        assert p22.noise_info()["max_pbs_input_noise"] <= p22.noise_info()["budget"]
+        backend = ClearBackend(p22, _params(O.PARAM_MESSAGE_2_CARRY_2_KS_PBS))
+        s = b"x" + sep + b"yz" + sep[:5]
+        out = run_clear(backend, fhestr.string_to_blocks(_params(), s, LONG_SEP_CAP))
+        assert decode_split(op, out, M, 2, LONG_SEP_CAP) == split_ref(op, s, sep, 2) and backend.off_centre == 0
