@@ -394,6 +394,7 @@ int build_integer_op(Circuit& c, const std::string& op, uint32_t n_blocks, uint6
 }
 #include "noise_model.h"
 #include "regex.h"
+#include "str_op_name.h"
 #include "str_program.h"
 
 struct fhe_plan {
@@ -801,29 +802,47 @@ static int cached_str_plan(fhe_engine* eng, const std::string& op, uint32_t a_ca
     return 0;
 }
 
-static uint32_t blocks_per_char(const fhe_plan* plan) {
-    uint32_t bits = 0;
-    while ((1u << bits) < plan->c->msg_modulus()) bits++;
-    return bits ? 8 / bits : 8;
-}
-
-// one-call FheString operations (host buffers): up to three encrypted operands, each `caps[i]` characters
-static int str_op_parts(fhe_engine* eng, const std::string& op, const uint64_t* const* operands, const uint32_t* caps,
-                        uint32_t n_operands, const uint8_t* clear, uint32_t clear_len, uint64_t* out) {
+// One run of a cached FheString plan on host buffers: every one-call string entry point ends here.  operands: up to three
+// encrypted strings of caps[i] characters, the plan's first inputs; counted: then the digits of an encrypted count, the
+// plan's last inputs.  n_outputs: the query of include/fhestr.h (out == NULL: only the number of output ciphertexts).
+static int run_str_op(fhe_engine* eng, const std::string& op, const uint64_t* const* operands, const uint32_t* caps, uint32_t n_operands,
+                      bool counted, const uint64_t* n_digits, const uint8_t* clear, uint32_t clear_len, uint64_t* out,
+                      uint32_t* n_outputs) {
     API_BEGIN
-    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(out);
-    uint32_t a_cap = caps[0], b_cap = 0;
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    const bool query = !out && n_outputs;
+    if (!query) CHECK_PTR(out);
+    uint32_t b_cap = 0;
     for (uint32_t i = 0; i < n_operands; i++) {
-        CHECK_PTR(operands[i]);
+        if (!query) CHECK_PTR(operands[i]);
         if (i) b_cap += caps[i];
     }
+    if (counted && !query) CHECK_PTR(n_digits);
     fhe_plan* plan = nullptr;
-    if (cached_str_plan(eng, op, a_cap, b_cap, clear, clear_len, &plan)) return 1;
-    const uint32_t bpc = plan->c->n_inputs() / (a_cap + b_cap);      // blocks per character
-    uint32_t counts[3] = {0, 0, 0};
-    for (uint32_t i = 0; i < n_operands; i++) counts[i] = caps[i] * bpc;
-    return plan->c->run_host_parts(operands, counts, n_operands, out);
+    if (cached_str_plan(eng, op, caps[0], b_cap, clear, clear_len, &plan)) return 1;
+    if (n_outputs) *n_outputs = plan->c->n_outputs();
+    if (query) return 0;
+    const uint32_t bpc = fhe::opname::blocks_per_char(plan->c->msg_modulus());
+    const uint64_t* parts[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t counts[4] = {0, 0, 0, 0}, placed = 0;
+    for (uint32_t i = 0; i < n_operands; i++) {
+        parts[i] = operands[i];
+        placed += counts[i] = caps[i] * bpc;
+    }
+    if (counted) {
+        if (placed >= plan->c->n_inputs()) return fail(op + ": the plan has no input left for the count's digits");
+        parts[n_operands] = n_digits;
+        counts[n_operands] = plan->c->n_inputs() - placed;
+    }
+    return plan->c->run_host_parts(parts, counts, n_operands + (counted ? 1 : 0), out);
     API_END
+}
+
+// the clear operand of the replace forms: from || to
+static std::vector<uint8_t> join(const uint8_t* from, uint32_t from_len, const uint8_t* to, uint32_t to_len) {
+    std::vector<uint8_t> joined(from, from + from_len);
+    joined.insert(joined.end(), to, to + to_len);
+    return joined;
 }
 
 static int str_op(fhe_engine* eng, const char* op, const uint64_t* a, uint32_t a_cap, const uint64_t* b,
@@ -831,7 +850,7 @@ static int str_op(fhe_engine* eng, const char* op, const uint64_t* a, uint32_t a
     if (!a) return fail("null pointer: a");
     const uint64_t* operands[2] = {a, b};
     const uint32_t caps[2] = {a_cap, b_cap};
-    return str_op_parts(eng, op, operands, caps, b ? 2 : 1, clear, clear_len, out);
+    return run_str_op(eng, op, operands, caps, b ? 2 : 1, false, nullptr, clear, clear_len, out, nullptr);
 }
 
 // `count` strings against ONE second operand in one pass (Circuit::run_batch_host): level l of all rows is one launch.
@@ -846,7 +865,7 @@ int fhe_str_op_many(fhe_engine* eng, const char* op, const uint64_t* rows, uint3
     CHECK_PTR(rows); CHECK_PTR(out);
     if (b_cap && !b) return fail("null pointer: b");
     if (a_cap + b_cap == 0) return fail("fhe_str_op_many: empty operands");
-    const uint32_t bpc = blocks_per_char(plan);
+    const uint32_t bpc = fhe::opname::blocks_per_char(plan->c->msg_modulus());
     // what the rows do not bring is shared: the second operand, then the digits of an encrypted count
     const bool shares = plan->c->n_inputs() > a_cap * bpc;
     if (shares && !b) return fail("null pointer: b (the shared operand: the pattern, then the digits of an encrypted count)");
@@ -912,13 +931,12 @@ int fhe_str_replace_general(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, 
     const std::string op = "replace:" + std::to_string(from_cap) + ":" + std::to_string(out_cap);
     const uint64_t* operands[3] = {a, from, to};
     const uint32_t caps[3] = {a_cap, from_cap, to_cap};
-    return str_op_parts(eng, op, operands, caps, to_cap ? 3 : 2, nullptr, 0, out);
+    return run_str_op(eng, op, operands, caps, to_cap ? 3 : 2, false, nullptr, nullptr, 0, out, nullptr);
 }
 int fhe_str_replace_clear_general(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint8_t* from, uint32_t from_len,
                                   const uint8_t* to, uint32_t to_len, uint32_t out_cap, uint64_t* out) {
     if ((from_len && !from) || (to_len && !to)) return fail("null pointer: from / to");
-    std::vector<uint8_t> both(from, from + from_len);
-    both.insert(both.end(), to, to + to_len);
+    const std::vector<uint8_t> both = join(from, from_len, to, to_len);
     const std::string op = "replace_clear:" + std::to_string(from_len) + ":" + std::to_string(out_cap);
     return str_op(eng, op.c_str(), a, a_cap, nullptr, 0, both.data(), (uint32_t)both.size(), out);
 }
@@ -931,13 +949,12 @@ int fhe_str_replacen(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const u
     const std::string op = "replacen:" + std::to_string(n) + ":" + std::to_string(from_cap) + ":" + std::to_string(out_cap);
     const uint64_t* operands[3] = {a, from, to};
     const uint32_t caps[3] = {a_cap, from_cap, to_cap};
-    return str_op_parts(eng, op, operands, caps, to_cap ? 3 : 2, nullptr, 0, out);
+    return run_str_op(eng, op, operands, caps, to_cap ? 3 : 2, false, nullptr, nullptr, 0, out, nullptr);
 }
 int fhe_str_replacen_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint8_t* from, uint32_t from_len,
                            const uint8_t* to, uint32_t to_len, uint32_t n, uint32_t out_cap, uint64_t* out) {
     if ((from_len && !from) || (to_len && !to)) return fail("null pointer: from / to");
-    std::vector<uint8_t> both(from, from + from_len);
-    both.insert(both.end(), to, to + to_len);
+    const std::vector<uint8_t> both = join(from, from_len, to, to_len);
     const std::string op = "replacen_clear:" + std::to_string(n) + ":" + std::to_string(from_len) + ":" + std::to_string(out_cap);
     return str_op(eng, op.c_str(), a, a_cap, nullptr, 0, both.data(), (uint32_t)both.size(), out);
 }
@@ -949,63 +966,29 @@ int fhe_str_split(fhe_engine* eng, const char* op, const uint64_t* a, uint32_t a
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(op);
     const std::string base(op);
-    static const char* const names[] = {"split", "rsplit", "split_terminator", "rsplit_terminator", "split_inclusive", "splitn",
-                                        "rsplitn", "split_once", "rsplit_once", "split_ascii_whitespace"};
-    if (std::find(std::begin(names), std::end(names), base) == std::end(names)) return fail("fhe_str_split: unknown operation: " + base);
+    const fhe::opname::Row* row = fhe::opname::find_row(base);          // a split row; the encrypted-count ones: fhe_str_splitn_encn
+    if (!row || row->family != fhe::opname::SPLIT || row->split.enc_count) return fail("fhe_str_split: unknown operation: " + base);
     if (pat && (clear || clear_len)) return fail("fhe_str_split: give an encrypted pattern or a clear one, not both");
     if (pat && pat_cap == 0) return fail("fhe_str_split: the encrypted pattern needs a capacity of at least one character");
-    const bool takes_pattern = base != "split_ascii_whitespace";
+    const bool takes_pattern = !row->unary();
     if (!takes_pattern && (pat || clear || clear_len)) return fail("split_ascii_whitespace takes no pattern");
     if (takes_pattern && !pat && !clear && clear_len) return fail("null clear pattern");
     const bool is_clear = takes_pattern && !pat;        // (an empty clear pattern is refused by the builder)
     std::string name = base + (is_clear ? "_clear" : "");
-    if (base != "split_once" && base != "rsplit_once") name += ":" + std::to_string(max_parts);
+    if (!row->split.once) name += ":" + std::to_string(max_parts);
     if (part_cap) name += ":" + std::to_string(part_cap);
-    fhe_plan* plan = nullptr;
-    if (cached_str_plan(eng, name, a_cap, pat ? pat_cap : 0, is_clear ? clear : nullptr, is_clear ? clear_len : 0, &plan)) return 1;
-    if (n_outputs) *n_outputs = plan->c->n_outputs();
-    if (!out && n_outputs) return 0;                    // query: how many output ciphertexts
-    CHECK_PTR(a); CHECK_PTR(out);
-    const uint32_t bpc = plan->c->n_inputs() / (a_cap + (pat ? pat_cap : 0));
+    if (out || !n_outputs) CHECK_PTR(a);                // (not a query)
     const uint64_t* operands[2] = {a, pat};
-    const uint32_t counts[2] = {a_cap * bpc, pat ? pat_cap * bpc : 0};
-    return plan->c->run_host_parts(operands, counts, pat ? 2 : 1, out);
+    const uint32_t caps[2] = {a_cap, pat ? pat_cap : 0};
+    return run_str_op(eng, name, operands, caps, pat ? 2 : 1, false, nullptr, is_clear ? clear : nullptr, is_clear ? clear_len : 0, out, n_outputs);
     API_END
 }
 
 // ---- encrypted counts: the D digits of n are the plan's last inputs (include/fhestr.h) ----
-static int str_op_counted(fhe_engine* eng, const std::string& op, const uint64_t* const* operands, const uint32_t* caps,
-                          uint32_t n_operands, const uint64_t* n_digits, const uint8_t* clear, uint32_t clear_len, uint64_t* out,
-                          uint32_t* n_outputs) {
-    API_BEGIN
-    CHECK_PTR(eng); LOCK_ENGINE(eng);
-    uint32_t b_cap = 0;
-    for (uint32_t i = 1; i < n_operands; i++) b_cap += caps[i];
-    fhe_plan* plan = nullptr;
-    if (cached_str_plan(eng, op, caps[0], b_cap, clear, clear_len, &plan)) return 1;
-    if (n_outputs) *n_outputs = plan->c->n_outputs();
-    if (!out && n_outputs) return 0;                    // query: how many output ciphertexts
-    CHECK_PTR(out); CHECK_PTR(n_digits);
-    const uint32_t bpc = blocks_per_char(plan);
-    const uint64_t* parts[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t counts[4] = {0, 0, 0, 0}, placed = 0;
-    for (uint32_t i = 0; i < n_operands; i++) {
-        CHECK_PTR(operands[i]);
-        parts[i] = operands[i];
-        counts[i] = caps[i] * bpc;
-        placed += counts[i];
-    }
-    if (placed >= plan->c->n_inputs()) return fail(op + ": the plan has no input left for the count's digits");
-    parts[n_operands] = n_digits;
-    counts[n_operands] = plan->c->n_inputs() - placed;
-    return plan->c->run_host_parts(parts, counts, n_operands + 1, out);
-    API_END
-}
-
 int fhe_str_repeat(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint64_t* n_digits, uint32_t max_count, uint64_t* out) {
     if (max_count == 0 || max_count > 255) return fail("repeat: max_count must be in 1..255");
     const uint64_t* operands[1] = {a};
-    return str_op_counted(eng, "repeat:" + std::to_string(max_count), operands, &a_cap, 1, n_digits, nullptr, 0, out, nullptr);
+    return run_str_op(eng, "repeat:" + std::to_string(max_count), operands, &a_cap, 1, true, n_digits, nullptr, 0, out, nullptr);
 }
 int fhe_str_replacen_encn(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint64_t* from, uint32_t from_cap,
                           const uint64_t* to, uint32_t to_cap, const uint64_t* n_digits, uint32_t n_max, uint32_t out_cap, uint64_t* out) {
@@ -1014,24 +997,24 @@ int fhe_str_replacen_encn(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, co
     const std::string op = "replacen_encn:" + std::to_string(n_max) + ":" + std::to_string(from_cap) + ":" + std::to_string(out_cap);
     const uint64_t* operands[3] = {a, from, to};
     const uint32_t caps[3] = {a_cap, from_cap, to_cap};
-    return str_op_counted(eng, op, operands, caps, to_cap ? 3 : 2, n_digits, nullptr, 0, out, nullptr);
+    return run_str_op(eng, op, operands, caps, to_cap ? 3 : 2, true, n_digits, nullptr, 0, out, nullptr);
 }
 int fhe_str_replacen_encn_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint8_t* from, uint32_t from_len,
                                 const uint8_t* to, uint32_t to_len, const uint64_t* n_digits, uint32_t n_max, uint32_t out_cap,
                                 uint64_t* out) {
     if ((from_len && !from) || (to_len && !to)) return fail("null pointer: from / to");
-    std::vector<uint8_t> both(from, from + from_len);
-    both.insert(both.end(), to, to + to_len);
+    const std::vector<uint8_t> both = join(from, from_len, to, to_len);
     const std::string op = "replacen_encn_clear:" + std::to_string(n_max) + ":" + std::to_string(from_len) + ":" + std::to_string(out_cap);
     const uint64_t* operands[1] = {a};
-    return str_op_counted(eng, op, operands, &a_cap, 1, n_digits, both.data(), (uint32_t)both.size(), out, nullptr);
+    return run_str_op(eng, op, operands, &a_cap, 1, true, n_digits, both.data(), (uint32_t)both.size(), out, nullptr);
 }
 int fhe_str_splitn_encn(fhe_engine* eng, const char* op, const uint64_t* a, uint32_t a_cap, const uint64_t* pat, uint32_t pat_cap,
                         const uint8_t* clear, uint32_t clear_len, const uint64_t* n_digits, uint32_t max_parts, uint32_t part_cap,
                         uint64_t* out, uint32_t* n_outputs) {
     if (!op) return fail("null pointer: op");
     const std::string base(op);
-    if (base != "splitn" && base != "rsplitn") return fail("fhe_str_splitn_encn: op must be \"splitn\" or \"rsplitn\", got: " + base);
+    const fhe::opname::Row* row = fhe::opname::find_row(base + "_encn");
+    if (!row || !row->split.enc_count) return fail("fhe_str_splitn_encn: op must be \"splitn\" or \"rsplitn\", got: " + base);
     if (pat && (clear || clear_len)) return fail("fhe_str_splitn_encn: give an encrypted pattern or a clear one, not both");
     if (pat && pat_cap == 0) return fail("fhe_str_splitn_encn: the encrypted pattern needs a capacity of at least one character");
     if (!pat && !clear && clear_len) return fail("null clear pattern");
@@ -1039,7 +1022,7 @@ int fhe_str_splitn_encn(fhe_engine* eng, const char* op, const uint64_t* a, uint
     if (part_cap) name += ":" + std::to_string(part_cap);
     const uint64_t* operands[2] = {a, pat};
     const uint32_t caps[2] = {a_cap, pat ? pat_cap : 0};
-    return str_op_counted(eng, name, operands, caps, pat ? 2 : 1, n_digits, pat ? nullptr : clear, pat ? 0 : clear_len, out, n_outputs);
+    return run_str_op(eng, name, operands, caps, pat ? 2 : 1, true, n_digits, pat ? nullptr : clear, pat ? 0 : clear_len, out, n_outputs);
 }
 
 int fhe_str_repeat_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, uint32_t count, uint64_t* out) {
@@ -1056,8 +1039,7 @@ int fhe_str_replace(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const ui
 int fhe_str_replace_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint8_t* from,
                           const uint8_t* to, uint32_t pat_len, uint64_t* out) {
     if (pat_len && (!from || !to)) return fail("null pointer: from / to");
-    std::vector<uint8_t> both(from, from + pat_len);
-    both.insert(both.end(), to, to + pat_len);
+    const std::vector<uint8_t> both = join(from, pat_len, to, pat_len);
     return str_op(eng, "replace_clear", a, a_cap, nullptr, 0, both.data(), 2 * pat_len, out);
 }
 int fhe_str_trim_start(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, uint64_t* out) {

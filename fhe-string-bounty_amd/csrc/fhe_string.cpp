@@ -23,6 +23,7 @@
 
 #include "circuit.h"
 #include "regex.h"
+#include "str_op_name.h"
 
 namespace fhe {
 
@@ -1301,30 +1302,7 @@ public:
             c.output(digit);
         }
     }
-    // Which operation of the family: see include/fhestr.h for the semantics of each.
-    struct SplitKind {
-        bool reverse = false, terminator = false, inclusive = false, limited = false, once = false, whitespace = false;
-        bool enc_count = false;        // splitn_encn / rsplitn_encn: n is encrypted, max_parts is its public bound
-    };
-    static bool split_kind(const std::string& base, SplitKind& k) {
-        k = SplitKind();
-        if (base == "split") return true;
-        if (base == "rsplit") { k.reverse = true; return true; }
-        if (base == "split_terminator") { k.terminator = true; return true; }
-        if (base == "rsplit_terminator") { k.reverse = k.terminator = true; return true; }
-        if (base == "split_inclusive") { k.inclusive = true; return true; }
-        if (base == "splitn") { k.limited = true; return true; }
-        if (base == "rsplitn") { k.reverse = k.limited = true; return true; }
-        if (base == "splitn_encn") { k.limited = k.enc_count = true; return true; }
-        if (base == "rsplitn_encn") { k.reverse = k.limited = k.enc_count = true; return true; }
-        if (base == "split_once") { k.once = true; return true; }
-        if (base == "rsplit_once") { k.reverse = k.once = true; return true; }
-        if (base == "split_ascii_whitespace") { k.whitespace = true; return true; }
-        return false;
-    }
-    // (like the split names, a name that does not build without its parameters)
-    static bool is_replacen(const std::string& base) { return base == "replacen" || base == "replacen_encn"; }
-    static bool is_replacen_encn(const std::string& base) { return base == "replacen_encn"; }
+    using SplitKind = opname::SplitKind;        // which operation of the family (str_op_name.h)
     // ---- encrypted counts ("Encrypted counts") ----
     // n arrives as D little-endian base-M digits, D the smallest with M^D > n_max (the public bound); every consumer
     // works from the thermometer g[q - 1] = [n >= q], q = 1 .. n_max, so a value above the bound acts as the bound.
@@ -1898,128 +1876,65 @@ public:
 };
 
 // ------------------------------------------------------------------------------------------------
-// op dispatch used by the C ABI: builds the circuit for `op` and declares its outputs
-int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t b_cap,
-                    const uint8_t* clear, uint32_t clear_len) {
-    StrOps s(c);
-    // "name:p1:p2": numeric parameters of the general replace (pattern capacity / length, output capacity)
-    std::vector<uint32_t> op_params;
-    std::string op_name = op;
-    {
-        size_t colon = op_name.find(':');
-        if (colon != std::string::npos) {
-            std::string rest = op_name.substr(colon + 1);
-            op_name = op_name.substr(0, colon);
-            size_t pos = 0;
-            while (pos <= rest.size()) {
-                size_t nxt = rest.find(':', pos);
-                if (nxt == std::string::npos) nxt = rest.size();
-                const std::string tok = rest.substr(pos, nxt - pos);
-                if (tok.empty() || tok.find_first_not_of("0123456789") != std::string::npos || tok.size() > 9)
-                    return fail("bad numeric parameter in string op: " + op);
-                op_params.push_back((uint32_t)std::stoul(tok));
-                pos = nxt + 1;
-            }
-        }
-    }
-    // matches_clear: clear = the pattern text /.../ of the reference's regex engine (regex.h).  There is no encrypted form
-    // and no reference-shaped one.  The name is compared whole, before the suffixes are parsed and outside the `base ==`
-    // chain below: tests/test_gpu_exact_plan.py reads that chain from this file and builds every name of it in both forms
-    // with the clear operand b"ab", which is no pattern; tests/test_gpu_regex.py runs matches_clear plans bit for bit on
-    // that test's rig instead.
-    const bool is_matches = op_name == "matches_clear";
-    if (op_name == "matches") return fail("matches takes a clear pattern: matches_clear");
-    if (op_name == "matches_reference" || op_name == "matches_reference_clear") return fail("unknown string op: " + op);
-    const std::string ref_suffix = "_reference";
-    for (const char* tail : {"_reference_clear", "_reference"}) {
-        const std::string t(tail);
-        if (op_name.size() > t.size() && op_name.compare(op_name.size() - t.size(), t.size(), t) == 0) {
-            s.packed_compare = false;          // the reference's block-by-block circuit shape
-            s.full_box_reduce = false;         // ... and its chunks of T - 1 comparison bits
-            op_name = op_name.substr(0, op_name.size() - t.size()) + (t == "_reference_clear" ? "_clear" : "");
-            break;
-        }
-    }
-    if (!s.ok) return fail("string ops need msg_mod = 2^b with b | 8 and carry_mod >= msg_mod");
-    if (a_cap == 0) return fail("string capacity must be > 0");
-    const bool is_clear = op_name.size() > 6 && op_name.compare(op_name.size() - 6, 6, "_clear") == 0;
-    const std::string base = is_clear ? op_name.substr(0, op_name.size() - 6) : op_name;
-    if (is_clear && !clear && clear_len) return fail("null clear pattern");
-    Str a = s.input_string(a_cap);
-    Str b;
-    StrOps::SplitKind split_kind;
-    const bool is_split = StrOps::split_kind(base, split_kind);
-    if (is_split && split_kind.whitespace && (is_clear || clear_len)) return fail("split_ascii_whitespace takes no pattern");
-    const bool unary = base == "to_upper" || base == "to_lower" || base == "trim_start" || base == "trim_end" ||
-                       base == "strip" || base == "trim" || base == "len" || base == "is_empty" || (is_split && split_kind.whitespace);
-    // replacen[_clear]:n:F:C = the general replace[_clear]:F:C cut after the first n occurrences
-    const bool is_replacen = StrOps::is_replacen(base), is_replacen_encn = StrOps::is_replacen_encn(base);
-    uint32_t replacen_n = 0;
-    if (is_replacen) {
-        if (op_params.size() != 3)
-            return fail(is_replacen_encn ? "replacen_encn takes three parameters: the count's bound n_max, the pattern capacity and the output capacity"
-                                         : "replacen takes three parameters: the count, the pattern capacity and the output capacity");
-        replacen_n = op_params[0];
-        op_params.erase(op_params.begin());
-        if (is_replacen_encn && replacen_n == 0) return fail("replacen_encn: n_max must be at least 1");
-    }
-    const bool is_replace = base == "replace" || is_replacen;
-    // repeat:<n_max>: the encrypted-count form of repeat_clear (a bare `repeat` stays refused below)
-    const bool counted_repeat = base == "repeat" && !is_clear && !op_params.empty();
-    if (counted_repeat && b_cap) return fail("repeat takes no second string: its inputs are the string and the count's digits");
-    if (!is_clear && !unary && !counted_repeat) {
-        if (b_cap == 0) return fail("pattern capacity must be > 0");
-        b = s.input_string(b_cap);
-    }
+// op dispatch used by the C ABI: builds the circuit for `op` and declares its outputs.  The names and their grammar are
+// defined in str_op_name.cpp.  build_string_op parses the name, runs the refusals that every family shares, creates the
+// inputs -- a, then b; the digits of an encrypted count come last, from the family's own function after its parameter
+// checks -- and OpBuilder::build switches on the family of the name's row.
+namespace {
+using opname::AT_END;
+using opname::AT_START;
+
+struct OpBuilder {
+    Circuit& c;
+    StrOps& s;
+    const opname::Name& n;
+    const opname::Row& row;
+    const Str &a, &b;                    // b: without characters for a clear, a unary and a counted form
+    const uint8_t* clear;
+    const uint32_t clear_len, a_cap;
     // an encrypted count: its digits are the plan's last inputs, after the string and the encrypted pattern operand(s)
     std::vector<uint32_t> count_g;
-    auto take_count = [&](uint32_t n_max) { count_g = s.count_thermometer(s.count_inputs(n_max), n_max); };
-    uint32_t n_digits = 0;
-    while ((1ull << (n_digits * s.bits_per_block)) < (uint64_t)a_cap + 1) n_digits++;
-    if (is_matches) {
-        if (!op_params.empty()) return fail("matches_clear takes no parameters");
+    void take_count(uint32_t n_max) { count_g = s.count_thermometer(s.count_inputs(n_max), n_max); }
+    uint32_t n_digits() const { return opname::count_digits(s.M, a_cap); }          // the digits that hold 0 .. a_cap
+    void output(const std::vector<uint32_t>& outs) { for (uint32_t o : outs) c.output(o); }
+
+    int build_matches() {         // clear = the pattern text /.../ of the reference's regex engine (regex.h)
+        if (!n.params.empty()) return fail("matches_clear takes no parameters");
         regex::Automaton g;
         std::string why;
         if (regex::compile(clear, clear_len, g, why)) return fail("matches_clear: " + why);
         if (g.literal().empty() && !s.matches_fits())
             return fail("matches_clear needs a nibble of a character as one lookup input: msg_mod * carry_mod >= 16 within the noise budget");
         c.output(s.matches(a, g));
-    } else if (base == "eq" || base == "ne") {
-        const bool want = base == "eq";
-        c.output(is_clear ? s.eq_clear(a, clear, clear_len, want) : s.eq(a, b, want));
-    } else if (base == "starts_with") {
-        c.output(is_clear ? s.starts_with_clear(a, clear, clear_len) : s.starts_with(a, b));
-    } else if (base == "ends_with") {
-        c.output(is_clear ? s.ends_with_clear(a, clear, clear_len) : s.ends_with(a, b));
-    } else if (base == "contains") {
-        c.output(is_clear ? s.contains_clear(a, clear, clear_len) : s.contains(a, b));
-    } else if (base == "lt" || base == "le" || base == "gt" || base == "ge") {
-        c.output(s.order_bit(s.compare_sign(a, is_clear ? nullptr : &b, clear, clear_len), base));
-    } else if (base == "eq_ignore_case") {
-        if (is_clear) {
-            std::vector<uint8_t> lower(clear, clear + clear_len);
-            for (auto& ch : lower) if (ch >= 'A' && ch <= 'Z') ch += 32;
-            c.output(s.eq_clear(s.case_folded(a), lower.data(), clear_len, true));
-        } else {
-            c.output(s.eq(s.case_folded(a), s.case_folded(b), true));
+        return 0;
+    }
+    uint32_t compare() {
+        if (row.how != opname::IGNORE_CASE) {
+            const bool want = row.how != opname::NEGATED;
+            return n.clear ? s.eq_clear(a, clear, clear_len, want) : s.eq(a, b, want);
         }
-    } else if (base == "is_empty") {
-        c.output(s.is_empty(a));
-    } else if (base == "len") {
-        std::vector<uint32_t> outs;
-        s.len(a, n_digits, outs);
-        for (uint32_t o : outs) c.output(o);
-    } else if (base == "strip_prefix" || base == "strip_suffix") {
+        if (!n.clear) return s.eq(s.case_folded(a), s.case_folded(b), true);
+        std::vector<uint8_t> lower(clear, clear + clear_len);
+        for (auto& ch : lower) if (ch >= 'A' && ch <= 'Z') ch += 32;
+        return s.eq_clear(s.case_folded(a), lower.data(), clear_len, true);
+    }
+    uint32_t affix() {
+        if (row.how == AT_START) return n.clear ? s.starts_with_clear(a, clear, clear_len) : s.starts_with(a, b);
+        if (row.how == AT_END) return n.clear ? s.ends_with_clear(a, clear, clear_len) : s.ends_with(a, b);
+        return n.clear ? s.contains_clear(a, clear, clear_len) : s.contains(a, b);
+    }
+    void build_strip_bit() {
+        const bool prefix = row.how == AT_START;
         uint32_t bit = 0;
-        Str r = is_clear ? (base == "strip_prefix" ? s.strip_prefix_clear(a, clear, clear_len, &bit)
-                                                   : s.strip_suffix_clear(a, clear, clear_len, &bit))
-                         : (base == "strip_prefix" ? s.strip_prefix(a, b, &bit) : s.strip_suffix(a, b, &bit));
+        Str r = n.clear ? (prefix ? s.strip_prefix_clear(a, clear, clear_len, &bit) : s.strip_suffix_clear(a, clear, clear_len, &bit))
+                        : (prefix ? s.strip_prefix(a, b, &bit) : s.strip_suffix(a, b, &bit));
         c.output(bit);          // first output: 1 iff the pattern was stripped
         s.emit(r);
-    } else if (base == "find" || base == "rfind") {
-        const bool from_end = base == "rfind";
-        std::vector<uint32_t> match;
-        if (is_clear) {
+    }
+    void build_find() {
+        const bool from_end = row.how == AT_END;
+        std::vector<uint32_t> match, outs;
+        if (n.clear) {
             if (clear_len > a_cap) match.assign(1, c.trivial(0));
             else if (clear_len == 0) match.assign(1, c.trivial(1));
             else match = s.window_matches_clear(a, clear, clear_len, a_cap - clear_len + 1);
@@ -2036,85 +1951,86 @@ int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t 
                 match.push_back(c.pbs(c.lin({{s.char_is_zero(b.ch[0]), 1}, {s.char_is_zero(a.ch[a_cap - 1]), 2}}, 0, 3), both));
             }
         }
-        std::vector<uint32_t> outs;
-        if (from_end && is_clear && clear_len == 0) {       // "".rfind in s == len(s)
+        if (from_end && n.clear && clear_len == 0) {       // "".rfind in s == len(s)
             outs.push_back(c.trivial(1));
             std::vector<uint32_t> digits;
-            s.len(a, n_digits, digits);
+            s.len(a, n_digits(), digits);
             outs.insert(outs.end(), digits.begin(), digits.end());
         } else {
-            s.find_from_matches(match, n_digits, outs, from_end);
+            s.find_from_matches(match, n_digits(), outs, from_end);
         }
-        for (uint32_t o : outs) c.output(o);
-    } else if (base == "concat") {
-        // out capacity = a_cap + (b_cap | clear_len); clear right operand: "concat_clear"
-        if (is_clear && clear_len == 0) s.emit(a);
-        else s.emit(s.concat(a, is_clear ? s.clear_string(clear, clear_len) : b));
-    } else if (base == "repeat") {
-        // clear repetition count in clear[0] (>= 1): out capacity = count * a_cap
-        if (counted_repeat) {
-            // copy i is masked by [n >= i + 1] before it is appended: zeroing the tail copies leaves a left-justified result
-            if (op_params.size() != 1) return fail("repeat takes one parameter: the count's bound n_max");
-            const uint32_t n_max = op_params[0];
-            if (n_max == 0 || n_max > 255) return fail("repeat: n_max must be in 1..255");
-            take_count(n_max);
-            Str r;
-            for (uint32_t i = 0; i < n_max; i++) {
-                Str copy;
-                copy.cap = a_cap;
-                copy.ch.resize(a_cap);
-                for (uint32_t j = 0; j < a_cap; j++) {
-                    StrOps::Scope sc(c, s.owner_for(j, a_cap));
-                    for (uint32_t k = 0; k < s.bpc; k++) copy.ch[j].push_back(s.gate_block(a.ch[j][k], count_g[i], true));
-                }
-                r = i ? s.concat(r, copy) : copy;
-            }
-            s.emit(r);
-        } else {
-            if (!is_clear || clear_len != 1 || clear[0] == 0) return fail("repeat_clear takes one clear byte: the count (>= 1)");
+        output(outs);
+    }
+    void build_unary_string() {
+        std::vector<uint32_t> outs;
+        switch (row.how) {
+        case AT_START: return s.emit(s.trim_start(a));
+        case AT_END: return s.emit(s.trim_end(a));
+        case opname::BOTH_ENDS: return s.emit(s.trim_start(s.trim_end(a)));
+        default: s.change_case(a, row.how == opname::LOWER, outs); output(outs);
+        }
+    }
+    int build_repeat() {
+        if (!n.counted_repeat()) {      // clear repetition count in clear[0] (>= 1): out capacity = count * a_cap
+            if (!n.clear || clear_len != 1 || clear[0] == 0) return fail("repeat_clear takes one clear byte: the count (>= 1)");
             Str r = a;
             for (uint32_t i = 1; i < clear[0]; i++) r = s.concat(r, a);
             s.emit(r);
+            return 0;
         }
-    } else if (base == "to_upper" || base == "to_lower") {
-        std::vector<uint32_t> outs;
-        s.change_case(a, base == "to_lower", outs);
-        for (uint32_t o : outs) c.output(o);
-    } else if (base == "trim_end") {
-        s.emit(s.trim_end(a));
-    } else if (base == "trim_start") {
-        s.emit(s.trim_start(a));
-    } else if (base == "strip" || base == "trim") {
-        s.emit(s.trim_start(s.trim_end(a)));
-    } else if (is_split) {
-        // name[_clear]:P[:C]   P = max_parts (splitn / rsplitn: n), C = capacity of every part (default a_cap)
-        // split_once[_clear][:C], rsplit_once[_clear][:C]: two parts
-        const bool once = split_kind.once;
-        if (op_params.size() > (once ? 1u : 2u) || (!once && op_params.empty()))
-            return fail(once ? "split_once takes at most one parameter: the part capacity"
-                             : "split takes one or two parameters: max_parts and the part capacity");
-        const uint32_t P = once ? 2 : op_params[0];
-        const bool has_cap = op_params.size() > (once ? 0u : 1u);
-        const uint32_t part_cap = has_cap ? op_params.back() : a_cap;
-        if (P == 0) return fail(split_kind.limited ? "splitn: n must be at least 1" : "split: max_parts must be at least 1");
+        // copy i is masked by [n >= i + 1] before it is appended: zeroing the tail copies leaves a left-justified result
+        if (n.params.size() != 1) return fail("repeat takes one parameter: the count's bound n_max");
+        const uint32_t n_max = n.params[0];
+        if (n_max == 0 || n_max > 255) return fail("repeat: n_max must be in 1..255");
+        take_count(n_max);
+        Str r;
+        for (uint32_t i = 0; i < n_max; i++) {
+            Str copy;
+            copy.cap = a_cap;
+            copy.ch.resize(a_cap);
+            for (uint32_t j = 0; j < a_cap; j++) {
+                StrOps::Scope sc(c, s.owner_for(j, a_cap));
+                for (uint32_t k = 0; k < s.bpc; k++) copy.ch[j].push_back(s.gate_block(a.ch[j][k], count_g[i], true));
+            }
+            r = i ? s.concat(r, copy) : copy;
+        }
+        s.emit(r);
+        return 0;
+    }
+    int build_split() {           // P = max_parts (splitn / rsplitn: n; split_once: two parts), C = capacity of every part (default a_cap)
+        const opname::SplitKind& kind = row.split;
+        if (!row.takes(n.params.size()))
+            return fail(kind.once ? "split_once takes at most one parameter: the part capacity"
+                                  : "split takes one or two parameters: max_parts and the part capacity");
+        const uint32_t P = kind.once ? 2 : n.params[0];
+        const uint32_t part_cap = n.params.size() == row.params ? n.params.back() : a_cap;
+        if (P == 0) return fail(kind.limited ? "splitn: n must be at least 1" : "split: max_parts must be at least 1");
         if (part_cap == 0) return fail("split: the part capacity must be > 0");
-        if (is_clear && clear_len == 0)
+        if (n.clear && clear_len == 0)
             return fail("split: a clear pattern must not be empty (the per-character split of an empty pattern is not supported)");
         if (s.T < 16) return fail("split needs a message * carry space of at least 16 values");
-        if (split_kind.enc_count) take_count(P);
-        s.split(a, split_kind, is_clear || split_kind.whitespace ? nullptr : &b, clear, clear_len, P, part_cap,
-                split_kind.enc_count ? &count_g : nullptr);
-    } else if (is_replace) {
-        // replace_clear[:F:C]  clear = from (F bytes; default: half) || to,   output capacity C (default a_cap)
-        // replace[:F:C]        b = encrypted from (capacity F; default: half) || to
-        //   without parameters: equal lengths, encrypted operands fill their capacity, rewritten in place;
-        //   with parameters: any lengths, encrypted operands may be zero padded (hidden lengths)
+        if (kind.enc_count) take_count(P);
+        s.split(a, kind, n.clear || kind.whitespace ? nullptr : &b, clear, clear_len, P, part_cap, kind.enc_count ? &count_g : nullptr);
+        return 0;
+    }
+    // clear = from (F bytes; default: half) || to, or b = encrypted from (capacity F; default: half) || to; output capacity C
+    //   without parameters: equal lengths, encrypted operands fill their capacity, rewritten in place;
+    //   with parameters: any lengths, encrypted operands may be zero padded (hidden lengths)
+    // replacen, replacen_encn = the general form cut after the first n occurrences (their three parameters are checked already)
+    int build_replace() {
+        const bool is_replacen = row.how != opname::AS_NAMED, is_replacen_encn = row.how == opname::COUNTED;
+        const uint32_t replacen_n = is_replacen ? n.params[0] : 0;
+        const std::vector<uint32_t> op_params(n.params.begin() + (is_replacen ? 1 : 0), n.params.end());
         if (!op_params.empty() && op_params.size() != 2) return fail("replace takes two parameters: pattern capacity and output capacity");
         const bool general = !op_params.empty();
         const uint32_t out_cap = general ? op_params[1] : a_cap;
         if (out_cap == 0) return fail("output capacity must be > 0");
         if (is_replacen_encn) take_count(replacen_n);
-        if (is_clear) {
+        auto keep_first_n = [&](StrOps::Occurrences& oc, uint32_t m, const std::vector<uint32_t>* nzf) {
+            if (is_replacen_encn) s.keep_counted_occurrences(oc, count_g, m, a_cap, nzf);
+            else if (is_replacen) s.keep_first_occurrences(oc, replacen_n, m, a_cap, nzf);
+        };
+        if (n.clear) {
             if (!general && clear_len % 2) return fail("replace_clear expects `from` and `to` of equal length, concatenated");
             const uint32_t m = general ? op_params[0] : clear_len / 2;
             if (m > clear_len) return fail("replace_clear: pattern length beyond the clear buffer");
@@ -2126,48 +2042,103 @@ int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t 
             else {
                 std::vector<uint32_t> match = s.window_matches_clear(a, clear, m, a_cap - m + 1);
                 StrOps::Occurrences oc = s.occurrences(match, m, a_cap, StrOps::has_border(clear, m), nullptr);
-                if (is_replacen_encn) s.keep_counted_occurrences(oc, count_g, m, a_cap, nullptr);
-                else if (is_replacen) s.keep_first_occurrences(oc, replacen_n, m, a_cap, nullptr);
+                keep_first_n(oc, m, nullptr);
                 s.emit(m == t && out_cap == a_cap ? s.replace_in_place(a, oc, m, to, nullptr)
                                                   : s.replace_general(a, oc, to, t, nullptr, out_cap));
             }
-        } else {
-            if (!general && b_cap % 2) return fail("replace expects `from` and `to` of equal capacity, concatenated");
-            const uint32_t m = general ? op_params[0] : b_cap / 2;
-            if (m == 0 || m > b_cap) return fail("replace: pattern capacity must be in 1..b_cap");
-            Str from, to;
-            from.cap = m;
-            to.cap = b_cap - m;
-            from.ch.assign(b.ch.begin(), b.ch.begin() + m);
-            to.ch.assign(b.ch.begin() + m, b.ch.end());
-            if (!general) {
-                if (m > a_cap) { s.emit(a); }
-                else {
-                    std::vector<uint32_t> match = s.window_matches(a, from, a_cap - m + 1, false);
-                    StrOps::Occurrences oc = s.occurrences(match, m, a_cap, true, nullptr);
-                    s.emit(s.replace_in_place(a, oc, m, nullptr, &to));
-                }
-            } else if (is_replacen && replacen_n == 0) {
-                s.emit(s.fit(a, out_cap));
-            } else {
-                // padded pattern: its zero tail matches anything; an occurrence runs over from[j] != 0 only.
-                // A pattern that decrypts to the empty string selects nothing (nzf[0] = 0).
-                std::vector<uint32_t> nzf;
-                for (uint32_t j = 0; j < m; j++) nzf.push_back(s.not_bit(s.char_is_zero(from.ch[j])));
-                std::vector<uint32_t> match = s.window_matches(a, from, a_cap, true);
-                for (uint32_t o = 0; o < match.size(); o++) {
-                    StrOps::Scope sc(c, s.owner_for(o, (uint32_t)match.size()));
-                    match[o] = s.and_bits(match[o], nzf[0]);
-                }
-                StrOps::Occurrences oc = s.occurrences(match, m, a_cap, true, &nzf);
-                if (is_replacen_encn) s.keep_counted_occurrences(oc, count_g, m, a_cap, &nzf);
-                else if (is_replacen) s.keep_first_occurrences(oc, replacen_n, m, a_cap, &nzf);
-                s.emit(s.replace_general(a, oc, nullptr, 0, to.cap ? &to : nullptr, out_cap));
-            }
+            return 0;
         }
-    } else {
-        return fail("unknown string op: " + op);
+        if (!general && b.cap % 2) return fail("replace expects `from` and `to` of equal capacity, concatenated");
+        const uint32_t m = general ? op_params[0] : b.cap / 2;
+        if (m == 0 || m > b.cap) return fail("replace: pattern capacity must be in 1..b_cap");
+        Str from, to;
+        from.cap = m;
+        to.cap = b.cap - m;
+        from.ch.assign(b.ch.begin(), b.ch.begin() + m);
+        to.ch.assign(b.ch.begin() + m, b.ch.end());
+        if (!general && m > a_cap) s.emit(a);
+        else if (!general) {
+            std::vector<uint32_t> match = s.window_matches(a, from, a_cap - m + 1, false);
+            StrOps::Occurrences oc = s.occurrences(match, m, a_cap, true, nullptr);
+            s.emit(s.replace_in_place(a, oc, m, nullptr, &to));
+        } else if (is_replacen && replacen_n == 0) {
+            s.emit(s.fit(a, out_cap));
+        } else {
+            // padded pattern: its zero tail matches anything; an occurrence runs over from[j] != 0 only.
+            // A pattern that decrypts to the empty string selects nothing (nzf[0] = 0).
+            std::vector<uint32_t> nzf;
+            for (uint32_t j = 0; j < m; j++) nzf.push_back(s.not_bit(s.char_is_zero(from.ch[j])));
+            std::vector<uint32_t> match = s.window_matches(a, from, a_cap, true);
+            for (uint32_t o = 0; o < match.size(); o++) {
+                StrOps::Scope sc(c, s.owner_for(o, (uint32_t)match.size()));
+                match[o] = s.and_bits(match[o], nzf[0]);
+            }
+            StrOps::Occurrences oc = s.occurrences(match, m, a_cap, true, &nzf);
+            keep_first_n(oc, m, &nzf);
+            s.emit(s.replace_general(a, oc, nullptr, 0, to.cap ? &to : nullptr, out_cap));
+        }
+        return 0;
     }
+
+    int build() {
+        std::vector<uint32_t> outs;
+        switch (row.family) {
+        case opname::COMPARE: c.output(compare()); break;
+        case opname::ORDER: c.output(s.order_bit(s.compare_sign(a, n.clear ? nullptr : &b, clear, clear_len), row.name)); break;
+        case opname::AFFIX: c.output(affix()); break;
+        case opname::FIND: build_find(); break;
+        case opname::STRIP_BIT: build_strip_bit(); break;
+        case opname::UNARY_STRING: build_unary_string(); break;
+        case opname::LEN: s.len(a, n_digits(), outs); output(outs); break;
+        case opname::IS_EMPTY: c.output(s.is_empty(a)); break;
+        case opname::CONCAT:         // out capacity = a_cap + (b_cap | clear_len); clear right operand: "concat_clear"
+            if (n.clear && clear_len == 0) s.emit(a);
+            else s.emit(s.concat(a, n.clear ? s.clear_string(clear, clear_len) : b));
+            break;
+        case opname::REPEAT: return build_repeat();
+        case opname::REPLACE: return build_replace();
+        case opname::SPLIT: return build_split();
+        case opname::MATCHES: return build_matches();
+        }
+        return 0;
+    }
+};
+}  // namespace
+
+int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t b_cap,
+                    const uint8_t* clear, uint32_t clear_len) {
+    StrOps s(c);
+    const opname::Name n = opname::parse(op);
+    if (n.status == opname::BAD_PARAMETER) return fail("bad numeric parameter in string op: " + op);
+    // matches_clear has no encrypted form and no reference-shaped one
+    if (n.is(opname::MATCHES) && !n.clear && !n.reference) return fail("matches takes a clear pattern: matches_clear");
+    if (n.is(opname::MATCHES) && n.reference) return fail("unknown string op: " + op);
+    if (n.reference) {
+        s.packed_compare = false;          // the reference's block-by-block circuit shape
+        s.full_box_reduce = false;         // ... and its chunks of T - 1 comparison bits
+    }
+    if (!s.ok) return fail("string ops need msg_mod = 2^b with b | 8 and carry_mod >= msg_mod");
+    if (a_cap == 0) return fail("string capacity must be > 0");
+    if (n.clear && !clear && clear_len) return fail("null clear pattern");
+    Str a = s.input_string(a_cap);
+    Str b;
+    if (n.is(opname::SPLIT) && n.row->split.whitespace && (n.clear || clear_len)) return fail("split_ascii_whitespace takes no pattern");
+    if (n.is(opname::REPLACE) && n.row->how != opname::AS_NAMED) {
+        const bool counted = n.row->how == opname::COUNTED;
+        if (!n.row->takes(n.params.size()))
+            return fail(counted ? "replacen_encn takes three parameters: the count's bound n_max, the pattern capacity and the output capacity"
+                                : "replacen takes three parameters: the count, the pattern capacity and the output capacity");
+        if (counted && n.params[0] == 0) return fail("replacen_encn: n_max must be at least 1");
+    }
+    // repeat:<n_max> takes no b (a bare `repeat` does: it is refused by its family, with the repeat_clear message)
+    if (n.counted_repeat() && b_cap) return fail("repeat takes no second string: its inputs are the string and the count's digits");
+    if (!n.clear && !(n.row && n.row->unary()) && !n.counted_repeat()) {
+        if (b_cap == 0) return fail("pattern capacity must be > 0");
+        b = s.input_string(b_cap);
+    }
+    if (!n.row) return fail("unknown string op: " + op);
+    OpBuilder builder{c, s, n, *n.row, a, b, clear, clear_len, a_cap, {}};
+    if (builder.build()) return 1;
     if (c.failed()) return fail("circuit build error: " + c.error());
     return 0;
 }

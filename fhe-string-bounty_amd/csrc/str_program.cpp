@@ -3,138 +3,86 @@
 #include "str_program.h"
 
 #include <atomic>
-#include <initializer_list>
+
+#include "str_op_name.h"
 
 namespace fhe {
 namespace program {
 
-uint32_t count_digits(uint32_t msg_mod, uint64_t n_max) {
-    uint32_t d = 1;
-    for (uint64_t span = msg_mod; span <= n_max; span *= msg_mod) d++;
-    return d;
-}
-
-static bool ends_with(const std::string& s, const std::string& tail) {
-    return s.size() > tail.size() && s.compare(s.size() - tail.size(), tail.size(), tail) == 0;
-}
-
-static bool one_of(const std::string& s, std::initializer_list<const char*> names) {
-    for (const char* n : names)
-        if (s == n) return true;
-    return false;
-}
-
-// The output layouts documented in include/fhestr.h, by plan name.
+// The output layouts documented in include/fhestr.h, by plan name (str_op_name.h: the parsed name and its table row).
 int op_layout(const std::string& op, uint32_t msg_mod, const uint32_t* caps, uint32_t n_caps, const uint8_t* clear,
               uint32_t clear_len, OpLayout& out, std::string& why) {
     out = OpLayout();
-    uint32_t bits = 0;
-    while ((1u << bits) < msg_mod) bits++;
-    if (bits == 0 || (1u << bits) != msg_mod || 8 % bits) {
+    const uint32_t bpc = opname::blocks_per_char(msg_mod);
+    if (bpc == 0) {
         why = "string ops need msg_mod = 2^b with b | 8 and carry_mod >= msg_mod";
         return 1;
     }
-    const uint32_t bpc = 8 / bits;
-    // "name:p1:p2"
-    std::string name = op;
-    std::vector<uint64_t> params;
-    const size_t colon = name.find(':');
-    if (colon != std::string::npos) {
-        const std::string rest = name.substr(colon + 1);
-        name = name.substr(0, colon);
-        size_t pos = 0;
-        while (pos <= rest.size()) {
-            size_t nxt = rest.find(':', pos);
-            if (nxt == std::string::npos) nxt = rest.size();
-            const std::string tok = rest.substr(pos, nxt - pos);
-            if (tok.empty() || tok.find_first_not_of("0123456789") != std::string::npos || tok.size() > 9) {
-                out.known = false;          // "bad numeric parameter", says the builder
-                return 0;
-            }
-            params.push_back(std::stoull(tok));
-            pos = nxt + 1;
-        }
+    const opname::Name n = opname::parse(op);
+    // no row, "bad numeric parameter", a matches without its clear pattern: the builder says what is wrong with the name
+    if (n.status != opname::OK || (n.is(opname::MATCHES) && !n.clear)) {
+        out.known = false;
+        return 0;
     }
-    // the reference-shaped forms have the layout of the default ones
-    if (ends_with(name, "_reference_clear")) name = name.substr(0, name.size() - 16) + "_clear";
-    else if (ends_with(name, "_reference")) name = name.substr(0, name.size() - 10);
-    const bool is_clear = ends_with(name, "_clear");
-    const std::string base = is_clear ? name.substr(0, name.size() - 6) : name;
+    const opname::Row& row = *n.row;
+    const std::vector<uint32_t>& params = n.params;
+    const bool full = params.size() == row.params;           // every parameter given (takes(): or none, or all but a part capacity)
     const uint64_t a_cap = n_caps ? caps[0] : 0;
     uint64_t b_cap = 0;
     for (uint32_t i = 1; i < n_caps; i++) b_cap += caps[i];
 
     auto bit = [&]() { out.results.push_back({BIT, 1, 1}); };
-    auto count = [&](uint64_t n_max) { out.results.push_back({COUNT, count_digits(msg_mod, n_max), (uint32_t)n_max}); };
+    auto count = [&](uint64_t n_max) { out.results.push_back({COUNT, opname::count_digits(msg_mod, n_max), (uint32_t)n_max}); };
     auto string = [&](uint64_t cap) { out.results.push_back({STRING, (uint32_t)(cap * bpc), (uint32_t)cap}); };
-    auto takes_count = [&](uint64_t n_max) {
-        out.takes_count = true;
-        out.count_n_max = (uint32_t)n_max;
-        out.count_digits = count_digits(msg_mod, n_max);
-    };
-    const bool split_counted = one_of(base, {"splitn_encn", "rsplitn_encn"});
-    const bool split_once = one_of(base, {"split_once", "rsplit_once"});
-    const bool split_ws = base == "split_ascii_whitespace";
-    const bool split_many = split_counted || split_ws ||
-                            one_of(base, {"split", "rsplit", "split_terminator", "rsplit_terminator", "split_inclusive", "splitn", "rsplitn"});
-    const bool replacen = one_of(base, {"replacen", "replacen_encn"});
-    const bool unary = split_ws || one_of(base, {"to_upper", "to_lower", "trim_start", "trim_end", "strip", "trim", "len", "is_empty"});
-    const bool counted_repeat = base == "repeat" && !is_clear && !params.empty();
 
     // ---- operands ----
-    if (unary || is_clear || counted_repeat) out.strings_min = out.strings_max = 1;
-    else if (base == "replace" || replacen) {                                                   // a, from, to (no `to`: deletion)
+    if (row.unary() || n.clear || n.counted_repeat()) out.strings_min = out.strings_max = 1;
+    else if (row.family == opname::REPLACE) {                                                   // a, from, to (no `to`: deletion)
         out.strings_min = 2;
         out.strings_max = 3;
         out.from_to = true;
-        if (base == "replace" && params.size() == 2) out.from_cap = (uint32_t)params[0];
-        if (replacen && params.size() == 3) out.from_cap = (uint32_t)params[1];
+        if (full) out.from_cap = params[params.size() - 2];
     }
     else out.strings_min = out.strings_max = 2;
-    if (counted_repeat) takes_count(params[0]);
-    if ((base == "replacen_encn" || split_counted) && !params.empty()) takes_count(params[0]);
-    if (out.takes_count && out.count_n_max == 0) {           // a bound of 0: "n_max must be at least 1", says the builder
-        out.known = false;
-        return 0;
+    const bool counted = n.counted_repeat() || row.how == opname::COUNTED || row.split.enc_count;
+    if (counted && !params.empty()) {
+        out.takes_count = true;
+        out.count_n_max = params[0];
+        out.count_digits = opname::count_digits(msg_mod, params[0]);
+        if (params[0] == 0) {                                // a bound of 0: "n_max must be at least 1", says the builder
+            out.known = false;
+            return 0;
+        }
     }
 
-    // ---- results ----
-    if (name == "matches_clear" ||
-        one_of(base, {"eq", "ne", "starts_with", "ends_with", "contains", "lt", "le", "gt", "ge", "eq_ignore_case", "is_empty"})) {
+    // ---- results (none where the builder will refuse: a missing parameter, a repeat_clear without its count) ----
+    switch (row.family) {
+    case opname::COMPARE: case opname::ORDER: case opname::AFFIX: case opname::IS_EMPTY: case opname::MATCHES:
         bit();
-    } else if (base == "find" || base == "rfind") {
-        bit();
-        count(a_cap);
-    } else if (base == "len") {
-        count(a_cap);
-    } else if (base == "strip_prefix" || base == "strip_suffix") {
-        bit();
-        string(a_cap);
-    } else if (one_of(base, {"to_upper", "to_lower", "trim_start", "trim_end", "strip", "trim"})) {
-        string(a_cap);
-    } else if (base == "concat") {
-        string(a_cap + (is_clear ? clear_len : b_cap));
-    } else if (base == "repeat") {
-        if (counted_repeat) string(params[0] * a_cap);
-        else if (is_clear && clear_len == 1 && clear && clear[0]) string((uint64_t)clear[0] * a_cap);
-    } else if (base == "replace") {
-        if (params.empty()) string(a_cap);
-        else if (params.size() == 2) string(params[1]);
-    } else if (replacen) {
-        if (params.size() == 3) string(params[2]);
-    } else if (split_once) {
-        if (params.size() <= 1) {
+        break;
+    case opname::FIND: bit(); count(a_cap); break;
+    case opname::LEN: count(a_cap); break;
+    case opname::STRIP_BIT: bit(); string(a_cap); break;
+    case opname::UNARY_STRING: string(a_cap); break;
+    case opname::CONCAT: string(a_cap + (n.clear ? clear_len : b_cap)); break;
+    case opname::REPEAT:
+        if (n.counted_repeat()) string(params[0] * a_cap);
+        else if (n.clear && clear_len == 1 && clear && clear[0]) string((uint64_t)clear[0] * a_cap);
+        break;
+    case opname::REPLACE:
+        if (row.takes(params.size())) string(full ? params.back() : a_cap);
+        break;
+    case opname::SPLIT:
+        if (!row.takes(params.size())) break;
+        if (row.split.once) {
             bit();
-            for (int p = 0; p < 2; p++) string(params.empty() ? a_cap : params[0]);
-        }
-    } else if (split_many) {
-        if (params.size() == 1 || params.size() == 2) {
+            for (int p = 0; p < 2; p++) string(full ? params[0] : a_cap);
+        } else {
             const uint64_t P = params[0];
             count(P + 1);
-            for (uint64_t p = 0; p < P && p < (1u << 16); p++) string(params.size() == 2 ? params[1] : a_cap);
+            for (uint64_t p = 0; p < P && p < (1u << 16); p++) string(full ? params[1] : a_cap);
         }
-    } else {
-        out.known = false;          // the builder says what is wrong with the name
+        break;
     }
     return 0;
 }
@@ -171,12 +119,11 @@ int Program::input_string(uint32_t cap, uint32_t& value, std::string& why) {
     if (usable(why)) return 1;
     if (cap == 0) { why = "string capacity must be > 0"; return 1; }
     const uint32_t M = b_.msg_modulus();
-    uint32_t bits = 0;
-    while ((1u << bits) < M) bits++;
-    if (bits == 0 || (1u << bits) != M || 8 % bits) { why = "string ops need msg_mod = 2^b with b | 8 and carry_mod >= msg_mod"; return 1; }
-    if ((uint64_t)cap * (8 / bits) > INDEX_MASK || values_.size() >= INDEX_MASK) { why = "string program: too large"; return 1; }
+    const uint32_t bpc = opname::blocks_per_char(M);
+    if (bpc == 0) { why = "string ops need msg_mod = 2^b with b | 8 and carry_mod >= msg_mod"; return 1; }
+    if ((uint64_t)cap * bpc > INDEX_MASK || values_.size() >= INDEX_MASK) { why = "string program: too large"; return 1; }
     std::vector<uint32_t> nodes;
-    for (uint32_t i = 0; i < cap * (8 / bits); i++) nodes.push_back(b_.input(M - 1));
+    for (uint32_t i = 0; i < cap * bpc; i++) nodes.push_back(b_.input(M - 1));
     value = add_value(STRING, cap, std::move(nodes), NO_OP);
     return 0;
 }
@@ -187,7 +134,7 @@ int Program::input_count(uint32_t n_max, uint32_t& value, std::string& why) {
     if (values_.size() >= INDEX_MASK) { why = "string program: too large"; return 1; }
     const uint32_t M = b_.msg_modulus();
     std::vector<uint32_t> nodes;
-    for (uint32_t i = 0; i < count_digits(M, n_max); i++) nodes.push_back(b_.input(M - 1));
+    for (uint32_t i = 0; i < opname::count_digits(M, n_max); i++) nodes.push_back(b_.input(M - 1));
     value = add_value(COUNT, n_max, std::move(nodes), NO_OP);
     return 0;
 }

@@ -37,7 +37,6 @@ struct OpLayout {
     std::vector<ResultSpec> results;             // in output order
 };
 
-uint32_t count_digits(uint32_t msg_mod, uint64_t n_max);     // the smallest D with msg_mod^D > n_max
 // 0, or nonzero with the reason in `why`.  caps: the capacities of the encrypted string operands as given (a first).
 // Refused here: a msg_mod no string operation works on.  A name the table does not know or cannot parse (known = false),
 // and one it knows but the builder refuses (a missing parameter, a malformed regular expression: no results), are left

@@ -12,8 +12,8 @@ Which test reaches what (csrc/circuit.cpp, csrc/lwe_kernels.hip.h):
     run_batch_host with `shared`  test_shared_operand                                     lwe_restride_kernel with in_inst = 0
     run_batch_dev                 test_device_arrays_and_guard_rows, test_compact_and_seeded_inputs
     run_level_rank, gather_outputs  test_sharded_on_one_gpu (whole pool of every rank after every level)
-Operation names come from the dispatch code itself (_dispatch_names); the `_reference` suffix and the `replace:F:C` forms,
-which the dispatch parses rather than compares, are listed by hand in VARIANTS.
+Operation names come from the library's own source (_dispatch_names: the table of string plan names, the integer dispatch);
+the `_reference` suffix and the `replace:F:C` forms, which the names' parser takes apart, are listed by hand in VARIANTS.
 The pool of run_host_parts and of the batch paths lives inside the plan and cannot be read from Python without a new
 entry point, so those paths are compared on their outputs; the sharded path is compared slot by slot.
 
@@ -130,13 +130,23 @@ def _assert_pool(got, want, plan, rank, when):
 
 # ---- the operation names the library accepts, read from its dispatch code --------------------------------------------------
 
+EXPECTED_STRING_BASES = {"eq", "ne", "lt", "le", "gt", "ge", "eq_ignore_case", "starts_with", "ends_with", "contains", "find", "rfind", "strip_prefix",
+                       "strip_suffix", "concat", "repeat", "replace", "to_upper", "to_lower", "trim_start", "trim_end", "strip", "trim", "len", "is_empty"}
+
+
 def _dispatch_names():
-    """(string bases, integer names) from build_string_op / build_integer_op: every name the dispatch compares with."""
+    """(string bases, integer names).  The string bases are read from the table of plan names (csrc/str_op_name.cpp, one
+    Row(name, family, forms, params, bare, ...) per line): the rows that build without parameters (bare), outside the
+    families this file does not run -- matches_clear takes a pattern text, which b"ab" is not, and runs bit for bit on
+    this rig in tests/test_gpu_regex.py; the split family has its own tests.  The integer names are every name that
+    build_integer_op compares with."""
     csrc = os.path.join(ROOT, "fhe-string-bounty_amd", "csrc")
-    with open(os.path.join(csrc, "fhe_string.cpp")) as f:
+    with open(os.path.join(csrc, "str_op_name.cpp")) as f:
         s = f.read()
-    s = s[s.index("int build_string_op("):]
-    strings = sorted(set(re.findall(r'\bbase == "(\w+)"', s)))
+    rows = re.findall(r'^ *Row\("(\w+)", (\w+), ([\w |]+), (\d+), (true|false)[,)]', s[s.index("const Row TABLE[] = {"):s.index("\n};")], re.M)
+    assert len(rows) == s.count("Row(\""), "a row of the table that this test cannot read"
+    strings = sorted(name for name, family, _, _, bare in rows if bare == "true" and family not in ("MATCHES", "SPLIT"))
+    assert set(strings) == EXPECTED_STRING_BASES and len(strings) == 25, sorted(set(strings) ^ EXPECTED_STRING_BASES)
     with open(os.path.join(csrc, "fhe_integer.cpp")) as f:
         s = f.read()
     s = s[s.index("int build_integer_op("):]

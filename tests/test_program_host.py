@@ -8,7 +8,8 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = [os.path.join(ROOT, "tests", "str_program_main.cpp"), os.path.join(ROOT, "fhe-string-bounty_amd", "csrc", "str_program.cpp")]
+SOURCES = [os.path.join(ROOT, "tests", "str_program_main.cpp"), os.path.join(ROOT, "fhe-string-bounty_amd", "csrc", "str_program.cpp"),
+           os.path.join(ROOT, "fhe-string-bounty_amd", "csrc", "str_op_name.cpp")]
 COMPILERS = ("/opt/rocm/lib/llvm/bin/clang++", "c++")
 
 # step -> the result values as kind:blocks:extent (msg_mod 4: four blocks per character), a_cap, b_cap, bound input blocks
