@@ -802,14 +802,15 @@ static int cached_str_plan(fhe_engine* eng, const std::string& op, uint32_t a_ca
     return 0;
 }
 
-// One run of a cached FheString plan on host buffers: every one-call string entry point ends here.  operands: up to three
-// encrypted strings of caps[i] characters, the plan's first inputs; counted: then the digits of an encrypted count, the
-// plan's last inputs.  n_outputs: the query of include/fhestr.h (out == NULL: only the number of output ciphertexts).
-static int run_str_op(fhe_engine* eng, const std::string& op, const uint64_t* const* operands, const uint32_t* caps, uint32_t n_operands,
-                      bool counted, const uint64_t* n_digits, const uint8_t* clear, uint32_t clear_len, uint64_t* out,
-                      uint32_t* n_outputs) {
+// One run of a cached FheString plan on host buffers, by plan name (include/fhestr.h): every one-call string entry point
+// below is a shorthand that ends here.  operands: up to three encrypted strings of caps[i] characters, the plan's first
+// inputs; n_digits: the digits of an encrypted count, the plan's last inputs (NULL: the plan takes none).
+int fhe_str_op(fhe_engine* eng, const char* name, const uint64_t* const* operands, const uint32_t* caps, uint32_t n_operands,
+               const uint64_t* n_digits, const uint8_t* clear, uint32_t clear_len, uint64_t* out, uint32_t* n_outputs) {
     API_BEGIN
-    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(name); CHECK_PTR(operands); CHECK_PTR(caps);
+    if (n_operands < 1 || n_operands > 3) return fail("fhe_str_op: one to three encrypted string operands");
+    const std::string op(name);
     const bool query = !out && n_outputs;
     if (!query) CHECK_PTR(out);
     uint32_t b_cap = 0;
@@ -817,7 +818,6 @@ static int run_str_op(fhe_engine* eng, const std::string& op, const uint64_t* co
         if (!query) CHECK_PTR(operands[i]);
         if (i) b_cap += caps[i];
     }
-    if (counted && !query) CHECK_PTR(n_digits);
     fhe_plan* plan = nullptr;
     if (cached_str_plan(eng, op, caps[0], b_cap, clear, clear_len, &plan)) return 1;
     if (n_outputs) *n_outputs = plan->c->n_outputs();
@@ -829,12 +829,12 @@ static int run_str_op(fhe_engine* eng, const std::string& op, const uint64_t* co
         parts[i] = operands[i];
         placed += counts[i] = caps[i] * bpc;
     }
-    if (counted) {
+    if (n_digits) {
         if (placed >= plan->c->n_inputs()) return fail(op + ": the plan has no input left for the count's digits");
         parts[n_operands] = n_digits;
         counts[n_operands] = plan->c->n_inputs() - placed;
     }
-    return plan->c->run_host_parts(parts, counts, n_operands + (counted ? 1 : 0), out);
+    return plan->c->run_host_parts(parts, counts, n_operands + (n_digits ? 1 : 0), out);
     API_END
 }
 
@@ -845,12 +845,13 @@ static std::vector<uint8_t> join(const uint8_t* from, uint32_t from_len, const u
     return joined;
 }
 
-static int str_op(fhe_engine* eng, const char* op, const uint64_t* a, uint32_t a_cap, const uint64_t* b,
-                  uint32_t b_cap, const uint8_t* clear, uint32_t clear_len, uint64_t* out) {
+// the shorthands on one string and at most one encrypted operand
+static int str_op_ab(fhe_engine* eng, const char* op, const uint64_t* a, uint32_t a_cap, const uint64_t* b,
+                     uint32_t b_cap, const uint8_t* clear, uint32_t clear_len, uint64_t* out) {
     if (!a) return fail("null pointer: a");
     const uint64_t* operands[2] = {a, b};
     const uint32_t caps[2] = {a_cap, b_cap};
-    return run_str_op(eng, op, operands, caps, b ? 2 : 1, false, nullptr, clear, clear_len, out, nullptr);
+    return fhe_str_op(eng, op, operands, caps, b ? 2 : 1, nullptr, clear, clear_len, out, nullptr);
 }
 
 // `count` strings against ONE second operand in one pass (Circuit::run_batch_host): level l of all rows is one launch.
@@ -877,11 +878,11 @@ int fhe_str_op_many(fhe_engine* eng, const char* op, const uint64_t* rows, uint3
     int fhe_str_##name(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint64_t* b,         \
                        uint32_t b_cap, uint64_t* out) {                                               \
         if (!b) return fail("null pointer: b");                                                       \
-        return str_op(eng, #name, a, a_cap, b, b_cap, nullptr, 0, out);                               \
+        return str_op_ab(eng, #name, a, a_cap, b, b_cap, nullptr, 0, out);                               \
     }                                                                                                 \
     int fhe_str_##name##_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint8_t* pat, \
                                uint32_t pat_len, uint64_t* out) {                                     \
-        return str_op(eng, #name "_clear", a, a_cap, nullptr, 0, pat, pat_len, out);                  \
+        return str_op_ab(eng, #name "_clear", a, a_cap, nullptr, 0, pat, pat_len, out);                  \
     }
 STR_BINARY(eq)
 STR_BINARY(ne)
@@ -900,7 +901,7 @@ STR_BINARY(concat)
 /* a clear regular expression (the pattern text /.../ of regex.h): out = one 0/1 block */
 int fhe_str_matches_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint8_t* regex, uint32_t regex_len, uint64_t* out) {
     if (regex_len && !regex) return fail("null pointer: regex");
-    return str_op(eng, "matches_clear", a, a_cap, nullptr, 0, regex, regex_len, out);
+    return str_op_ab(eng, "matches_clear", a, a_cap, nullptr, 0, regex, regex_len, out);
 }
 int fhe_regex_check(const uint8_t* regex, uint32_t len, uint32_t* n_positions, uint32_t* max_len) {
     API_BEGIN
@@ -917,11 +918,11 @@ int fhe_regex_check(const uint8_t* regex, uint32_t len, uint32_t* n_positions, u
 /* encrypted (zero padded) pattern: out = 1 + a_cap * blocks LWEs, stripped bit first */
 int fhe_str_strip_prefix(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint64_t* pat, uint32_t pat_cap, uint64_t* out) {
     if (!pat) return fail("null pointer: pat");
-    return str_op(eng, "strip_prefix", a, a_cap, pat, pat_cap, nullptr, 0, out);
+    return str_op_ab(eng, "strip_prefix", a, a_cap, pat, pat_cap, nullptr, 0, out);
 }
 int fhe_str_strip_suffix(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint64_t* pat, uint32_t pat_cap, uint64_t* out) {
     if (!pat) return fail("null pointer: pat");
-    return str_op(eng, "strip_suffix", a, a_cap, pat, pat_cap, nullptr, 0, out);
+    return str_op_ab(eng, "strip_suffix", a, a_cap, pat, pat_cap, nullptr, 0, out);
 }
 int fhe_str_replace_general(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint64_t* from, uint32_t from_cap,
                             const uint64_t* to, uint32_t to_cap, uint32_t out_cap, uint64_t* out) {
@@ -931,14 +932,14 @@ int fhe_str_replace_general(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, 
     const std::string op = "replace:" + std::to_string(from_cap) + ":" + std::to_string(out_cap);
     const uint64_t* operands[3] = {a, from, to};
     const uint32_t caps[3] = {a_cap, from_cap, to_cap};
-    return run_str_op(eng, op, operands, caps, to_cap ? 3 : 2, false, nullptr, nullptr, 0, out, nullptr);
+    return fhe_str_op(eng, op.c_str(), operands, caps, to_cap ? 3 : 2, nullptr, nullptr, 0, out, nullptr);
 }
 int fhe_str_replace_clear_general(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint8_t* from, uint32_t from_len,
                                   const uint8_t* to, uint32_t to_len, uint32_t out_cap, uint64_t* out) {
     if ((from_len && !from) || (to_len && !to)) return fail("null pointer: from / to");
     const std::vector<uint8_t> both = join(from, from_len, to, to_len);
     const std::string op = "replace_clear:" + std::to_string(from_len) + ":" + std::to_string(out_cap);
-    return str_op(eng, op.c_str(), a, a_cap, nullptr, 0, both.data(), (uint32_t)both.size(), out);
+    return str_op_ab(eng, op.c_str(), a, a_cap, nullptr, 0, both.data(), (uint32_t)both.size(), out);
 }
 
 int fhe_str_replacen(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint64_t* from, uint32_t from_cap,
@@ -949,14 +950,14 @@ int fhe_str_replacen(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const u
     const std::string op = "replacen:" + std::to_string(n) + ":" + std::to_string(from_cap) + ":" + std::to_string(out_cap);
     const uint64_t* operands[3] = {a, from, to};
     const uint32_t caps[3] = {a_cap, from_cap, to_cap};
-    return run_str_op(eng, op, operands, caps, to_cap ? 3 : 2, false, nullptr, nullptr, 0, out, nullptr);
+    return fhe_str_op(eng, op.c_str(), operands, caps, to_cap ? 3 : 2, nullptr, nullptr, 0, out, nullptr);
 }
 int fhe_str_replacen_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint8_t* from, uint32_t from_len,
                            const uint8_t* to, uint32_t to_len, uint32_t n, uint32_t out_cap, uint64_t* out) {
     if ((from_len && !from) || (to_len && !to)) return fail("null pointer: from / to");
     const std::vector<uint8_t> both = join(from, from_len, to, to_len);
     const std::string op = "replacen_clear:" + std::to_string(n) + ":" + std::to_string(from_len) + ":" + std::to_string(out_cap);
-    return str_op(eng, op.c_str(), a, a_cap, nullptr, 0, both.data(), (uint32_t)both.size(), out);
+    return str_op_ab(eng, op.c_str(), a, a_cap, nullptr, 0, both.data(), (uint32_t)both.size(), out);
 }
 
 // the split family: one plan name per (operation, clear / encrypted pattern, max_parts, part capacity)
@@ -980,33 +981,36 @@ int fhe_str_split(fhe_engine* eng, const char* op, const uint64_t* a, uint32_t a
     if (out || !n_outputs) CHECK_PTR(a);                // (not a query)
     const uint64_t* operands[2] = {a, pat};
     const uint32_t caps[2] = {a_cap, pat ? pat_cap : 0};
-    return run_str_op(eng, name, operands, caps, pat ? 2 : 1, false, nullptr, is_clear ? clear : nullptr, is_clear ? clear_len : 0, out, n_outputs);
+    return fhe_str_op(eng, name.c_str(), operands, caps, pat ? 2 : 1, nullptr, is_clear ? clear : nullptr, is_clear ? clear_len : 0, out, n_outputs);
     API_END
 }
 
 // ---- encrypted counts: the D digits of n are the plan's last inputs (include/fhestr.h) ----
 int fhe_str_repeat(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint64_t* n_digits, uint32_t max_count, uint64_t* out) {
     if (max_count == 0 || max_count > 255) return fail("repeat: max_count must be in 1..255");
+    CHECK_PTR(n_digits);
     const uint64_t* operands[1] = {a};
-    return run_str_op(eng, "repeat:" + std::to_string(max_count), operands, &a_cap, 1, true, n_digits, nullptr, 0, out, nullptr);
+    return fhe_str_op(eng, ("repeat:" + std::to_string(max_count)).c_str(), operands, &a_cap, 1, n_digits, nullptr, 0, out, nullptr);
 }
 int fhe_str_replacen_encn(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint64_t* from, uint32_t from_cap,
                           const uint64_t* to, uint32_t to_cap, const uint64_t* n_digits, uint32_t n_max, uint32_t out_cap, uint64_t* out) {
     if (!from || from_cap == 0) return fail("replacen: `from` needs a capacity of at least one character");
     if (to_cap && !to) return fail("null pointer: to");
+    CHECK_PTR(n_digits);
     const std::string op = "replacen_encn:" + std::to_string(n_max) + ":" + std::to_string(from_cap) + ":" + std::to_string(out_cap);
     const uint64_t* operands[3] = {a, from, to};
     const uint32_t caps[3] = {a_cap, from_cap, to_cap};
-    return run_str_op(eng, op, operands, caps, to_cap ? 3 : 2, true, n_digits, nullptr, 0, out, nullptr);
+    return fhe_str_op(eng, op.c_str(), operands, caps, to_cap ? 3 : 2, n_digits, nullptr, 0, out, nullptr);
 }
 int fhe_str_replacen_encn_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint8_t* from, uint32_t from_len,
                                 const uint8_t* to, uint32_t to_len, const uint64_t* n_digits, uint32_t n_max, uint32_t out_cap,
                                 uint64_t* out) {
     if ((from_len && !from) || (to_len && !to)) return fail("null pointer: from / to");
+    CHECK_PTR(n_digits);
     const std::vector<uint8_t> both = join(from, from_len, to, to_len);
     const std::string op = "replacen_encn_clear:" + std::to_string(n_max) + ":" + std::to_string(from_len) + ":" + std::to_string(out_cap);
     const uint64_t* operands[1] = {a};
-    return run_str_op(eng, op, operands, &a_cap, 1, true, n_digits, both.data(), (uint32_t)both.size(), out, nullptr);
+    return fhe_str_op(eng, op.c_str(), operands, &a_cap, 1, n_digits, both.data(), (uint32_t)both.size(), out, nullptr);
 }
 int fhe_str_splitn_encn(fhe_engine* eng, const char* op, const uint64_t* a, uint32_t a_cap, const uint64_t* pat, uint32_t pat_cap,
                         const uint8_t* clear, uint32_t clear_len, const uint64_t* n_digits, uint32_t max_parts, uint32_t part_cap,
@@ -1018,58 +1022,59 @@ int fhe_str_splitn_encn(fhe_engine* eng, const char* op, const uint64_t* a, uint
     if (pat && (clear || clear_len)) return fail("fhe_str_splitn_encn: give an encrypted pattern or a clear one, not both");
     if (pat && pat_cap == 0) return fail("fhe_str_splitn_encn: the encrypted pattern needs a capacity of at least one character");
     if (!pat && !clear && clear_len) return fail("null clear pattern");
+    if (out || !n_outputs) CHECK_PTR(n_digits);         // (not a query)
     std::string name = base + "_encn" + (pat ? "" : "_clear") + ":" + std::to_string(max_parts);
     if (part_cap) name += ":" + std::to_string(part_cap);
     const uint64_t* operands[2] = {a, pat};
     const uint32_t caps[2] = {a_cap, pat ? pat_cap : 0};
-    return run_str_op(eng, name, operands, caps, pat ? 2 : 1, true, n_digits, pat ? nullptr : clear, pat ? 0 : clear_len, out, n_outputs);
+    return fhe_str_op(eng, name.c_str(), operands, caps, pat ? 2 : 1, n_digits, pat ? nullptr : clear, pat ? 0 : clear_len, out, n_outputs);
 }
 
 int fhe_str_repeat_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, uint32_t count, uint64_t* out) {
     if (count == 0 || count > 255) return fail("repeat: count must be in 1..255");
     const uint8_t c = (uint8_t)count;
-    return str_op(eng, "repeat_clear", a, a_cap, nullptr, 0, &c, 1, out);
+    return str_op_ab(eng, "repeat_clear", a, a_cap, nullptr, 0, &c, 1, out);
 }
 
 int fhe_str_replace(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint64_t* from_to,
                     uint32_t pat_cap, uint64_t* out) {
     if (!from_to) return fail("null pointer: from_to");
-    return str_op(eng, "replace", a, a_cap, from_to, 2 * pat_cap, nullptr, 0, out);
+    return str_op_ab(eng, "replace", a, a_cap, from_to, 2 * pat_cap, nullptr, 0, out);
 }
 int fhe_str_replace_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint8_t* from,
                           const uint8_t* to, uint32_t pat_len, uint64_t* out) {
     if (pat_len && (!from || !to)) return fail("null pointer: from / to");
     const std::vector<uint8_t> both = join(from, pat_len, to, pat_len);
-    return str_op(eng, "replace_clear", a, a_cap, nullptr, 0, both.data(), 2 * pat_len, out);
+    return str_op_ab(eng, "replace_clear", a, a_cap, nullptr, 0, both.data(), 2 * pat_len, out);
 }
 int fhe_str_trim_start(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, uint64_t* out) {
-    return str_op(eng, "trim_start", a, a_cap, nullptr, 0, nullptr, 0, out);
+    return str_op_ab(eng, "trim_start", a, a_cap, nullptr, 0, nullptr, 0, out);
 }
 int fhe_str_trim_end(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, uint64_t* out) {
-    return str_op(eng, "trim_end", a, a_cap, nullptr, 0, nullptr, 0, out);
+    return str_op_ab(eng, "trim_end", a, a_cap, nullptr, 0, nullptr, 0, out);
 }
 int fhe_str_strip(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, uint64_t* out) {
-    return str_op(eng, "strip", a, a_cap, nullptr, 0, nullptr, 0, out);
+    return str_op_ab(eng, "strip", a, a_cap, nullptr, 0, nullptr, 0, out);
 }
 int fhe_str_len(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, uint64_t* out) {
-    return str_op(eng, "len", a, a_cap, nullptr, 0, nullptr, 0, out);
+    return str_op_ab(eng, "len", a, a_cap, nullptr, 0, nullptr, 0, out);
 }
 int fhe_str_is_empty(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, uint64_t* out) {
-    return str_op(eng, "is_empty", a, a_cap, nullptr, 0, nullptr, 0, out);
+    return str_op_ab(eng, "is_empty", a, a_cap, nullptr, 0, nullptr, 0, out);
 }
 int fhe_str_strip_prefix_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint8_t* pat,
                                uint32_t pat_len, uint64_t* out) {
-    return str_op(eng, "strip_prefix_clear", a, a_cap, nullptr, 0, pat, pat_len, out);
+    return str_op_ab(eng, "strip_prefix_clear", a, a_cap, nullptr, 0, pat, pat_len, out);
 }
 int fhe_str_strip_suffix_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, const uint8_t* pat,
                                uint32_t pat_len, uint64_t* out) {
-    return str_op(eng, "strip_suffix_clear", a, a_cap, nullptr, 0, pat, pat_len, out);
+    return str_op_ab(eng, "strip_suffix_clear", a, a_cap, nullptr, 0, pat, pat_len, out);
 }
 int fhe_str_to_upper(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, uint64_t* out) {
-    return str_op(eng, "to_upper", a, a_cap, nullptr, 0, nullptr, 0, out);
+    return str_op_ab(eng, "to_upper", a, a_cap, nullptr, 0, nullptr, 0, out);
 }
 int fhe_str_to_lower(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, uint64_t* out) {
-    return str_op(eng, "to_lower", a, a_cap, nullptr, 0, nullptr, 0, out);
+    return str_op_ab(eng, "to_lower", a, a_cap, nullptr, 0, nullptr, 0, out);
 }
 
 // ---- string programs: several FheString operations in one plan (str_program.h) ----

@@ -7,8 +7,10 @@ library or a GPU is missing every call fails loudly -- there is no CPU fallback 
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 import sys
+import typing
 from dataclasses import dataclass
 
 import numpy as np
@@ -154,7 +156,7 @@ EXPORTS = [
     "fhe_plan_create", "fhe_plan_destroy", "fhe_plan_input", "fhe_plan_lut", "fhe_plan_lin", "fhe_plan_pbs",
     "fhe_plan_output", "fhe_plan_finalize", "fhe_plan_info", "fhe_plan_level_info", "fhe_plan_export_level",
     "fhe_plan_run", "fhe_plan_run_level_rank_dev", "fhe_plan_gather_outputs_dev", "fhe_str_plan_create",
-    "fhe_plan_level_rank_info", "fhe_plan_noise_info", "fhe_noise_model", "fhe_noise_model_is_calibrated", "fhe_params_supported", "fhe_plan_run_batch", "fhe_plan_run_batch_dev", "fhe_str_op_many", "fhe_plan_set_noise_budget",
+    "fhe_plan_level_rank_info", "fhe_plan_noise_info", "fhe_noise_model", "fhe_noise_model_is_calibrated", "fhe_params_supported", "fhe_plan_run_batch", "fhe_plan_run_batch_dev", "fhe_str_op", "fhe_str_op_many", "fhe_plan_set_noise_budget",
     "fhe_host_alloc", "fhe_host_free",
     "fhe_plan_pbs_signed", "fhe_plan_pbs_full_box", "fhe_plan_set_owner_hint",
     "fhe_str_to_upper", "fhe_str_to_lower", "fhe_plan_create_offline", "fhe_str_plan_create_offline",
@@ -279,6 +281,7 @@ def lib() -> C.CDLL:
     sig("fhe_plan_run", vp, vp, vp)
     sig("fhe_plan_run_batch", vp, u32, vp, vp)
     sig("fhe_plan_run_batch_dev", vp, u32, vp, vp)
+    sig("fhe_str_op", vp, C.c_char_p, vp, vp, u32, vp, vp, u32, vp, C.POINTER(u32))
     sig("fhe_str_op_many", vp, C.c_char_p, vp, u32, u32, vp, u32, vp, u32, vp, C.POINTER(u32))
     sig("fhe_plan_run_level_rank_dev", vp, vp, u32, u32)
     sig("fhe_plan_level_rank_info", vp, u32, u32, C.POINTER(u32))
@@ -1329,6 +1332,95 @@ class SplitResult:
         return iter((self.count, self.parts))
 
 
+# ---- one call, resolved once: the plan name and what goes with it ----
+# FheStringOps and StringProgram both describe the operands of a call and ask the resolvers below; neither formats a plan
+# name itself.  A string operand is described by its capacity (int), a clear pattern by its bytes, a clear count by an
+# int and an encrypted count by NMax(its public bound); None stands for an operand the operation does not take.
+
+class NMax(int):
+    """The description of an encrypted count operand: its public bound n_max."""
+
+
+class StrCall(typing.NamedTuple):
+    """A resolved call: the plan `name` with its parameters, `b_cap` (the capacities of the encrypted pattern operands
+    together), the `clear` bytes (None: the plan takes none) and `order`: which of the described operands -- by position,
+    the string first -- are the plan's inputs, in the plan's order: the string, the encrypted pattern operand(s), then
+    the encrypted count, whose digits are the last inputs."""
+    name: str
+    b_cap: int
+    clear: "bytes | None"
+    order: tuple
+
+
+def _is_clear(x) -> bool:
+    return isinstance(x, (bytes, bytearray))
+
+
+def _patterns(what, *pats):
+    """The pattern operands of one call, clear or encrypted alike: (name suffix, b_cap, clear bytes, their positions)."""
+    pats = [p for p in pats if p is not None]
+    clear = [_is_clear(p) for p in pats]
+    if not any(clear):
+        return "", sum(pats), None, tuple(range(1, 1 + len(pats)))
+    if not all(clear):
+        raise FheError(f"{what}: `from` and `to` are both clear bytes or both encrypted strings")
+    return "_clear", 0, b"".join(map(bytes, pats)), ()
+
+
+def resolve_binary(op, a_cap, b=None) -> StrCall:
+    """The operations on a string and at most one pattern: the comparisons, find / rfind, strip_prefix / strip_suffix,
+    concat, matches (b: the pattern text), and with b=None the unary ones."""
+    suffix, b_cap, clear, order = _patterns(op, b)
+    return StrCall(op + suffix, b_cap, clear, (0,) + order)
+
+
+def _from_to(what, frm, to, general):
+    suffix, b_cap, clear, order = _patterns(what, frm, to)
+    if general and clear is None and frm == 0:
+        raise FheError(f"{what}: `from` needs a capacity of at least one character")
+    return suffix, b_cap, clear, order, len(frm) if clear is not None else frm, len(to) if clear is not None else to
+
+
+def resolve_replace(a_cap, frm, to, out_cap=None) -> StrCall:
+    """out_cap=None: the equal-length in-place form."""
+    suffix, b_cap, clear, order, f, t = _from_to("replace", frm, to, out_cap is not None)
+    if out_cap is None and f != t:
+        raise FheError(f"replace: `from` and `to` of different {'lengths' if suffix else 'capacities'} need an output capacity (out_cap)")
+    return StrCall("replace" + suffix + ("" if out_cap is None else f":{f}:{int(out_cap)}"), b_cap, clear, (0,) + order)
+
+
+def resolve_replacen(a_cap, frm, to, n, out_cap=None) -> StrCall:
+    """n: a clear int or NMax(n_max); out_cap=None: the capacity of the string."""
+    suffix, b_cap, clear, order, f, _ = _from_to("replacen", frm, to, True)
+    counted = isinstance(n, NMax)
+    name = f"replacen{'_encn' if counted else ''}{suffix}:{int(n)}:{f}:{int(a_cap if out_cap is None else out_cap)}"
+    return StrCall(name, b_cap, clear, (0,) + order + ((3,) if counted else ()))
+
+
+def resolve_repeat(a_cap, count) -> StrCall:
+    """count: a clear int (1..255) or NMax(n_max)."""
+    if isinstance(count, NMax):
+        return StrCall(f"repeat:{int(count)}", 0, None, (0, 1))
+    if not 1 <= int(count) <= 255:
+        raise FheError("repeat: count must be in 1..255")
+    return StrCall("repeat_clear", 0, bytes([int(count)]), (0,))
+
+
+def resolve_split(op, a_cap, pat, max_parts, part_cap=None) -> StrCall:
+    """The split family; pat=None: split_ascii_whitespace; max_parts: a clear int or NMax(n_max) (splitn / rsplitn)."""
+    counted = isinstance(max_parts, NMax)
+    if counted and op not in ("splitn", "rsplitn"):
+        raise FheError(f"{op}: only splitn and rsplitn take an encrypted count")
+    if part_cap is not None and int(part_cap) <= 0:
+        raise FheError("split: the part capacity must be > 0")
+    suffix, b_cap, clear, order = _patterns(op, pat)
+    if order and b_cap == 0:
+        raise FheError(f"{op}: the encrypted pattern needs a capacity of at least one character")
+    name = (op + ("_encn" if counted else "") + suffix + ("" if op in ("split_once", "rsplit_once") else f":{int(max_parts)}") +
+            ("" if part_cap is None else f":{int(part_cap)}"))
+    return StrCall(name, b_cap, clear, (0,) + order + ((2,) if counted else ()))
+
+
 class FheStringOps:
     """FheString operator surface over one engine (eq/ne/starts_with/ends_with/contains/find/
     to_upper/to_lower, ..., replace / replacen, the split family).  Strings are (cap*blocks, kN+1) arrays of big-key LWEs (see string_to_blocks)."""
@@ -1358,23 +1450,58 @@ class FheStringOps:
             plan = self._plans[key] = Plan.string_op(self.engine, op, a_cap, b_cap, bytes(clear) if clear is not None else None)
         return plan
 
-    def _stage(self, d_in, placed):
-        """Fill the plan's device input buffer d_in (rows of big_size words).  placed: (first row, operand) pairs; an
-        expanded operand is uploaded as it is, a PackedString goes up as GLWEs and is unpacked -- extracted and refreshed
-        -- into its rows on the device (Engine.unpack): its expanded form never crosses PCIe."""
+    def _on_device(self, what, plan, rows, shared=()):
+        """`plan` on device buffers (the device route: see _run), one instance per entry of rows: the instance's operands
+        in the plan's input order, expanded arrays or PackedStrings.  shared: the operands that follow, the same for
+        every instance.  An expanded operand is uploaded as it is; a PackedString goes up as GLWEs and is unpacked --
+        extracted and refreshed -- into its rows on the device (Engine.unpack): its expanded form never crosses PCIe; a
+        shared one is unpacked once, into the first instance, and copied to the others on the device.  Returns (the
+        output tensor (instances, n_outputs, kN+1), what must stay alive until the engine has been synchronised)."""
         import torch
-        dev = f"cuda:{self.engine.device}"
-        flat = d_in.view(-1, self.engine.params.big_size)
-        todo = []
-        for row, x in placed:
+        big, dev = self.engine.params.big_size, f"cuda:{self.engine.device}"
+        info = plan.info()
+
+        def size(x):
+            return x.count if isinstance(x, PackedString) else x.shape[0]
+
+        n_shared = sum(map(size, shared))
+        for xs in rows:
+            if sum(map(size, xs)) + n_shared != info["n_inputs"]:
+                raise FheError(f"{what}: the plan takes {info['n_inputs']} input blocks, got {sum(map(size, xs)) + n_shared}")
+        d_in = torch.empty((len(rows), info["n_inputs"], big), dtype=torch.int64, device=dev)
+        d_out = torch.empty((len(rows), info["n_outputs"], big), dtype=torch.int64, device=dev)
+        flat = d_in.view(-1, big)
+        todo = []                                           # (first row, blocks, GLWEs on the device) of the packed operands
+
+        def place(row, x):
             if isinstance(x, PackedString):
                 todo.append((row, x.count, torch.from_numpy(np.ascontiguousarray(x).view(np.int64).reshape(-1)).to(dev)))
             else:
                 flat[row:row + x.shape[0]].copy_(torch.from_numpy(x.view(np.int64)))
+            return row + size(x)
+
+        for r, xs in enumerate(rows):
+            at = r * info["n_inputs"]
+            for x in xs:
+                at = place(at, x)
+        at, unpacked = info["n_inputs"] - n_shared, []
+        for x in shared:
+            if isinstance(x, PackedString):
+                unpacked.append((at, size(x)))
+                at = place(at, x)
+            else:
+                d_in[:, at:at + size(x)].copy_(torch.from_numpy(x.view(np.int64)).to(dev))
+                at += size(x)
         torch.cuda.synchronize()                            # torch's stream is not ordered with the engine's
         for row, count, d_glwes in todo:
             self.engine.unpack(d_in=d_glwes.data_ptr(), count=count, refresh=True, d_out=flat[row].data_ptr())
-        return todo                                         # keeps the GLWEs alive until the caller has synchronised
+        if unpacked and len(rows) > 1:
+            self.engine.synchronize()
+            for lo, n in unpacked:
+                d_in[1:, lo:lo + n].copy_(d_in[0, lo:lo + n])
+            torch.cuda.synchronize()
+        plan.run_batch_dev(d_in.data_ptr(), d_out.data_ptr(), len(rows))
+        return d_out, (todo, d_in)
 
     def _finish(self, d_out, n_blocks, packed):
         if packed:
@@ -1383,32 +1510,35 @@ class FheStringOps:
         self.engine.synchronize()
         return d_out.cpu().numpy().view(np.uint64)
 
-    def _packed(self, op, a_cap, b_cap, clear, operands, packed=True):
-        """The device route, taken with packed=True and whenever an operand is a PackedString: the operation's plan runs
-        on device buffers.  Packed operands are unpacked into the plan's input buffer there (_stage).  packed=True: the
-        output goes through the packing keyswitch where it lies (Engine.load_packing_key first) and only the GLWEs come
-        back, as a PackedString: (n_glwe, k+1, N), output block j at coefficient j % N of GLWE j // N; decrypt with
-        ClientKey.decrypt_packed, or pass it to the next operation.  Otherwise the output LWEs are downloaded.
-        Plans are kept per (operation, capacities, clear pattern)."""
-        d_out, n_out, keep = self._run_device(op, a_cap, b_cap, clear, operands)
-        return self._finish(d_out, n_out, packed)
+    def _run_device(self, name, a_cap, b_cap, clear, operands):
+        """One instance of the operation's plan on device buffers: (output tensor (n_outputs, kN+1), what must stay alive
+        until the engine has been synchronised).  Plans are kept per (plan name, capacities, clear bytes)."""
+        d_out, keep = self._on_device(name, self._plan(name, a_cap, b_cap, clear), [operands])
+        return d_out[0], keep
 
-    def _run_device(self, op, a_cap, b_cap, clear, operands):
-        """The operation's plan on device buffers (see _packed): (output tensor, its rows, what must stay alive until the
-        engine has been synchronised)."""
-        import torch
-        big = self.engine.params.big_size
-        plan = self._plan(op, a_cap, b_cap, clear)
-        info = plan.info()
-        sizes = [x.count if isinstance(x, PackedString) else x.shape[0] for x in operands]
-        if sum(sizes) != info["n_inputs"]:
-            raise FheError(f"{op}: the plan takes {info['n_inputs']} input blocks, got {sum(sizes)}")
-        dev = f"cuda:{self.engine.device}"
-        d_in = torch.empty((info["n_inputs"], big), dtype=torch.int64, device=dev)
-        d_out = torch.empty((info["n_outputs"], big), dtype=torch.int64, device=dev)
-        keep = self._stage(d_in, list(zip(np.cumsum([0] + sizes[:-1]).tolist(), operands)))
-        plan.run_dev(d_in.data_ptr(), d_out.data_ptr())
-        return d_out, info["n_outputs"], (keep, d_in)
+    def _run(self, name, a_cap, b_cap, clear, operands, packed=False, digits=None):
+        """One resolved call (StrCall): the plan's outputs, (n_outputs, kN+1).  operands: the string and the encrypted
+        pattern operand(s); digits: those of an encrypted count, the plan's last inputs.
+        The device route, taken with packed=True and whenever an operand is a PackedString: the plan runs on device
+        buffers (_on_device).  packed=True: the output goes through the packing keyswitch where it lies
+        (Engine.load_packing_key first) and only the GLWEs come back, as a PackedString: (n_glwe, k+1, N), output block j
+        at coefficient j % N of GLWE j // N; decrypt with ClientKey.decrypt_packed, or pass it to the next operation.
+        Otherwise the output LWEs are downloaded.
+        The host route: fhe_str_op on the operands where they lie, each a part of the plan's inputs."""
+        if self._dev(packed, *operands, digits):
+            d_out, keep = self._run_device(name, a_cap, b_cap, clear, operands + ([digits] if digits is not None else []))
+            return self._finish(d_out, d_out.shape[0], packed)
+        parts = operands[:1] + [x for x in operands[1:] if x.shape[0]]      # an empty operand (`to` of capacity 0) is no input
+        ptrs = (C.c_void_p * len(parts))(*[x.ctypes.data for x in parts])
+        caps = (C.c_uint32 * len(parts))(*[x.shape[0] // self.bpc for x in parts])
+        buf = (C.c_uint8 * max(1, len(clear)))(*clear) if clear is not None else None
+        args = (self.engine.handle, name.encode(), ptrs, caps, len(parts), _ptr(digits) if digits is not None else None,
+                buf, len(clear) if clear is not None else 0)
+        n_out = C.c_uint32(0)
+        _check(lib().fhe_str_op(*args, None, C.byref(n_out)))               # outputs (builds and caches the plan)
+        out = self._alloc((n_out.value, self.engine.params.big_size))
+        _check(lib().fhe_str_op(*args, _ptr(out), C.byref(n_out)))
+        return out
 
     def _cap(self, ct):
         if isinstance(ct, PackedString):
@@ -1432,25 +1562,30 @@ class FheStringOps:
             raise FheError(f"an encrypted count with n_max = {count.n_max} travels in {want} digits, got {have}")
         return digits
 
+    def _describe(self, x):
+        """One operand of a call: (what the plan takes of it, its description for the resolvers: see StrCall)."""
+        if x is None or _is_clear(x) or isinstance(x, (int, np.integer)):
+            return x, x
+        if isinstance(x, EncryptedCount):
+            return self._count_operand(x), NMax(x.n_max)
+        return self._cap(x)
+
+    def _resolved(self, resolve, args, **kw):
+        """Resolve a call on `args` (the string first): (the StrCall, a_cap, the string and the encrypted pattern
+        operand(s) in the plan's order, the digits of the encrypted count or None)."""
+        given, described = zip(*map(self._describe, args))
+        call = resolve(*described, **kw)
+        operands = [given[i] for i in call.order]
+        digits = operands.pop() if isinstance(described[call.order[-1]], NMax) else None
+        return call, described[0], operands, digits
+
+    def _call(self, resolve, args, packed, **kw):
+        call, a_cap, operands, digits = self._resolved(resolve, args, **kw)
+        return self._run(call.name, a_cap, call.b_cap, call.clear, operands, packed, digits)
+
     def _binary(self, op, a, b, packed=False):
-        a, a_cap = self._cap(a)
-        if self._dev(packed, a, b):
-            if isinstance(b, (bytes, bytearray)):
-                return self._packed(op + "_clear", a_cap, 0, b, [a], packed)
-            b, b_cap = self._cap(b)
-            return self._packed(op, a_cap, b_cap, None, [a, b], packed)
-        n_dig = 0
-        while (self.engine.params.msg_mod ** n_dig) < a_cap + 1:
-            n_dig += 1
-        n_out = 1 + n_dig if op in ("find", "rfind") else 1
-        out = self._alloc((n_out, self.engine.params.big_size))
-        if isinstance(b, (bytes, bytearray)):
-            buf = (C.c_uint8 * max(1, len(b)))(*b)
-            _check(getattr(lib(), f"fhe_str_{op}_clear")(self.engine.handle, _ptr(a), a_cap, buf, len(b), _ptr(out)))
-        else:
-            b, b_cap = self._cap(b)
-            _check(getattr(lib(), f"fhe_str_{op}")(self.engine.handle, _ptr(a), a_cap, _ptr(b), b_cap, _ptr(out)))
-        return out
+        """b: an encrypted string, clear bytes, or None for the unary operations."""
+        return self._call(functools.partial(resolve_binary, op), (a, b), packed)
 
     def op_many(self, op, rows, b=None, packed=False, count: "EncryptedCount | None" = None):
         """`op` on every row against ONE second operand in a single pass (fhe_str_op_many): rows (count, cap*blocks, kN+1),
@@ -1492,38 +1627,11 @@ class FheStringOps:
         return out
 
     def _packed_many(self, name, rows, a_cap, enc, clear, packed=True, digits=None):
-        """The device route of op_many (see _packed): rows is a list of expanded (cap*blocks, kN+1) arrays or PackedStrings;
-        the shared operands (enc: the pattern, digits: an encrypted count) are placed once and copied to every row."""
-        import torch
-        big = self.engine.params.big_size
-        plan = self._plan(name, a_cap, enc[1] if enc else 0, clear)
-        info = plan.info()
-        count, n_a = len(rows), a_cap * self.bpc
+        """The device route of op_many: rows is a list of expanded (cap*blocks, kN+1) arrays or PackedStrings; the shared
+        operands (enc: the pattern, digits: an encrypted count) are placed once and copied to every row."""
         shared = ([enc[0]] if enc else []) + ([digits] if digits is not None else [])
-        sizes = [x.count if isinstance(x, PackedString) else x.shape[0] for x in shared]
-        if n_a + sum(sizes) != info["n_inputs"]:
-            raise FheError(f"{name}: the plan takes {info['n_inputs']} input blocks per row, got {n_a + sum(sizes)}")
-        dev = f"cuda:{self.engine.device}"
-        d_in = torch.empty((count, info["n_inputs"], big), dtype=torch.int64, device=dev)
-        d_out = torch.empty((count, info["n_outputs"], big), dtype=torch.int64, device=dev)
-        placed = [(r * info["n_inputs"], x) for r, x in enumerate(rows)]
-        at, unpacked = n_a, []
-        for x, size in zip(shared, sizes):
-            if isinstance(x, PackedString):                 # unpacked once, into row 0's slot, then copied on the device
-                placed.append((at, x))
-                unpacked.append((at, size))
-            else:
-                d_in[:, at:at + size].copy_(torch.from_numpy(x.view(np.int64)).to(dev))
-            at += size
-        keep = self._stage(d_in, placed)
-        if unpacked and count > 1:
-            self.engine.synchronize()
-            for lo, size in unpacked:
-                d_in[1:, lo:lo + size].copy_(d_in[0, lo:lo + size])
-            torch.cuda.synchronize()
-        plan.run_batch_dev(d_in.data_ptr(), d_out.data_ptr(), count)
-        out = self._finish(d_out, count * info["n_outputs"], packed)
-        return out if packed else out.reshape(count, info["n_outputs"], big)
+        d_out, keep = self._on_device(name, self._plan(name, a_cap, enc[1] if enc else 0, clear), [[r] for r in rows], shared)
+        return self._finish(d_out, d_out.shape[0] * d_out.shape[1], packed)
 
     def eq_many(self, rows, b): return self.op_many("eq", rows, b)[:, 0]
     def ne_many(self, rows, b): return self.op_many("ne", rows, b)[:, 0]
@@ -1555,215 +1663,60 @@ class FheStringOps:
         text of the reference's regex engine, "/^[0-9]+$/", "/ab|cd/i" (grammar and deviations: include/fhestr.h)."""
         return self._binary("matches", a, self._regex(regex), packed)[0]
 
-    def _n_digits(self, cap):
-        n = 0
-        while (self.engine.params.msg_mod ** n) < cap + 1:
-            n += 1
-        return n
-
-    def len(self, a, packed=False):
-        a, a_cap = self._cap(a)
-        if self._dev(packed, a):
-            return self._packed("len", a_cap, 0, None, [a], packed)
-        out = self._alloc((self._n_digits(a_cap), self.engine.params.big_size))
-        _check(lib().fhe_str_len(self.engine.handle, _ptr(a), a_cap, _ptr(out)))
-        return out
-
-    def is_empty(self, a, packed=False):
-        a, a_cap = self._cap(a)
-        if self._dev(packed, a):
-            return self._packed("is_empty", a_cap, 0, None, [a], packed)[0]
-        out = self._alloc((1, self.engine.params.big_size))
-        _check(lib().fhe_str_is_empty(self.engine.handle, _ptr(a), a_cap, _ptr(out)))
-        return out[0]
+    def len(self, a, packed=False): return self._binary("len", a, None, packed)
+    def is_empty(self, a, packed=False): return self._binary("is_empty", a, None, packed)[0]
 
     def _strip_affix(self, op, a, pat, packed=False):
         """pat: clear bytes, or an encrypted (zero padded) pattern.  packed=True: ONE packed array, the flag at
         coefficient 0 and the string's blocks after it."""
-        a, a_cap = self._cap(a)
-        if self._dev(packed, a, pat):
-            if isinstance(pat, (bytes, bytearray)):
-                out = self._packed(op + "_clear", a_cap, 0, pat, [a], packed)
-            else:
-                pat, p_cap = self._cap(pat)
-                out = self._packed(op, a_cap, p_cap, None, [a, pat], packed)
-            return out if packed else (out[0], out[1:])
-        out = self._alloc((1 + a.shape[0], self.engine.params.big_size))
-        if isinstance(pat, (bytes, bytearray)):
-            buf = (C.c_uint8 * max(1, len(pat)))(*pat)
-            _check(getattr(lib(), f"fhe_str_{op}_clear")(self.engine.handle, _ptr(a), a_cap, buf, len(pat), _ptr(out)))
-        else:
-            pat, p_cap = self._cap(pat)
-            _check(getattr(lib(), f"fhe_str_{op}")(self.engine.handle, _ptr(a), a_cap, _ptr(pat), p_cap, _ptr(out)))
-        return out[0], out[1:]
+        out = self._binary(op, a, pat, packed)
+        return out if packed else (out[0], out[1:])
 
     def strip_prefix(self, a, pat, packed=False): return self._strip_affix("strip_prefix", a, pat, packed)
     def strip_suffix(self, a, pat, packed=False): return self._strip_affix("strip_suffix", a, pat, packed)
 
-    def _unary(self, op, a, packed=False):
-        a, a_cap = self._cap(a)
-        if self._dev(packed, a):
-            return self._packed(op, a_cap, 0, None, [a], packed)
-        out = self._alloc(a.shape)
-        _check(getattr(lib(), f"fhe_str_{op}")(self.engine.handle, _ptr(a), a_cap, _ptr(out)))
-        return out
-
-    def trim_start(self, a, packed=False): return self._unary("trim_start", a, packed)
-    def trim_end(self, a, packed=False): return self._unary("trim_end", a, packed)
-    def strip(self, a, packed=False): return self._unary("strip", a, packed)
+    def trim_start(self, a, packed=False): return self._binary("trim_start", a, None, packed)
+    def trim_end(self, a, packed=False): return self._binary("trim_end", a, None, packed)
+    def strip(self, a, packed=False): return self._binary("strip", a, None, packed)
+    def to_upper(self, a, packed=False): return self._binary("to_upper", a, None, packed)
+    def to_lower(self, a, packed=False): return self._binary("to_lower", a, None, packed)
 
     def replace(self, a, frm, to, out_cap: int | None = None, packed=False):
         """Replace every leftmost non-overlapping occurrence of frm by to (bytes.replace).  frm / to: both
         clear bytes, or both encrypted strings.  out_cap=None: the equal-length in-place form (encrypted
         operands unpadded).  With out_cap: any lengths, encrypted operands may be zero padded, the result
         has out_cap characters."""
-        a, a_cap = self._cap(a)
-        big = self.engine.params.big_size
-        clear = isinstance(frm, (bytes, bytearray))
-        if self._dev(packed, a, frm, to):
-            if clear:
-                if out_cap is None and len(frm) != len(to):
-                    raise FheError("replace: `from` and `to` of different lengths need an output capacity (out_cap)")
-                name = "replace_clear" if out_cap is None else f"replace_clear:{len(frm)}:{out_cap}"
-                return self._packed(name, a_cap, 0, bytes(frm) + bytes(to), [a], packed)
-            frm, f_cap = self._cap(frm)
-            to, t_cap = self._cap(to)
-            if out_cap is None and f_cap != t_cap:
-                raise FheError("replace: `from` and `to` of different capacities need an output capacity (out_cap)")
-            name = "replace" if out_cap is None else f"replace:{f_cap}:{out_cap}"
-            return self._packed(name, a_cap, f_cap + t_cap, None, [a, frm, to], packed)
-        if out_cap is None:
-            out = self._alloc(a.shape)
-            if clear:
-                if len(frm) != len(to):
-                    raise FheError("replace: `from` and `to` of different lengths need an output capacity (out_cap)")
-                fb = (C.c_uint8 * max(1, len(frm)))(*frm)
-                tb = (C.c_uint8 * max(1, len(to)))(*to)
-                _check(lib().fhe_str_replace_clear(self.engine.handle, _ptr(a), a_cap, fb, tb, len(frm), _ptr(out)))
-            else:
-                frm, f_cap = self._cap(frm)
-                to, t_cap = self._cap(to)
-                if f_cap != t_cap:
-                    raise FheError("replace: `from` and `to` of different capacities need an output capacity (out_cap)")
-                both = np.concatenate([frm, to])
-                _check(lib().fhe_str_replace(self.engine.handle, _ptr(a), a_cap, _ptr(both), f_cap, _ptr(out)))
-            return out
-        out = self._alloc((out_cap * self.bpc, big))
-        if clear:
-            fb = (C.c_uint8 * max(1, len(frm)))(*frm)
-            tb = (C.c_uint8 * max(1, len(to)))(*to)
-            _check(lib().fhe_str_replace_clear_general(self.engine.handle, _ptr(a), a_cap, fb, len(frm), tb, len(to),
-                                                       out_cap, _ptr(out)))
-        else:
-            frm, f_cap = self._cap(frm)
-            to, t_cap = self._cap(to)
-            _check(lib().fhe_str_replace_general(self.engine.handle, _ptr(a), a_cap, _ptr(frm), f_cap,
-                                                 _ptr(to) if t_cap else None, t_cap, out_cap, _ptr(out)))
-        return out
+        return self._call(resolve_replace, (a, frm, to), packed, out_cap=out_cap)
 
     def replacen(self, a, frm, to, n: "int | EncryptedCount", out_cap: int | None = None, packed=False):
         """Replace the first n leftmost non-overlapping occurrences of frm by to (bytes.replace(frm, to, n), Rust's
         str::replacen).  frm / to: both clear bytes, or both encrypted strings (may be zero padded); any lengths; the
         result has out_cap characters (default: the capacity of a) and is cut there.  A clear empty frm is refused.
         n: a clear int, or an EncryptedCount -- then min(n, n_max) occurrences are replaced, n = 0 returns a."""
-        a, a_cap = self._cap(a)
-        big = self.engine.params.big_size
-        out_cap = a_cap if out_cap is None else out_cap
-        clear = isinstance(frm, (bytes, bytearray))
-        if isinstance(n, EncryptedCount):
-            digits, n_max = self._count_operand(n), n.n_max
-            if self._dev(packed, a, frm, to, digits):
-                if clear:
-                    return self._packed(f"replacen_encn_clear:{n_max}:{len(frm)}:{out_cap}", a_cap, 0, bytes(frm) + bytes(to), [a, digits], packed)
-                frm, f_cap = self._cap(frm)
-                to, t_cap = self._cap(to)
-                return self._packed(f"replacen_encn:{n_max}:{f_cap}:{out_cap}", a_cap, f_cap + t_cap, None, [a, frm, to, digits], packed)
-            out = self._alloc((out_cap * self.bpc, big))
-            if clear:
-                fb = (C.c_uint8 * max(1, len(frm)))(*frm)
-                tb = (C.c_uint8 * max(1, len(to)))(*to)
-                _check(lib().fhe_str_replacen_encn_clear(self.engine.handle, _ptr(a), a_cap, fb, len(frm), tb, len(to), _ptr(digits),
-                                                         n_max, out_cap, _ptr(out)))
-            else:
-                frm, f_cap = self._cap(frm)
-                to, t_cap = self._cap(to)
-                _check(lib().fhe_str_replacen_encn(self.engine.handle, _ptr(a), a_cap, _ptr(frm), f_cap, _ptr(to) if t_cap else None,
-                                                   t_cap, _ptr(digits), n_max, out_cap, _ptr(out)))
-            return out
-        if self._dev(packed, a, frm, to):
-            if clear:
-                return self._packed(f"replacen_clear:{n}:{len(frm)}:{out_cap}", a_cap, 0, bytes(frm) + bytes(to), [a], packed)
-            frm, f_cap = self._cap(frm)
-            to, t_cap = self._cap(to)
-            return self._packed(f"replacen:{n}:{f_cap}:{out_cap}", a_cap, f_cap + t_cap, None, [a, frm, to], packed)
-        out = self._alloc((out_cap * self.bpc, big))
-        if clear:
-            fb = (C.c_uint8 * max(1, len(frm)))(*frm)
-            tb = (C.c_uint8 * max(1, len(to)))(*to)
-            _check(lib().fhe_str_replacen_clear(self.engine.handle, _ptr(a), a_cap, fb, len(frm), tb, len(to), n, out_cap, _ptr(out)))
-        else:
-            frm, f_cap = self._cap(frm)
-            to, t_cap = self._cap(to)
-            _check(lib().fhe_str_replacen(self.engine.handle, _ptr(a), a_cap, _ptr(frm), f_cap, _ptr(to) if t_cap else None, t_cap,
-                                          n, out_cap, _ptr(out)))
-        return out
-
-    def _count_digits(self, max_parts):
-        n = 1
-        while self.engine.params.msg_mod ** n <= max_parts + 1:
-            n += 1
-        return n
+        return self._call(resolve_replacen, (a, frm, to, n), packed, out_cap=out_cap)
 
     def _split(self, op, a, pat, max_parts, part_cap=None, packed=False):
         """The split family (include/fhestr.h, fhe_str_split).  pat: clear bytes, an expanded encrypted (zero padded)
         pattern, a PackedString, or None (split_ascii_whitespace).  Returns a SplitResult.  max_parts may be an
         EncryptedCount (splitn / rsplitn only): then its n_max is the number of parts returned."""
-        digits = None
-        if isinstance(max_parts, EncryptedCount):
-            if op not in ("splitn", "rsplitn"):
-                raise FheError(f"{op}: only splitn and rsplitn take an encrypted count")
-            digits, max_parts = self._count_operand(max_parts), max_parts.n_max
-        a, a_cap = self._cap(a)
-        big = self.engine.params.big_size
+        call, a_cap, operands, digits = self._resolved(functools.partial(resolve_split, op), (a, pat, max_parts), part_cap=part_cap)
         once = op in ("split_once", "rsplit_once")
-        P = 2 if once else int(max_parts)
-        if part_cap is not None and int(part_cap) <= 0:
-            raise FheError("split: the part capacity must be > 0")
+        P = 2 if once else int(max_parts.n_max if digits is not None else max_parts)
         cap = a_cap if part_cap is None else int(part_cap)
-        n_head = 1 if once else self._count_digits(P)
         n_part = cap * self.bpc
-        clear = bytes(pat) if isinstance(pat, (bytes, bytearray)) else None
-        enc = None if (pat is None or clear is not None) else self._cap(pat)
-        if self._dev(packed, a, pat, digits):
-            name = (op + ("_encn" if digits is not None else "") + ("_clear" if clear is not None else "") + ("" if once else f":{P}") +
-                    (f":{cap}" if part_cap is not None else ""))
-            d_out, n_out, keep = self._run_device(name, a_cap, enc[1] if enc else 0, clear,
-                                                  [a] + ([enc[0]] if enc else []) + ([digits] if digits is not None else []))
-            if n_out != n_head + P * n_part:
-                raise FheError(f"{name}: the plan has {n_out} outputs, expected {n_head + P * n_part}")
-            if not packed:
-                self.engine.synchronize()
-                out = d_out.cpu().numpy().view(np.uint64)
-            else:
-                # the count blocks and every part packed on their own, where they lie: a part is the next operation's operand
-                count = PackedString(self.engine.pack(d_out[:n_head], count=n_head), n_head, 0)
-                parts = [PackedString(self.engine.pack(d_out[n_head + p * n_part: n_head + (p + 1) * n_part], count=n_part), n_part, cap)
-                         for p in range(P)]
-                return SplitResult(count, parts)
+
+        if packed:
+            # the count blocks and every part packed on their own, where they lie: a part is the next operation's operand
+            out, keep = self._run_device(call.name, a_cap, call.b_cap, call.clear, operands + ([digits] if digits is not None else []))
+            take = lambda lo, hi, c: PackedString(self.engine.pack(out[lo:hi], count=hi - lo), hi - lo, c)
         else:
-            buf = (C.c_uint8 * max(1, len(clear)))(*clear) if clear is not None else None
-            args = (self.engine.handle, op.encode(), _ptr(a), a_cap, _ptr(enc[0]) if enc else None, enc[1] if enc else 0,
-                    buf, len(clear) if clear is not None else 0) + ((_ptr(digits),) if digits is not None else ()) + (
-                    P, 0 if part_cap is None else cap)
-            entry = lib().fhe_str_split if digits is None else lib().fhe_str_splitn_encn
-            n_out = C.c_uint32(0)
-            _check(entry(*args, None, C.byref(n_out)))                      # builds and caches the plan
-            if n_out.value != n_head + P * n_part:
-                raise FheError(f"{op}: the plan has {n_out.value} outputs, expected {n_head + P * n_part}")
-            out = self._alloc((n_out.value, big))
-            _check(entry(*args, _ptr(out), C.byref(n_out)))
-        head = out[0] if once else out[:n_head]
-        return SplitResult(head, [out[n_head + p * n_part: n_head + (p + 1) * n_part] for p in range(P)])
+            out = self._run(call.name, a_cap, call.b_cap, call.clear, operands, False, digits)
+            take = lambda lo, hi, c: out[lo:hi]
+        n_head = out.shape[0] - P * n_part                  # the count's digits; split_once / rsplit_once: the one block `found`
+        if n_head < 1:
+            raise FheError(f"{call.name}: the plan has {out.shape[0]} outputs, too few for {P} parts of {n_part} blocks")
+        head = out[0] if once and not packed else take(0, n_head, 0)
+        return SplitResult(head, [take(n_head + p * n_part, n_head + (p + 1) * n_part, cap) for p in range(P)])
 
     def split(self, a, pat, max_parts, part_cap=None, packed=False): return self._split("split", a, pat, max_parts, part_cap, packed)
     def rsplit(self, a, pat, max_parts, part_cap=None, packed=False): return self._split("rsplit", a, pat, max_parts, part_cap, packed)
@@ -1778,41 +1731,12 @@ class FheStringOps:
 
     def concat(self, a, b, packed=False):
         """a ++ b (padding of a removed); b encrypted (any capacity) or clear bytes."""
-        a, a_cap = self._cap(a)
-        if self._dev(packed, a, b):
-            if isinstance(b, (bytes, bytearray)):
-                return self._packed("concat_clear", a_cap, 0, b, [a], packed)
-            b, b_cap = self._cap(b)
-            return self._packed("concat", a_cap, b_cap, None, [a, b], packed)
-        if isinstance(b, (bytes, bytearray)):
-            out = self._alloc(((a_cap + len(b)) * self.bpc, self.engine.params.big_size))
-            buf = (C.c_uint8 * max(1, len(b)))(*b)
-            _check(lib().fhe_str_concat_clear(self.engine.handle, _ptr(a), a_cap, buf, len(b), _ptr(out)))
-        else:
-            b, b_cap = self._cap(b)
-            out = self._alloc(((a_cap + b_cap) * self.bpc, self.engine.params.big_size))
-            _check(lib().fhe_str_concat(self.engine.handle, _ptr(a), a_cap, _ptr(b), b_cap, _ptr(out)))
-        return out
+        return self._binary("concat", a, b, packed)
 
     def repeat(self, a, count: "int | EncryptedCount", packed=False):
         """a repeated count times.  count: a clear int (1..255), or an EncryptedCount (n_max 1..255): the result then has
         n_max * a_cap characters and holds min(n, n_max) copies -- none for n = 0."""
-        a, a_cap = self._cap(a)
-        if isinstance(count, EncryptedCount):
-            digits = self._count_operand(count)
-            if self._dev(packed, a, digits):
-                return self._packed(f"repeat:{count.n_max}", a_cap, 0, None, [a, digits], packed)
-            out = self._alloc((count.n_max * a_cap * self.bpc, self.engine.params.big_size))
-            _check(lib().fhe_str_repeat(self.engine.handle, _ptr(a), a_cap, _ptr(digits), count.n_max, _ptr(out)))
-            return out
-        if self._dev(packed, a):
-            return self._packed("repeat_clear", a_cap, 0, bytes([count]), [a], packed)
-        out = self._alloc((count * a_cap * self.bpc, self.engine.params.big_size))
-        _check(lib().fhe_str_repeat_clear(self.engine.handle, _ptr(a), a_cap, count, _ptr(out)))
-        return out
-
-    def to_upper(self, a, packed=False): return self._unary("to_upper", a, packed)
-    def to_lower(self, a, packed=False): return self._unary("to_lower", a, packed)
+        return self._call(resolve_repeat, (a, count), packed)
 
 
 def _register_with_engine(engine, obj):
@@ -1935,10 +1859,20 @@ class StringProgram:
         self.n_ops += 1
         return [ProgramValue(self, res[i]) for i in range(n.value)]
 
-    def _binary(self, op, a, b):
-        if isinstance(b, (bytes, bytearray)):
-            return self.op(op + "_clear", a, clear=bytes(b))
-        return self.op(op, a, b)
+    def _call(self, resolve, *args, **kw):
+        """An operation of FheStringOps on symbolic operands, resolved as there: the list of its result values."""
+        def describe(x):
+            if isinstance(x, ProgramValue):
+                return NMax(x.extent) if x.kind == "count" else x.extent      # (a bit where a string belongs: op refuses it)
+            if x is None or _is_clear(x) or isinstance(x, (int, np.integer)):
+                return x
+            raise FheError(f"operands are values of a StringProgram or clear, got {type(x).__name__}")
+
+        call = resolve(*map(describe, args), **kw)
+        return self.op(call.name, *[args[i] for i in call.order], clear=call.clear)
+
+    def _binary(self, op, a, b=None):
+        return self._call(functools.partial(resolve_binary, op), a, b)
 
     def eq(self, a, b): return self._binary("eq", a, b)[0]
     def ne(self, a, b): return self._binary("ne", a, b)[0]
@@ -1952,58 +1886,33 @@ class StringProgram:
     def ge(self, a, b): return self._binary("ge", a, b)[0]
     def find(self, a, b): return tuple(self._binary("find", a, b))          # (found, index)
     def rfind(self, a, b): return tuple(self._binary("rfind", a, b))
-    def matches(self, a, regex): return self.op("matches_clear", a, clear=FheStringOps._regex(regex))[0]
-    def len(self, a): return self.op("len", a)[0]
-    def is_empty(self, a): return self.op("is_empty", a)[0]
-    def to_upper(self, a): return self.op("to_upper", a)[0]
-    def to_lower(self, a): return self.op("to_lower", a)[0]
-    def trim_start(self, a): return self.op("trim_start", a)[0]
-    def trim_end(self, a): return self.op("trim_end", a)[0]
-    def strip(self, a): return self.op("strip", a)[0]
+    def matches(self, a, regex): return self._binary("matches", a, FheStringOps._regex(regex))[0]
+    def len(self, a): return self._binary("len", a)[0]
+    def is_empty(self, a): return self._binary("is_empty", a)[0]
+    def to_upper(self, a): return self._binary("to_upper", a)[0]
+    def to_lower(self, a): return self._binary("to_lower", a)[0]
+    def trim_start(self, a): return self._binary("trim_start", a)[0]
+    def trim_end(self, a): return self._binary("trim_end", a)[0]
+    def strip(self, a): return self._binary("strip", a)[0]
     def strip_prefix(self, a, pat): return tuple(self._binary("strip_prefix", a, pat))      # (stripped, string)
     def strip_suffix(self, a, pat): return tuple(self._binary("strip_suffix", a, pat))
     def concat(self, a, b): return self._binary("concat", a, b)[0]
 
     def repeat(self, a, count):
         """count: a clear int (1..255), or a symbolic count: then its n_max copies at most, the capacity n_max * a.cap."""
-        if isinstance(count, ProgramValue):
-            return self.op(f"repeat:{count.n_max}", a, count)[0]
-        return self.op("repeat_clear", a, clear=bytes([count]))[0]
+        return self._call(resolve_repeat, a, count)[0]
 
     def replace(self, a, frm, to, out_cap: int | None = None):
         """As FheStringOps.replace: frm / to both clear bytes or both symbolic strings; out_cap=None is the equal-length
         in-place form."""
-        if isinstance(frm, (bytes, bytearray)):
-            if out_cap is None and len(frm) != len(to):
-                raise FheError("replace: `from` and `to` of different lengths need an output capacity (out_cap)")
-            name = "replace_clear" if out_cap is None else f"replace_clear:{len(frm)}:{out_cap}"
-            return self.op(name, a, clear=bytes(frm) + bytes(to))[0]
-        if out_cap is None and frm.cap != to.cap:
-            raise FheError("replace: `from` and `to` of different capacities need an output capacity (out_cap)")
-        return self.op("replace" if out_cap is None else f"replace:{frm.cap}:{out_cap}", a, frm, to)[0]
+        return self._call(resolve_replace, a, frm, to, out_cap=out_cap)[0]
 
     def replacen(self, a, frm, to, n, out_cap: int | None = None):
         """As FheStringOps.replacen; n: a clear int or a symbolic count."""
-        out_cap = a.cap if out_cap is None else out_cap
-        counted = isinstance(n, ProgramValue)
-        head = f"replacen_encn{{}}:{n.n_max}" if counted else f"replacen{{}}:{int(n)}"
-        tail = (n,) if counted else ()
-        if isinstance(frm, (bytes, bytearray)):
-            return self.op(head.format("_clear") + f":{len(frm)}:{out_cap}", a, *tail, clear=bytes(frm) + bytes(to))[0]
-        return self.op(head.format("") + f":{frm.cap}:{out_cap}", a, frm, to, *tail)[0]
+        return self._call(resolve_replacen, a, frm, to, n, out_cap=out_cap)[0]
 
     def _split(self, op, a, pat, max_parts, part_cap=None):
-        tail = ()
-        if isinstance(max_parts, ProgramValue):
-            if op not in ("splitn", "rsplitn"):
-                raise FheError(f"{op}: only splitn and rsplitn take an encrypted count")
-            op, tail, max_parts = op + "_encn", (max_parts,), max_parts.n_max
-        once = op in ("split_once", "rsplit_once")
-        clear = bytes(pat) if isinstance(pat, (bytes, bytearray)) else None
-        name = op + ("_clear" if clear is not None else "") + ("" if once else f":{int(max_parts)}") + (
-            f":{int(part_cap)}" if part_cap is not None else "")
-        operands = (a,) + (() if pat is None or clear is not None else (pat,)) + tail
-        res = self.op(name, *operands, clear=clear)
+        res = self._call(functools.partial(resolve_split, op), a, pat, max_parts, part_cap=part_cap)
         return ProgramSplit(res[0], res[1:])
 
     def split(self, a, pat, max_parts, part_cap=None): return self._split("split", a, pat, max_parts, part_cap)
@@ -2088,18 +1997,12 @@ class CompiledProgram:
         on the device.  Results in output order: a bit as one ciphertext row, a string as (cap*blocks, kN+1), a count as an
         EncryptedCount, a split as a SplitResult; packed=True: every string-valued result (the parts of a split
         included) as a PackedString of its own, ready to be the next operation's operand."""
-        import torch
         if self._ops is None:
             raise FheError("offline program: no engine bound")
         if len(operands) != len(self.inputs):
             raise FheError(f"the program takes {len(self.inputs)} operands, got {len(operands)}")
-        big, dev = self.params.big_size, f"cuda:{self.engine.device}"
-        xs = [self._operand(v, x) for v, x in zip(self.inputs, operands)]
-        rows = np.cumsum([0] + [v.blocks for v in self.inputs[:-1]]).tolist()
-        d_in = torch.empty((self._info["n_inputs"], big), dtype=torch.int64, device=dev)
-        d_out = torch.empty((self._info["n_outputs"], big), dtype=torch.int64, device=dev)
-        keep = self._ops._stage(d_in, list(zip(rows, xs)))
-        self.plan.run_dev(d_in.data_ptr(), d_out.data_ptr())
+        d_out, keep = self._ops._on_device("program", self.plan, [[self._operand(v, x) for v, x in zip(self.inputs, operands)]])
+        d_out = d_out[0]                                    # (one instance)
         self.engine.synchronize()
         host = None if packed and all(v.kind == "string" for o in self.outputs
                                       for v in ([o.count] + o.parts if isinstance(o, ProgramSplit) else [o])) else d_out.cpu().numpy().view(np.uint64)

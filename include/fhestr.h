@@ -465,6 +465,20 @@ int fhe_str_replacen_encn_clear(fhe_engine *eng, const uint64_t *a, uint32_t a_c
 int fhe_str_splitn_encn(fhe_engine *eng, const char *op, const uint64_t *a, uint32_t a_cap, const uint64_t *pat,
                         uint32_t pat_cap, const uint8_t *clear, uint32_t clear_len, const uint64_t *n_digits,
                         uint32_t max_parts, uint32_t part_cap, uint64_t *out, uint32_t *n_outputs);
+/* ANY FheString operation in one call, by its plan name: the single-row sibling of fhe_str_op_many below, and where every
+ * fhe_str_<operation> entry point of this section ends.  Those are shorthands: each one spells a plan name from its
+ * arguments (the names are given with them above) and calls this.  `name` is a plan name of fhe_str_plan_create with its
+ * parameters ("eq", "find_clear", "replace:2:6", "split_clear:3", "replacen_encn:1:2:6", "matches_clear").  operands: the
+ * n_operands (1..3) encrypted strings the plan takes, in its input order -- the string, then the encrypted pattern
+ * operand(s): b, or from and to (an empty `to` is left out) --, operands[i] = caps[i] * blocks ciphertexts; they are read
+ * where they lie, as parts of the plan's inputs.  n_digits: the D digit ciphertexts of an encrypted count, the plan's last
+ * inputs (NULL when the plan takes no encrypted count).  clear / clear_len: the plan's clear bytes (a pattern, from || to,
+ * the one byte of repeat_clear, a regular expression), NULL / 0 when it takes none.  out = the plan's outputs (the layout
+ * given with the operation above); *n_outputs (optional) = their number; with out == NULL the call only builds the plan
+ * and returns that number, as for fhe_str_split.  The plan is built on the first call and kept (the cache of all one-call
+ * operations: most recently used first). */
+int fhe_str_op(fhe_engine *eng, const char *name, const uint64_t *const *operands, const uint32_t *caps, uint32_t n_operands,
+               const uint64_t *n_digits, const uint8_t *clear, uint32_t clear_len, uint64_t *out, uint32_t *n_outputs);
 /* Many strings against ONE second operand in one pass (fhe_plan_run_batch on the operation's cached plan): `op` is an
  * operation name of fhe_str_plan_create ("eq", "ne", "contains", "find", "starts_with", "to_lower", ...; "<op>_clear" with
  * a clear pattern), rows = [count][a_cap * blocks] ciphertexts, b = the shared encrypted operand ([b_cap * blocks]

@@ -509,3 +509,81 @@ def test_page_locked_host_buffers_give_the_same_results(toy_k1):
     del locked, got, hit
     zero = fhestr.pinned_empty((0, 3))
     assert zero.shape == (0, 3)
+
+
+# ---- the per-operation C entry points, called directly ----
+# FheStringOps goes through the generic fhe_str_op; the fhe_str_<operation> entry points are the C clients' shorthands for
+# the same plan names and end in the same run, so their outputs are the same bits.  Shapes: a of capacity 4, patterns of
+# capacity 2, out_cap 6, n = 1 (n_max = 1).
+_PAT, _TO, _RX = b"ab", b"X", b"/a+b/"
+_ORDER = ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat")
+
+
+def _p(x):
+    import ctypes as C
+    return x.ctypes.data_as(C.c_void_p)
+
+
+def _buf(b):
+    import ctypes as C
+    return (C.c_uint8 * max(1, len(b)))(*b)
+
+
+def _entry_cases():
+    """(id, entry(lib, engine handle, operands, out) -> rc, the FheStringOps call on the same operands)"""
+    cases = []
+
+    def add(name, entry, method):
+        cases.append(pytest.param(entry, method, id=name))
+
+    for n in ("to_upper", "to_lower", "trim_start", "trim_end", "strip", "len", "is_empty"):
+        add(n, lambda L, h, x, o, n=n: getattr(L, f"fhe_str_{n}")(h, _p(x.a), 4, o), lambda ops, x, n=n: getattr(ops, n)(x.a))
+    for n in _ORDER + ("strip_prefix", "strip_suffix"):
+        add(n, lambda L, h, x, o, n=n: getattr(L, f"fhe_str_{n}")(h, _p(x.a), 4, _p(x.b), 2, o), lambda ops, x, n=n: getattr(ops, n)(x.a, x.b))
+        add(n + "_clear", lambda L, h, x, o, n=n: getattr(L, f"fhe_str_{n}_clear")(h, _p(x.a), 4, _buf(_PAT), 2, o),
+            lambda ops, x, n=n: getattr(ops, n)(x.a, _PAT))
+    add("matches_clear", lambda L, h, x, o: L.fhe_str_matches_clear(h, _p(x.a), 4, _buf(_RX), len(_RX), o), lambda ops, x: ops.matches(x.a, _RX))
+    add("replace", lambda L, h, x, o: L.fhe_str_replace(h, _p(x.a), 4, _p(np.concatenate([x.b, x.to])), 2, o), lambda ops, x: ops.replace(x.a, x.b, x.to))
+    add("replace_clear", lambda L, h, x, o: L.fhe_str_replace_clear(h, _p(x.a), 4, _buf(_PAT), _buf(b"XY"), 2, o), lambda ops, x: ops.replace(x.a, _PAT, b"XY"))
+    add("replace_clear_general", lambda L, h, x, o: L.fhe_str_replace_clear_general(h, _p(x.a), 4, _buf(_PAT), 2, _buf(_TO), 1, 6, o),
+        lambda ops, x: ops.replace(x.a, _PAT, _TO, out_cap=6))
+    add("replacen_clear", lambda L, h, x, o: L.fhe_str_replacen_clear(h, _p(x.a), 4, _buf(_PAT), 2, _buf(_TO), 1, 1, 6, o),
+        lambda ops, x: ops.replacen(x.a, _PAT, _TO, 1, out_cap=6))
+    add("replacen_encn_clear", lambda L, h, x, o: L.fhe_str_replacen_encn_clear(h, _p(x.a), 4, _buf(_PAT), 2, _buf(_TO), 1, _p(x.n.digits), 1, 6, o),
+        lambda ops, x: ops.replacen(x.a, _PAT, _TO, x.n, out_cap=6))
+    for tag, to, to_ptr, to_cap in (("", lambda x: x.to, lambda x: _p(x.to), 2), ("_empty_to", lambda x: x.empty, lambda x: None, 0)):
+        add("replace_general" + tag, lambda L, h, x, o, p=to_ptr, c=to_cap: L.fhe_str_replace_general(h, _p(x.a), 4, _p(x.b), 2, p(x), c, 6, o),
+            lambda ops, x, to=to: ops.replace(x.a, x.b, to(x), out_cap=6))
+        add("replacen" + tag, lambda L, h, x, o, p=to_ptr, c=to_cap: L.fhe_str_replacen(h, _p(x.a), 4, _p(x.b), 2, p(x), c, 1, 6, o),
+            lambda ops, x, to=to: ops.replacen(x.a, x.b, to(x), 1, out_cap=6))
+        add("replacen_encn" + tag, lambda L, h, x, o, p=to_ptr, c=to_cap: L.fhe_str_replacen_encn(h, _p(x.a), 4, _p(x.b), 2, p(x), c, _p(x.n.digits), 1, 6, o),
+            lambda ops, x, to=to: ops.replacen(x.a, x.b, to(x), x.n, out_cap=6))
+    add("repeat", lambda L, h, x, o: L.fhe_str_repeat(h, _p(x.a), 4, _p(x.n.digits), 1, o), lambda ops, x: ops.repeat(x.a, x.n))
+    add("repeat_clear", lambda L, h, x, o: L.fhe_str_repeat_clear(h, _p(x.a), 4, 1, o), lambda ops, x: ops.repeat(x.a, 1))
+    add("split", lambda L, h, x, o: L.fhe_str_split(h, b"split", _p(x.a), 4, _p(x.b), 2, None, 0, 2, 0, o, None), lambda ops, x: ops.split(x.a, x.b, 2))
+    add("split_clear", lambda L, h, x, o: L.fhe_str_split(h, b"split", _p(x.a), 4, None, 0, _buf(_PAT), 2, 2, 0, o, None),
+        lambda ops, x: ops.split(x.a, _PAT, 2))
+    add("splitn_encn", lambda L, h, x, o: L.fhe_str_splitn_encn(h, b"splitn", _p(x.a), 4, _p(x.b), 2, None, 0, _p(x.n.digits), 1, 0, o, None),
+        lambda ops, x: ops.splitn(x.a, x.b, x.n))
+    return cases
+
+
+@pytest.mark.parametrize("entry,method", _entry_cases())
+def test_c_entry_points_are_the_generic_call(toy_k1, entry, method):
+    """Every per-operation C entry point, called through ctypes, writes bit for bit what the FheStringOps method returns
+    on the host route (fhe_str_op): one plan, one run_host_parts.  With and without an occurrence of the pattern; a `to` of
+    capacity 0 goes in as a NULL pointer."""
+    import types
+    import fhestr
+    ops, P = _ops(toy_k1), gpu_engine(toy_k1).params
+    for s in (b"abXa", b"cdcd"):
+        x = types.SimpleNamespace(a=_enc(toy_k1, s, 4), b=_enc(toy_k1, _PAT, 2), to=_enc(toy_k1, _TO, 2),
+                                  empty=np.zeros((0, P.big_size), dtype=np.uint64),
+                                  n=fhestr.EncryptedCount(toy_k1.ck.encrypt_many(fhestr.encode_count(P, 1, 1)), 1))
+        res = method(ops, x)
+        if isinstance(res, fhestr.SplitResult):
+            res = [res.count] + res.parts
+        want = np.vstack([np.atleast_2d(r) for r in (res if isinstance(res, (tuple, list)) else [res])])
+        got = np.zeros_like(want)
+        assert entry(fhestr.lib(), gpu_engine(toy_k1).handle, x, _p(got)) == 0, fhestr.lib().fhe_last_error().decode()
+        assert np.array_equal(got, want), s

@@ -62,8 +62,8 @@ FAMILIES = [
     ("replacen_encn_clear:2:1:8", (8, ("count", 2)), b"bXY"), ("split_clear:2", (8,), b","), ("rsplit_once", (8, 4), None),
     ("repeat:2", (8, ("count", 2)), None), ("matches_clear", (8,), DIGITS), ("len", (8,), None),
 ]
-# what FheStringOps computes for the same calls today: (kind, blocks, capacity / n_max) of every result, 4 blocks per
-# character, counts in the digits FheStringOps._n_digits / _count_digits give
+# what FheStringOps returns for the same calls: (kind, blocks, capacity / n_max) of every result, 4 blocks per
+# character, counts in as many base-4 digits as their largest value needs
 LAYOUTS = {
     "eq": [("bit", 1, 1)], "contains_clear": [("bit", 1, 1)], "find": [("bit", 1, 1), ("count", 2, 8)], "lt": [("bit", 1, 1)],
     "to_lower": [("string", 32, 8)], "strip": [("string", 32, 8)], "concat": [("string", 48, 12)],
