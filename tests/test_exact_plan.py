@@ -37,7 +37,7 @@ def _build(name, p, world=1):
 PLANS = {O.TOY_K1.name: ["eq", "contains", "find", "to_lower", "replace_clear", "int_lt", "int_scalar_add", "mixed", "mixed_hinted"],
          O.TOY_K2.name: ["eq", "contains_clear", "find_clear", "len", "replace_clear", "int_cmux", "int_scalar_eq", "mixed", "mixed_hinted"]}
 CASES = [(p, name) for p in SHAPES for name in PLANS[p.name]]
-# eq and contains reduce their comparison bits one slice of the characters per rank (csrc/fhe_string.cpp: owner_for, then
+# eq and contains reduce their comparison bits one slice of the characters per rank (csrc/str_ops.h: owner_for, then
 # all_true / any_true per slice), so for world > 1 they are ANOTHER circuit than for world 1 (TOY_K1, world 2: eq 7 PBS
 # against 9, contains 16 against 17) and their words differ.  Every other plan here is one circuit in every world: its
 # outputs must equal world 1's word for word.

@@ -397,7 +397,7 @@ def test_compact_and_seeded_inputs(p):
 
 def _sharded_plans(rig, world):
     """(name, plan for `world`, the same circuit finalised for world 1 or None).  eq and contains reduce one slice of the
-    characters per rank (csrc/fhe_string.cpp, owner_for): for world > 1 that is another circuit than world 1's, with
+    characters per rank (csrc/str_ops.h, owner_for): for world > 1 that is another circuit than world 1's, with
     other words.  The others are one circuit in every world, so their outputs must be world 1's word for word."""
     yield "eq", rig.string_op("eq", 8, 8, None, world), None
     yield "contains", rig.string_op("contains", 8, 2, None, world), None

@@ -130,7 +130,7 @@ def test_p22_replace_to_lower_strip_64_chars(p22):
 ])
 def test_p22_replace_encrypted_pattern_64_chars_blocked_scan(p22, s, frm, to):
     """replace with an ENCRYPTED pattern and replacement on PARAM_MESSAGE_2_CARRY_2, 64 characters: the
-    leftmost non-overlapping occurrences come from the blocked scan (fhe_string.cpp: occurrences_scan; two offsets per
+    leftmost non-overlapping occurrences come from the blocked scan (str_replace.cpp: occurrences_scan; two offsets per
     chain step for these unpadded 3- and 4-character patterns), against bytes.replace; then the padded (hidden-length) form."""
     import fhestr
     ops = _ops(p22)
@@ -335,7 +335,7 @@ def test_string_ops_with_4_bit_blocks_large_n():
 
 
 def test_clear_patterns_by_classes_on_4_bit_blocks():
-    """Clear patterns on 4-bit blocks go through the class-doubling matcher (fhe_string.cpp,
+    """Clear patterns on 4-bit blocks go through the class-doubling matcher (str_match.cpp,
     window_matches_clear_classes): lengths that are and are not powers of two, repeated characters and
     self-overlapping patterns, present / absent / at both ends; contains, find, replace and strip against Python."""
     import fhestr

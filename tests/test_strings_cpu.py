@@ -136,13 +136,13 @@ def test_plan_shapes_match_survey_counts():
     # eq enc-enc 256 chars = 1024 + 69 + 5 + 1 PBS, depth 4; enc-clear = 551
     info = _plan("eq_reference", 256, 256).info()
     assert (info["n_pbs"], info["n_levels"], info["n_inputs"], info["n_outputs"]) == (1099, 4, 2048, 1)
-    # default: two blocks per PBS through the padding bit (fhe_string.cpp: packed_pair_eq)
+    # default: two blocks per PBS through the padding bit (str_ops.cpp: packed_pair_eq)
     # ... and reductions of 16 bits per lookup (Circuit::pbs_full_box) instead of the reference's 15
     assert _plan("eq", 256, 256).info()["n_pbs"] == 512 + 32 + 2 + 1
     info = _plan("eq_clear", 256, 0, b"x" * 200).info()
     assert (info["n_pbs"], info["n_levels"]) == (547, 4)
     # contains, 16-char encrypted pattern in 256 chars: AND over the 16 chars and OR over the 256 offsets lose a level each,
-    # and two pattern characters share one lookup of the (offset, character) level (fhe_string.cpp: group_match)
+    # and two pattern characters share one lookup of the (offset, character) level (str_match.cpp: group_match)
     plan = _plan("contains", 256, 16)
     assert [plan.level_info(l)["jobs"] for l in range(plan.info()["n_levels"])] == [7968, 1992, 256, 16, 1]
     plan = _plan("contains_reference", 256, 16)
@@ -565,7 +565,7 @@ def test_find_contains_over_more_than_16_offsets(toy_k1, s, pat):
 
 @pytest.mark.parametrize("pat_len", [0, 1, 2, 3, 4, 5])
 def test_two_pattern_characters_per_lookup_every_padding_position(toy_k1, pat_len):
-    """group_match (fhe_string.cpp): pairs of pattern characters share one lookup, weighted so that padding counts as a
+    """group_match (str_match.cpp): pairs of pattern characters share one lookup, weighted so that padding counts as a
     match and one wrong block of a live character cannot be made up.  Pattern capacity 5 (two pairs + a single), every
     length 0 .. 5 (the padding starts inside a pair, between pairs, nowhere), haystacks that match, that differ in the
     first / second character of a pair only, in one block only, and windows that run past the end of the haystack."""
@@ -592,7 +592,7 @@ def test_two_pattern_characters_per_lookup_every_padding_position(toy_k1, pat_le
 @pytest.mark.parametrize("s,frm", [(b"aaaaaaa", b"aa"), (b"aaaaaa", b"aaa"), (b"abaabaab", b"aba"), (b"aaaaaaaa", b"a"), (b"ababababa", b"ab"),
                                    (b"aabaabaa", b"aab"), (b"xaaaaaax", b"aaa"), (b"aaaaaaaa", b"aaa")])
 def test_replace_occurrence_recurrence_two_offsets_per_level(toy_k1, s, frm):
-    """occurrences() (fhe_string.cpp) settles two offsets per lookup level: self-overlapping patterns of every true
+    """occurrences() (str_replace.cpp) settles two offsets per lookup level: self-overlapping patterns of every true
     length inside a capacity-3 padded encrypted pattern (the blocking of the next offset depends on whether the pattern is
     longer than one character), leftmost non-overlapping selection as bytes.replace does it.  Oracle-executed."""
     import fhestr
@@ -686,7 +686,7 @@ def test_instances_sharded_over_ranks_gloo(world):
         assert calls == [slices[r][1] - slices[r][0]]
 
 
-# ---- replace with an ENCRYPTED pattern at scale: the blocked occurrence scan (fhe_string.cpp: occurrences_scan) ----
+# ---- replace with an ENCRYPTED pattern at scale: the blocked occurrence scan (str_replace.cpp: occurrences_scan) ----
 def _periodic(unit, n):
     return (unit * (n // len(unit) + 1))[:n]
 
