@@ -279,6 +279,56 @@ int fhe_engine_unpack_info(fhe_engine* eng, uint32_t info[4]) {
     API_END
 }
 
+int fhe_engine_narrow_glwes(fhe_engine* eng, const uint64_t* glwes_host, uint32_t held, uint32_t bits, uint64_t* narrow_host) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    if (held) { CHECK_PTR(glwes_host); CHECK_PTR(narrow_host); }
+    return eng->impl->narrow_glwes_host(glwes_host, held, bits, narrow_host);
+    API_END
+}
+
+int fhe_engine_narrow_glwes_dev(fhe_engine* eng, const uint64_t* d_glwes, uint32_t held, uint32_t bits, uint64_t* d_narrow) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    if (held) { CHECK_PTR(d_glwes); CHECK_PTR(d_narrow); }
+    return eng->impl->narrow_glwes_dev(d_glwes, held, bits, d_narrow);
+    API_END
+}
+
+int fhe_engine_widen_narrow_dev(fhe_engine* eng, const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint64_t* d_glwes) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    if (held) { CHECK_PTR(d_narrow); CHECK_PTR(d_glwes); }
+    return eng->impl->widen_narrow_dev(d_narrow, held, bits, d_glwes);
+    API_END
+}
+
+int fhe_engine_unpack_narrow(fhe_engine* eng, const uint64_t* narrow_host, uint32_t held, uint32_t bits, uint32_t first, uint32_t count,
+                             int refresh, uint64_t* cts_host) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    if (count) { CHECK_PTR(narrow_host); CHECK_PTR(cts_host); }
+    return eng->impl->unpack_narrow_host(narrow_host, held, bits, first, count, refresh, cts_host);
+    API_END
+}
+
+int fhe_engine_unpack_narrow_dev(fhe_engine* eng, const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count,
+                                 int refresh, uint64_t* d_cts) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    if (count) { CHECK_PTR(d_narrow); CHECK_PTR(d_cts); }
+    return eng->impl->unpack_narrow_dev(d_narrow, held, bits, first, count, refresh, d_cts);
+    API_END
+}
+
+int fhe_engine_narrow_info(fhe_engine* eng, uint32_t info[5]) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(info);
+    eng->impl->packing.narrow_info(info);
+    return 0;
+    API_END
+}
+
 int fhe_engine_cluster_fallbacks(fhe_engine* eng, uint32_t* count) {
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(count);

@@ -18,6 +18,7 @@
 
 #include "det_math.h"
 #include "engine.h"
+#include "glwe_narrow.h"
 #include "noise_model.h"
 
 namespace fhe {
@@ -196,15 +197,22 @@ static double packing_variance(const fhe_params_t& p, const fhe_packing_params_t
 // The bound a plan enforces at every PBS input (default_noise_budget): the failure probability of the reference-shaped
 // worst case, with the same slack and the same safety on shapes whose V_pbs is unmeasured.  A packed coefficient is a PBS
 // output (one nominal variance) plus the packing's own terms, decoded at delta / 2.
-static bool packing_meets_bound(const fhe_params_t& p, const fhe_packing_params_t& pp) {
+// `extra`: variance added to the coefficient after the packing (the narrowing's, narrow_noise).
+// Returns log2 of the coefficient's decoding failure probability; *target receives the bound.
+static double packed_log2_pfail(const fhe_params_t& p, const fhe_packing_params_t& pp, double extra, double* target) {
     const double max_level = (double)(p.msg_mod * p.carry_mod - 1) / (double)(p.msg_mod > 1 ? p.msg_mod - 1 : 1);
     NoiseModel m = noise_model(p);
     if (!noise_model_is_calibrated(p)) m.v_pbs *= kUncalibratedSafety;
-    const double target = m.log2_pfail(max_level * max_level) + (p.grouping_factor == 2 ? 0.0 : kPfailSlackLog2);
+    *target = m.log2_pfail(max_level * max_level) + (p.grouping_factor == 2 ? 0.0 : kPfailSlackLog2);
     NoiseModel packed = m;
-    packed.v_ks = packing_variance(p, pp);
+    packed.v_ks = packing_variance(p, pp) + extra;
     packed.v_ms = 0;
-    return packed.log2_pfail(1.0) <= target;
+    return packed.log2_pfail(1.0);
+}
+
+static bool packing_meets_bound(const fhe_params_t& p, const fhe_packing_params_t& pp) {
+    double target;
+    return packed_log2_pfail(p, pp, 0.0, &target) <= target;
 }
 
 // A packed PBS output extracted again (glwe_extract_kernels.hip.h moves words, it adds nothing): the PBS output's one
@@ -213,6 +221,21 @@ static bool packing_meets_bound(const fhe_params_t& p, const fhe_packing_params_
 void packing_unpack_noise(const fhe_params_t& p, const fhe_packing_params_t& pp, double out[2]) {
     out[0] = 1.0 + packing_variance(p, pp) / noise_model(p).v_pbs;
     out[1] = default_noise_budget(p);
+}
+
+// Narrowing to b bits (glwe_narrow.h) rounds every word of the GLWE to a multiple of 2^-b: an extracted block's phase
+// gathers the body's rounding error and, through the binary key, about k N / 2 of the mask's -- the average-case form of
+// v_ms and v_pbs_round, uniform errors of variance 2^-2b / 12 each.
+static double narrow_variance(const fhe_params_t& p, uint32_t bits) {
+    return (1.0 + (double)p.k * p.N / 2.0) / 12.0 * ldexp(1.0, -2 * (int)bits);
+}
+
+void narrow_noise(const fhe_params_t& p, const fhe_packing_params_t& pp, uint32_t bits, double out[3]) {
+    double unpack[2], target;
+    packing_unpack_noise(p, pp, unpack);
+    out[0] = unpack[0] + narrow_variance(p, bits) / noise_model(p).v_pbs;
+    out[1] = unpack[1];
+    out[2] = packed_log2_pfail(p, pp, narrow_variance(p, bits), &target);
 }
 
 // glwe_sample_extraction.rs:91-147 at coefficient c: the mask of polynomial q reversed from c downwards, the wrapped part
@@ -462,6 +485,69 @@ int fhe_packing_unpack_noise(const fhe_params_t* params, const fhe_packing_param
     if (fhe::packing_params_check(*params, *pp)) return 1;
     fhe::packing_unpack_noise(*params, *pp, out);
     return 0;
+}
+
+// ---- narrow packed results (glwe_narrow.h) ----
+int fhe_narrow_noise(const fhe_params_t* params, const fhe_packing_params_t* pp, uint32_t bits, double out[3]) {
+    if (!params || !pp || !out) return fhe::fail("null pointer");
+    out[0] = out[1] = out[2] = 0;
+    if (!fhe::narrow_bits_ok(bits)) return fhe::fail("narrow: the width must be 8 .. 32 bits");
+    if (fhe::packing_params_check(*params, *pp)) return 1;
+    fhe::narrow_noise(*params, *pp, bits, out);
+    return 0;
+}
+
+int fhe_narrow_default_bits(const fhe_params_t* params, const fhe_packing_params_t* pp, int operand, uint32_t* bits) {
+    if (!params || !pp || !bits) return fhe::fail("null pointer");
+    *bits = 0;
+    if (fhe::packing_params_check(*params, *pp)) return 1;
+    double v[3], target;
+    fhe::packed_log2_pfail(*params, *pp, 0.0, &target);
+    for (uint32_t b = fhe::NARROW_BITS_MIN; b <= fhe::NARROW_BITS_MAX; b++) {
+        fhe::narrow_noise(*params, *pp, b, v);
+        if (operand ? v[0] <= v[1] : v[2] <= target) {
+            *bits = b;
+            return 0;
+        }
+    }
+    return fhe::fail("narrow: no width of 8 .. 32 bits is " + std::string(operand ? "operand" : "client") + "-grade under the packing pair (" +
+                     std::to_string(pp->base_log) + ", " + std::to_string(pp->level) + "): at 32 bits " +
+                     (operand ? "a raw extracted block carries " + std::to_string(v[0]) + " nominal variances, the PBS-input budget is " + std::to_string(v[1])
+                              : "log2 of the decoding failure probability is " + std::to_string(v[2]) + ", the bound " + std::to_string(target)));
+}
+
+size_t fhe_narrow_len(const fhe_params_t* params, uint32_t held, uint32_t bits) {
+    return params ? fhe::narrow_len(params->N, params->k, held, bits) : 0;
+}
+
+static int narrow_answer(const char* why) { return why ? fhe::fail(why) : 0; }
+
+int fhe_glwe_narrow_host(const fhe_params_t* params, const uint64_t* glwes, uint32_t held, uint32_t bits, uint64_t* narrow) {
+    if (!params || (held && (!glwes || !narrow))) return fhe::fail("null pointer");
+    return narrow_answer(fhe::glwe_narrow(params->N, params->k, glwes, held, bits, narrow));
+}
+
+int fhe_glwe_widen_host(const fhe_params_t* params, const uint64_t* narrow, uint32_t held, uint32_t bits, uint64_t* glwes) {
+    if (!params || (held && (!glwes || !narrow))) return fhe::fail("null pointer");
+    return narrow_answer(fhe::glwe_widen(params->N, params->k, narrow, held, bits, glwes));
+}
+
+int fhe_narrow_sample_extract_host(const fhe_params_t* params, const uint64_t* narrow, uint32_t held, uint32_t bits, uint32_t first,
+                                   uint32_t count, uint64_t* cts) {
+    if (!params || (count && (!narrow || !cts))) return fhe::fail("null pointer");
+    return narrow_answer(fhe::narrow_sample_extract(params->N, params->k, narrow, held, bits, first, count, cts));
+}
+
+int fhe_client_decrypt_narrow(fhe_client_key* ck, const uint64_t* narrow, uint32_t held, uint32_t bits, uint64_t* msgs) {
+    if (!ck || (held && (!narrow || !msgs))) return fhe::fail("null pointer");
+    try {
+        const auto& c = *ck->impl;
+        std::vector<uint64_t> glwes(fhe_packed_glwe_len(&c.p, held));
+        if (narrow_answer(fhe::glwe_widen(c.p.N, c.p.k, narrow, held, bits, glwes.data()))) return 1;
+        return fhe_client_decrypt_packed(ck, glwes.data(), held, msgs);
+    } catch (const std::exception& e) {
+        return fhe::fail(e.what());
+    }
 }
 
 int fhe_client_secret_keys(fhe_client_key* ck, uint64_t* glwe_sk, uint64_t* small_sk) {

@@ -119,6 +119,10 @@ struct PackingState {
     uint32_t unpack_last[4] = {0, 0, 0, 0};         // fhe_engine_unpack_info: ran, rows, workgroups, refreshed
     void pack_info(uint32_t out[5]) const { std::copy(pack_last, pack_last + 5, out); }
     void unpack_info(uint32_t out[4]) const { std::copy(unpack_last, unpack_last + 4, out); }
+    // narrow packed results (glwe_narrow_kernels.hip.h): staging of fhe_engine_narrow_glwes / fhe_engine_unpack_narrow
+    DeviceBuffer<uint64_t> narrow_in, narrow_out;
+    uint32_t narrow_last[5] = {0, 0, 0, 0, 0};      // fhe_engine_narrow_info: ran, kernel (FHE_NARROW_KERNEL_*), list words / rows / GLWE words, workgroups, bits
+    void narrow_info(uint32_t out[5]) const { std::copy(narrow_last, narrow_last + 5, out); }
 };
 
 struct Engine {
@@ -218,6 +222,12 @@ struct Engine {
     int pack_lwes_host(const uint64_t* cts, uint32_t count, uint64_t* glwes);
     int unpack_glwes_dev(const uint64_t* d_glwes, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts);
     int unpack_glwes_host(const uint64_t* glwes, uint32_t first, uint32_t count, int refresh, uint64_t* cts);
+    int refresh_rows_dev(uint64_t* d_cts, uint32_t count);   // one ks_pbs level with the identity table, in place: what both unpack forms end with
+    int narrow_glwes_dev(const uint64_t* d_glwes, uint32_t held, uint32_t bits, uint64_t* d_narrow);
+    int widen_narrow_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint64_t* d_glwes);
+    int narrow_glwes_host(const uint64_t* glwes, uint32_t held, uint32_t bits, uint64_t* narrow);
+    int unpack_narrow_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts);
+    int unpack_narrow_host(const uint64_t* narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int refresh, uint64_t* cts);
     uint32_t rotate_registers() const;             // VGPRs of variant's rotation kernel, 0 if unknown
     void keyswitch_info(uint32_t info[6]) const;   // ks_last and the register count shadow_keyswitch_fits judges by; changes nothing
     int ks_pbs_dev(const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint64_t* d_big_out, uint32_t count, bool allow_pipeline = false);
@@ -250,6 +260,9 @@ int params_supported(const fhe_params_t& p);   // 0, or 1 with the reason in fhe
 int packing_params_check(const fhe_params_t& p, const fhe_packing_params_t& pp);
 // client.cpp: out[0] variance of a raw extracted block of a packed PBS output in nominal units, out[1] the PBS-input budget
 void packing_unpack_noise(const fhe_params_t& p, const fhe_packing_params_t& pp, double out[2]);
+// client.cpp: the same block after the GLWE was narrowed to `bits` (glwe_narrow.h): out[0] its variance in nominal units,
+// out[1] the PBS-input budget, out[2] log2 of the probability that the client decodes such a coefficient wrongly
+void narrow_noise(const fhe_params_t& p, const fhe_packing_params_t& pp, uint32_t bits, double out[3]);
 
 }  // namespace fhe
 

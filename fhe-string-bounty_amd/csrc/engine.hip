@@ -26,6 +26,7 @@
 #include "ks_mfma_kernels.hip.h"
 #include "packing_ks_kernels.hip.h"
 #include "glwe_extract_kernels.hip.h"
+#include "glwe_narrow_kernels.hip.h"
 #include "seeded_kernels.hip.h"
 #include "compact_kernels.hip.h"
 
@@ -523,6 +524,14 @@ int Engine::unpack_glwes_dev(const uint64_t* d_glwes, uint32_t first, uint32_t c
     packing.unpack_last[0] = 1; packing.unpack_last[1] = count; packing.unpack_last[2] = count * chunks; packing.unpack_last[3] = 0;
     HIP_TRY(hipGetLastError());
     if (!refresh) return 0;
+    if (refresh_rows_dev(d_cts, count)) return 1;
+    packing.unpack_last[3] = 1;
+    return 0;
+}
+
+// The refresh of both unpack forms: count extracted rows at d_cts through one keyswitch + PBS with the identity table over
+// the whole message-and-carry space, in place, on the engine's stream.
+int Engine::refresh_rows_dev(uint64_t* d_cts, uint32_t count) {
     const uint32_t M = p.msg_mod * p.carry_mod;
     std::vector<uint64_t> table(M), acc;
     for (uint32_t x = 0; x < M; x++) table[x] = x;
@@ -531,9 +540,7 @@ int Engine::unpack_glwes_dev(const uint64_t* d_glwes, uint32_t first, uint32_t c
     if (lut_upload_dedup(acc, &id)) return 1;
     if (reserve_idle(packing.unpack_idx, (size_t)count * 4)) return 1;   // an earlier refresh may still read the smaller array
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)packing.unpack_idx.ptr, (int)id, count, stream));
-    if (ks_pbs_dev(d_cts, packing.unpack_idx, d_cts, count)) return 1;   // the keyswitch has read every row before the rotation writes one
-    packing.unpack_last[3] = 1;
-    return 0;
+    return ks_pbs_dev(d_cts, packing.unpack_idx, d_cts, count);   // the keyswitch has read every row before the rotation writes one
 }
 
 int Engine::unpack_glwes_host(const uint64_t* glwes, uint32_t first, uint32_t count, int refresh, uint64_t* cts) {
@@ -545,6 +552,99 @@ int Engine::unpack_glwes_host(const uint64_t* glwes, uint32_t first, uint32_t co
     if (reserve_idle(packing.unpack_in, in_words * 8) || reserve_idle(packing.unpack_out, count * big * 8)) return 1;
     HIP_TRY(hipMemcpyAsync(packing.unpack_in, glwes + (size_t)g_lo * glwe_len, in_words * 8, hipMemcpyHostToDevice, stream));
     if (unpack_glwes_dev(packing.unpack_in, first % p.N, count, refresh, packing.unpack_out)) return 1;
+    HIP_TRY(hipMemcpyAsync(cts, packing.unpack_out, count * big * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return refresh ? multi_cu.check() : 0;
+}
+
+// ---- narrow packed results (glwe_narrow.h, glwe_narrow_kernels.hip.h) -------------------------------------------------
+// The packed GLWEs of `held` blocks at d_glwes (what pack_lwes_dev wrote) -> their narrow list at d_narrow, narrow_len
+// words.  Ordered on the engine's stream under pack_lwes_dev's contract.
+int Engine::narrow_glwes_dev(const uint64_t* d_glwes, uint32_t held, uint32_t bits, uint64_t* d_narrow) {
+    if (use()) return 1;
+    const uint64_t words = narrow_len(p.N, p.k, held, bits);
+    if (!words) return held ? fail("narrow_glwes: the width must be 8 .. 32 bits and the polynomial size a power of two") : 0;
+    if (leave_pipelined_run()) return 1;
+    const uint32_t kN = p.k * p.N, stride = (uint32_t)narrow_stream_words((size_t)kN + p.N, bits);
+    const uint64_t wgs = (words + 255) / 256;
+    if (wgs > 0x7FFFFFFFull) return fail("narrow_glwes: too many blocks for one launch");
+    hipLaunchKernelGGL(glwe_narrow_kernel, dim3((uint32_t)wgs), dim3(256), 0, stream, d_glwes, d_narrow, p.N, kN, held, bits, stride, words);
+    const uint32_t last[5] = {1, FHE_NARROW_KERNEL_NARROW, (uint32_t)words, (uint32_t)wgs, bits};
+    std::copy(last, last + 5, packing.narrow_last);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The inverse layout change on the device: the narrow list at d_narrow -> ceil(held / N) full GLWEs at d_glwes, what
+// unpack_glwes_dev reads.  Same contract.
+int Engine::widen_narrow_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint64_t* d_glwes) {
+    if (use()) return 1;
+    if (!narrow_len(p.N, p.k, held, bits)) return held ? fail("widen_narrow: the width must be 8 .. 32 bits and the polynomial size a power of two") : 0;
+    if (leave_pipelined_run()) return 1;
+    const uint32_t kN = p.k * p.N, stride = (uint32_t)narrow_stream_words((size_t)kN + p.N, bits);
+    const uint64_t words = (((uint64_t)held + p.N - 1) / p.N) * ((uint64_t)kN + p.N), wgs = (words + 255) / 256;
+    if (wgs > 0x7FFFFFFFull) return fail("widen_narrow: too many blocks for one launch");
+    hipLaunchKernelGGL(glwe_widen_kernel, dim3((uint32_t)wgs), dim3(256), 0, stream, d_narrow, d_glwes, p.N, kN, held, bits, stride, words);
+    const uint32_t last[5] = {1, FHE_NARROW_KERNEL_WIDEN, (uint32_t)words, (uint32_t)wgs, bits};
+    std::copy(last, last + 5, packing.narrow_last);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int Engine::narrow_glwes_host(const uint64_t* glwes, uint32_t held, uint32_t bits, uint64_t* narrow) {
+    if (use()) return 1;
+    const size_t words = narrow_len(p.N, p.k, held, bits), in_words = (size_t)(((uint64_t)held + p.N - 1) / p.N) * (p.k + 1) * p.N;
+    if (!words) return narrow_glwes_dev(nullptr, held, bits, nullptr);      // nothing held, or the refusal
+    if (reserve_idle(packing.narrow_in, in_words * 8) || reserve_idle(packing.narrow_out, words * 8)) return 1;
+    HIP_TRY(hipMemcpyAsync(packing.narrow_in, glwes, in_words * 8, hipMemcpyHostToDevice, stream));
+    if (narrow_glwes_dev(packing.narrow_in, held, bits, packing.narrow_out)) return 1;
+    HIP_TRY(hipMemcpyAsync(narrow, packing.narrow_out, words * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return 0;
+}
+
+// Blocks first .. first + count - 1 of the narrow list of `held` blocks at d_narrow -> count big-key LWEs at d_cts: the
+// rows unpack_glwes_dev would extract from the widened GLWEs, under its contract on streams and alignment.  The refresh is
+// judged with the narrowing's term on top of the packing's (narrow_noise).
+int Engine::unpack_narrow_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts) {
+    if (use()) return 1;
+    if (!narrow_bits_ok(bits)) return fail("unpack_narrow: the width must be 8 .. 32 bits");
+    if (!narrow_len(p.N, p.k, 1, bits)) return fail("unpack_narrow: polynomial size must be a power of two, (k + 1) N below 2^27");
+    if ((uint64_t)first + count > held)
+        return fail("unpack_narrow: blocks " + std::to_string(first) + " .. " + std::to_string((uint64_t)first + count) + " asked of a list that holds " + std::to_string(held));
+    if (count == 0) return 0;
+    if (refresh) {
+        if (!packing.key) return fail("unpack_narrow: the refresh needs the loaded packing key's decomposition to judge the blocks' noise; none is loaded");
+        double v[3];
+        narrow_noise(p, packing.pp, bits, v);
+        if (!(v[0] <= v[1]))
+            return fail("unpack_narrow: refresh refused, a raw block extracted at " + std::to_string(bits) + " bits under the packing pair (" +
+                        std::to_string(packing.pp.base_log) + ", " + std::to_string(packing.pp.level) + ") carries " + std::to_string(v[0]) +
+                        " nominal variances, the PBS-input budget is " + std::to_string(v[1]));
+    }
+    if (leave_pipelined_run()) return 1;
+    const uint32_t kN = p.k * p.N, stride = (uint32_t)narrow_stream_words((size_t)kN + p.N, bits);
+    const uint32_t chunks = (kN / 2 + GLWE_EXTRACT_PAIRS_PER_WG - 1) / GLWE_EXTRACT_PAIRS_PER_WG;
+    if ((uint64_t)count * chunks > 0x7FFFFFFFull) return fail("unpack_narrow: too many ciphertexts for one launch");
+    hipLaunchKernelGGL(narrow_sample_extract_kernel, dim3(count * chunks), dim3(256), 0, stream, d_narrow, d_cts, p.N, kN, held, bits, stride, first,
+                       count, chunks);
+    const uint32_t last[5] = {1, FHE_NARROW_KERNEL_EXTRACT, count, count * chunks, bits};
+    std::copy(last, last + 5, packing.narrow_last);
+    HIP_TRY(hipGetLastError());
+    return refresh ? refresh_rows_dev(d_cts, count) : 0;
+}
+
+int Engine::unpack_narrow_host(const uint64_t* narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int refresh, uint64_t* cts) {
+    if (use()) return 1;
+    if (count == 0 || !narrow_len(p.N, p.k, held, bits) || (uint64_t)first + count > held)
+        return unpack_narrow_dev(nullptr, held, bits, first, count, refresh, nullptr);   // nothing to do, or the refusal
+    const size_t big = (size_t)p.k * p.N + 1, stride = narrow_stream_words((size_t)(p.k + 1) * p.N, bits);
+    const uint32_t g_lo = first / p.N, g_hi = (first + count - 1) / p.N;     // only the streams the range touches go up
+    const uint32_t held_up = std::min<uint64_t>(held, ((uint64_t)g_hi + 1) * p.N) - g_lo * p.N;   // a list of its own: streams g_lo .. g_hi
+    const size_t in_words = narrow_len(p.N, p.k, held_up, bits);
+    if (reserve_idle(packing.narrow_in, in_words * 8) || reserve_idle(packing.unpack_out, count * big * 8)) return 1;
+    HIP_TRY(hipMemcpyAsync(packing.narrow_in, narrow + (size_t)g_lo * stride, in_words * 8, hipMemcpyHostToDevice, stream));
+    if (unpack_narrow_dev(packing.narrow_in, held_up, bits, first - g_lo * p.N, count, refresh, packing.unpack_out)) return 1;
     HIP_TRY(hipMemcpyAsync(cts, packing.unpack_out, count * big * 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return refresh ? multi_cu.check() : 0;

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "glwe_narrow.h"
 
 namespace {
 
@@ -460,6 +461,54 @@ int fhe_wire_read_glwe_list(const fhe_params_t* p, const uint8_t* in, size_t in_
     for (uint64_t g = 0; g < n; g++)
         if (glwe_body_read(r, p, glwes + (size_t)g * (p->k + 1) * p->N)) return 1;
     *n_glwes = (uint32_t)n;
+    if (consumed) *consumed = r.pos;
+    return 0;
+}
+
+// The narrow list (glwe_narrow.h) is this project's own container: glwe_dimension, polynomial_size, bits and held as u64,
+// then a bincode Vec<u64> of the words.
+int fhe_wire_write_narrow_list(const fhe_params_t* p, const uint64_t* narrow, uint32_t held, uint32_t bits, uint8_t* out, size_t out_cap,
+                               size_t* written) {
+    if (!p || (held && !narrow)) return fail("null pointer");
+    const size_t words = fhe::narrow_len(p->N, p->k, held, bits);
+    if (held && !words) return fail("narrow list: the width must be 8 .. 32 bits and the polynomial size a power of two");
+    if (const char* why = fhe::narrow_tail_check(p->N, p->k, narrow, held, bits)) return fail(why);
+    Writer w{out, out_cap};
+    w.u64(p->k);
+    w.u64(p->N);
+    w.u64(bits);
+    w.u64(held);
+    w.vec_u64(narrow, words);
+    return finish(w, written);
+}
+
+int fhe_wire_read_narrow_list(const fhe_params_t* p, const uint8_t* in, size_t in_len, uint64_t* narrow, size_t narrow_cap_words,
+                              uint32_t max_held, uint32_t* held, uint32_t* bits, size_t* consumed) {
+    if (!p || !in || !held || !bits) return fail("null pointer");
+    Reader r{in, in_len};
+    const uint64_t k = r.u64(), N = r.u64(), b = r.u64(), h = r.u64();
+    if (!r.err.empty()) return fail("narrow list: " + r.err);
+    if (k != p->k || N != p->N)
+        return fail("narrow list does not match the parameter set (glwe dimension " + std::to_string(k) + ", polynomial size " + std::to_string(N) + ")");
+    if (b < fhe::NARROW_BITS_MIN || b > fhe::NARROW_BITS_MAX) return fail("narrow list: a width of " + std::to_string(b) + " bits, 8 .. 32 are valid");
+    if (h > max_held) return fail("narrow list: " + std::to_string(h) + " blocks, the caller accepts " + std::to_string(max_held));
+    const size_t want = fhe::narrow_len(p->N, p->k, (uint32_t)h, (uint32_t)b);
+    if (h && !want) return fail("narrow list: unsupported polynomial size");
+    const size_t at = r.pos;
+    const uint64_t n = r.u64();
+    if (!r.err.empty()) return fail("narrow list: " + r.err);
+    if (n != want) return fail("narrow list: " + std::to_string(n) + " words, " + std::to_string(h) + " blocks at " + std::to_string(b) + " bits take " + std::to_string(want));
+    if (n > (r.len - r.pos) / 8) return fail("narrow list: truncated input");
+    *held = (uint32_t)h;
+    *bits = (uint32_t)b;
+    if (!narrow) {                                          // the header only: size the buffer with fhe_narrow_len and call again
+        if (consumed) *consumed = at;
+        return 0;
+    }
+    if (want > narrow_cap_words) return fail("narrow list: " + std::to_string(want) + " words, the destination holds " + std::to_string(narrow_cap_words));
+    std::memcpy(narrow, in + r.pos, want * 8);
+    r.pos += want * 8;
+    if (const char* why = fhe::narrow_tail_check(p->N, p->k, narrow, *held, *bits)) return fail(why);
     if (consumed) *consumed = r.pos;
     return 0;
 }

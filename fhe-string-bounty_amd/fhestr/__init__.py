@@ -170,6 +170,10 @@ EXPORTS = [
     "fhe_wire_write_glwe_ciphertext", "fhe_wire_read_glwe_ciphertext", "fhe_wire_write_glwe_list", "fhe_wire_read_glwe_list",
     "fhe_glwe_sample_extract_host", "fhe_packing_unpack_noise", "fhe_engine_unpack_glwes", "fhe_engine_unpack_glwes_dev",
     "fhe_engine_unpack_info",
+    "fhe_narrow_noise", "fhe_narrow_default_bits", "fhe_narrow_len", "fhe_glwe_narrow_host", "fhe_glwe_widen_host",
+    "fhe_narrow_sample_extract_host", "fhe_client_decrypt_narrow", "fhe_engine_narrow_glwes", "fhe_engine_narrow_glwes_dev",
+    "fhe_engine_widen_narrow_dev", "fhe_engine_unpack_narrow", "fhe_engine_unpack_narrow_dev", "fhe_engine_narrow_info", "fhe_wire_write_narrow_list",
+    "fhe_wire_read_narrow_list",
 ] + [f"fhe_str_{n}{s}" for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat")
      for s in ("", "_clear")] + ["fhe_str_repeat_clear", "fhe_str_split", "fhe_str_replacen", "fhe_str_replacen_clear",
                                    "fhe_str_repeat", "fhe_str_replacen_encn", "fhe_str_replacen_encn_clear", "fhe_str_splitn_encn",
@@ -354,6 +358,22 @@ def lib() -> C.CDLL:
     sig("fhe_engine_unpack_glwes", vp, vp, u32, u32, i32, vp)
     sig("fhe_engine_unpack_glwes_dev", vp, vp, u32, u32, i32, vp)
     sig("fhe_engine_unpack_info", vp, C.POINTER(u32))
+    sig("fhe_narrow_noise", PP, KP, u32, C.POINTER(C.c_double))
+    sig("fhe_narrow_default_bits", PP, KP, i32, C.POINTER(u32))
+    L.fhe_narrow_len.restype = C.c_size_t
+    L.fhe_narrow_len.argtypes = [PP, u32, u32]
+    sig("fhe_glwe_narrow_host", PP, vp, u32, u32, vp)
+    sig("fhe_glwe_widen_host", PP, vp, u32, u32, vp)
+    sig("fhe_narrow_sample_extract_host", PP, vp, u32, u32, u32, u32, vp)
+    sig("fhe_client_decrypt_narrow", vp, vp, u32, u32, vp)
+    sig("fhe_engine_narrow_glwes", vp, vp, u32, u32, vp)
+    sig("fhe_engine_narrow_glwes_dev", vp, vp, u32, u32, vp)
+    sig("fhe_engine_widen_narrow_dev", vp, vp, u32, u32, vp)
+    sig("fhe_engine_unpack_narrow", vp, vp, u32, u32, u32, u32, i32, vp)
+    sig("fhe_engine_unpack_narrow_dev", vp, vp, u32, u32, u32, u32, i32, vp)
+    sig("fhe_engine_narrow_info", vp, C.POINTER(u32))
+    sig("fhe_wire_write_narrow_list", PP, vp, u32, u32, vp, C.c_size_t, C.POINTER(C.c_size_t))
+    sig("fhe_wire_read_narrow_list", PP, vp, C.c_size_t, vp, C.c_size_t, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_size_t))
     for name in ("fhe_params_ksk_len", "fhe_params_bsk_len"):
         getattr(L, name).restype = C.c_size_t
         getattr(L, name).argtypes = [PP]
@@ -676,6 +696,103 @@ class Engine:
         if pksk.size != n:
             raise FheError("packing key: size does not match the parameter set and decomposition")
         _check(lib().fhe_engine_load_packing_key(self._h, C.byref(_pp(pp)), _ptr(pksk)))
+        self.packing_pair = (int(pp[0]), int(pp[1]))        # what Narrow(bits=None) takes its default width for
+
+    def narrow(self, glwes=None, held: int | None = None, bits: int | None = None, d_in: int | None = None, d_out: int | None = None):
+        """Packed GLWEs narrowed to `bits`-bit coefficients on the GPU (csrc/glwe_narrow_kernels.hip.h; the definition:
+        include/fhestr.h, "narrow packed results"): the GLWEs of `held` blocks -> narrow_len(params, held, bits) words.
+        glwes: a host array (Engine.pack's, a PackedString gives `held` itself) -> returns a NarrowString; or a torch device
+        tensor / d_in: the GLWEs where Engine.pack(d_out=...) wrote them.  With d_out the list is written there
+        (asynchronous on the engine's stream) and nothing is returned.  bits=None: the operand-grade default for the
+        loaded packing key's pair (narrow_default_bits)."""
+        p = self.params
+        if glwes is not None and hasattr(glwes, "data_ptr"):
+            keep, d_in = glwes, glwes.data_ptr()
+        if held is None:
+            held = getattr(glwes, "count", None)
+        if held is None:
+            raise FheError("narrow: the number of blocks the GLWEs hold is required")
+        if bits is None:
+            bits = self._default_narrow_bits()
+        words = narrow_len(p, held, bits)
+        if held and not words:
+            raise FheError(f"narrow: a width of {bits} bits is refused (8 .. 32)")
+        if d_in:
+            if d_out:
+                _check(lib().fhe_engine_narrow_glwes_dev(self._h, C.c_void_p(d_in), held, bits, C.c_void_p(d_out)))
+                return None
+            import torch
+            out = torch.empty((max(words, 1),), dtype=torch.int64, device=f"cuda:{self.device}")
+            torch.cuda.synchronize()
+            _check(lib().fhe_engine_narrow_glwes_dev(self._h, C.c_void_p(d_in), held, bits, C.c_void_p(out.data_ptr())))
+            self.synchronize()
+            return NarrowString(out[:words].cpu().numpy().view(np.uint64), held, held // blocks_per_char(p), bits)
+        glwes = _u64(glwes).reshape(-1)
+        if glwes.size != packed_glwe_len(p, held):
+            raise FheError(f"narrow: {glwes.size} words are not the packed GLWEs of {held} blocks of this parameter set")
+        out = np.zeros(words, dtype=np.uint64)
+        _check(lib().fhe_engine_narrow_glwes(self._h, _ptr(glwes), held, bits, _ptr(out)))
+        return NarrowString(out, held, held // blocks_per_char(p), bits)
+
+    def widen(self, d_in: int, held: int, bits: int, d_out: int):
+        """A narrow list on the device back to full GLWEs on the device (fhe_engine_widen_narrow_dev): d_out receives
+        packed_glwe_len(params, held) words, what Engine.unpack(d_in=...) reads.  Asynchronous on the engine's stream."""
+        _check(lib().fhe_engine_widen_narrow_dev(self._h, C.c_void_p(d_in), held, bits, C.c_void_p(d_out)))
+
+    def _default_narrow_bits(self) -> int:
+        pair = getattr(self, "packing_pair", None)
+        if pair is None:
+            raise FheError("Narrow(bits=None) takes its width from the packing pair given to load_packing_key; none is loaded")
+        return narrow_default_bits(self.params, pair, operand=True)
+
+    def unpack_narrow(self, narrow=None, held: int | None = None, bits: int | None = None, count: int | None = None, first: int = 0,
+                      refresh: bool = True, d_in: int | None = None, d_out: int | None = None):
+        """Blocks first .. first + count - 1 of a narrow list back into big-key LWEs on the GPU, extracted straight from
+        the list (narrow_sample_extract_kernel): the rows Engine.unpack gives on the widened GLWEs, with the same meaning of
+        refresh, d_in and d_out.  narrow: a NarrowString (which brings held and bits), a host array, or a torch device
+        tensor / d_in.  count=None: all blocks from `first` on.  The refresh is judged with narrow_noise for the loaded
+        packing key's pair and `bits`."""
+        p = self.params
+        if narrow is not None and hasattr(narrow, "data_ptr"):
+            keep, d_in = narrow, narrow.data_ptr()
+        held = getattr(narrow, "count", None) if held is None else held
+        bits = getattr(narrow, "bits", None) if bits is None else bits
+        if held is None or bits is None:
+            raise FheError("unpack_narrow: the blocks the list holds and its width are required")
+        if count is None:
+            count = held - first
+        args = (held, bits, first, count, int(bool(refresh)))
+        if d_in:
+            if d_out:
+                _check(lib().fhe_engine_unpack_narrow_dev(self._h, C.c_void_p(d_in), *args, C.c_void_p(d_out)))
+                return None
+            import torch
+            out = torch.empty((max(count, 0), p.big_size), dtype=torch.int64, device=f"cuda:{self.device}")
+            torch.cuda.synchronize()
+            _check(lib().fhe_engine_unpack_narrow_dev(self._h, C.c_void_p(d_in), *args, C.c_void_p(out.data_ptr())))
+            self.synchronize()
+            return out.cpu().numpy().view(np.uint64)
+        narrow = _u64(narrow).reshape(-1)
+        if narrow.size != narrow_len(p, held, bits):
+            raise FheError(f"unpack_narrow: {narrow.size} words are not the narrow list of {held} blocks at {bits} bits of this parameter set")
+        if d_out:
+            import torch
+            d_narrow = torch.from_numpy(narrow.view(np.int64)).to(f"cuda:{self.device}")
+            torch.cuda.synchronize()
+            _check(lib().fhe_engine_unpack_narrow_dev(self._h, C.c_void_p(d_narrow.data_ptr()), *args, C.c_void_p(d_out)))
+            self.synchronize()                              # d_narrow is released on return
+            return None
+        out = np.zeros((max(count, 0), p.big_size), dtype=np.uint64)
+        _check(lib().fhe_engine_unpack_narrow(self._h, _ptr(narrow), *args, _ptr(out)))
+        return out
+
+    def narrow_info(self) -> dict:
+        """What the last narrow / unpack_narrow launched (fhe_engine_narrow_info), recorded when it was enqueued: `kernel`
+        is "narrow" (then `items` counts the list's words), "extract" (rows) or "widen" (GLWE words)."""
+        a = (C.c_uint32 * 5)()
+        _check(lib().fhe_engine_narrow_info(self._h, a))
+        ran, kernel, items, workgroups, bits = (int(x) for x in a)
+        return {"ran": bool(ran), "kernel": {0: None, 1: "narrow", 2: "extract", 3: "widen"}[kernel], "items": items, "workgroups": workgroups, "bits": bits}
 
     def pack(self, cts=None, count: int | None = None, d_in: int | None = None, d_out: int | None = None):
         """Packing keyswitch on the GPU (csrc/packing_ks_kernels.hip.h): big-key LWEs -> ceil(count / N) GLWEs, LWE j at
@@ -918,6 +1035,20 @@ class ClientKey:
         _check(lib().fhe_client_decrypt_packed(self._h, _ptr(glwes), count, _ptr(out)))
         return out.astype(np.int64)
 
+    def decrypt_narrow(self, narrow, held: int | None = None, bits: int | None = None) -> np.ndarray:
+        """message-and-carry value of the `held` blocks of a narrow list (Engine.narrow, packed=Narrow()): the phase of the
+        widened GLWEs, decoded like decrypt_packed.  A NarrowString brings held and bits itself."""
+        held = getattr(narrow, "count", None) if held is None else held
+        bits = getattr(narrow, "bits", None) if bits is None else bits
+        if held is None or bits is None:
+            raise FheError("decrypt_narrow: the blocks the list holds and its width are required")
+        narrow = _u64(narrow).reshape(-1)
+        if narrow.size != narrow_len(self.params, held, bits):
+            raise FheError(f"decrypt_narrow: {narrow.size} words are not the narrow list of {held} blocks at {bits} bits of this parameter set")
+        out = np.zeros(held, dtype=np.uint64)
+        _check(lib().fhe_client_decrypt_narrow(self._h, _ptr(narrow), held, bits, _ptr(out)))
+        return out.astype(np.int64)
+
     def secret_keys(self):
         p = self.params
         g = np.zeros(p.k * p.N, dtype=np.uint64)
@@ -994,6 +1125,99 @@ class PackedString(np.ndarray):
     def __array_finalize__(self, obj):
         self.count = getattr(obj, "count", 0)
         self.capacity = getattr(obj, "capacity", 0)
+
+
+def narrow_len(params: Params, held: int, bits: int) -> int:
+    """u64 words of the narrow list of `held` packed blocks at `bits` bits (fhe_narrow_len); 0 = refused (bits outside 8 .. 32)."""
+    return int(lib().fhe_narrow_len(C.byref(params.c()), held, bits))
+
+
+def narrow_noise(params: Params, pp, bits: int) -> tuple:
+    """(variance of a raw block extracted from a packed PBS output narrowed to `bits`, in nominal units; the default
+    PBS-input budget; log2 of the probability that the client decodes such a coefficient wrongly): fhe_narrow_noise."""
+    a = (C.c_double * 3)()
+    _check(lib().fhe_narrow_noise(C.byref(params.c()), C.byref(_pp(pp)), bits, a))
+    return float(a[0]), float(a[1]), float(a[2])
+
+
+def narrow_default_bits(params: Params, pp, operand: bool = True) -> int:
+    """The smallest width a narrow list may have under the packing pair pp: operand=True, to come back as an operand
+    (Engine.unpack_narrow with refresh); operand=False, to be decrypted by the client.  Raises when no width qualifies."""
+    bits = C.c_uint32()
+    _check(lib().fhe_narrow_default_bits(C.byref(params.c()), C.byref(_pp(pp)), int(bool(operand)), C.byref(bits)))
+    return int(bits.value)
+
+
+def glwe_narrow_host(params: Params, glwes, held: int, bits: int) -> np.ndarray:
+    """Narrowing as a plain CPU loop (fhe_glwe_narrow_host): the packed GLWEs of `held` blocks -> narrow_len words.
+    Bit-identical to Engine.narrow."""
+    glwes = _u64(glwes).reshape(-1)
+    if glwes.size != packed_glwe_len(params, held):
+        raise FheError(f"glwe_narrow_host: {glwes.size} words are not the packed GLWEs of {held} blocks of this parameter set")
+    words = narrow_len(params, held, bits)
+    if held and not words:
+        raise FheError(f"glwe_narrow_host: a width of {bits} bits is refused (8 .. 32)")
+    out = np.zeros(words, dtype=np.uint64)
+    _check(lib().fhe_glwe_narrow_host(C.byref(params.c()), _ptr(glwes), held, bits, _ptr(out)))
+    return out
+
+
+def _narrow_words(what, params, narrow, held, bits):
+    narrow = _u64(narrow).reshape(-1)
+    if narrow.size != narrow_len(params, held, bits) or (held and not narrow.size):
+        raise FheError(f"{what}: {narrow.size} words are not the narrow list of {held} blocks at {bits} bits of this parameter set")
+    return narrow
+
+
+def glwe_widen_host(params: Params, narrow, held: int, bits: int) -> np.ndarray:
+    """A narrow list back to full GLWEs (fhe_glwe_widen_host): (n_glwe, k+1, N), the body coefficients that hold no block 0."""
+    narrow = _narrow_words("glwe_widen_host", params, narrow, held, bits)
+    out = np.zeros((-(-held // params.N), params.k + 1, params.N), dtype=np.uint64)
+    _check(lib().fhe_glwe_widen_host(C.byref(params.c()), _ptr(narrow), held, bits, _ptr(out)))
+    return out
+
+
+def narrow_sample_extract_host(params: Params, narrow, held: int, bits: int, count: int, first: int = 0) -> np.ndarray:
+    """Sample extraction straight from a narrow list as a plain CPU loop (fhe_narrow_sample_extract_host): (count, kN+1),
+    word for word glwe_sample_extract_host of glwe_widen_host.  Bit-identical to Engine.unpack_narrow(..., refresh=False)."""
+    narrow = _narrow_words("narrow_sample_extract_host", params, narrow, held, bits)
+    out = np.zeros((count, params.big_size), dtype=np.uint64)
+    _check(lib().fhe_narrow_sample_extract_host(C.byref(params.c()), _ptr(narrow), held, bits, first, count, _ptr(out)))
+    return out
+
+
+class NarrowString(np.ndarray):
+    """Narrow packed results as a value that goes back in: the words of the narrow list as one row (1, narrow_len) -- so
+    that x[0] of a one-output operation keeps the type, like a PackedString's -- with `count`, the blocks it holds,
+    `capacity`, count // blocks per character, and `bits`, the width of a coefficient.  ClientKey.decrypt_narrow and
+    Engine.unpack_narrow take it as it is; every FheStringOps method accepts it in place of an expanded operand."""
+
+    def __new__(cls, words, count: int, capacity: int, bits: int):
+        obj = _u64(words).reshape(1, -1).view(cls)
+        obj.count, obj.capacity, obj.bits = int(count), int(capacity), int(bits)
+        return obj
+
+    def __array_finalize__(self, obj):
+        self.count = getattr(obj, "count", 0)
+        self.capacity = getattr(obj, "capacity", 0)
+        self.bits = getattr(obj, "bits", 0)
+
+
+_PACKED = (PackedString, NarrowString)     # the operand forms that go up packed and are unpacked, with refresh, on the device
+
+
+class Narrow:
+    """packed=Narrow(bits): like packed=True, and the packed result is narrowed on the device to `bits`-bit coefficients
+    (Engine.narrow); only the narrow words come back, as a NarrowString.  bits=None: the operand-grade default for the
+    packing pair given to Engine.load_packing_key, so the result may go straight into the next operation; a result meant
+    for the client alone may take narrow_default_bits(params, pp, operand=False)."""
+    __slots__ = ("bits",)
+
+    def __init__(self, bits: int | None = None):
+        self.bits = None if bits is None else int(bits)
+
+    def __bool__(self):
+        return True
 
 
 def compact_pk_len(params: Params) -> int:
@@ -1297,7 +1521,7 @@ def encode_count(params: Params, n: int, n_max: int) -> np.ndarray:
 class EncryptedCount:
     """An encrypted count for FheStringOps.repeat / replacen / splitn / rsplitn: `digits`, the ciphertexts of its
     little-endian base-msg_mod digits -- fresh encryptions of encode_count(...), or what len, find / rfind (without the
-    found block) or a split's count returned, expanded (D, kN+1) or a PackedString -- and the public bound `n_max` that
+    found block) or a split's count returned, expanded (D, kN+1), a PackedString or a NarrowString -- and the public bound `n_max` that
     travels with them.  n_max=None: the largest value the digits hold, msg_mod^D - 1 (needs `params`)."""
     __slots__ = ("digits", "n_max")
 
@@ -1306,7 +1530,7 @@ class EncryptedCount:
         if n_max is None:
             if params is None:
                 raise FheError("EncryptedCount: give n_max, or params to take the largest value the digits hold")
-            d = digits.count if isinstance(digits, PackedString) else int(np.asarray(digits).shape[0])
+            d = digits.count if isinstance(digits, _PACKED) else int(np.asarray(digits).shape[0])
             n_max = params.msg_mod ** d - 1
         if int(n_max) < 1:
             raise FheError("an encrypted count needs a bound n_max >= 1")
@@ -1462,7 +1686,7 @@ class FheStringOps:
         info = plan.info()
 
         def size(x):
-            return x.count if isinstance(x, PackedString) else x.shape[0]
+            return x.count if isinstance(x, _PACKED) else x.shape[0]
 
         n_shared = sum(map(size, shared))
         for xs in rows:
@@ -1471,11 +1695,11 @@ class FheStringOps:
         d_in = torch.empty((len(rows), info["n_inputs"], big), dtype=torch.int64, device=dev)
         d_out = torch.empty((len(rows), info["n_outputs"], big), dtype=torch.int64, device=dev)
         flat = d_in.view(-1, big)
-        todo = []                                           # (first row, blocks, GLWEs on the device) of the packed operands
+        todo = []                                           # (first row, the operand, its words on the device) of the packed operands
 
         def place(row, x):
-            if isinstance(x, PackedString):
-                todo.append((row, x.count, torch.from_numpy(np.ascontiguousarray(x).view(np.int64).reshape(-1)).to(dev)))
+            if isinstance(x, _PACKED):
+                todo.append((row, x, torch.from_numpy(np.ascontiguousarray(x).view(np.int64).reshape(-1)).to(dev)))
             else:
                 flat[row:row + x.shape[0]].copy_(torch.from_numpy(x.view(np.int64)))
             return row + size(x)
@@ -1486,15 +1710,18 @@ class FheStringOps:
                 at = place(at, x)
         at, unpacked = info["n_inputs"] - n_shared, []
         for x in shared:
-            if isinstance(x, PackedString):
+            if isinstance(x, _PACKED):
                 unpacked.append((at, size(x)))
                 at = place(at, x)
             else:
                 d_in[:, at:at + size(x)].copy_(torch.from_numpy(x.view(np.int64)).to(dev))
                 at += size(x)
         torch.cuda.synchronize()                            # torch's stream is not ordered with the engine's
-        for row, count, d_glwes in todo:
-            self.engine.unpack(d_in=d_glwes.data_ptr(), count=count, refresh=True, d_out=flat[row].data_ptr())
+        for row, x, d_words in todo:
+            if isinstance(x, NarrowString):
+                self.engine.unpack_narrow(d_in=d_words.data_ptr(), held=x.count, bits=x.bits, refresh=True, d_out=flat[row].data_ptr())
+            else:
+                self.engine.unpack(d_in=d_words.data_ptr(), count=x.count, refresh=True, d_out=flat[row].data_ptr())
         if unpacked and len(rows) > 1:
             self.engine.synchronize()
             for lo, n in unpacked:
@@ -1503,10 +1730,28 @@ class FheStringOps:
         plan.run_batch_dev(d_in.data_ptr(), d_out.data_ptr(), len(rows))
         return d_out, (todo, d_in)
 
+    def _packed_out(self, d_rows, n_blocks, cap, packed):
+        """n_blocks result rows on the device, packed where they lie: a PackedString, or with packed=Narrow(...) narrowed
+        on the device too, so that only the narrow words cross PCIe: a NarrowString."""
+        if not isinstance(packed, Narrow):
+            return PackedString(self.engine.pack(d_rows, count=n_blocks), n_blocks, cap)   # synchronises
+        import torch
+        p, eng = self.engine.params, self.engine
+        bits = packed.bits if packed.bits is not None else eng._default_narrow_bits()
+        words = narrow_len(p, n_blocks, bits)
+        if not words:
+            raise FheError(f"Narrow: a width of {bits} bits is refused (8 .. 32)")
+        d_glwes = torch.empty((packed_glwe_len(p, n_blocks),), dtype=torch.int64, device=d_rows.device)
+        d_narrow = torch.empty((words,), dtype=torch.int64, device=d_rows.device)
+        torch.cuda.synchronize()
+        eng.pack(d_in=d_rows.data_ptr(), count=n_blocks, d_out=d_glwes.data_ptr())
+        eng.narrow(d_in=d_glwes.data_ptr(), held=n_blocks, bits=bits, d_out=d_narrow.data_ptr())
+        eng.synchronize()
+        return NarrowString(d_narrow.cpu().numpy().view(np.uint64), n_blocks, cap, bits)
+
     def _finish(self, d_out, n_blocks, packed):
         if packed:
-            out = self.engine.pack(d_out, count=n_blocks)   # synchronises
-            return PackedString(out, n_blocks, n_blocks // self.bpc)
+            return self._packed_out(d_out, n_blocks, n_blocks // self.bpc, packed)
         self.engine.synchronize()
         return d_out.cpu().numpy().view(np.uint64)
 
@@ -1541,7 +1786,7 @@ class FheStringOps:
         return out
 
     def _cap(self, ct):
-        if isinstance(ct, PackedString):
+        if isinstance(ct, _PACKED):
             return ct, ct.count // self.bpc
         ct = _u64(ct).reshape(-1, self.engine.params.big_size)
         return ct, ct.shape[0] // self.bpc
@@ -1549,14 +1794,14 @@ class FheStringOps:
     @staticmethod
     def _dev(packed, *operands):
         """Does this call take the device route?  (packed output asked for, or a packed operand given)"""
-        return bool(packed) or any(isinstance(x, PackedString) for x in operands)
+        return bool(packed) or any(isinstance(x, _PACKED) for x in operands)
 
     def _count_operand(self, count: "EncryptedCount"):
         """The digit ciphertexts of an encrypted count, checked against its bound."""
         digits = count.digits
-        if not isinstance(digits, PackedString):
+        if not isinstance(digits, _PACKED):
             digits = _u64(digits).reshape(-1, self.engine.params.big_size)
-        have = digits.count if isinstance(digits, PackedString) else digits.shape[0]
+        have = digits.count if isinstance(digits, _PACKED) else digits.shape[0]
         want = count_input_digits(self.engine.params, count.n_max)
         if have != want:
             raise FheError(f"an encrypted count with n_max = {count.n_max} travels in {want} digits, got {have}")
@@ -1601,9 +1846,9 @@ class FheStringOps:
         enc = None if (b is None or clear is not None) else self._cap(b)
         base, colon, op_params = op.partition(":")          # a parametrised plan name ("split:3", "split_clear:3") keeps its parameters last
         name = base + ("_clear" if clear is not None and not base.endswith("_clear") else "") + colon + op_params
-        if isinstance(rows, (list, tuple)) and any(isinstance(r, PackedString) for r in rows):
+        if isinstance(rows, (list, tuple)) and any(isinstance(r, _PACKED) for r in rows):
             rows = [self._cap(r)[0] for r in rows]
-            sizes = {r.count if isinstance(r, PackedString) else r.shape[0] for r in rows}
+            sizes = {r.count if isinstance(r, _PACKED) else r.shape[0] for r in rows}
             if len(sizes) != 1:
                 raise FheError("op_many expects rows of one capacity")
             return self._packed_many(name, rows, sizes.pop() // self.bpc, enc, clear, packed, digits)
@@ -1708,7 +1953,7 @@ class FheStringOps:
         if packed:
             # the count blocks and every part packed on their own, where they lie: a part is the next operation's operand
             out, keep = self._run_device(call.name, a_cap, call.b_cap, call.clear, operands + ([digits] if digits is not None else []))
-            take = lambda lo, hi, c: PackedString(self.engine.pack(out[lo:hi], count=hi - lo), hi - lo, c)
+            take = lambda lo, hi, c: self._packed_out(out[lo:hi], hi - lo, c, packed)
         else:
             out = self._run(call.name, a_cap, call.b_cap, call.clear, operands, False, digits)
             take = lambda lo, hi, c: out[lo:hi]
@@ -1966,9 +2211,9 @@ class CompiledProgram:
             if x.n_max != v.n_max:
                 raise FheError(f"the count input was declared with n_max = {v.n_max}, got {x.n_max}")
             x = x.digits
-        if not isinstance(x, PackedString):
+        if not isinstance(x, _PACKED):
             x = _u64(x).reshape(-1, self.params.big_size)
-        have = x.count if isinstance(x, PackedString) else x.shape[0]
+        have = x.count if isinstance(x, _PACKED) else x.shape[0]
         if have != v.blocks:
             raise FheError(f"the {v.kind} input of {v.extent} takes {v.blocks} blocks, got {have}")
         return x
@@ -2027,7 +2272,7 @@ class CompiledProgram:
             raise FheError(f"run_many: {len(self.inputs)} operands per instance, the rows bring {n_row} and {len(shared)} are shared")
         tail = [self._operand(v, x) for v, x in zip(self.inputs[n_row:], shared)]
         heads = [[self._operand(v, x) for v, x in zip(self.inputs, r)] for r in rows]
-        if any(isinstance(x, PackedString) for xs in heads + [tail] for x in xs):
+        if any(isinstance(x, _PACKED) for xs in heads + [tail] for x in xs):
             raise FheError("run_many takes expanded operands")
         inputs = np.stack([np.concatenate(xs + tail) for xs in heads])
         out = self.plan.run_batch(np.ascontiguousarray(inputs).view(np.uint64))

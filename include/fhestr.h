@@ -698,6 +698,65 @@ int fhe_engine_unpack_glwes_dev(fhe_engine *eng, const uint64_t *d_glwes, uint32
  * rows (= count), info[2] workgroups, info[3] 1 if the rows were refreshed. */
 int fhe_engine_unpack_info(fhe_engine *eng, uint32_t info[4]);
 
+/* ---- narrow packed results: b-bit coefficients, only the coefficients that hold a block -------------
+ * The project's own form (the reference has no counterpart; csrc/glwe_narrow.h).  A packed GLWE's modulus is switched
+ * down to 2^b, the body coefficients that hold no block are dropped and the rest is bit-packed.  For a width
+ * 8 <= b <= 32:
+ *     narrow_b(x) = ((x + 2^(63-b)) >> (64-b)) mod 2^b     round to nearest, ties upwards; words within 2^(63-b) of 2^64
+ *                                                          wrap to 0
+ *     widen_b(v)  = v << (64-b)
+ * A packed list of `held` blocks has G = ceil(held / N) GLWEs of [k+1][N] u64 (what fhe_engine_pack_lwes writes); GLWE g
+ * holds m_g = min(N, held - g N) blocks.  Its narrow form is a bit stream of kN + m_g fields of b bits each:
+ *   field f     narrow_b of word f of the GLWE -- the body follows the mask, so the fields are its first kN + m_g words
+ *   bit t       of the stream is bit (t & 63) of u64 word t >> 6; the unused high bits of a stream's last word are 0
+ *   stream g    starts at word g W of the list, W = ceil((kN + N) b / 64); the last one has ceil((kN + m_g) b / 64) words
+ * so any field is addressed from (g, f, b) alone and two equal lists are equal byte for byte.  A 256-character string
+ * under PARAM_MESSAGE_2_CARRY_2 (1,024 blocks) takes (2048 + 1024) * 16 / 8 = 6,144 bytes at 16 bits and 4,992 at 13,
+ * against 32,768 packed.  Widening gives full GLWEs whose body coefficients past m_g are 0: they encrypt nothing and
+ * nobody reads them.  Everything here is exact integer arithmetic: host and GPU give the same words.
+ * Noise: narrowing adds V_narrow(b) = (1 + kN/2) / 12 * 2^(-2b) (torus units) to an extracted block's phase, the
+ * average-case form of the modulus switch's term. */
+/* out[0]: fhe_packing_unpack_noise's out[0] + V_narrow(bits) / V_pbs, the nominal variance of a block extracted from a
+ * narrowed packed PBS output; out[1]: the PBS-input budget; out[2]: log2 of the probability that the client decodes such
+ * a coefficient wrongly at delta / 2 (the model fhe_packing_default_params judges with, V_narrow added to the packing's
+ * term). */
+int fhe_narrow_noise(const fhe_params_t *params, const fhe_packing_params_t *pp, uint32_t bits, double out[3]);
+/* The smallest width in 8 .. 32: operand = 1, with out[0] <= out[1] (the narrow list may come back as an operand:
+ * fhe_engine_unpack_narrow with refresh); operand = 0, whose out[2] meets the failure bound of
+ * fhe_packing_default_params (a result for the client).  Refused, naming the pair, when no width qualifies. */
+int fhe_narrow_default_bits(const fhe_params_t *params, const fhe_packing_params_t *pp, int operand, uint32_t *bits);
+size_t fhe_narrow_len(const fhe_params_t *params, uint32_t held, uint32_t bits);   /* u64 words of the list; 0 = refused */
+/* The plain loops on the host (parity; callers without a GPU).  glwes: ceil(held / N) full GLWEs; narrow: fhe_narrow_len
+ * words.  fhe_narrow_sample_extract_host gives rows first .. first + count - 1 as count x (kN+1) words, word for word
+ * what fhe_glwe_sample_extract_host gives on fhe_glwe_widen_host's output; first + count > held is refused. */
+int fhe_glwe_narrow_host(const fhe_params_t *params, const uint64_t *glwes, uint32_t held, uint32_t bits, uint64_t *narrow);
+int fhe_glwe_widen_host(const fhe_params_t *params, const uint64_t *narrow, uint32_t held, uint32_t bits, uint64_t *glwes);
+int fhe_narrow_sample_extract_host(const fhe_params_t *params, const uint64_t *narrow, uint32_t held, uint32_t bits,
+                                   uint32_t first, uint32_t count, uint64_t *cts);
+/* Coefficient j % N of the phase of widened GLWE j / N for j < held, decoded like fhe_client_decrypt_packed. */
+int fhe_client_decrypt_narrow(fhe_client_key *ck, const uint64_t *narrow, uint32_t held, uint32_t bits, uint64_t *msgs);
+/* On the GPU (csrc/glwe_narrow_kernels.hip.h).  fhe_engine_narrow_glwes: host GLWEs in, host list out; synchronises.
+ * _dev: the GLWEs where fhe_engine_pack_lwes_dev wrote them, the list into d_narrow (fhe_narrow_len words, 8-byte
+ * aligned); asynchronous on the engine's stream under that call's contract. */
+int fhe_engine_narrow_glwes(fhe_engine *eng, const uint64_t *glwes_host, uint32_t held, uint32_t bits, uint64_t *narrow_host);
+int fhe_engine_narrow_glwes_dev(fhe_engine *eng, const uint64_t *d_glwes, uint32_t held, uint32_t bits, uint64_t *d_narrow);
+/* The way back on the device: the list at d_narrow -> ceil(held / N) full GLWEs at d_glwes (what
+ * fhe_engine_unpack_glwes_dev reads), bit-identical to fhe_glwe_widen_host; same contract. */
+int fhe_engine_widen_narrow_dev(fhe_engine *eng, const uint64_t *d_narrow, uint32_t held, uint32_t bits, uint64_t *d_glwes);
+/* Sample extraction straight from the narrow list: the rows fhe_engine_unpack_glwes gives on the widened GLWEs, under
+ * its contract on streams, throughput modes and alignment.  first + count > held is refused (here it can be checked).
+ * refresh = 1 is judged with fhe_narrow_noise for the loaded packing key's pair and `bits`: refused when no packing key
+ * is loaded or when out[0] > out[1]; the reason is in fhe_last_error.  The host form uploads only the streams the range
+ * touches.  These calls leave fhe_engine_unpack_info as it was. */
+int fhe_engine_unpack_narrow(fhe_engine *eng, const uint64_t *narrow_host, uint32_t held, uint32_t bits, uint32_t first,
+                             uint32_t count, int refresh, uint64_t *cts_host);
+int fhe_engine_unpack_narrow_dev(fhe_engine *eng, const uint64_t *d_narrow, uint32_t held, uint32_t bits, uint32_t first,
+                                 uint32_t count, int refresh, uint64_t *d_cts);
+/* What the last of the five calls above launched, recorded on the host when it was enqueued: info[0] 1 once a launch
+ * ran, info[1] the kernel (1 = narrowing, 2 = extraction, 3 = widening), info[2] list words written / rows extracted /
+ * GLWE words written, info[3] workgroups, info[4] bits. */
+int fhe_engine_narrow_info(fhe_engine *eng, uint32_t info[5]);
+
 /* ---- tfhe-rs wire format (serde + bincode 1.x, fixed-width little endian) ---------------------- */
 /* Byte forms of core_crypto's LweCiphertext<Vec<u64>>, LweKeyswitchKey<Vec<u64>>, standard-domain
  * LweBootstrapKey<Vec<u64>> and shortint::Ciphertext as tfhe-rs 0.5 writes them with bincode::serialize /
@@ -844,6 +903,16 @@ int fhe_wire_write_glwe_list(const fhe_params_t *p, const uint64_t *glwes, uint3
                              size_t *written);
 int fhe_wire_read_glwe_list(const fhe_params_t *p, const uint8_t *in, size_t in_len, uint64_t *glwes, uint32_t max_glwes,
                             uint32_t *n_glwes, size_t *consumed);
+/* The narrow list ("narrow packed results" above).  This is the project's own container, it has no reference
+ * counterpart: glwe_dimension, polynomial_size, bits and held as little-endian u64, then a bincode Vec<u64> of the
+ * fhe_narrow_len words.  The reader checks k and N against the parameter set, 8 <= bits <= 32, held <= max_held, the
+ * word count against fhe_narrow_len and that every tail bit is 0 (the writer refuses a list with one set), and never
+ * reads past in_len.  narrow may be NULL to read *held and *bits only (then size the buffer with fhe_narrow_len and
+ * call again); otherwise it has room for narrow_cap_words words. */
+int fhe_wire_write_narrow_list(const fhe_params_t *p, const uint64_t *narrow, uint32_t held, uint32_t bits, uint8_t *out,
+                               size_t out_cap, size_t *written);
+int fhe_wire_read_narrow_list(const fhe_params_t *p, const uint8_t *in, size_t in_len, uint64_t *narrow,
+                              size_t narrow_cap_words, uint32_t max_held, uint32_t *held, uint32_t *bits, size_t *consumed);
 
 #ifdef __cplusplus
 }
