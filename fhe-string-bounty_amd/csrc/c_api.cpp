@@ -9,6 +9,7 @@
 
 #include "det_math.h"
 #include "engine.h"
+#include "transcipher.h"
 
 using fhe::fail;
 
@@ -1264,6 +1265,173 @@ int fhe_str_program_finish(fhe_str_program* prog, uint32_t world, fhe_plan** out
     *out = new fhe_plan{prog->backend.c, true};
     prog->backend.c = nullptr;      // the plan owns the circuit from here on ...
     prog->eng = nullptr;            // ... and the program, now a table of values, may outlive the engine
+    return 0;
+    API_END
+}
+
+// ---- transciphering (stream_cipher.h, transcipher.h; the device side: transcipher_dev.hip) ----------------------------
+static int tc_answer(const char* why) { return why ? fail(why) : 0; }
+
+int fhe_stream_cipher_info(uint32_t cipher, uint32_t info[3]) {
+    API_BEGIN
+    CHECK_PTR(info);
+    info[0] = info[1] = info[2] = 0;
+    if (!fhe::stream_cipher_ok(cipher)) return fail("stream cipher: unknown cipher (FHE_STREAM_TRIVIUM or FHE_STREAM_KREYVIUM)");
+    info[0] = info[1] = fhe::stream_key_bits(cipher);
+    info[2] = fhe::STREAM_WARMUP_STEPS;
+    return 0;
+    API_END
+}
+
+int fhe_stream_cipher_keystream(uint32_t cipher, const uint8_t* key, const uint8_t* iv, uint64_t first_byte, uint8_t* out, size_t n_bytes) {
+    API_BEGIN
+    CHECK_PTR(key); CHECK_PTR(iv);
+    if (n_bytes) CHECK_PTR(out);
+    return tc_answer(fhe::stream_keystream(cipher, key, iv, first_byte, out, n_bytes));
+    API_END
+}
+
+int fhe_transcipher_supported(const fhe_params_t* params, uint32_t cipher) {
+    API_BEGIN
+    CHECK_PTR(params);
+    return tc_answer(fhe::tc_supported(*params, cipher));
+    API_END
+}
+
+int fhe_transcipher_table(const fhe_params_t* params, uint32_t table, uint64_t* values, uint32_t* n_tables) {
+    API_BEGIN
+    CHECK_PTR(params); CHECK_PTR(n_tables);
+    *n_tables = 0;
+    fhe::TcShape sh;
+    if (const char* why = fhe::tc_shape(*params, FHE_STREAM_KREYVIUM, 1, &sh)) return fail(why);   // the tables do not depend on the cipher; Kreyvium uses all of them
+    *n_tables = fhe::TC_TABLE_G + 2 * sh.bits;
+    if (!values) return 0;
+    if (table >= *n_tables) return fail("transcipher: table number out of range");
+    for (uint32_t v = 0; v < params->msg_mod * params->carry_mod; v++) values[v] = fhe::tc_table_value(table, v);
+    return 0;
+    API_END
+}
+
+size_t fhe_transcipher_ring_len(const fhe_params_t* params, uint32_t streams) {
+    return params ? fhe::tc_ring_rows(streams) * ((size_t)params->k * params->N + 1) : 0;
+}
+
+int fhe_transcipher_init_host(const fhe_params_t* params, uint32_t cipher, uint32_t streams, const uint64_t* key, const uint8_t* ivs, uint64_t* ring) {
+    API_BEGIN
+    CHECK_PTR(params); CHECK_PTR(key); CHECK_PTR(ivs); CHECK_PTR(ring);
+    fhe::TcShape sh;
+    if (const char* why = fhe::tc_shape(*params, cipher, streams, &sh)) return fail(why);
+    return tc_answer(fhe::tc_init(sh, key, ivs, ring));
+    API_END
+}
+
+int fhe_transcipher_gather_host(const fhe_params_t* params, uint32_t cipher, uint32_t streams, int32_t round, uint32_t rows, const uint64_t* ring,
+                                const uint64_t* key, const uint8_t* ivs, const uint8_t* data, uint32_t n_bytes, uint32_t m, uint64_t* pbs_in,
+                                uint32_t* tables) {
+    API_BEGIN
+    CHECK_PTR(params); CHECK_PTR(ring); CHECK_PTR(key); CHECK_PTR(ivs); CHECK_PTR(pbs_in); CHECK_PTR(tables);
+    fhe::TcShape sh;
+    if (const char* why = fhe::tc_shape(*params, cipher, streams, &sh)) return fail(why);
+    return tc_answer(fhe::tc_gather(sh, round, rows, ring, key, ivs, rows == fhe::TC_DATA_ROWS ? data : nullptr, n_bytes, m, nullptr, pbs_in, tables));
+    API_END
+}
+
+int fhe_transcipher_apply_host(const fhe_params_t* params, uint32_t cipher, uint32_t streams, int32_t round, const uint64_t* ring, uint32_t n_bytes,
+                               uint32_t m, uint64_t* out) {
+    API_BEGIN
+    CHECK_PTR(params); CHECK_PTR(ring); CHECK_PTR(out);
+    fhe::TcShape sh;
+    if (const char* why = fhe::tc_shape(*params, cipher, streams, &sh)) return fail(why);
+    if ((uint64_t)8 * m >= n_bytes) return fail("transcipher: round m of a call starts at byte 8 m, past the call's bytes");
+    return tc_answer(fhe::tc_apply(sh, round, ring, n_bytes, m, out));
+    API_END
+}
+
+int fhe_engine_transcipher_init(fhe_engine* eng, uint32_t cipher, uint32_t streams, const uint64_t* key, const uint8_t* ivs, uint64_t* ring) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(key); CHECK_PTR(ivs); CHECK_PTR(ring);
+    return eng->impl->transcipher_init_host(cipher, streams, key, ivs, ring);
+    API_END
+}
+
+int fhe_engine_transcipher_gather(fhe_engine* eng, uint32_t cipher, uint32_t streams, int32_t round, uint32_t rows, const uint64_t* ring,
+                                  const uint64_t* key, const uint8_t* ivs, const uint8_t* data, uint32_t n_bytes, uint32_t m, uint64_t* pbs_in,
+                                  uint32_t* tables) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(ring); CHECK_PTR(key); CHECK_PTR(ivs); CHECK_PTR(pbs_in); CHECK_PTR(tables);
+    return eng->impl->transcipher_gather_host(cipher, streams, round, rows, ring, key, ivs, data, n_bytes, m, pbs_in, tables);
+    API_END
+}
+
+int fhe_engine_transcipher_apply(fhe_engine* eng, uint32_t cipher, uint32_t streams, int32_t round, const uint64_t* ring, uint32_t n_bytes, uint32_t m,
+                                 uint64_t* out) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(ring); CHECK_PTR(out);
+    return eng->impl->transcipher_apply_host(cipher, streams, round, ring, n_bytes, m, out);
+    API_END
+}
+
+struct fhe_transcipher {
+    fhe_engine* eng;
+    fhe::Transcipher* impl;      // owned by eng->impl->transciphers
+};
+
+int fhe_transcipher_create(fhe_engine* eng, uint32_t cipher, const uint64_t* key_cts, uint32_t max_streams, fhe_transcipher** out) {
+    API_BEGIN
+    CHECK_PTR(out);
+    *out = nullptr;
+    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(key_cts);
+    fhe::Transcipher* t = nullptr;
+    if (fhe::Transcipher::create(*eng->impl, cipher, key_cts, max_streams, &t)) return 1;
+    *out = new fhe_transcipher{eng, t};
+    return 0;
+    API_END
+}
+
+int fhe_transcipher_destroy(fhe_transcipher* tc) {
+    API_BEGIN
+    if (!tc) return 0;
+    {
+        LOCK_ENGINE(tc->eng);
+        fhe::Engine& e = *tc->eng->impl;
+        if (e.use() || e.sync_all_streams()) return 1;              // launches in flight still read its buffers
+        for (auto it = e.transciphers.begin(); it != e.transciphers.end(); ++it)
+            if (it->get() == tc->impl) { e.transciphers.erase(it); break; }
+    }
+    delete tc;
+    return 0;
+    API_END
+}
+
+int fhe_transcipher_begin(fhe_transcipher* tc, const uint8_t* ivs, uint32_t n_streams) {
+    API_BEGIN
+    CHECK_PTR(tc); LOCK_ENGINE(tc->eng); CHECK_PTR(ivs);
+    return tc->impl->begin(ivs, n_streams);
+    API_END
+}
+
+int fhe_transcipher_next(fhe_transcipher* tc, const uint8_t* data, uint32_t n_bytes, int refresh, uint64_t* out_host, uint64_t* d_out) {
+    API_BEGIN
+    CHECK_PTR(tc); LOCK_ENGINE(tc->eng);
+    if (n_bytes) CHECK_PTR(data);
+    return tc->impl->next(data, n_bytes, refresh, out_host, d_out);
+    API_END
+}
+
+int fhe_transcipher_info(fhe_transcipher* tc, uint32_t info[8]) {
+    API_BEGIN
+    CHECK_PTR(tc); LOCK_ENGINE(tc->eng); CHECK_PTR(info);
+    tc->impl->info(info);
+    return 0;
+    API_END
+}
+
+int fhe_transcipher_timing(fhe_transcipher* tc, int on, double ms[3], uint32_t* rounds) {
+    API_BEGIN
+    CHECK_PTR(tc); LOCK_ENGINE(tc->eng);
+    tc->impl->timed = on != 0;
+    if (ms) for (int i = 0; i < 3; i++) ms[i] = tc->impl->phase_ms[i];
+    if (rounds) *rounds = tc->impl->timed_rounds;
     return 0;
     API_END
 }

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -125,6 +126,40 @@ struct PackingState {
     void narrow_info(uint32_t out[5]) const { std::copy(narrow_last, narrow_last + 5, out); }
 };
 
+// Transciphering (transcipher.h, transcipher_kernels.hip.h; members in transcipher_dev.hip): the resident encrypted key bits
+// of one stream-cipher key and the round ring of up to max_streams strings encrypted under it, each with its own IV,
+// advancing in lockstep -- one ks_pbs level per round for all of them.  Owned by its engine (Engine::transciphers), every
+// launch on the engine's stream.
+struct Engine;
+struct Transcipher {
+    Engine* e = nullptr;
+    uint32_t cipher = 0, max_streams = 0, bits = 0;
+    uint32_t n_streams = 0;             // 0 until begin()
+    int32_t round = 0;                  // the next round: TC_WARMUP_ROUNDS after begin(), then one more per 8 bytes
+    DeviceBuffer<uint64_t> key;         // L rows K_1 .. K_L
+    DeviceBuffer<uint64_t> ring;        // tc_ring_rows(max_streams) rows
+    DeviceBuffer<uint64_t> pbs_in;      // the gather's output: max_streams x 256 rows
+    DeviceBuffer<uint32_t> tables;      // and its table indices
+    DeviceBuffer<uint8_t> ivs, data;    // the streams' clear IVs; the clear cipher bytes of the current next()
+    DeviceBuffer<uint64_t> out;         // staging of next() with a host destination
+    uint32_t lut_of[20] = {};           // table number (transcipher.h) -> the engine's table index, through lut_upload_dedup
+    uint32_t warm_rounds = 0, data_rounds = 0;   // since begin()
+    uint64_t pbs_rows = 0;              // lookups since begin(), all streams, the refresh included
+    // per-phase device times of the data rounds since begin(), measured only when `timed` (each round then ends in a
+    // synchronisation): gather, ks_pbs, apply in ms, and the rounds measured
+    bool timed = false;
+    double phase_ms[3] = {0, 0, 0};
+    uint32_t timed_rounds = 0;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+
+    static int create(Engine& e, uint32_t cipher, const uint64_t* key_cts, uint32_t max_streams, Transcipher** out);
+    ~Transcipher();
+    int begin(const uint8_t* ivs_host, uint32_t streams);
+    int next(const uint8_t* data_host, uint32_t n_bytes, int refresh, uint64_t* out_host, uint64_t* d_out);
+    int run_round(uint32_t rows, uint32_t n_bytes, uint32_t m, uint64_t* d_blocks);
+    void info(uint32_t out[8]) const;
+};
+
 struct Engine {
     std::recursive_mutex mu;      // taken by every C ABI entry point that touches this engine (c_api.cpp, LOCK_ENGINE)
     fhe_params_t p{};
@@ -186,6 +221,7 @@ struct Engine {
     // (FHE_KS_KERNEL_*), row tiles / samples per workgroup, K chunks (grid.z), K steps / input coefficients per chunk, K steps / in_dim
     uint32_t ks_last[5] = {0, 0, 0, 0, 0};
     PackingState packing;
+    std::vector<std::unique_ptr<Transcipher>> transciphers;   // fhe_transcipher_create .. fhe_transcipher_destroy, or the engine's end
 
     static int create(const fhe_params_t& p, int device, Engine** out);
     ~Engine();
@@ -245,6 +281,11 @@ struct Engine {
                      uint32_t out_slot, uint32_t out_inst);
     int lincomb_host(const uint64_t* pool, uint32_t pool_count, const uint32_t* off, const uint32_t* src,
                      const int32_t* coeff, const uint64_t* cst, uint64_t* out, uint32_t jobs);
+    // the three transcipher kernels on host arrays, one launch each (transcipher_dev.hip): what tests compare with transcipher.cpp
+    int transcipher_init_host(uint32_t cipher, uint32_t S, const uint64_t* key, const uint8_t* ivs, uint64_t* ring);
+    int transcipher_gather_host(uint32_t cipher, uint32_t S, int32_t round, uint32_t rows, const uint64_t* ring, const uint64_t* key, const uint8_t* ivs,
+                                const uint8_t* data, uint32_t n_bytes, uint32_t m, uint64_t* pbs_in, uint32_t* tables);
+    int transcipher_apply_host(uint32_t cipher, uint32_t S, int32_t round, const uint64_t* ring, uint32_t n_bytes, uint32_t m, uint64_t* out);
     int last_kernel_ms(float ms[2]);
     int kernel_times(double total_ms[2], uint32_t* calls, bool reset);
     int synchronize();

@@ -84,6 +84,7 @@ int Engine::create(const fhe_params_t& p, int device, Engine** out) {
 Engine::~Engine() {
     (void)hipSetDevice(device);
     if (stream) (void)sync_all_streams();
+    transciphers.clear();
     for (auto& e : ring) if (e) (void)hipEventDestroy(e);
     pipe.destroy();
     if (own_stream) (void)hipStreamDestroy(own_stream);

@@ -174,6 +174,10 @@ EXPORTS = [
     "fhe_narrow_sample_extract_host", "fhe_client_decrypt_narrow", "fhe_engine_narrow_glwes", "fhe_engine_narrow_glwes_dev",
     "fhe_engine_widen_narrow_dev", "fhe_engine_unpack_narrow", "fhe_engine_unpack_narrow_dev", "fhe_engine_narrow_info", "fhe_wire_write_narrow_list",
     "fhe_wire_read_narrow_list",
+    "fhe_stream_cipher_info", "fhe_stream_cipher_keystream", "fhe_transcipher_supported", "fhe_transcipher_table", "fhe_transcipher_ring_len",
+    "fhe_transcipher_init_host", "fhe_transcipher_gather_host", "fhe_transcipher_apply_host", "fhe_engine_transcipher_init",
+    "fhe_engine_transcipher_gather", "fhe_engine_transcipher_apply", "fhe_transcipher_create", "fhe_transcipher_destroy",
+    "fhe_transcipher_begin", "fhe_transcipher_next", "fhe_transcipher_info", "fhe_transcipher_timing",
 ] + [f"fhe_str_{n}{s}" for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat")
      for s in ("", "_clear")] + ["fhe_str_repeat_clear", "fhe_str_split", "fhe_str_replacen", "fhe_str_replacen_clear",
                                    "fhe_str_repeat", "fhe_str_replacen_encn", "fhe_str_replacen_encn_clear", "fhe_str_splitn_encn",
@@ -374,6 +378,24 @@ def lib() -> C.CDLL:
     sig("fhe_engine_narrow_info", vp, C.POINTER(u32))
     sig("fhe_wire_write_narrow_list", PP, vp, u32, u32, vp, C.c_size_t, C.POINTER(C.c_size_t))
     sig("fhe_wire_read_narrow_list", PP, vp, C.c_size_t, vp, C.c_size_t, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_size_t))
+    sig("fhe_stream_cipher_info", u32, C.POINTER(u32))
+    sig("fhe_stream_cipher_keystream", u32, vp, vp, C.c_uint64, vp, C.c_size_t)
+    sig("fhe_transcipher_supported", PP, u32)
+    sig("fhe_transcipher_table", PP, u32, vp, C.POINTER(u32))
+    L.fhe_transcipher_ring_len.restype = C.c_size_t
+    L.fhe_transcipher_ring_len.argtypes = [PP, u32]
+    sig("fhe_transcipher_init_host", PP, u32, u32, vp, vp, vp)
+    sig("fhe_transcipher_gather_host", PP, u32, u32, C.c_int32, u32, vp, vp, vp, vp, u32, u32, vp, vp)
+    sig("fhe_transcipher_apply_host", PP, u32, u32, C.c_int32, vp, u32, u32, vp)
+    sig("fhe_engine_transcipher_init", vp, u32, u32, vp, vp, vp)
+    sig("fhe_engine_transcipher_gather", vp, u32, u32, C.c_int32, u32, vp, vp, vp, vp, u32, u32, vp, vp)
+    sig("fhe_engine_transcipher_apply", vp, u32, u32, C.c_int32, vp, u32, u32, vp)
+    sig("fhe_transcipher_create", vp, u32, vp, u32, C.POINTER(vp))
+    sig("fhe_transcipher_destroy", vp)
+    sig("fhe_transcipher_begin", vp, vp, u32)
+    sig("fhe_transcipher_next", vp, vp, u32, i32, vp, vp)
+    sig("fhe_transcipher_info", vp, C.POINTER(u32))
+    sig("fhe_transcipher_timing", vp, i32, C.POINTER(C.c_double), C.POINTER(u32))
     for name in ("fhe_params_ksk_len", "fhe_params_bsk_len"):
         getattr(L, name).restype = C.c_size_t
         getattr(L, name).argtypes = [PP]
@@ -490,6 +512,119 @@ def _u64(a) -> np.ndarray:
 
 def _ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
+
+
+# ---- transciphering (include/fhestr.h, "transciphering"; csrc/stream_cipher.h, csrc/transcipher.h) ----
+TRIVIUM, KREYVIUM = 1, 2          # FHE_STREAM_TRIVIUM, FHE_STREAM_KREYVIUM
+_STREAM_CIPHERS = {"trivium": TRIVIUM, "kreyvium": KREYVIUM, TRIVIUM: TRIVIUM, KREYVIUM: KREYVIUM}
+
+
+def _cipher_id(cipher) -> int:
+    try:
+        return _STREAM_CIPHERS[cipher.lower() if isinstance(cipher, str) else int(cipher)]
+    except (KeyError, ValueError, TypeError):
+        raise FheError(f"unknown stream cipher {cipher!r}: 'trivium' or 'kreyvium'") from None
+
+
+def stream_cipher_info(cipher) -> dict:
+    """{"key_bits", "iv_bits", "warmup_steps"} of 'trivium' (80-bit: for its published vectors and parity with the
+    reference) or 'kreyvium' (128-bit: the one that matches the 128-bit parameter sets)."""
+    a = (C.c_uint32 * 3)()
+    _check(lib().fhe_stream_cipher_info(_cipher_id(cipher), a))
+    return {"key_bits": int(a[0]), "iv_bits": int(a[1]), "warmup_steps": int(a[2])}
+
+
+def _cipher_bytes(cipher, what: str, b) -> np.ndarray:
+    n = stream_cipher_info(cipher)["key_bits"] // 8
+    a = np.frombuffer(bytes(b), dtype=np.uint8)
+    if a.size != n:
+        raise FheError(f"a {what} of this cipher is {n} bytes, got {a.size}")
+    return np.ascontiguousarray(a)
+
+
+def stream_key_bits(cipher, key: bytes) -> np.ndarray:
+    """The L bits of a key (or IV) in spec order K_1 .. K_L: K_j = x[L - j] with x[8 j + l] = bit l of byte j."""
+    return np.unpackbits(_cipher_bytes(cipher, "key", key), bitorder="little")[::-1].astype(np.uint64)
+
+
+def stream_keystream(cipher, key: bytes, iv: bytes, n_bytes: int, first_byte: int = 0) -> bytes:
+    """Keystream bytes first_byte .. first_byte + n_bytes - 1 in the clear (fhe_stream_cipher_keystream; client side)."""
+    k, v = _cipher_bytes(cipher, "key", key), _cipher_bytes(cipher, "IV", iv)
+    out = np.zeros(max(int(n_bytes), 1), dtype=np.uint8)
+    _check(lib().fhe_stream_cipher_keystream(_cipher_id(cipher), _ptr(k), _ptr(v), C.c_uint64(first_byte), _ptr(out), int(n_bytes)))
+    return out[:n_bytes].tobytes()
+
+
+def stream_encrypt(cipher, key: bytes, iv: bytes, data: bytes, offset: int = 0) -> bytes:
+    """data XOR the keystream from byte `offset`: encrypts and decrypts.  What a client sends to Transcipher.next; the
+    offset of a call's bytes is Transcipher.offset before that call (every call starts on an 8-byte boundary)."""
+    ks = np.frombuffer(stream_keystream(cipher, key, iv, len(data), offset), dtype=np.uint8)
+    return (np.frombuffer(bytes(data), dtype=np.uint8) ^ ks).tobytes()
+
+
+def transcipher_supported(params: "Params", cipher):
+    """(True, "") if the parameter set can run the cipher homomorphically, else (False, reason).  Needs no device."""
+    if lib().fhe_transcipher_supported(C.byref(params.c()), _cipher_id(cipher)) == 0:
+        return True, ""
+    return False, lib().fhe_last_error().decode()
+
+
+def transcipher_tables(params: "Params") -> np.ndarray:
+    """The lookup tables of a round over the message-and-carry values, (n_tables, msg_mod * carry_mod): f_3, 1 - f_3, f_4,
+    1 - f_4, then g_{i,c} at 4 + 2 i + c (csrc/transcipher.h)."""
+    n = C.c_uint32(0)
+    _check(lib().fhe_transcipher_table(C.byref(params.c()), 0, None, C.byref(n)))
+    out = np.zeros((n.value, params.msg_mod * params.carry_mod), dtype=np.uint64)
+    for t in range(n.value):
+        _check(lib().fhe_transcipher_table(C.byref(params.c()), t, _ptr(out[t]), C.byref(n)))
+    return out
+
+
+def transcipher_ring_len(params: "Params", streams: int) -> int:
+    return int(lib().fhe_transcipher_ring_len(C.byref(params.c()), streams))
+
+
+def _tc_ivs(cipher, ivs, streams: int) -> np.ndarray:
+    n = stream_cipher_info(cipher)["key_bits"] // 8
+    if isinstance(ivs, np.ndarray):
+        a = np.ascontiguousarray(ivs, dtype=np.uint8).reshape(-1)
+    else:
+        a = np.ascontiguousarray(np.frombuffer(b"".join(bytes(v) for v in ivs), dtype=np.uint8))
+    if a.size != streams * n:
+        raise FheError(f"{streams} IVs of this cipher are {streams * n} bytes, got {a.size}")
+    return a
+
+
+def _tc_round(params, call, engine, cipher, streams, round, rows, ring, key, ivs, data, m):
+    """gather through the host loops (engine None) or the kernel: (pbs_in (S, rows, big), tables (S, rows))."""
+    p = params
+    if data is not None:
+        data = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, dtype=np.uint8)
+        data = np.ascontiguousarray(data).reshape(streams, -1)
+    pbs_in = np.zeros((streams, rows, p.big_size), dtype=np.uint64)
+    tables = np.zeros((streams, rows), dtype=np.uint32)
+    head = (engine._h,) if engine is not None else (C.byref(p.c()),)
+    _check(call(*head, _cipher_id(cipher), streams, round, rows, _ptr(_u64(ring)), _ptr(_u64(key)), _ptr(_tc_ivs(cipher, ivs, streams)),
+                _ptr(data) if data is not None else None, data.shape[1] if data is not None else 0, m, _ptr(pbs_in), _ptr(tables)))
+    return pbs_in, tables
+
+
+def transcipher_init_host(params: "Params", cipher, streams: int, key, ivs, ring=None) -> np.ndarray:
+    """The ring with the blocks of rounds -1 and -2 written by the host loop (fhe_transcipher_init_host); the other rows as
+    `ring` had them (zeros when None).  key: (L, big) rows K_1 .. K_L."""
+    ring = np.zeros(transcipher_ring_len(params, streams), dtype=np.uint64) if ring is None else _u64(ring).reshape(-1).copy()
+    _check(lib().fhe_transcipher_init_host(C.byref(params.c()), _cipher_id(cipher), streams, _ptr(_u64(key)), _ptr(_tc_ivs(cipher, ivs, streams)), _ptr(ring)))
+    return ring
+
+
+def transcipher_gather_host(params: "Params", cipher, streams: int, round: int, rows: int, ring, key, ivs, data=None, m: int = 0):
+    return _tc_round(params, lib().fhe_transcipher_gather_host, None, cipher, streams, round, rows, ring, key, ivs, data, m)
+
+
+def transcipher_apply_host(params: "Params", cipher, streams: int, round: int, ring, n_bytes: int, m: int, out) -> np.ndarray:
+    """`out` ((S * n_bytes * blocks_per_char, big), updated in place and returned) with the blocks of call round m summed in."""
+    _check(lib().fhe_transcipher_apply_host(C.byref(params.c()), _cipher_id(cipher), streams, round, _ptr(_u64(ring)), n_bytes, m, _ptr(out)))
+    return out
 
 
 class Engine:
@@ -697,6 +832,26 @@ class Engine:
             raise FheError("packing key: size does not match the parameter set and decomposition")
         _check(lib().fhe_engine_load_packing_key(self._h, C.byref(_pp(pp)), _ptr(pksk)))
         self.packing_pair = (int(pp[0]), int(pp[1]))        # what Narrow(bits=None) takes its default width for
+
+    def transcipher(self, cipher, key_cts, max_streams: int = 1) -> "Transcipher":
+        """A Transcipher for one stream-cipher key on this engine (server keys loaded): key_cts are the encrypted key bits
+        of ClientKey.encrypt_stream_key, (L, kN+1) in spec order; up to max_streams strings run in lockstep."""
+        return Transcipher(self, cipher, key_cts, max_streams)
+
+    def transcipher_init(self, cipher, streams: int, key, ivs, ring=None) -> np.ndarray:
+        """transcipher_init_host through transcipher_init_kernel."""
+        ring = np.zeros(transcipher_ring_len(self.params, streams), dtype=np.uint64) if ring is None else _u64(ring).reshape(-1).copy()
+        _check(lib().fhe_engine_transcipher_init(self._h, _cipher_id(cipher), streams, _ptr(_u64(key)), _ptr(_tc_ivs(cipher, ivs, streams)), _ptr(ring)))
+        return ring
+
+    def transcipher_gather(self, cipher, streams: int, round: int, rows: int, ring, key, ivs, data=None, m: int = 0):
+        """transcipher_gather_host through transcipher_gather_kernel."""
+        return _tc_round(self.params, lib().fhe_engine_transcipher_gather, self, cipher, streams, round, rows, ring, key, ivs, data, m)
+
+    def transcipher_apply(self, cipher, streams: int, round: int, ring, n_bytes: int, m: int, out) -> np.ndarray:
+        """transcipher_apply_host through transcipher_apply_kernel."""
+        _check(lib().fhe_engine_transcipher_apply(self._h, _cipher_id(cipher), streams, round, _ptr(_u64(ring)), n_bytes, m, _ptr(out)))
+        return out
 
     def narrow(self, glwes=None, held: int | None = None, bits: int | None = None, d_in: int | None = None, d_out: int | None = None):
         """Packed GLWEs narrowed to `bits`-bit coefficients on the GPU (csrc/glwe_narrow_kernels.hip.h; the definition:
@@ -959,6 +1114,78 @@ class Engine:
         return float(ms[0]), float(ms[1]), int(calls.value)
 
 
+class Transcipher:
+    """Strings encrypted under Trivium / Kreyvium turned into encrypted strings on the GPU (fhe_transcipher_*):
+    begin(ivs) runs the warm-up of one string per IV, next(data) returns the next characters of each as the block
+    ciphertexts FheStringOps and StringProgram take.  Every next starts on an 8-byte keystream boundary: `offset` is
+    the keystream byte the coming call starts at, which the client passes to stream_encrypt for that call's bytes."""
+
+    def __init__(self, engine: "Engine", cipher, key_cts, max_streams: int = 1):
+        self.engine, self.cipher, self.params = engine, _cipher_id(cipher), engine.params
+        key_cts = _u64(key_cts).reshape(-1)
+        L = stream_cipher_info(cipher)["key_bits"]
+        if key_cts.size != L * self.params.big_size:
+            raise FheError(f"transcipher: {L} key-bit ciphertexts of {self.params.big_size} words expected, got {key_cts.size} words")
+        self._h = C.c_void_p()
+        _check(lib().fhe_transcipher_create(engine._h, self.cipher, _ptr(key_cts), max_streams, C.byref(self._h)))
+        self.max_streams, self.streams = max_streams, 0
+
+    def close(self):
+        if self._h and self.engine._h:          # the engine owns it: gone with the engine at the latest
+            lib().fhe_transcipher_destroy(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def begin(self, ivs):
+        """ivs: one IV (bytes) per string, at most max_streams."""
+        ivs = [ivs] if isinstance(ivs, (bytes, bytearray)) else list(ivs)
+        _check(lib().fhe_transcipher_begin(self._h, _ptr(_tc_ivs(self.cipher, ivs, len(ivs))), len(ivs)))
+        self.streams = len(ivs)
+        return self
+
+    def next(self, data, refresh: bool = True, d_out: int | None = None):
+        """data: the clear cipher bytes, one equally long bytes object per string (or one for a single string).  Returns
+        (streams, n_bytes * blocks_per_char, kN+1) block ciphertexts, a single string squeezed to 2-D like
+        encrypt_string's; with d_out (a device pointer with room for them) they are written there, asynchronously on the
+        engine's stream, and nothing is returned."""
+        single = isinstance(data, (bytes, bytearray))
+        rows = [bytes(data)] if single else [bytes(d) for d in data]
+        if self.streams and (len(rows) != self.streams or len({len(r) for r in rows}) != 1):
+            raise FheError(f"transcipher: next takes {self.streams} equally long byte strings")
+        n = len(rows[0])
+        buf = np.ascontiguousarray(np.frombuffer(b"".join(rows), dtype=np.uint8))
+        if not self.streams:                    # the library's own refusal: next before begin
+            _check(lib().fhe_transcipher_next(self._h, _ptr(buf), n, int(bool(refresh)), None, None))
+        if d_out:
+            _check(lib().fhe_transcipher_next(self._h, _ptr(buf), n, int(bool(refresh)), None, C.c_void_p(d_out)))
+            return None
+        out = np.zeros((self.streams, n * blocks_per_char(self.params), self.params.big_size), dtype=np.uint64)
+        _check(lib().fhe_transcipher_next(self._h, _ptr(buf), n, int(bool(refresh)), _ptr(out), None))
+        return out[0] if single else out
+
+    def info(self) -> dict:
+        a = (C.c_uint32 * 8)()
+        _check(lib().fhe_transcipher_info(self._h, a))
+        v = [int(x) for x in a]
+        return {"cipher": v[0], "max_streams": v[1], "streams": v[2], "warmup_rounds": v[3], "data_rounds": v[4], "pbs": v[5] | (v[6] << 32), "offset": v[7]}
+
+    @property
+    def offset(self) -> int:
+        return self.info()["offset"]
+
+    def timing(self, on: bool = True) -> dict:
+        """Switch the per-phase timing of data rounds on or off and return what was measured since begin: ms of the gather,
+        keyswitch + PBS and apply phases and the rounds they cover.  Measurement only: a timed round synchronises."""
+        ms, n = (C.c_double * 3)(), C.c_uint32(0)
+        _check(lib().fhe_transcipher_timing(self._h, int(bool(on)), ms, C.byref(n)))
+        return {"gather_ms": ms[0], "ks_pbs_ms": ms[1], "apply_ms": ms[2], "rounds": n.value}
+
+
 class ClientKey:
     """Client side (CPU): mirrors shortint::ClientKey (tfhe/src/shortint/client_key/mod.rs)."""
 
@@ -992,6 +1219,11 @@ class ClientKey:
         out = np.zeros(cts.shape[0], dtype=np.uint64)
         _check(lib().fhe_client_decrypt(self._h, _ptr(cts), cts.shape[0], _ptr(out)))
         return out.astype(np.int64)
+
+    def encrypt_stream_key(self, cipher, key: bytes) -> np.ndarray:
+        """The key bits of a stream-cipher key as ciphertexts of 0 / 1, (L, kN+1) in spec order K_1 .. K_L: what
+        Engine.transcipher takes.  Uploaded once per key; the strings then travel as stream_encrypt's bytes."""
+        return self.encrypt(stream_key_bits(cipher, key))
 
     def gen_server_keys(self, threads: int | None = None):
         p = self.params

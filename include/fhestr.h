@@ -757,6 +757,91 @@ int fhe_engine_unpack_narrow_dev(fhe_engine *eng, const uint64_t *d_narrow, uint
  * GLWE words written, info[3] workgroups, info[4] bits. */
 int fhe_engine_narrow_info(fhe_engine *eng, uint32_t info[5]);
 
+/* ---- transciphering: strings encrypted under a stream cipher, the keystream removed on the GPU ----------
+ * The client encrypts its string with Trivium or Kreyvium (1 byte per character plus the IV) and uploads the cipher's
+ * key BITS as big-key LWE ciphertexts once (80 or 128 of them, each a 0 or a 1; any input path carries them).  The
+ * server generates the keystream homomorphically, 64 steps per lookup level, and removes it: what comes out are the block
+ * ciphertexts every fhe_str_* call takes (the reference's apps/trivium, trivium_shortint.rs / kreyvium_shortint.rs, on
+ * this engine's batched PBS).  Definition, tables and noise: csrc/stream_cipher.h, csrc/transcipher.h.
+ *
+ * Trivium is an 80-bit cipher: it is offered for its published test vectors and for parity with the reference.
+ * Kreyvium is the one whose 128-bit key matches the 128-bit parameter sets.
+ *
+ * Bit order (the reference's and the published vectors'): a key or IV of L = 80 / 128 bits is given as L / 8 bytes, the bit
+ * array is x[8 j + l] = bit l (LSB first) of byte j, spec bit K_j (1 .. L) is x[L - j]; keystream bit 8 j + l is bit l
+ * of keystream byte j. */
+#define FHE_STREAM_TRIVIUM 1u
+#define FHE_STREAM_KREYVIUM 2u
+/* info[0] key bits, info[1] IV bits, info[2] warm-up steps discarded before the first keystream bit (1152) */
+int fhe_stream_cipher_info(uint32_t cipher, uint32_t info[3]);
+/* Keystream bytes first_byte .. first_byte + n_bytes - 1 in the clear (client side, host only). */
+int fhe_stream_cipher_keystream(uint32_t cipher, const uint8_t *key, const uint8_t *iv, uint64_t first_byte, uint8_t *out,
+                                size_t n_bytes);
+/* 0 if the parameter set can run the cipher homomorphically, else 1 with the reason in fhe_last_error.  Needs no device.
+ * Supported: msg_mod * carry_mod >= 16 (a state update feeds a lookup values up to 14), log2(msg_mod) divides 8, and the
+ * noise model puts every lookup input (35 or 54 nominal variances for a state update, 6 or 7 for the keystream) within
+ * the plans' default PBS-input budget. */
+int fhe_transcipher_supported(const fhe_params_t *params, uint32_t cipher);
+/* Table number `table` (0 .. *n_tables - 1: f_3, 1 - f_3, f_4, 1 - f_4, then g_{i,c} at 4 + 2 i + c) over the
+ * msg_mod * carry_mod message-and-carry values.  values may be NULL to read *n_tables only. */
+int fhe_transcipher_table(const fhe_params_t *params, uint32_t table, uint64_t *values, uint32_t *n_tables);
+/* The round on the host, plain loops (csrc/transcipher.cpp): the pin of the kernels, and what a test runs on trivial
+ * ciphertexts.  ring: fhe_transcipher_ring_len words (4 slots x streams x 256 rows); key: L rows K_1 .. K_L; ivs:
+ * streams x L / 8 bytes.  init writes the blocks of rounds -1 and -2.  gather writes the streams x rows (192 warm-up, 256
+ * data) lookup inputs of round `round` (>= 0; data rounds start at 18) and their table numbers; the lookups' outputs
+ * belong in ring slot round mod 4, streams x rows rows back to back from word (round mod 4) x streams x 256 x (kN + 1).
+ * data: streams x n_bytes clear cipher bytes of one fhe_transcipher_next call, m the round within that call.  apply sums
+ * the keystream lookups of data round `round` into the blocks of characters 8 m .. of out (streams x n_bytes x
+ * blocks-per-character rows). */
+size_t fhe_transcipher_ring_len(const fhe_params_t *params, uint32_t streams);
+int fhe_transcipher_init_host(const fhe_params_t *params, uint32_t cipher, uint32_t streams, const uint64_t *key,
+                              const uint8_t *ivs, uint64_t *ring);
+int fhe_transcipher_gather_host(const fhe_params_t *params, uint32_t cipher, uint32_t streams, int32_t round, uint32_t rows,
+                                const uint64_t *ring, const uint64_t *key, const uint8_t *ivs, const uint8_t *data,
+                                uint32_t n_bytes, uint32_t m, uint64_t *pbs_in, uint32_t *tables);
+int fhe_transcipher_apply_host(const fhe_params_t *params, uint32_t cipher, uint32_t streams, int32_t round,
+                               const uint64_t *ring, uint32_t n_bytes, uint32_t m, uint64_t *out);
+/* The same three through the kernels (csrc/transcipher_kernels.hip.h), host arrays in and out, one launch each;
+ * synchronise.  Word for word what the host loops give. */
+int fhe_engine_transcipher_init(fhe_engine *eng, uint32_t cipher, uint32_t streams, const uint64_t *key, const uint8_t *ivs,
+                                uint64_t *ring);
+int fhe_engine_transcipher_gather(fhe_engine *eng, uint32_t cipher, uint32_t streams, int32_t round, uint32_t rows,
+                                  const uint64_t *ring, const uint64_t *key, const uint8_t *ivs, const uint8_t *data,
+                                  uint32_t n_bytes, uint32_t m, uint64_t *pbs_in, uint32_t *tables);
+int fhe_engine_transcipher_apply(fhe_engine *eng, uint32_t cipher, uint32_t streams, int32_t round, const uint64_t *ring,
+                                 uint32_t n_bytes, uint32_t m, uint64_t *out);
+
+/* One cipher key on one engine (server keys loaded), for up to max_streams strings at a time.  key_cts: host rows, the
+ * encryptions of the key bits in spec order K_1 .. K_L; they are made resident.  Owned by the engine: its device memory goes with the
+ * engine at the latest; call fhe_transcipher_destroy before fhe_engine_destroy, the handle must not be used after it.  Every call below takes the engine's lock and ends a pipelined run like any serial path. */
+typedef struct fhe_transcipher fhe_transcipher;
+int fhe_transcipher_create(fhe_engine *eng, uint32_t cipher, const uint64_t *key_cts, uint32_t max_streams,
+                           fhe_transcipher **out);
+int fhe_transcipher_destroy(fhe_transcipher *tc);
+/* Start n_streams <= max_streams strings, stream s under IV ivs[s L / 8 ..]: the initial state and the 18 warm-up rounds,
+ * all streams in lockstep, one lookup level of n_streams x 192 inputs per round.  Asynchronous on the engine's stream.
+ * May be called again: it starts over. */
+int fhe_transcipher_begin(fhe_transcipher *tc, const uint8_t *ivs, uint32_t n_streams);
+/* The next n_bytes characters of every stream.  data: n_streams x n_bytes clear cipher bytes, string s at data[s n_bytes ..].
+ * Result: n_streams x n_bytes x blocks-per-character big-key block ciphertexts in the layout of an encrypted string,
+ * to exactly one of out_host (synchronises) and d_out (asynchronous on the engine's stream).
+ * EVERY CALL STARTS ON AN 8-BYTE KEYSTREAM BOUNDARY and consumes ceil(n_bytes / 8) rounds of 64 keystream bits: the
+ * keystream bytes a call leaves over are skipped.  The client passes the matching offset -- 8 x the rounds consumed so
+ * far, info[7] of fhe_transcipher_info -- when it encrypts the bytes of the next call.
+ * refresh = 1 (the default of the Python layer): the blocks, sums of log2(msg_mod) lookups each, go through one more
+ * lookup level with the identity table and come out as nominal plan inputs.  refresh = 0 leaves them at log2(msg_mod)
+ * nominal variances. */
+int fhe_transcipher_next(fhe_transcipher *tc, const uint8_t *data, uint32_t n_bytes, int refresh, uint64_t *out_host,
+                         uint64_t *d_out);
+/* info[0] cipher, [1] max_streams, [2] streams of the current run (0 before begin), [3] warm-up rounds and [4] data rounds
+ * since begin, [5] / [6] low / high word of the lookups since begin (all streams, refreshes included), [7] the keystream
+ * byte the next call starts at. */
+int fhe_transcipher_info(fhe_transcipher *tc, uint32_t info[8]);
+/* Per-phase device times of the data rounds, for measurement (scripts/transcipher_timing.py): on = 1 makes every data
+ * round end in a synchronisation and accumulates ms[0] gather, ms[1] keyswitch + PBS, ms[2] apply over *rounds rounds
+ * since begin.  ms / rounds may be NULL to switch only. */
+int fhe_transcipher_timing(fhe_transcipher *tc, int on, double ms[3], uint32_t *rounds);
+
 /* ---- tfhe-rs wire format (serde + bincode 1.x, fixed-width little endian) ---------------------- */
 /* Byte forms of core_crypto's LweCiphertext<Vec<u64>>, LweKeyswitchKey<Vec<u64>>, standard-domain
  * LweBootstrapKey<Vec<u64>> and shortint::Ciphertext as tfhe-rs 0.5 writes them with bincode::serialize /
