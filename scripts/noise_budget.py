@@ -33,12 +33,26 @@ def log2_pfail(std, bound):
     return (-(z * z) / 2 - math.log(z * math.sqrt(math.pi / 2))) / math.log(2)
 
 
+def small_key_errors(small, want, small_sel, N):
+    """Phase error of keyswitched ciphertexts `small` (count, n + 1) against the plaintexts `want` (u64) under the small key
+    with ones at small_sel, as fractions of the torus: (after the keyswitch, after the modulus switch of every element to
+    [0, 2N] -- fft_impl/common.rs:26-43, phase mod 2N)."""
+    logN = N.bit_length() - 1
+    with np.errstate(over="ignore"):
+        phase = small[:, -1] - small[:, small_sel].sum(axis=1, dtype=np.uint64)
+        e_ks = (phase - want).astype(np.int64).astype(np.float64) / 2.0**64
+        ms = ((small >> np.uint64(64 - logN - 2)) + np.uint64(1)) >> np.uint64(1)
+        ph_ms = (ms[:, -1].astype(np.int64) - ms[:, small_sel].astype(np.int64).sum(axis=1)) % (2 * N)
+        want_ms = (want.astype(np.float64) / 2.0**64) * (2 * N)
+        d = (ph_ms - want_ms + N) % (2 * N) - N
+    return e_ks, d / (2 * N)
+
+
 def measure(ks, eng, samples=8192, chunk=1024, seed=0x5EED0004):
     """Returns {shape: {"norm2": ..., "std_ks": ..., "std_ms": ..., "log2_pfail": ...}, "pbs_out_std": ...}
     (stds as fractions of the torus)."""
     import oracle as O
     p = ks.params
-    logN = p.N.bit_length() - 1
     M = p.msg_mod
     delta = p.delta
     lut, _ = ks.sk.generate_lookup_table(lambda x: x)
@@ -75,15 +89,7 @@ def measure(ks, eng, samples=8192, chunk=1024, seed=0x5EED0004):
             lin = eng.lincomb(nominal, jobs[name])
             small = eng.keyswitch(lin)
             want = (values[name].astype(np.int64).astype(np.uint64) * np.uint64(delta))
-            with np.errstate(over="ignore"):
-                phase = small[:, -1] - small[:, sel].sum(axis=1, dtype=np.uint64)
-                e_ks = (phase - want).astype(np.int64).astype(np.float64) / 2.0**64
-                # modulus switch of every element to [0, 2N] (common.rs:26-43), phase mod 2N
-                ms = ((small >> np.uint64(64 - logN - 2)) + np.uint64(1)) >> np.uint64(1)
-                ph_ms = (ms[:, -1].astype(np.int64) - ms[:, sel].astype(np.int64).sum(axis=1)) % (2 * p.N)
-                want_ms = (want.astype(np.float64) / 2.0**64) * (2 * p.N)
-                d = (ph_ms - want_ms + p.N) % (2 * p.N) - p.N
-                e_ms = d / (2 * p.N)
+            e_ks, e_ms = small_key_errors(small, want, sel, p.N)
             errs[name]["ks"].append(e_ks)
             errs[name]["ms"].append(e_ms)
         done += S
@@ -125,7 +131,6 @@ def measure_product(P, shapes, samples=2048, chunk=512, seed=0x5EED0014, eng=Non
     else:
         g, s = ck.secret_keys()
     try:
-        logN = P.N.bit_length() - 1
         Mtot = P.msg_mod * P.carry_mod
         delta = (1 << 63) // Mtot
         ident, _ = eng.generate_lookup_table(lambda x: x)
@@ -156,15 +161,9 @@ def measure_product(P, shapes, samples=2048, chunk=512, seed=0x5EED0014, eng=Non
                 value = sum(c * msgs[r] for r, c in enumerate(co))
                 small = eng.keyswitch(eng.lincomb(nominal, jobs))
                 want = value.astype(np.int64).astype(np.uint64) * np.uint64(delta)
-                with np.errstate(over="ignore"):
-                    phase = small[:, -1] - small[:, small_sel].sum(axis=1, dtype=np.uint64)
-                    e_ks = (phase - want).astype(np.int64).astype(np.float64) / 2.0**64
-                    ms = ((small >> np.uint64(64 - logN - 2)) + np.uint64(1)) >> np.uint64(1)
-                    ph_ms = (ms[:, -1].astype(np.int64) - ms[:, small_sel].astype(np.int64).sum(axis=1)) % (2 * P.N)
-                    want_ms = (want.astype(np.float64) / 2.0**64) * (2 * P.N)
-                    d = (ph_ms - want_ms + P.N) % (2 * P.N) - P.N
+                e_ks, e_ms = small_key_errors(small, want, small_sel, P.N)
                 errs[name]["ks"].append(e_ks)
-                errs[name]["ms"].append(d / (2 * P.N))
+                errs[name]["ms"].append(e_ms)
             done += S
         half = m["half_box"]
         out = {"params": P.name, "samples": samples, "half_box": half, "model": m,

@@ -81,8 +81,10 @@ static int run(const fhe_params_t& p, uint32_t cipher, uint32_t S, uint64_t seed
 }
 
 int main() {
-    // TOY_K1 (16 values, 2-bit blocks) and a 256-value shape with 4-bit blocks; toy noise, so the model accepts both
-    const fhe_params_t shapes[2] = {{16, 1, 256, 10, 2, 4, 4, 4, 4, 1e-12, 1e-15, 0}, {16, 2, 128, 10, 2, 4, 4, 16, 16, 1e-12, 1e-15, 0}};
+    // TOY_K1 (16 values, 2-bit blocks), a 256-value shape with 4-bit blocks, and the 1-bit and 8-bit shapes W1 and W8 of
+    // tests/transcipher_ref.py (8 blocks per character; 8 rows per block and 20 tables); the model accepts all four
+    const fhe_params_t shapes[4] = {{16, 1, 256, 10, 2, 4, 4, 4, 4, 1e-12, 1e-15, 0}, {16, 2, 128, 10, 2, 4, 4, 16, 16, 1e-12, 1e-15, 0},
+                                    {16, 1, 256, 10, 2, 4, 4, 2, 8, 1e-12, 1e-15, 0}, {16, 3, 512, 20, 1, 4, 4, 256, 1, 1e-12, 1e-15, 0}};
     for (const auto& p : shapes)
         for (uint32_t cipher : {FHE_STREAM_TRIVIUM, FHE_STREAM_KREYVIUM})
             for (uint32_t S : {1u, 3u})
