@@ -228,7 +228,7 @@ int fhe_engine_keyswitch_info(fhe_engine* eng, uint32_t info[6]) {
 int fhe_engine_load_packing_key(fhe_engine* eng, const fhe_packing_params_t* pp, const uint64_t* pksk) {
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(pp); CHECK_PTR(pksk);
-    return eng->impl->load_packing_key(*pp, pksk);
+    return eng->impl->packing.load_key(*pp, pksk);
     API_END
 }
 
@@ -236,7 +236,7 @@ int fhe_engine_pack_lwes(fhe_engine* eng, const uint64_t* cts, uint32_t count, u
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng);
     if (count) { CHECK_PTR(cts); CHECK_PTR(glwes_host); }
-    return eng->impl->pack_lwes_host(cts, count, glwes_host);
+    return eng->impl->packing.pack_host(cts, count, glwes_host);
     API_END
 }
 
@@ -244,7 +244,7 @@ int fhe_engine_pack_lwes_dev(fhe_engine* eng, const uint64_t* d_cts, uint32_t co
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng);
     if (count) { CHECK_PTR(d_cts); CHECK_PTR(d_glwes); }
-    return eng->impl->pack_lwes_dev(d_cts, count, d_glwes);
+    return eng->impl->packing.pack_dev(d_cts, count, d_glwes);
     API_END
 }
 
@@ -260,7 +260,7 @@ int fhe_engine_unpack_glwes(fhe_engine* eng, const uint64_t* glwes_host, uint32_
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng);
     if (count) { CHECK_PTR(glwes_host); CHECK_PTR(cts_host); }
-    return eng->impl->unpack_glwes_host(glwes_host, first, count, refresh, cts_host);
+    return eng->impl->packing.unpack_host(glwes_host, first, count, refresh, cts_host);
     API_END
 }
 
@@ -268,7 +268,7 @@ int fhe_engine_unpack_glwes_dev(fhe_engine* eng, const uint64_t* d_glwes, uint32
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng);
     if (count) { CHECK_PTR(d_glwes); CHECK_PTR(d_cts); }
-    return eng->impl->unpack_glwes_dev(d_glwes, first, count, refresh, d_cts);
+    return eng->impl->packing.unpack_dev(d_glwes, first, count, refresh, d_cts);
     API_END
 }
 
@@ -284,7 +284,7 @@ int fhe_engine_narrow_glwes(fhe_engine* eng, const uint64_t* glwes_host, uint32_
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng);
     if (held) { CHECK_PTR(glwes_host); CHECK_PTR(narrow_host); }
-    return eng->impl->narrow_glwes_host(glwes_host, held, bits, narrow_host);
+    return eng->impl->packing.narrow_host(glwes_host, held, bits, narrow_host);
     API_END
 }
 
@@ -292,7 +292,7 @@ int fhe_engine_narrow_glwes_dev(fhe_engine* eng, const uint64_t* d_glwes, uint32
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng);
     if (held) { CHECK_PTR(d_glwes); CHECK_PTR(d_narrow); }
-    return eng->impl->narrow_glwes_dev(d_glwes, held, bits, d_narrow);
+    return eng->impl->packing.narrow_dev(d_glwes, held, bits, d_narrow);
     API_END
 }
 
@@ -300,7 +300,7 @@ int fhe_engine_widen_narrow_dev(fhe_engine* eng, const uint64_t* d_narrow, uint3
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng);
     if (held) { CHECK_PTR(d_narrow); CHECK_PTR(d_glwes); }
-    return eng->impl->widen_narrow_dev(d_narrow, held, bits, d_glwes);
+    return eng->impl->packing.widen_dev(d_narrow, held, bits, d_glwes);
     API_END
 }
 
@@ -309,7 +309,7 @@ int fhe_engine_unpack_narrow(fhe_engine* eng, const uint64_t* narrow_host, uint3
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng);
     if (count) { CHECK_PTR(narrow_host); CHECK_PTR(cts_host); }
-    return eng->impl->unpack_narrow_host(narrow_host, held, bits, first, count, refresh, cts_host);
+    return eng->impl->packing.unpack_narrow_host(narrow_host, held, bits, first, count, refresh, cts_host);
     API_END
 }
 
@@ -318,7 +318,7 @@ int fhe_engine_unpack_narrow_dev(fhe_engine* eng, const uint64_t* d_narrow, uint
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng);
     if (count) { CHECK_PTR(d_narrow); CHECK_PTR(d_cts); }
-    return eng->impl->unpack_narrow_dev(d_narrow, held, bits, first, count, refresh, d_cts);
+    return eng->impl->packing.unpack_narrow_dev(d_narrow, held, bits, first, count, refresh, d_cts);
     API_END
 }
 

@@ -1,5 +1,6 @@
-// engine.h -- internal C++ interface of the engine (the public surface is include/fhestr.h).  Its members are defined in
-// engine.hip, and in blind_rotate.hip where they need a blind-rotation kernel.
+// engine.h -- internal C++ interface of the engine (the public surface is include/fhestr.h).  Engine's members are defined in
+// engine.hip, and in blind_rotate.hip where they need a blind-rotation kernel; Packing's in packing_dev.hip, Transcipher's
+// in transcipher_dev.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -107,30 +108,42 @@ struct Pipeline {
 };
 static_assert(EngineSettings::OVERLAP_MAX == Pipeline::MAX_LANES, "every width the settings accept has its lane");
 
-// The packing keyswitch (packing_ks_kernels.hip.h) and the packed inputs (glwe_extract_kernels.hip.h): the resident key,
-// the staging of the host entry points and what the last launch of each did.
-struct PackingState {
+// The packed-ciphertext family (members in packing_dev.hip): the packing keyswitch (packing_ks_kernels.hip.h), the packed
+// inputs (glwe_extract_kernels.hip.h) and the narrow packed results (glwe_narrow.h, glwe_narrow_kernels.hip.h) -- the
+// resident key, the staging of the host entry points, the launches and what the last launch of each did.  Owned by its
+// engine (Engine::packing), every launch on the engine's stream.
+struct Engine;
+struct Packing {
+    Engine* e = nullptr;                 // set in Engine::create
     DeviceBuffer<int8_t> key;            // the packing key's balanced base-256 digit planes in MFMA B-fragment order
     fhe_packing_params_t pp{0, 0};       // its decomposition
     DeviceBuffer<int8_t> digits;         // the batch's digit fragments; same reuse rules as PipeLane::digits: zeroed at allocation, grown, rows past the batch never read
     DeviceBuffer<uint64_t> pack_in, pack_out;       // staging of fhe_engine_pack_lwes (host ciphertexts)
     uint32_t pack_last[5] = {0, 0, 0, 0, 0};        // fhe_engine_packing_info: ran, MT, K chunks, K steps per chunk, K steps
-    DeviceBuffer<uint64_t> unpack_in, unpack_out;   // staging of fhe_engine_unpack_glwes
-    DeviceBuffer<uint32_t> unpack_idx;              // the refresh's table indices: the identity table's id, once per block of the largest refresh so far
+    DeviceBuffer<uint64_t> unpack_in, unpack_out;   // staging of fhe_engine_unpack_glwes; unpack_out also of fhe_engine_unpack_narrow
     uint32_t unpack_last[4] = {0, 0, 0, 0};         // fhe_engine_unpack_info: ran, rows, workgroups, refreshed
+    DeviceBuffer<uint64_t> narrow_in, narrow_out;   // staging of fhe_engine_narrow_glwes; narrow_in also of fhe_engine_unpack_narrow
+    uint32_t narrow_last[5] = {0, 0, 0, 0, 0};      // fhe_engine_narrow_info: ran, kernel (FHE_NARROW_KERNEL_*), list words / rows / GLWE words, workgroups, bits
     void pack_info(uint32_t out[5]) const { std::copy(pack_last, pack_last + 5, out); }
     void unpack_info(uint32_t out[4]) const { std::copy(unpack_last, unpack_last + 4, out); }
-    // narrow packed results (glwe_narrow_kernels.hip.h): staging of fhe_engine_narrow_glwes / fhe_engine_unpack_narrow
-    DeviceBuffer<uint64_t> narrow_in, narrow_out;
-    uint32_t narrow_last[5] = {0, 0, 0, 0, 0};      // fhe_engine_narrow_info: ran, kernel (FHE_NARROW_KERNEL_*), list words / rows / GLWE words, workgroups, bits
     void narrow_info(uint32_t out[5]) const { std::copy(narrow_last, narrow_last + 5, out); }
+
+    int load_key(const fhe_packing_params_t& pp, const uint64_t* pksk);
+    int pack_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_glwes);
+    int pack_host(const uint64_t* cts, uint32_t count, uint64_t* glwes);
+    int unpack_dev(const uint64_t* d_glwes, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts);
+    int unpack_host(const uint64_t* glwes, uint32_t first, uint32_t count, int refresh, uint64_t* cts);
+    int narrow_dev(const uint64_t* d_glwes, uint32_t held, uint32_t bits, uint64_t* d_narrow);
+    int narrow_host(const uint64_t* glwes, uint32_t held, uint32_t bits, uint64_t* narrow);
+    int widen_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint64_t* d_glwes);
+    int unpack_narrow_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts);
+    int unpack_narrow_host(const uint64_t* narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int refresh, uint64_t* cts);
 };
 
 // Transciphering (transcipher.h, transcipher_kernels.hip.h; members in transcipher_dev.hip): the resident encrypted key bits
 // of one stream-cipher key and the round ring of up to max_streams strings encrypted under it, each with its own IV,
 // advancing in lockstep -- one ks_pbs level per round for all of them.  Owned by its engine (Engine::transciphers), every
 // launch on the engine's stream.
-struct Engine;
 struct Transcipher {
     Engine* e = nullptr;
     uint32_t cipher = 0, max_streams = 0, bits = 0;
@@ -220,7 +233,8 @@ struct Engine {
     // what the last launch_keyswitch launched (fhe_engine_keyswitch_info; recorded only, read by no decision): kernel
     // (FHE_KS_KERNEL_*), row tiles / samples per workgroup, K chunks (grid.z), K steps / input coefficients per chunk, K steps / in_dim
     uint32_t ks_last[5] = {0, 0, 0, 0, 0};
-    PackingState packing;
+    Packing packing;                    // the packed-ciphertext family: pack, unpack, narrow (packing_dev.hip)
+    DeviceBuffer<uint32_t> refresh_idx; // refresh_rows_dev's table indices: the identity table's id, once per row of the largest refresh so far
     std::vector<std::unique_ptr<Transcipher>> transciphers;   // fhe_transcipher_create .. fhe_transcipher_destroy, or the engine's end
 
     static int create(const fhe_params_t& p, int device, Engine** out);
@@ -253,17 +267,7 @@ struct Engine {
     int launch_blind_rotate(const uint64_t* d_sm, const uint32_t* d_lut_idx, uint64_t* d_big, uint32_t count, hipStream_t on = nullptr, bool two_per_cu = false,
                             bool one_workgroup_only = false);   // never a kernel that needs several workgroups resident at once (MultiCuRuntime::settle's re-run)
     bool shadow_keyswitch_fits();
-    int load_packing_key(const fhe_packing_params_t& pp, const uint64_t* pksk);
-    int pack_lwes_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_glwes);
-    int pack_lwes_host(const uint64_t* cts, uint32_t count, uint64_t* glwes);
-    int unpack_glwes_dev(const uint64_t* d_glwes, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts);
-    int unpack_glwes_host(const uint64_t* glwes, uint32_t first, uint32_t count, int refresh, uint64_t* cts);
-    int refresh_rows_dev(uint64_t* d_cts, uint32_t count);   // one ks_pbs level with the identity table, in place: what both unpack forms end with
-    int narrow_glwes_dev(const uint64_t* d_glwes, uint32_t held, uint32_t bits, uint64_t* d_narrow);
-    int widen_narrow_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint64_t* d_glwes);
-    int narrow_glwes_host(const uint64_t* glwes, uint32_t held, uint32_t bits, uint64_t* narrow);
-    int unpack_narrow_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts);
-    int unpack_narrow_host(const uint64_t* narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int refresh, uint64_t* cts);
+    int refresh_rows_dev(uint64_t* d_cts, uint32_t count);   // one ks_pbs level with the identity table, in place: what both unpack forms and Transcipher::next end with
     uint32_t rotate_registers() const;             // VGPRs of variant's rotation kernel, 0 if unknown
     void keyswitch_info(uint32_t info[6]) const;   // ks_last and the register count shadow_keyswitch_fits judges by; changes nothing
     int ks_pbs_dev(const uint64_t* d_big_in, const uint32_t* d_lut_idx, uint64_t* d_big_out, uint32_t count, bool allow_pipeline = false);

@@ -1,6 +1,7 @@
-// engine.hip -- host side of libfhestr.so: device memory, key residency, the keyswitch / packing / extraction launches and the
-// ks_pbs pipeline.  The blind-rotation kernels, their variant registry and their launches are blind_rotate.hip's; this file
-// sees a variant's shape flags through blind_rotate.h.
+// engine.hip -- host side of libfhestr.so: device memory, key residency, the keyswitch launches (with the matrix-core launch
+// pieces the packing keyswitch shares: ks_mfma_launch.h) and the ks_pbs pipeline.  The blind-rotation kernels, their variant
+// registry and their launches are blind_rotate.hip's; this file sees a variant's shape flags through blind_rotate.h.  The
+// packed-ciphertext family (pack, unpack, narrow) is fhe::Packing's, in packing_dev.hip.
 //
 // The reference keeps a ServerKey {key_switching_key, bootstrapping_key (Fourier)} in host memory
 // and runs one ciphertext at a time through thread-local scratch
@@ -23,10 +24,8 @@
 #include "blind_rotate.h"
 #include "keygen_kernels.hip.h"
 #include "lwe_kernels.hip.h"
-#include "ks_mfma_kernels.hip.h"
-#include "packing_ks_kernels.hip.h"
-#include "glwe_extract_kernels.hip.h"
-#include "glwe_narrow_kernels.hip.h"
+#include "ks_mfma_launch.h"
+#include "ks_mfma_prep_kernels.hip.h"
 #include "seeded_kernels.hip.h"
 #include "compact_kernels.hip.h"
 
@@ -72,6 +71,7 @@ int Engine::create(const fhe_params_t& p, int device, Engine** out) {
     e->variant_large = vp.large;
     e->cfg = cfg;
     e->pipe.width = cfg.overlap_width;
+    e->packing.e = e.get();
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     e->cu_count = prop.multiProcessorCount;
@@ -281,7 +281,7 @@ int Engine::install_keys(DeviceBuffer<uint64_t>&& ksk_std, DeviceBuffer<uint64_t
         const KsMfmaGeom g = ks_mfma_geom(p.k * p.N, p.n + 1, p.ks_level, p.ks_base_log);
         const size_t bytes = (size_t)g.col_groups * g.steps * 8 * 1024;
         if (d_ksk_mfma.alloc(bytes)) return 1;
-        hipLaunchKernelGGL(ksk_repack_mfma_kernel, dim3(g.col_groups, g.steps), dim3(64), 0, stream, d_ksk_std.ptr, d_ksk_mfma.ptr, g);
+        ks_mfma_repack(d_ksk_std, d_ksk_mfma, g, stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));
     }
@@ -352,16 +352,8 @@ int Engine::ensure_batch(uint32_t count) {
     return d_in.reserve(count * big * 8) || d_out.reserve(count * big * 8) || reserve_idle(pipe.lane[0].small, count * small * 8) || d_idx.reserve((size_t)count * 4);
 }
 
-// ---- matrix-core keyswitch: the host plan its two users share (launch_keyswitch, pack_lwes_dev) ------------------------
-// int8 matrix product on the matrix cores: digits -> A fragments, then 32x32x32 tiles over (samples, columns x planes, rows)
-struct KsMfmaLaunch {
-    uint32_t row_tiles, mt, gy;   // 32-sample tiles; of them per workgroup (64 mt threads); grid.y
-    uint32_t chunks, spc;         // K chunks (grid.z), K steps per chunk
-    size_t digit_bytes;           // A fragments of the batch
-    dim3 grid(const KsMfmaGeom& g) const { return dim3(g.col_groups, gy, chunks); }
-    void info(uint32_t out[5], uint32_t first, const KsMfmaGeom& g) const { out[0] = first; out[1] = mt; out[2] = chunks; out[3] = spc; out[4] = g.steps; }
-};
-static KsMfmaLaunch ks_mfma_plan(const KsMfmaGeom& g, uint32_t count, uint32_t base_log, int cu_count, uint32_t chunks_override) {
+// ---- matrix-core keyswitch: the host pieces its two users share (launch_keyswitch, Packing::pack_dev; ks_mfma_launch.h) ----
+KsMfmaLaunch ks_mfma_plan(const KsMfmaGeom& g, uint32_t count, uint32_t base_log, int cu_count, uint32_t chunks_override) {
     KsMfmaLaunch l{};
     l.row_tiles = (count + 31) / 32;
     l.digit_bytes = (size_t)l.row_tiles * g.steps * 1024;
@@ -379,10 +371,7 @@ static KsMfmaLaunch ks_mfma_plan(const KsMfmaGeom& g, uint32_t count, uint32_t b
     l.chunks = (g.steps + l.spc - 1) / l.spc;
     return l;
 }
-// The batch's digit fragments on stream s.  The buffer is zeroed when it is allocated and only grows: the pad slots stay
-// zero, rows past the batch are never read.  Another stream's launch may still read the allocation being replaced.
-static int ks_mfma_digits(Engine& e, DeviceBuffer<int8_t>& digits, const KsMfmaLaunch& l, const KsMfmaGeom& g, const uint64_t* d_lwes,
-                          uint32_t count, hipStream_t s) {
+int ks_mfma_digits(Engine& e, DeviceBuffer<int8_t>& digits, const KsMfmaLaunch& l, const KsMfmaGeom& g, const uint64_t* d_lwes, uint32_t count, hipStream_t s) {
     if (digits.bytes < l.digit_bytes) {
         if (e.reserve_idle(digits, l.digit_bytes)) return 1;
         HIP_TRY(hipMemsetAsync(digits, 0, l.digit_bytes, s));
@@ -390,6 +379,9 @@ static int ks_mfma_digits(Engine& e, DeviceBuffer<int8_t>& digits, const KsMfmaL
     KsDecomposeArgs da{d_lwes, digits, g, count};
     hipLaunchKernelGGL(ks_decompose_kernel, dim3((2 * g.steps + 255) / 256, count), dim3(256), 0, s, da);
     return 0;
+}
+void ks_mfma_repack(const uint64_t* d_std, int8_t* planes, const KsMfmaGeom& g, hipStream_t s) {
+    hipLaunchKernelGGL(ksk_repack_mfma_kernel, dim3(g.col_groups, g.steps), dim3(64), 0, s, d_std, planes, g);
 }
 
 int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t count, DeviceBuffer<int8_t>& digits, hipStream_t on, bool shadow) {
@@ -430,108 +422,8 @@ int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t cou
     return 0;
 }
 
-// ---- packing keyswitch (packing_ks_kernels.hip.h) ---------------------------------------------------------------------
-// The key [kN][level][k+1][N] goes up once and is rewritten into balanced base-256 digit planes by the keyswitch's own
-// ksk_repack_mfma_kernel with (k+1) N columns; the 64-bit layout is then released.
-int Engine::load_packing_key(const fhe_packing_params_t& pp, const uint64_t* pksk) {
-    if (use()) return 1;
-    if (packing_params_check(p, pp)) return 1;
-    if (sync_all_streams()) return 1;                       // a launch in flight may still read the previous key or its digits
-    const char* const who = "load_packing_key";
-    packing.key.release();
-    packing.digits.release();      // the pad slots depend on the level count
-    for (auto& w : packing.pack_last) w = 0;
-    const KsMfmaGeom g = ks_mfma_geom(p.k * p.N, (p.k + 1) * p.N, pp.level, pp.base_log);
-    const size_t words = (size_t)g.in_dim * pp.level * g.out_size;
-    DeviceBuffer<uint64_t> d_std;
-    DeviceBuffer<int8_t> planes;      // becomes the resident key only once it is complete
-    if (d_std.alloc(words * 8)) return 1;
-    if (under(who, planes.alloc((size_t)g.col_groups * g.steps * 8 * 1024)) ||
-        under(who, hipMemcpyAsync(d_std, pksk, words * 8, hipMemcpyHostToDevice, stream)))
-        return 1;
-    hipLaunchKernelGGL(ksk_repack_mfma_kernel, dim3(g.col_groups, g.steps), dim3(64), 0, stream, d_std.ptr, planes.ptr, g);
-    if (under(who, hipGetLastError()) || under(who, hipStreamSynchronize(stream))) return 1;
-    d_std.release();      // the 64-bit layout (3.2 GB at N = 8192) goes as soon as the repack is done
-    packing.key = std::move(planes);
-    packing.pp = pp;
-    return 0;
-}
-
-// count big-key LWEs at d_cts -> ceil(count / N) GLWEs at d_glwes: memset, digits, product with the rotate-and-sum
-// epilogue.  Ordered on the engine's stream; nothing synchronises -- except in the throughput modes
-// (fhe_engine_set_pipeline 1 / 2), whose calls write their outputs on other streams: there the call first waits for every
-// stream and ends the pipelined run, like any serial call (include/fhestr.h says so).
-int Engine::pack_lwes_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_glwes) {
-    if (use()) return 1;
-    if (!packing.key) return fail("packing key not loaded");
-    if (count == 0) return 0;
-    if (count > 65535u) return fail("batch too large for one packing launch (max 65535 LWEs)");   // grid.y of the digit kernel
-    if (leave_pipelined_run()) return 1;                    // pipelined calls may still write the input on another stream
-    const uint32_t in_dim = p.k * p.N, out_size = (p.k + 1) * p.N;
-    const KsMfmaGeom g = ks_mfma_geom(in_dim, out_size, packing.pp.level, packing.pp.base_log);
-    const uint32_t n_glwe = (count + p.N - 1) / p.N;
-    HIP_TRY(hipMemsetAsync(d_glwes, 0, (size_t)n_glwe * out_size * 8, stream));
-    const KsMfmaLaunch l = ks_mfma_plan(g, count, packing.pp.base_log, cu_count, cfg.ks_chunks_override);
-    if (ks_mfma_digits(*this, packing.digits, l, g, d_cts, count, stream)) return 1;
-    PackKsArgs pa{d_cts, packing.key, packing.digits, d_glwes, g, count, l.row_tiles, l.spc, p.N, p.k * p.N / 32};
-    switch (l.mt) {
-        case 1: hipLaunchKernelGGL(packing_ks_mfma_kernel<1>, l.grid(g), dim3(64), 0, stream, pa); break;
-        case 2: hipLaunchKernelGGL(packing_ks_mfma_kernel<2>, l.grid(g), dim3(128), 0, stream, pa); break;
-        case 4: hipLaunchKernelGGL(packing_ks_mfma_kernel<4>, l.grid(g), dim3(256), 0, stream, pa); break;
-        default: hipLaunchKernelGGL(packing_ks_mfma_kernel<8>, l.grid(g), dim3(512), 0, stream, pa); break;
-    }
-    l.info(packing.pack_last, 1, g);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int Engine::pack_lwes_host(const uint64_t* cts, uint32_t count, uint64_t* glwes) {
-    if (use()) return 1;
-    if (!packing.key) return fail("packing key not loaded");
-    if (count == 0) return 0;
-    const size_t big = (size_t)p.k * p.N + 1, out_words = (size_t)((count + p.N - 1) / p.N) * (p.k + 1) * p.N;
-    if (reserve_idle(packing.pack_in, count * big * 8) || reserve_idle(packing.pack_out, out_words * 8)) return 1;
-    HIP_TRY(hipMemcpyAsync(packing.pack_in, cts, count * big * 8, hipMemcpyHostToDevice, stream));
-    if (pack_lwes_dev(packing.pack_in, count, packing.pack_out)) return 1;
-    HIP_TRY(hipMemcpyAsync(glwes, packing.pack_out, out_words * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return 0;
-}
-
-// ---- packed inputs (glwe_extract_kernels.hip.h) -----------------------------------------------------------------------
-// Blocks first .. first + count - 1 of the packed GLWEs at d_glwes (block j = coefficient j % N of GLWE j / N, the layout
-// pack_lwes_dev writes) -> count big-key LWEs at d_cts.  Ordered on the engine's stream, nothing synchronises -- except,
-// like pack_lwes_dev, in the throughput modes, and once per engine when the first refresh uploads the identity table.
-// refresh: the extracted blocks carry the packing keyswitch's noise on top of a PBS output's, a plan's inputs are declared
-// nominal (circuit.cpp: noise = 1.0); one ks_pbs level with the identity table over the whole message-and-carry space
-// brings them back, in place.  Refused where the model puts a raw block above the PBS-input budget.
-int Engine::unpack_glwes_dev(const uint64_t* d_glwes, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts) {
-    if (use()) return 1;
-    if (count == 0) return 0;
-    const uint32_t kN = p.k * p.N;
-    if (p.N < 2 || (p.N & (p.N - 1))) return fail("unpack_glwes: polynomial size must be a power of two");
-    if (refresh) {
-        if (!packing.key) return fail("unpack_glwes: the refresh needs the loaded packing key's decomposition to judge the blocks' noise; none is loaded");
-        double v[2];
-        packing_unpack_noise(p, packing.pp, v);
-        if (!(v[0] <= v[1]))
-            return fail("unpack_glwes: refresh refused, a raw extracted block carries " + std::to_string(v[0]) +
-                        " nominal variances, the PBS-input budget is " + std::to_string(v[1]));
-    }
-    if (leave_pipelined_run()) return 1;                    // pipelined calls may still read or write these buffers on other streams
-    const uint32_t chunks = (kN / 2 + GLWE_EXTRACT_PAIRS_PER_WG - 1) / GLWE_EXTRACT_PAIRS_PER_WG;
-    if ((uint64_t)count * chunks > 0x7FFFFFFFull) return fail("unpack_glwes: too many ciphertexts for one launch");
-    hipLaunchKernelGGL(glwe_sample_extract_kernel, dim3(count * chunks), dim3(256), 0, stream, d_glwes, d_cts, p.N, kN, first, count, chunks);
-    packing.unpack_last[0] = 1; packing.unpack_last[1] = count; packing.unpack_last[2] = count * chunks; packing.unpack_last[3] = 0;
-    HIP_TRY(hipGetLastError());
-    if (!refresh) return 0;
-    if (refresh_rows_dev(d_cts, count)) return 1;
-    packing.unpack_last[3] = 1;
-    return 0;
-}
-
-// The refresh of both unpack forms: count extracted rows at d_cts through one keyswitch + PBS with the identity table over
-// the whole message-and-carry space, in place, on the engine's stream.
+// The refresh of both unpack forms (packing_dev.hip) and of Transcipher::next: count rows at d_cts through one keyswitch +
+// PBS with the identity table over the whole message-and-carry space, in place, on the engine's stream.
 int Engine::refresh_rows_dev(uint64_t* d_cts, uint32_t count) {
     const uint32_t M = p.msg_mod * p.carry_mod;
     std::vector<uint64_t> table(M), acc;
@@ -539,116 +431,9 @@ int Engine::refresh_rows_dev(uint64_t* d_cts, uint32_t count) {
     fill_accumulator(table.data(), acc);
     uint32_t id = 0;
     if (lut_upload_dedup(acc, &id)) return 1;
-    if (reserve_idle(packing.unpack_idx, (size_t)count * 4)) return 1;   // an earlier refresh may still read the smaller array
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)packing.unpack_idx.ptr, (int)id, count, stream));
-    return ks_pbs_dev(d_cts, packing.unpack_idx, d_cts, count);   // the keyswitch has read every row before the rotation writes one
-}
-
-int Engine::unpack_glwes_host(const uint64_t* glwes, uint32_t first, uint32_t count, int refresh, uint64_t* cts) {
-    if (use()) return 1;
-    if (count == 0) return 0;
-    const size_t big = (size_t)p.k * p.N + 1, glwe_len = (size_t)(p.k + 1) * p.N;
-    const uint64_t g_lo = first / p.N, g_hi = ((uint64_t)first + count - 1) / p.N;      // only the GLWEs the range touches go up
-    const size_t in_words = (size_t)(g_hi - g_lo + 1) * glwe_len;
-    if (reserve_idle(packing.unpack_in, in_words * 8) || reserve_idle(packing.unpack_out, count * big * 8)) return 1;
-    HIP_TRY(hipMemcpyAsync(packing.unpack_in, glwes + (size_t)g_lo * glwe_len, in_words * 8, hipMemcpyHostToDevice, stream));
-    if (unpack_glwes_dev(packing.unpack_in, first % p.N, count, refresh, packing.unpack_out)) return 1;
-    HIP_TRY(hipMemcpyAsync(cts, packing.unpack_out, count * big * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return refresh ? multi_cu.check() : 0;
-}
-
-// ---- narrow packed results (glwe_narrow.h, glwe_narrow_kernels.hip.h) -------------------------------------------------
-// The packed GLWEs of `held` blocks at d_glwes (what pack_lwes_dev wrote) -> their narrow list at d_narrow, narrow_len
-// words.  Ordered on the engine's stream under pack_lwes_dev's contract.
-int Engine::narrow_glwes_dev(const uint64_t* d_glwes, uint32_t held, uint32_t bits, uint64_t* d_narrow) {
-    if (use()) return 1;
-    const uint64_t words = narrow_len(p.N, p.k, held, bits);
-    if (!words) return held ? fail("narrow_glwes: the width must be 8 .. 32 bits and the polynomial size a power of two") : 0;
-    if (leave_pipelined_run()) return 1;
-    const uint32_t kN = p.k * p.N, stride = (uint32_t)narrow_stream_words((size_t)kN + p.N, bits);
-    const uint64_t wgs = (words + 255) / 256;
-    if (wgs > 0x7FFFFFFFull) return fail("narrow_glwes: too many blocks for one launch");
-    hipLaunchKernelGGL(glwe_narrow_kernel, dim3((uint32_t)wgs), dim3(256), 0, stream, d_glwes, d_narrow, p.N, kN, held, bits, stride, words);
-    const uint32_t last[5] = {1, FHE_NARROW_KERNEL_NARROW, (uint32_t)words, (uint32_t)wgs, bits};
-    std::copy(last, last + 5, packing.narrow_last);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// The inverse layout change on the device: the narrow list at d_narrow -> ceil(held / N) full GLWEs at d_glwes, what
-// unpack_glwes_dev reads.  Same contract.
-int Engine::widen_narrow_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint64_t* d_glwes) {
-    if (use()) return 1;
-    if (!narrow_len(p.N, p.k, held, bits)) return held ? fail("widen_narrow: the width must be 8 .. 32 bits and the polynomial size a power of two") : 0;
-    if (leave_pipelined_run()) return 1;
-    const uint32_t kN = p.k * p.N, stride = (uint32_t)narrow_stream_words((size_t)kN + p.N, bits);
-    const uint64_t words = (((uint64_t)held + p.N - 1) / p.N) * ((uint64_t)kN + p.N), wgs = (words + 255) / 256;
-    if (wgs > 0x7FFFFFFFull) return fail("widen_narrow: too many blocks for one launch");
-    hipLaunchKernelGGL(glwe_widen_kernel, dim3((uint32_t)wgs), dim3(256), 0, stream, d_narrow, d_glwes, p.N, kN, held, bits, stride, words);
-    const uint32_t last[5] = {1, FHE_NARROW_KERNEL_WIDEN, (uint32_t)words, (uint32_t)wgs, bits};
-    std::copy(last, last + 5, packing.narrow_last);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int Engine::narrow_glwes_host(const uint64_t* glwes, uint32_t held, uint32_t bits, uint64_t* narrow) {
-    if (use()) return 1;
-    const size_t words = narrow_len(p.N, p.k, held, bits), in_words = (size_t)(((uint64_t)held + p.N - 1) / p.N) * (p.k + 1) * p.N;
-    if (!words) return narrow_glwes_dev(nullptr, held, bits, nullptr);      // nothing held, or the refusal
-    if (reserve_idle(packing.narrow_in, in_words * 8) || reserve_idle(packing.narrow_out, words * 8)) return 1;
-    HIP_TRY(hipMemcpyAsync(packing.narrow_in, glwes, in_words * 8, hipMemcpyHostToDevice, stream));
-    if (narrow_glwes_dev(packing.narrow_in, held, bits, packing.narrow_out)) return 1;
-    HIP_TRY(hipMemcpyAsync(narrow, packing.narrow_out, words * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return 0;
-}
-
-// Blocks first .. first + count - 1 of the narrow list of `held` blocks at d_narrow -> count big-key LWEs at d_cts: the
-// rows unpack_glwes_dev would extract from the widened GLWEs, under its contract on streams and alignment.  The refresh is
-// judged with the narrowing's term on top of the packing's (narrow_noise).
-int Engine::unpack_narrow_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts) {
-    if (use()) return 1;
-    if (!narrow_bits_ok(bits)) return fail("unpack_narrow: the width must be 8 .. 32 bits");
-    if (!narrow_len(p.N, p.k, 1, bits)) return fail("unpack_narrow: polynomial size must be a power of two, (k + 1) N below 2^27");
-    if ((uint64_t)first + count > held)
-        return fail("unpack_narrow: blocks " + std::to_string(first) + " .. " + std::to_string((uint64_t)first + count) + " asked of a list that holds " + std::to_string(held));
-    if (count == 0) return 0;
-    if (refresh) {
-        if (!packing.key) return fail("unpack_narrow: the refresh needs the loaded packing key's decomposition to judge the blocks' noise; none is loaded");
-        double v[3];
-        narrow_noise(p, packing.pp, bits, v);
-        if (!(v[0] <= v[1]))
-            return fail("unpack_narrow: refresh refused, a raw block extracted at " + std::to_string(bits) + " bits under the packing pair (" +
-                        std::to_string(packing.pp.base_log) + ", " + std::to_string(packing.pp.level) + ") carries " + std::to_string(v[0]) +
-                        " nominal variances, the PBS-input budget is " + std::to_string(v[1]));
-    }
-    if (leave_pipelined_run()) return 1;
-    const uint32_t kN = p.k * p.N, stride = (uint32_t)narrow_stream_words((size_t)kN + p.N, bits);
-    const uint32_t chunks = (kN / 2 + GLWE_EXTRACT_PAIRS_PER_WG - 1) / GLWE_EXTRACT_PAIRS_PER_WG;
-    if ((uint64_t)count * chunks > 0x7FFFFFFFull) return fail("unpack_narrow: too many ciphertexts for one launch");
-    hipLaunchKernelGGL(narrow_sample_extract_kernel, dim3(count * chunks), dim3(256), 0, stream, d_narrow, d_cts, p.N, kN, held, bits, stride, first,
-                       count, chunks);
-    const uint32_t last[5] = {1, FHE_NARROW_KERNEL_EXTRACT, count, count * chunks, bits};
-    std::copy(last, last + 5, packing.narrow_last);
-    HIP_TRY(hipGetLastError());
-    return refresh ? refresh_rows_dev(d_cts, count) : 0;
-}
-
-int Engine::unpack_narrow_host(const uint64_t* narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int refresh, uint64_t* cts) {
-    if (use()) return 1;
-    if (count == 0 || !narrow_len(p.N, p.k, held, bits) || (uint64_t)first + count > held)
-        return unpack_narrow_dev(nullptr, held, bits, first, count, refresh, nullptr);   // nothing to do, or the refusal
-    const size_t big = (size_t)p.k * p.N + 1, stride = narrow_stream_words((size_t)(p.k + 1) * p.N, bits);
-    const uint32_t g_lo = first / p.N, g_hi = (first + count - 1) / p.N;     // only the streams the range touches go up
-    const uint32_t held_up = std::min<uint64_t>(held, ((uint64_t)g_hi + 1) * p.N) - g_lo * p.N;   // a list of its own: streams g_lo .. g_hi
-    const size_t in_words = narrow_len(p.N, p.k, held_up, bits);
-    if (reserve_idle(packing.narrow_in, in_words * 8) || reserve_idle(packing.unpack_out, count * big * 8)) return 1;
-    HIP_TRY(hipMemcpyAsync(packing.narrow_in, narrow + (size_t)g_lo * stride, in_words * 8, hipMemcpyHostToDevice, stream));
-    if (unpack_narrow_dev(packing.narrow_in, held_up, bits, first - g_lo * p.N, count, refresh, packing.unpack_out)) return 1;
-    HIP_TRY(hipMemcpyAsync(cts, packing.unpack_out, count * big * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return refresh ? multi_cu.check() : 0;
+    if (reserve_idle(refresh_idx, (size_t)count * 4)) return 1;   // an earlier refresh may still read the smaller array
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)refresh_idx.ptr, (int)id, count, stream));
+    return ks_pbs_dev(d_cts, refresh_idx, d_cts, count);   // the keyswitch has read every row before the rotation writes one
 }
 
 void Engine::keyswitch_info(uint32_t info[6]) const {

@@ -21,6 +21,8 @@
 //   digits[row tile][step][lane][16] int8              exactly the A fragments, written by ks_decompose_kernel
 // K is split over workgroups (grid.z) so that the launch fills the GPU; partial sums meet in 64-bit integer atomics
 // (wrapping addition is associative and commutative: deterministic, bit-exact).
+// This header holds the geometry, the argument structs and the product kernel (a template: instantiated where it is launched).
+// ksk_repack_mfma_kernel and ks_decompose_kernel, which are not templates, are in ks_mfma_prep_kernels.hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -52,76 +54,12 @@ __host__ __device__ inline KsMfmaGeom ks_mfma_geom(uint32_t in_dim, uint32_t out
     return g;
 }
 
-// Key words -> balanced base-256 digit planes in B-fragment order.  One thread per (column group, step, lane, plane-octet).
-__global__ void __launch_bounds__(64) ksk_repack_mfma_kernel(const uint64_t* __restrict__ ksk, int8_t* __restrict__ out, KsMfmaGeom g) {
-    const uint32_t cg = blockIdx.x, step = blockIdx.y, lane = threadIdx.x;
-    const uint32_t c = lane & 31, h = lane >> 5;
-    const uint32_t col = cg * 32 + c;
-    int8_t frag[8][16];
-#pragma unroll
-    for (int t = 0; t < 8; t++)
-#pragma unroll
-        for (int j = 0; j < 16; j++) frag[t][j] = 0;
-    for (uint32_t j = 0; j < g.epg * g.level; j++) {
-        const uint32_t i = (step * 2 + h) * g.epg + j / g.level, lv = j % g.level;
-        uint64_t k = 0;
-        if (i < g.in_dim && col < g.out_size) k = ksk[((size_t)i * g.level + lv) * g.out_size + col];
-#pragma unroll
-        for (int t = 0; t < 8; t++) {
-            const int8_t s = (int8_t)(uint8_t)(k & 0xff);        // balanced digit: low byte read as signed
-            frag[t][j] = s;
-            k = (k - (uint64_t)(int64_t)s) >> 8;                  // exact: k - s is a multiple of 256 (mod 2^64)
-        }
-    }
-    int8_t* dst = out + (((size_t)cg * g.steps + step) * 8) * 1024 + (size_t)lane * 16;
-#pragma unroll
-    for (int t = 0; t < 8; t++) {
-        ksm_v4i w;
-        __builtin_memcpy(&w, frag[t], 16);
-        *reinterpret_cast<ksm_v4i*>(dst + (size_t)t * 1024) = w;
-    }
-}
-
 struct KsDecomposeArgs {
     const uint64_t* lwe_in;     // [batch][in_dim + 1]
     int8_t* digits;             // [row tile][step][64][16], pad slots zeroed at allocation and never written
     KsMfmaGeom g;
     uint32_t batch;
 };
-
-// One thread per (sample, 16-slot group): the reference's signed decomposition (level L first, iter.rs:101-127) of the
-// group's floor(16 / level) mask elements, stored as ONE 16-byte A-fragment element (pad slots written as zero digits).
-__global__ void __launch_bounds__(256) ks_decompose_kernel(KsDecomposeArgs a) {
-    const uint32_t grp = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-    if (grp >= 2 * a.g.steps) return;
-    const uint32_t L = a.g.level, bl = a.g.base_log, rep = bl * L;
-    const uint64_t mask = (1ull << bl) - 1;
-    const uint64_t* src = a.lwe_in + (size_t)b * (a.g.in_dim + 1);
-    int8_t frag[16];
-#pragma unroll
-    for (int j = 0; j < 16; j++) frag[j] = 0;
-    for (uint32_t e = 0; e < a.g.epg; e++) {
-        const uint32_t i = grp * a.g.epg + e;
-        const uint64_t x = i < a.g.in_dim ? src[i] : 0;
-        const uint64_t t = x >> (63 - rep);
-        uint64_t state = ((t + 1) >> 1) & ((1ull << rep) - 1);
-        for (uint32_t lv = 0; lv < L; lv++) {
-            uint64_t res = state & mask;
-            state >>= bl;
-            uint64_t carry = ((res - 1ull) | state) & res;
-            carry >>= bl - 1;
-            state += carry;
-            const int8_t d = (int8_t)((int32_t)(uint32_t)res - (int32_t)((uint32_t)carry << bl));
-            // frag[e * L + lv] without a dynamically indexed private array
-#pragma unroll
-            for (int j = 0; j < 16; j++) frag[j] = (uint32_t)j == e * L + lv ? d : frag[j];
-        }
-    }
-    const uint32_t step = grp >> 1, h = grp & 1;
-    ksm_v4i w;
-    __builtin_memcpy(&w, frag, 16);
-    *reinterpret_cast<ksm_v4i*>(a.digits + (((size_t)(b >> 5) * a.g.steps + step) * 64 + (h * 32 + (b & 31))) * 16) = w;
-}
 
 struct KsMfmaArgs {
     const uint64_t* lwe_in;     // bodies are added here

@@ -1,0 +1,28 @@
+// ks_mfma_launch.h -- the host side the two matrix-core products share: the LWE keyswitch (Engine::launch_keyswitch,
+// engine.hip) and the packing keyswitch (Packing::pack_dev, packing_dev.hip).  Declared here, defined once, in engine.hip,
+// next to the only inclusion of the two operand kernels (ks_mfma_prep_kernels.hip.h).
+#pragma once
+#include "device_buffer.h"
+#include "ks_mfma_kernels.hip.h"
+
+namespace fhe {
+
+struct Engine;
+
+// int8 matrix product on the matrix cores: digits -> A fragments, then 32x32x32 tiles over (samples, columns x planes, rows)
+struct KsMfmaLaunch {
+    uint32_t row_tiles, mt, gy;   // 32-sample tiles; of them per workgroup (64 mt threads); grid.y
+    uint32_t chunks, spc;         // K chunks (grid.z), K steps per chunk
+    size_t digit_bytes;           // A fragments of the batch
+    dim3 grid(const KsMfmaGeom& g) const { return dim3(g.col_groups, gy, chunks); }
+    void info(uint32_t out[5], uint32_t first, const KsMfmaGeom& g) const { out[0] = first; out[1] = mt; out[2] = chunks; out[3] = spc; out[4] = g.steps; }
+};
+KsMfmaLaunch ks_mfma_plan(const KsMfmaGeom& g, uint32_t count, uint32_t base_log, int cu_count, uint32_t chunks_override);
+// The batch's digit fragments on stream s.  The buffer is zeroed when it is allocated and only grows: the pad slots stay
+// zero, rows past the batch are never read.  Another stream's launch may still read the allocation being replaced.
+int ks_mfma_digits(Engine& e, DeviceBuffer<int8_t>& digits, const KsMfmaLaunch& l, const KsMfmaGeom& g, const uint64_t* d_lwes, uint32_t count, hipStream_t s);
+// A key's words at d_std -> its balanced base-256 digit planes in B-fragment order at planes (col_groups x steps x 8 KB), on
+// stream s.  Only the launch: the caller reads hipGetLastError and synchronises under its own name.
+void ks_mfma_repack(const uint64_t* d_std, int8_t* planes, const KsMfmaGeom& g, hipStream_t s);
+
+}  // namespace fhe

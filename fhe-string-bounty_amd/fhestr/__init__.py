@@ -853,6 +853,24 @@ class Engine:
         _check(lib().fhe_engine_transcipher_apply(self._h, _cipher_id(cipher), streams, round, _ptr(_u64(ring)), n_bytes, m, _ptr(out)))
         return out
 
+    def _dev_to_host(self, dev, d_in: int, shape) -> np.ndarray:
+        """pack / unpack / narrow / unpack_narrow on a device input without d_out: dev(d_in, pointer) writes `shape` words
+        into a device tensor allocated here, which comes back as a host array once the engine's stream is idle."""
+        import torch
+        out = torch.empty(shape, dtype=torch.int64, device=f"cuda:{self.device}")
+        torch.cuda.synchronize()
+        dev(d_in, out.data_ptr())
+        self.synchronize()
+        return out.cpu().numpy().view(np.uint64)
+
+    def _host_to_dev(self, dev, words: np.ndarray, d_out: int) -> None:
+        """unpack / unpack_narrow of a host array into d_out: the words go up, dev(pointer, d_out) reads them there."""
+        import torch
+        d_in = torch.from_numpy(words.view(np.int64)).to(f"cuda:{self.device}")
+        torch.cuda.synchronize()
+        dev(d_in.data_ptr(), d_out)
+        self.synchronize()                                  # d_in is released on return
+
     def narrow(self, glwes=None, held: int | None = None, bits: int | None = None, d_in: int | None = None, d_out: int | None = None):
         """Packed GLWEs narrowed to `bits`-bit coefficients on the GPU (csrc/glwe_narrow_kernels.hip.h; the definition:
         include/fhestr.h, "narrow packed results"): the GLWEs of `held` blocks -> narrow_len(params, held, bits) words.
@@ -872,16 +890,11 @@ class Engine:
         words = narrow_len(p, held, bits)
         if held and not words:
             raise FheError(f"narrow: a width of {bits} bits is refused (8 .. 32)")
+        dev = lambda src, dst: _check(lib().fhe_engine_narrow_glwes_dev(self._h, C.c_void_p(src), held, bits, C.c_void_p(dst)))
         if d_in:
             if d_out:
-                _check(lib().fhe_engine_narrow_glwes_dev(self._h, C.c_void_p(d_in), held, bits, C.c_void_p(d_out)))
-                return None
-            import torch
-            out = torch.empty((max(words, 1),), dtype=torch.int64, device=f"cuda:{self.device}")
-            torch.cuda.synchronize()
-            _check(lib().fhe_engine_narrow_glwes_dev(self._h, C.c_void_p(d_in), held, bits, C.c_void_p(out.data_ptr())))
-            self.synchronize()
-            return NarrowString(out[:words].cpu().numpy().view(np.uint64), held, held // blocks_per_char(p), bits)
+                return dev(d_in, d_out)
+            return NarrowString(self._dev_to_host(dev, d_in, (max(words, 1),))[:words], held, held // blocks_per_char(p), bits)
         glwes = _u64(glwes).reshape(-1)
         if glwes.size != packed_glwe_len(p, held):
             raise FheError(f"narrow: {glwes.size} words are not the packed GLWEs of {held} blocks of this parameter set")
@@ -917,26 +930,16 @@ class Engine:
         if count is None:
             count = held - first
         args = (held, bits, first, count, int(bool(refresh)))
+        dev = lambda src, dst: _check(lib().fhe_engine_unpack_narrow_dev(self._h, C.c_void_p(src), *args, C.c_void_p(dst)))
         if d_in:
             if d_out:
-                _check(lib().fhe_engine_unpack_narrow_dev(self._h, C.c_void_p(d_in), *args, C.c_void_p(d_out)))
-                return None
-            import torch
-            out = torch.empty((max(count, 0), p.big_size), dtype=torch.int64, device=f"cuda:{self.device}")
-            torch.cuda.synchronize()
-            _check(lib().fhe_engine_unpack_narrow_dev(self._h, C.c_void_p(d_in), *args, C.c_void_p(out.data_ptr())))
-            self.synchronize()
-            return out.cpu().numpy().view(np.uint64)
+                return dev(d_in, d_out)
+            return self._dev_to_host(dev, d_in, (max(count, 0), p.big_size))
         narrow = _u64(narrow).reshape(-1)
         if narrow.size != narrow_len(p, held, bits):
             raise FheError(f"unpack_narrow: {narrow.size} words are not the narrow list of {held} blocks at {bits} bits of this parameter set")
         if d_out:
-            import torch
-            d_narrow = torch.from_numpy(narrow.view(np.int64)).to(f"cuda:{self.device}")
-            torch.cuda.synchronize()
-            _check(lib().fhe_engine_unpack_narrow_dev(self._h, C.c_void_p(d_narrow.data_ptr()), *args, C.c_void_p(d_out)))
-            self.synchronize()                              # d_narrow is released on return
-            return None
+            return self._host_to_dev(dev, narrow, d_out)
         out = np.zeros((max(count, 0), p.big_size), dtype=np.uint64)
         _check(lib().fhe_engine_unpack_narrow(self._h, _ptr(narrow), *args, _ptr(out)))
         return out
@@ -963,16 +966,10 @@ class Engine:
         if d_in:
             if count is None:
                 raise FheError("pack: a device buffer needs a count")
+            dev = lambda src, dst: _check(lib().fhe_engine_pack_lwes_dev(self._h, C.c_void_p(src), count, C.c_void_p(dst)))
             if d_out:
-                _check(lib().fhe_engine_pack_lwes_dev(self._h, C.c_void_p(d_in), count, C.c_void_p(d_out)))
-                return None
-            import torch
-            n_glwe = -(-count // p.N)
-            out = torch.empty((n_glwe, p.k + 1, p.N), dtype=torch.int64, device=f"cuda:{self.device}")
-            torch.cuda.synchronize()
-            _check(lib().fhe_engine_pack_lwes_dev(self._h, C.c_void_p(d_in), count, C.c_void_p(out.data_ptr())))
-            self.synchronize()
-            return out.cpu().numpy().view(np.uint64)
+                return dev(d_in, d_out)
+            return self._dev_to_host(dev, d_in, (-(-count // p.N), p.k + 1, p.N))
         cts = _u64(cts).reshape(-1, p.big_size)
         out = np.zeros((-(-cts.shape[0] // p.N), p.k + 1, p.N), dtype=np.uint64)
         _check(lib().fhe_engine_pack_lwes(self._h, _ptr(cts), cts.shape[0], _ptr(out)))
@@ -1003,26 +1000,16 @@ class Engine:
             count = getattr(glwes, "count", None)
         if count is None:
             raise FheError("unpack: a block count is required")
+        dev = lambda src, dst: _check(lib().fhe_engine_unpack_glwes_dev(self._h, C.c_void_p(src), first, count, int(bool(refresh)), C.c_void_p(dst)))
         if d_in:
             if d_out:
-                _check(lib().fhe_engine_unpack_glwes_dev(self._h, C.c_void_p(d_in), first, count, int(bool(refresh)), C.c_void_p(d_out)))
-                return None
-            import torch
-            out = torch.empty((count, p.big_size), dtype=torch.int64, device=f"cuda:{self.device}")
-            torch.cuda.synchronize()
-            _check(lib().fhe_engine_unpack_glwes_dev(self._h, C.c_void_p(d_in), first, count, int(bool(refresh)), C.c_void_p(out.data_ptr())))
-            self.synchronize()
-            return out.cpu().numpy().view(np.uint64)
+                return dev(d_in, d_out)
+            return self._dev_to_host(dev, d_in, (count, p.big_size))
         glwes = _u64(glwes).reshape(-1)
         if glwes.size < packed_glwe_len(p, first + count) or glwes.size % ((p.k + 1) * p.N):
             raise FheError(f"unpack: {glwes.size} words do not hold packed block {first + count - 1} of this parameter set")
         if d_out:
-            import torch
-            d_glwes = torch.from_numpy(glwes.view(np.int64)).to(f"cuda:{self.device}")
-            torch.cuda.synchronize()
-            _check(lib().fhe_engine_unpack_glwes_dev(self._h, C.c_void_p(d_glwes.data_ptr()), first, count, int(bool(refresh)), C.c_void_p(d_out)))
-            self.synchronize()                              # d_glwes is released on return
-            return None
+            return self._host_to_dev(dev, glwes, d_out)
         out = np.zeros((count, p.big_size), dtype=np.uint64)
         _check(lib().fhe_engine_unpack_glwes(self._h, _ptr(glwes), first, count, int(bool(refresh)), _ptr(out)))
         return out

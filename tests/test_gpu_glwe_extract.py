@@ -1,4 +1,4 @@
-"""Packed GLWE ciphertexts as inputs on the GPU (csrc/glwe_extract_kernels.hip.h, Engine::unpack_glwes_dev) against exact
+"""Packed GLWE ciphertexts as inputs on the GPU (csrc/glwe_extract_kernels.hip.h, Packing::unpack_dev) against exact
 integers (tests/exact_extract.py).  Every raw comparison is equality of all words; every check reads
 fhe_engine_unpack_info, so a host fallback could not pass.
 

@@ -1,4 +1,4 @@
-"""Narrow packed GLWE results on the GPU (csrc/glwe_narrow_kernels.hip.h, Engine::narrow_glwes_dev / unpack_narrow_dev)
+"""Narrow packed GLWE results on the GPU (csrc/glwe_narrow_kernels.hip.h, Packing::narrow_dev / unpack_narrow_dev)
 against exact integers (tests/exact_narrow.py, tests/exact_extract.py).  Every raw comparison is equality of all words;
 every check reads fhe_engine_narrow_info, so a host fallback could not pass.
 
@@ -7,6 +7,8 @@ every check reads fhe_engine_narrow_info, so a host fallback could not pass.
                             host entry and _dev into a 16-byte aligned buffer and one off by 8 bytes, with guards
   test_rows_spanning_workgroups  (8192, 1), 3 rows: two workgroups per row
   test_zero_count_is_a_no_op
+  test_shared_staging_across_families  one engine in throughput mode 2, host arrays: unpack, unpack_narrow, a larger unpack, narrow --
+                            the staging buffers the two families share are grown by one after the other used them
   test_pack_narrow_unpack_raw  toy twin and PARAM_MESSAGE_2_CARRY_2, 64 blocks: pack -> narrow on the device -> raw unpack decrypts
   test_refresh, test_refresh_refusals
   test_raw_noise            2,048 device-packed PBS outputs, narrowed at the operand-grade default, unpacked raw: phase-error
@@ -198,6 +200,32 @@ def test_zero_count_is_a_no_op():
     with pytest.raises(fhestr.FheError, match="8 .. 32"):
         eng.narrow(np.zeros((1, 2, 256), dtype=np.uint64), 5, 7)
     assert eng.narrow_info() == before
+
+
+def test_shared_staging_across_families():
+    """The host forms stage through buffers two families share: the extracted rows of unpack and unpack_narrow leave through
+    one, the GLWEs of narrow and the list of unpack_narrow enter through another.  Each is used by one family, then by the
+    other, then grown by the first, under throughput mode 2 (a growth waits for every stream); every result is exact."""
+    import fhestr
+    N, k = min(s for s in GPU_SHAPES if s[1] == 1)
+    held = 2 * N + 3
+    glwes, narrow, wide = _case(N, k, held, 16)
+    eng = fhestr.Engine(fhestr.Params(8, k, N, 10, LEVELS[(N, k)], 4, 2, 4, 4, 1e-12, 1e-15, f"NARROW_N{N}_K{k}"), 0)
+    try:
+        eng.set_pipeline(2)
+        unpacked = lambda count: {"ran": True, "rows": count, "workgroups": _workgroups(N, k, count), "refreshed": False}
+        _same(eng.unpack(glwes, 5, first=N + 1, refresh=False), extract_exact(glwes, k, N, N + 1, 5), "unpack of 5")
+        assert eng.unpack_info() == unpacked(5) and not eng.narrow_info()["ran"]
+        _same(eng.unpack_narrow(narrow, held, 16, count=7, first=N - 2, refresh=False), extract_exact(wide, k, N, N - 2, 7), "unpack_narrow of 7")
+        assert eng.narrow_info() == {"ran": True, "kernel": "extract", "items": 7, "workgroups": _workgroups(N, k, 7), "bits": 16}
+        assert eng.unpack_info() == unpacked(5)
+        _same(eng.unpack(glwes, N + 9, first=N + 1, refresh=False), extract_exact(glwes, k, N, N + 1, N + 9), f"unpack of {N + 9}")
+        assert eng.unpack_info() == unpacked(N + 9)
+        got = eng.narrow(glwes, held, 16)
+        _same(np.asarray(got).reshape(-1), narrow, f"narrow of {held}")
+        assert eng.narrow_info() == {"ran": True, "kernel": "narrow", "items": narrow.size, "workgroups": -(-narrow.size // 256), "bits": 16}
+    finally:
+        eng.close()
 
 
 # ---- with real keys -----------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""The packing keyswitch on the GPU (csrc/packing_ks_kernels.hip.h, Engine::pack_lwes_dev) against exact integers
+"""The packing keyswitch on the GPU (csrc/packing_ks_kernels.hip.h, Packing::pack_dev) against exact integers
 (tests/exact_packing.py).  Every comparison is equality of all words of all GLWEs; every check prints and asserts
 fhe_engine_packing_info (row tiles per workgroup, K chunks, K steps per chunk).  Shapes are the smallest at which the
 kernel can still go wrong:
@@ -104,7 +104,7 @@ def _steps(p, pp):
 
 
 def _geometry(p, pp, B, override=0):
-    """The host arithmetic of Engine::pack_lwes_dev, from the parameters: (MT, chunks, steps per chunk, steps)."""
+    """The host arithmetic of Packing::pack_dev, from the parameters: (MT, chunks, steps per chunk, steps)."""
     steps = _steps(p, pp)
     col_groups = (p.k + 1) * p.N // 32
     row_tiles = -(-B // 32)
