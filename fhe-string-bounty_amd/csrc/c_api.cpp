@@ -256,6 +256,45 @@ int fhe_engine_packing_info(fhe_engine* eng, uint32_t info[5]) {
     API_END
 }
 
+int fhe_engine_load_ring_packing_key(fhe_engine* eng, const fhe_packing_params_t* pp, const uint64_t* key) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(pp); CHECK_PTR(key);
+    return eng->impl->packing.load_ring_key(*pp, key);
+    API_END
+}
+
+int fhe_engine_ring_pack_lwes(fhe_engine* eng, const uint64_t* cts, uint32_t count, uint64_t* glwes_host) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    if (count) { CHECK_PTR(cts); CHECK_PTR(glwes_host); }
+    return eng->impl->packing.ring_pack_host(cts, count, glwes_host);
+    API_END
+}
+
+int fhe_engine_ring_pack_lwes_dev(fhe_engine* eng, const uint64_t* d_cts, uint32_t count, uint64_t* d_glwes) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    if (count) { CHECK_PTR(d_cts); CHECK_PTR(d_glwes); }
+    return eng->impl->packing.ring_pack_dev(d_cts, count, d_glwes);
+    API_END
+}
+
+int fhe_engine_ring_pack_info(fhe_engine* eng, uint64_t info[5]) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(info);
+    std::copy(eng->impl->packing.ring_last, eng->impl->packing.ring_last + 5, info);
+    return 0;
+    API_END
+}
+
+int fhe_engine_ring_ntt(fhe_engine* eng, uint32_t N, int inverse, uint32_t* polys, uint32_t count) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng);
+    if (count) CHECK_PTR(polys);
+    return eng->impl->packing.ring_ntt_host(N, inverse, polys, count);
+    API_END
+}
+
 int fhe_engine_unpack_glwes(fhe_engine* eng, const uint64_t* glwes_host, uint32_t first, uint32_t count, int refresh, uint64_t* cts_host) {
     API_BEGIN
     CHECK_PTR(eng); LOCK_ENGINE(eng);

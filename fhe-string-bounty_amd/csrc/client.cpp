@@ -20,6 +20,7 @@
 #include "engine.h"
 #include "glwe_narrow.h"
 #include "noise_model.h"
+#include "ring_packing.h"
 
 namespace fhe {
 
@@ -138,6 +139,26 @@ struct ClientKey {
                 uint64_t* body = glwe + (size_t)p.k * p.N;
                 std::memset(body, 0, p.N * sizeof(uint64_t));
                 body[0] = glwe_sk[i] << (64 - pp.base_log * level);
+                glwe_encrypt_assign(glwe, r);
+            }
+        }
+    }
+    // ring_packing.h: tree level l, key polynomial q, level row `it` -> GLWE encryption of S_q(X^t) << (64 - base_log (L - it)), t = 2^l + 1
+    void gen_ring_packing_key_range(const fhe_packing_params_t& pp, const Seed256& key_seed, uint64_t* key, size_t lo, size_t hi) const {
+        const uint32_t N = p.N;
+        const size_t glwe_len = (size_t)(p.k + 1) * N;
+        for (size_t row = lo; row < hi; row++) {            // row = (l - 1) k + q
+            const uint32_t level = (uint32_t)(row / p.k) + 1, q = (uint32_t)(row % p.k), tinv = ring_tinv(N, level);
+            Rng r(key_seed, 0x52504B0000000000ull + row);
+            for (uint32_t it = 0; it < pp.level; it++) {
+                uint64_t* glwe = key + (row * pp.level + it) * glwe_len;
+                uint64_t* body = glwe + (size_t)p.k * N;
+                const uint32_t shift = 64 - pp.base_log * (pp.level - it);
+                for (uint32_t c = 0; c < N; c++) {
+                    bool neg;
+                    const uint64_t bit = glwe_sk[(size_t)q * N + ring_auto_source(N, tinv, c, &neg)];
+                    body[c] = (neg ? 0 - bit : bit) << shift;
+                }
                 glwe_encrypt_assign(glwe, r);
             }
         }
@@ -484,6 +505,102 @@ int fhe_packing_unpack_noise(const fhe_params_t* params, const fhe_packing_param
     out[0] = out[1] = 0;
     if (fhe::packing_params_check(*params, *pp)) return 1;
     fhe::packing_unpack_noise(*params, *pp, out);
+    return 0;
+}
+
+// ---- ring packing (ring_packing.h) ----
+static int ring_answer(const std::string& why) { return why.empty() ? 0 : fhe::fail(why); }
+
+int fhe_ring_packing_default_params(const fhe_params_t* params, fhe_packing_params_t* out) {
+    if (!params || !out) return fhe::fail("null pointer");
+    return ring_answer(fhe::ring_packing_default_params(*params, out));
+}
+
+size_t fhe_ring_packing_key_len(const fhe_params_t* params, const fhe_packing_params_t* pp) {
+    if (!params || !pp || ring_answer(fhe::ring_packing_check(*params, *pp))) return 0;
+    return (size_t)fhe::ring_packing_key_words(*params, *pp);
+}
+
+int fhe_ring_packing_noise(const fhe_params_t* params, const fhe_packing_params_t* pp, double out[2]) {
+    if (!params || !pp || !out) return fhe::fail("null pointer");
+    out[0] = out[1] = 0;
+    if (ring_answer(fhe::ring_packing_check(*params, *pp))) return 1;
+    fhe::ring_packing_noise(*params, *pp, out);
+    return 0;
+}
+
+int fhe_ring_narrow_noise(const fhe_params_t* params, const fhe_packing_params_t* pp, uint32_t bits, double out[3]) {
+    if (!params || !pp || !out) return fhe::fail("null pointer");
+    out[0] = out[1] = out[2] = 0;
+    if (!fhe::narrow_bits_ok(bits)) return fhe::fail("narrow: the width must be 8 .. 32 bits");
+    if (ring_answer(fhe::ring_packing_check(*params, *pp))) return 1;
+    fhe::ring_narrow_noise(*params, *pp, bits, out);
+    return 0;
+}
+
+uint64_t fhe_ring_pack_keyswitches(const fhe_params_t* params, uint32_t count) {
+    return params && params->N ? fhe::ring_pack_keyswitches(params->N, count) : 0;
+}
+
+int fhe_client_gen_ring_packing_key(fhe_client_key* ck, const fhe_packing_params_t* pp, const uint8_t seed[32], uint64_t* key_out, int threads) {
+    if (!ck || !pp || !seed || !key_out) return fhe::fail("null pointer");
+    try {
+        const auto& c = *ck->impl;
+        if (ring_answer(fhe::ring_packing_check(c.p, *pp))) return 1;
+        const fhe::Seed256 key_seed = fhe::seed_from_bytes(seed);
+        const fhe_packing_params_t dec = *pp;
+        const size_t rows = (size_t)fhe::ring_log2(c.p.N) * c.p.k;
+        threads = (int)std::max<size_t>(1, std::min<size_t>(std::min(threads, 64), rows));
+        std::vector<std::thread> pool;
+        for (int t = 0; t < threads; t++)
+            pool.emplace_back([&, t] { c.gen_ring_packing_key_range(dec, key_seed, key_out, rows * t / threads, rows * (t + 1) / threads); });
+        for (auto& th : pool) th.join();
+    } catch (const std::exception& e) {
+        return fhe::fail(e.what());
+    }
+    return 0;
+}
+
+int fhe_ring_pack_host(const fhe_params_t* params, const fhe_packing_params_t* pp, const uint64_t* key, const uint64_t* cts, uint32_t count,
+                       uint64_t* glwes) {
+    if (!params || !pp || !key || (count && (!cts || !glwes))) return fhe::fail("null pointer");
+    try {
+        return ring_answer(fhe::ring_pack(*params, *pp, key, cts, count, glwes));
+    } catch (const std::exception& e) {
+        return fhe::fail(e.what());
+    }
+}
+
+static int ring_size_ok(uint32_t N) {
+    if (N < fhe::RING_N_MIN || N > fhe::RING_N_MAX || (N & (N - 1))) return fhe::fail("ring transform: the size must be a power of two in 4 .. 32768");
+    return 0;
+}
+
+int fhe_ring_ntt_host(uint32_t N, int inverse, uint32_t* polys, uint32_t count) {
+    if (count && !polys) return fhe::fail("null pointer");
+    if (ring_size_ok(N)) return 1;
+    try {
+        fhe::RingTables tb;
+        fhe::ring_tables(N, &tb);
+        for (size_t x = 0; x < (size_t)count * N; x++)
+            if (polys[x] >= fhe::RING_P) return fhe::fail("ring transform: a residue is not below P");
+        for (uint32_t x = 0; x < count; x++) (inverse ? fhe::ring_ntt_inverse : fhe::ring_ntt_forward)(tb, polys + (size_t)x * N);
+    } catch (const std::exception& e) {
+        return fhe::fail(e.what());
+    }
+    return 0;
+}
+
+int fhe_ring_product_host(uint32_t N, uint32_t terms, const int32_t* a, const int32_t* b, int64_t* out) {
+    if (!a || !b || !out) return fhe::fail("null pointer");
+    if (ring_size_ok(N)) return 1;
+    try {
+        fhe::RingTables tb;
+        fhe::ring_tables(N, &tb);
+        fhe::ring_product(tb, terms, a, b, out);
+    } catch (const std::exception& e) {
+        return fhe::fail(e.what());
+    }
     return 0;
 }
 

@@ -138,6 +138,20 @@ struct Packing {
     int widen_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint64_t* d_glwes);
     int unpack_narrow_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts);
     int unpack_narrow_host(const uint64_t* narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int refresh, uint64_t* cts);
+
+    // Ring packing (ring_packing.h, ring_packing_kernels.hip.h): a second route to the same packed GLWEs, through log2(N)
+    // automorphism keys.  With a matrix key loaded as well, the refresh gate judges by the matrix key's pair, as before.
+    DeviceBuffer<uint32_t> ring_key;     // the automorphism keys' transformed digit planes [log2 N][k L][k+1][8][N]
+    fhe_packing_params_t ring_pp{0, 0};
+    DeviceBuffer<uint32_t> ring_tw;      // twiddles of the key's N: N forward, then N inverse
+    uint32_t ring_n_inv = 0;
+    DeviceBuffer<uint64_t> ring_slots;   // the leaves and the nodes that replace them: count x [k+1][N]
+    DeviceBuffer<unsigned char> ring_tmp;   // one batch of merges: transformed digits, permuted bodies, lifted products
+    uint64_t ring_last[5] = {0, 0, 0, 0, 0};   // fhe_engine_ring_pack_info: ran, tree levels, automorphism keyswitches, launches, scratch bytes
+    int load_ring_key(const fhe_packing_params_t& pp, const uint64_t* key);
+    int ring_pack_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_glwes);
+    int ring_pack_host(const uint64_t* cts, uint32_t count, uint64_t* glwes);
+    int ring_ntt_host(uint32_t N, int inverse, uint32_t* polys, uint32_t count);   // the device transform on its own, host arrays
 };
 
 // Transciphering (transcipher.h, transcipher_kernels.hip.h; members in transcipher_dev.hip): the resident encrypted key bits

@@ -1,7 +1,8 @@
 // packing_dev.hip -- fhe::Packing (engine.h): the packed-ciphertext family of the engine.  The packing keyswitch (LWEs ->
 // GLWEs, packing_ks_kernels.hip.h), the packed inputs (GLWEs -> LWEs, glwe_extract_kernels.hip.h) and the narrow packed
 // results (GLWEs <-> b-bit lists -> LWEs, glwe_narrow_kernels.hip.h): the resident packing key, every launch of the three
-// kernel headers, the staging of the host forms and the fhe_engine_*_info records.  packing_ks_mfma_kernel<MT> is
+// kernel headers, the staging of the host forms and the fhe_engine_*_info records; and ring packing, the second route from
+// LWEs to the same GLWEs (ring_packing.h, ring_packing_kernels.hip.h), with its own resident key.  packing_ks_mfma_kernel<MT> is
 // instantiated here only; its operand kernels and launch plan are the keyswitch's, reached through ks_mfma_launch.h.  The
 // refresh after an extraction is Engine::refresh_rows_dev.
 //
@@ -11,6 +12,7 @@
 #include "packing_ks_kernels.hip.h"
 #include "glwe_extract_kernels.hip.h"
 #include "glwe_narrow_kernels.hip.h"
+#include "ring_packing_kernels.hip.h"
 
 namespace fhe {
 
@@ -31,6 +33,14 @@ static int staged(Engine& e, DeviceBuffer<uint64_t>& in, const uint64_t* src, si
 // The refresh gate of both unpack forms: the loaded key's decomposition decides whether a raw block -- extracted from a
 // full GLWE (bits = 0: packing_unpack_noise) or from a list narrowed to `bits` (narrow_noise) -- is within the PBS-input budget.
 static int refresh_gate(const Packing& pk, const char* who, uint32_t bits) {
+    if (!pk.key && pk.ring_key) {           // only the ring key is loaded: its model judges (ring_packing.h)
+        double v[3];
+        if (bits) ring_narrow_noise(pk.e->p, pk.ring_pp, bits, v); else ring_packing_noise(pk.e->p, pk.ring_pp, v);
+        if (v[0] <= v[1]) return 0;
+        return fail(std::string(who) + ": refresh refused, a raw block extracted" + (bits ? " at " + std::to_string(bits) + " bits" : std::string()) +
+                    " under the ring packing pair (" + std::to_string(pk.ring_pp.base_log) + ", " + std::to_string(pk.ring_pp.level) + ") carries " +
+                    std::to_string(v[0]) + " nominal variances, the PBS-input budget is " + std::to_string(v[1]));
+    }
     if (!pk.key) return fail(std::string(who) + ": the refresh needs the loaded packing key's decomposition to judge the blocks' noise; none is loaded");
     double v[3];
     if (bits) narrow_noise(pk.e->p, pk.pp, bits, v); else packing_unpack_noise(pk.e->p, pk.pp, v);
@@ -235,6 +245,138 @@ int Packing::unpack_narrow_host(const uint64_t* narrow, uint32_t held, uint32_t 
     const uint32_t held_up = std::min<uint64_t>(held, ((uint64_t)g_hi + 1) * p.N) - g_lo * p.N;   // a list of its own: streams g_lo .. g_hi
     return staged(*e, narrow_in, narrow + (size_t)g_lo * stride, narrow_len(p.N, p.k, held_up, bits), unpack_out, cts, count * big, refresh,
                   [&](const uint64_t* d_narrow, uint64_t* d_cts) { return unpack_narrow_dev(d_narrow, held_up, bits, first - g_lo * p.N, count, refresh, d_cts); });
+}
+
+// ---- ring packing (ring_packing.h, ring_packing_kernels.hip.h) --------------------------------------------------------
+// Scratch is bounded.  The leaves and the nodes that replace them take count (k+1) N words: at most RING_SLOTS_CAP bytes,
+// a longer list is refused (4,096 LWEs at N = 32768, k = 1).  A level's merges run in batches of at most RING_TMP_CAP bytes
+// of transformed digits and lifted products (2.7 MB per merge at N = 32768 with five levels), whatever the list's length.
+constexpr size_t RING_SLOTS_CAP = 2ull << 30, RING_TMP_CAP = 256ull << 20;
+
+static uint32_t ring_threads(uint32_t N) { return std::min(RING_THREADS_MAX, N / 2); }
+
+template <class K>
+static int ring_allow_lds(K kernel, uint32_t N) {
+    HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(N * 4)));
+    return 0;
+}
+
+// N forward twiddles, then N inverse ones, at `tw`; ordered on `stream`, which the caller waits for while `tb` lives.
+static int ring_upload_tables(const RingTables& tb, DeviceBuffer<uint32_t>& tw, hipStream_t stream) {
+    if (tw.alloc((size_t)tb.N * 8)) return 1;
+    HIP_TRY(hipMemcpyAsync(tw.ptr, tb.fwd.data(), (size_t)tb.N * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(tw.ptr + tb.N, tb.inv.data(), (size_t)tb.N * 4, hipMemcpyHostToDevice, stream));
+    return 0;
+}
+
+// The key [log2 N][k][level][k+1][N] goes up once, every polynomial is rewritten into its eight transformed digit planes,
+// and the 64-bit form is released.  A matrix packing key stays as it is.
+int Packing::load_ring_key(const fhe_packing_params_t& new_pp, const uint64_t* key64) {
+    if (e->use()) return 1;
+    const fhe_params_t& p = e->p;
+    const std::string why = ring_packing_check(p, new_pp);
+    if (!why.empty()) return fail(why);
+    if (e->sync_all_streams()) return 1;                    // a launch in flight may still read the previous key
+    const char* const who = "load_ring_packing_key";
+    ring_key.release();
+    for (auto& w : ring_last) w = 0;
+    const uint32_t N = p.N, logN = ring_log2(N);
+    const size_t words = (size_t)ring_packing_key_words(p, new_pp), rows = words / N;
+    RingTables tb;
+    ring_tables(N, &tb);
+    DeviceBuffer<uint64_t> d_std;
+    DeviceBuffer<uint32_t> planes;      // becomes the resident key only once it is complete
+    if (under(who, d_std.alloc(words * 8)) || under(who, planes.alloc(words * RING_PLANES * 4)) || under(who, ring_upload_tables(tb, ring_tw, e->stream)) ||
+        under(who, hipMemcpyAsync(d_std, key64, words * 8, hipMemcpyHostToDevice, e->stream)))
+        return 1;
+    if (ring_allow_lds(ring_key_planes_kernel, N) || ring_allow_lds(ring_digits_kernel, N) || ring_allow_lds(ring_mac_kernel, N)) return 1;
+    hipLaunchKernelGGL(ring_key_planes_kernel, dim3((uint32_t)rows, RING_PLANES), dim3(ring_threads(N)), N * 4, e->stream, d_std.ptr, planes.ptr, ring_tw.ptr, N, logN);
+    if (under(who, hipGetLastError()) || under(who, hipStreamSynchronize(e->stream))) return 1;
+    ring_key = std::move(planes);
+    ring_pp = new_pp;
+    ring_n_inv = tb.n_inv;
+    return 0;
+}
+
+// count big-key LWEs at d_cts -> ceil(count / N) GLWEs at d_glwes in pack_dev's layout, under pack_dev's contract: ordered
+// on the engine's stream, nothing synchronises except to leave a pipelined run and to grow the scratch.
+int Packing::ring_pack_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_glwes) {
+    if (e->use()) return 1;
+    if (!ring_key) return fail("ring packing key not loaded");
+    if (count == 0) return 0;
+    const fhe_params_t& p = e->p;
+    const uint32_t N = p.N, k = p.k, k1 = k + 1, L = ring_pp.level, kL = k * L, logN = ring_log2(N);
+    const size_t glwe_len = (size_t)k1 * N, slot_bytes = (size_t)count * glwe_len * 8;
+    if (count > 65535u) return fail("batch too large for one ring packing call (max 65535 LWEs)");   // grid.y of the leaf kernel
+    if (slot_bytes > RING_SLOTS_CAP)
+        return fail("ring packing: " + std::to_string(count) + " LWEs need " + std::to_string(slot_bytes) + " bytes of leaves, the cap is " +
+                    std::to_string(RING_SLOTS_CAP) + "; pack the list in parts of whole GLWEs");
+    if (e->leave_pipelined_run()) return 1;                 // pipelined calls may still write the input on another stream
+    const uint32_t full_groups = count / N, c_last = count % N;
+    const size_t per_merge = (size_t)N * 8 + (size_t)kL * N * 4 + (size_t)k1 * RING_PLANES * N * 4;
+    const uint64_t widest = (uint64_t)full_groups * (N / 2) + std::min(N / 2, c_last);      // level 1
+    const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({widest, RING_TMP_CAP / per_merge, 65535u}));   // grid.z of the combine kernel
+    if (e->reserve_idle(ring_slots, slot_bytes) || e->reserve_idle(ring_tmp, batch * per_merge)) return 1;
+    RingLevelArgs a{};
+    a.slots = ring_slots;
+    a.sigma_b = reinterpret_cast<uint64_t*>(ring_tmp.ptr);
+    a.digits = reinterpret_cast<uint32_t*>(ring_tmp.ptr + (size_t)batch * N * 8);
+    a.lifted = reinterpret_cast<int32_t*>(ring_tmp.ptr + (size_t)batch * N * 8 + (size_t)batch * kL * N * 4);
+    a.fwd = ring_tw;
+    a.inv = ring_tw.ptr + N;
+    a.N = N; a.logN = logN; a.k = k; a.L = L; a.base_log = ring_pp.base_log; a.n_inv = ring_n_inv;
+    a.full_groups = full_groups; a.c_last = c_last;
+    hipLaunchKernelGGL(ring_leaf_kernel, dim3((uint32_t)((glwe_len + 255) / 256), count), dim3(256), 0, e->stream, d_cts, ring_slots.ptr, N, logN, k);
+    uint64_t launches = 1, keyswitches = 0;
+    const uint32_t threads = ring_threads(N);
+    for (uint32_t level = 1; level <= logN; level++) {
+        a.s = N >> level;
+        a.tinv = ring_tinv(N, level);
+        a.key = ring_key.ptr + (size_t)(level - 1) * kL * k1 * RING_PLANES * N;
+        a.final_out = level == logN ? d_glwes : nullptr;
+        const uint32_t merges = full_groups * a.s + std::min(a.s, c_last);
+        for (a.first = 0; a.first < merges; a.first += batch) {
+            const uint32_t now = std::min(batch, merges - a.first);
+            hipLaunchKernelGGL(ring_digits_kernel, dim3(now, kL + 1), dim3(threads), N * 4, e->stream, a);
+            hipLaunchKernelGGL(ring_mac_kernel, dim3(now, k1 * RING_PLANES), dim3(threads), N * 4, e->stream, a);
+            hipLaunchKernelGGL(ring_combine_kernel, dim3((N + 255) / 256, k1, now), dim3(256), 0, e->stream, a);
+            launches += 3;
+        }
+        keyswitches += merges;
+    }
+    const uint64_t last[5] = {1, logN, keyswitches, launches, ring_slots.bytes + ring_tmp.bytes};
+    std::copy(last, last + 5, ring_last);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int Packing::ring_pack_host(const uint64_t* cts, uint32_t count, uint64_t* glwes) {
+    if (e->use()) return 1;
+    if (!ring_key) return fail("ring packing key not loaded");
+    if (count == 0) return 0;
+    const fhe_params_t& p = e->p;
+    const size_t big = (size_t)p.k * p.N + 1, out_words = (size_t)((count + p.N - 1) / p.N) * (p.k + 1) * p.N;
+    return staged(*e, pack_in, cts, count * big, pack_out, glwes, out_words, 0,
+                  [&](const uint64_t* d_cts, uint64_t* d_glwes) { return ring_pack_dev(d_cts, count, d_glwes); });
+}
+
+// The device transform on its own: count polynomials of N residues below P, host arrays, in place; synchronises.
+int Packing::ring_ntt_host(uint32_t N, int inverse, uint32_t* polys, uint32_t count) {
+    if (e->use()) return 1;
+    if (N < RING_N_MIN || N > RING_N_MAX || (N & (N - 1))) return fail("ring transform: the size must be a power of two in 4 .. 32768");
+    if (count == 0) return 0;
+    for (size_t x = 0; x < (size_t)count * N; x++)
+        if (polys[x] >= RING_P) return fail("ring transform: a residue is not below P");
+    RingTables tb;
+    ring_tables(N, &tb);
+    DeviceBuffer<uint32_t> tw, d;
+    if (ring_upload_tables(tb, tw, e->stream) || d.alloc((size_t)count * N * 4) || ring_allow_lds(ring_ntt_kernel, N)) return 1;
+    HIP_TRY(hipMemcpyAsync(d.ptr, polys, (size_t)count * N * 4, hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(ring_ntt_kernel, dim3(count), dim3(ring_threads(N)), N * 4, e->stream, d.ptr, tw.ptr, tw.ptr + N, N, ring_log2(N), tb.n_inv, inverse);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(polys, d.ptr, (size_t)count * N * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return 0;
 }
 
 }  // namespace fhe

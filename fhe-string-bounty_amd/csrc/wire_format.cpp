@@ -409,6 +409,51 @@ int fhe_wire_read_packing_key(const fhe_params_t* p, const uint8_t* in, size_t i
     return 0;
 }
 
+// The ring packing key (csrc/ring_packing.h) in the packing key's layout: { data, decomp_base_log, decomp_level_count,
+// output_glwe_size, output_polynomial_size, ciphertext_modulus }, data = [log2 N][k][level][k+1][N].  Parity unpinned.
+int fhe_wire_write_ring_packing_key(const fhe_params_t* p, const fhe_packing_params_t* pp, const uint64_t* key, uint8_t* out, size_t out_cap,
+                                    size_t* written) {
+    if (!p || !pp || !key) return fail("null pointer");
+    const size_t words = fhe_ring_packing_key_len(p, pp);
+    if (!words) return 1;                                   // reason set by the parameter check
+    Writer w{out, out_cap};
+    w.vec_u64(key, words);
+    w.u64(pp->base_log);
+    w.u64(pp->level);
+    w.u64((uint64_t)p->k + 1);
+    w.u64(p->N);
+    w.native_modulus_u64();
+    return finish(w, written);
+}
+
+int fhe_wire_read_ring_packing_key(const fhe_params_t* p, const uint8_t* in, size_t in_len, fhe_packing_params_t* pp, uint64_t* key,
+                                   size_t key_cap_words, size_t* consumed) {
+    if (!p || !in || !pp) return fail("null pointer");
+    Reader r{in, in_len};
+    const uint64_t n = r.u64();                             // the data come first: step over them to the dimensions
+    if (r.err.empty() && n > (r.len - r.pos) / 8) r.err = "truncated input";
+    if (!r.err.empty()) return fail("RingPackingKey: " + r.err);
+    const size_t data_pos = r.pos;
+    r.pos += (size_t)n * 8;
+    const uint64_t base_log = r.u64(), level = r.u64(), glwe_size = r.u64(), poly = r.u64();
+    r.native_modulus_u64();
+    if (!r.err.empty()) return fail("RingPackingKey: " + r.err);
+    if (base_log > 64 || level > 64) return fail("RingPackingKey: decomposition out of range");
+    const fhe_packing_params_t got{(uint32_t)base_log, (uint32_t)level};
+    const size_t want = fhe_ring_packing_key_len(p, &got);
+    if (!want) return 1;
+    if (glwe_size != (uint64_t)p->k + 1 || poly != p->N || n != want)
+        return fail("RingPackingKey does not match the parameter set (GLWE size " + std::to_string(glwe_size) + ", polynomial size " +
+                    std::to_string(poly) + ", " + std::to_string(n) + " words)");
+    *pp = got;
+    if (key) {
+        if (key_cap_words < want) return fail("RingPackingKey: destination holds fewer than " + std::to_string(want) + " words");
+        std::memcpy(key, in + data_pos, want * 8);
+    }
+    if (consumed) *consumed = r.pos;
+    return 0;
+}
+
 static void glwe_body_write(Writer& w, const fhe_params_t* p, const uint64_t* glwe) {
     w.vec_u64(glwe, (size_t)(p->k + 1) * p->N);
     w.u64(p->N);

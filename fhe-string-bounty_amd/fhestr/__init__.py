@@ -167,6 +167,10 @@ EXPORTS = [
     "fhe_packing_default_params", "fhe_packing_key_len", "fhe_packed_glwe_len", "fhe_client_gen_packing_key",
     "fhe_client_decrypt_packed", "fhe_packing_keyswitch_host", "fhe_engine_load_packing_key", "fhe_engine_pack_lwes",
     "fhe_engine_pack_lwes_dev", "fhe_engine_packing_info", "fhe_wire_write_packing_key", "fhe_wire_read_packing_key",
+    "fhe_ring_packing_default_params", "fhe_ring_packing_key_len", "fhe_ring_packing_noise", "fhe_ring_narrow_noise",
+    "fhe_ring_pack_keyswitches", "fhe_client_gen_ring_packing_key", "fhe_ring_pack_host", "fhe_ring_ntt_host", "fhe_ring_product_host",
+    "fhe_engine_load_ring_packing_key", "fhe_engine_ring_pack_lwes", "fhe_engine_ring_pack_lwes_dev", "fhe_engine_ring_pack_info",
+    "fhe_engine_ring_ntt", "fhe_wire_write_ring_packing_key", "fhe_wire_read_ring_packing_key",
     "fhe_wire_write_glwe_ciphertext", "fhe_wire_read_glwe_ciphertext", "fhe_wire_write_glwe_list", "fhe_wire_read_glwe_list",
     "fhe_glwe_sample_extract_host", "fhe_packing_unpack_noise", "fhe_engine_unpack_glwes", "fhe_engine_unpack_glwes_dev",
     "fhe_engine_unpack_info",
@@ -357,6 +361,22 @@ def lib() -> C.CDLL:
     sig("fhe_engine_pack_lwes", vp, vp, u32, vp)
     sig("fhe_engine_pack_lwes_dev", vp, vp, u32, vp)
     sig("fhe_engine_packing_info", vp, C.POINTER(u32))
+    sig("fhe_ring_packing_default_params", PP, KP)
+    L.fhe_ring_packing_key_len.restype = C.c_size_t
+    L.fhe_ring_packing_key_len.argtypes = [PP, KP]
+    sig("fhe_ring_packing_noise", PP, KP, C.POINTER(C.c_double))
+    sig("fhe_ring_narrow_noise", PP, KP, u32, C.POINTER(C.c_double))
+    L.fhe_ring_pack_keyswitches.restype = C.c_uint64
+    L.fhe_ring_pack_keyswitches.argtypes = [PP, u32]
+    sig("fhe_client_gen_ring_packing_key", vp, KP, vp, vp, i32)
+    sig("fhe_ring_pack_host", PP, KP, vp, vp, u32, vp)
+    sig("fhe_ring_ntt_host", u32, i32, vp, u32)
+    sig("fhe_ring_product_host", u32, u32, vp, vp, vp)
+    sig("fhe_engine_load_ring_packing_key", vp, KP, vp)
+    sig("fhe_engine_ring_pack_lwes", vp, vp, u32, vp)
+    sig("fhe_engine_ring_pack_lwes_dev", vp, vp, u32, vp)
+    sig("fhe_engine_ring_pack_info", vp, C.POINTER(C.c_uint64))
+    sig("fhe_engine_ring_ntt", vp, u32, i32, vp, u32)
     sig("fhe_glwe_sample_extract_host", PP, vp, u32, u32, vp)
     sig("fhe_packing_unpack_noise", PP, KP, C.POINTER(C.c_double))
     sig("fhe_engine_unpack_glwes", vp, vp, u32, u32, i32, vp)
@@ -833,6 +853,36 @@ class Engine:
         _check(lib().fhe_engine_load_packing_key(self._h, C.byref(_pp(pp)), _ptr(pksk)))
         self.packing_pair = (int(pp[0]), int(pp[1]))        # what Narrow(bits=None) takes its default width for
 
+    def load_ring_packing_key(self, pp, key):
+        """Upload a ring packing key (ClientKey.gen_ring_packing_key) and rewrite it into transformed digit planes
+        (csrc/ring_packing_kernels.hip.h).  With no matrix packing key loaded, Engine.pack, packed=True and the refresh
+        gate of unpack / unpack_narrow take the ring route; with one loaded they behave as before."""
+        key = _u64(key).reshape(-1)
+        n = ring_packing_key_len(self.params, pp)
+        if not n:
+            raise FheError(lib().fhe_last_error().decode())
+        if key.size != n:
+            raise FheError("ring packing key: size does not match the parameter set and decomposition")
+        _check(lib().fhe_engine_load_ring_packing_key(self._h, C.byref(_pp(pp)), _ptr(key)))
+        self.ring_packing_pair = (int(pp[0]), int(pp[1]))
+
+    def _ring_route(self) -> bool:
+        return getattr(self, "packing_pair", None) is None and getattr(self, "ring_packing_pair", None) is not None
+
+    def ring_pack_info(self) -> dict:
+        """What the last ring packing call enqueued (fhe_engine_ring_pack_info)."""
+        a = (C.c_uint64 * 5)()
+        _check(lib().fhe_engine_ring_pack_info(self._h, a))
+        ran, levels, keyswitches, launches, scratch = (int(x) for x in a)
+        return {"ran": bool(ran), "levels": levels, "keyswitches": keyswitches, "launches": launches, "scratch_bytes": scratch}
+
+    def ring_ntt(self, polys, inverse: bool = False) -> np.ndarray:
+        """The device's negacyclic transform mod 2^32 - 2^20 + 1 on its own (fhe_engine_ring_ntt): (count, N) residues -> a new array."""
+        out = np.ascontiguousarray(polys, dtype=np.uint32).copy()
+        out = out.reshape(-1, out.shape[-1])
+        _check(lib().fhe_engine_ring_ntt(self._h, out.shape[1], int(bool(inverse)), _ptr(out), out.shape[0]))
+        return out
+
     def transcipher(self, cipher, key_cts, max_streams: int = 1) -> "Transcipher":
         """A Transcipher for one stream-cipher key on this engine (server keys loaded): key_cts are the encrypted key bits
         of ClientKey.encrypt_stream_key, (L, kN+1) in spec order; up to max_streams strings run in lockstep."""
@@ -909,6 +959,8 @@ class Engine:
 
     def _default_narrow_bits(self) -> int:
         pair = getattr(self, "packing_pair", None)
+        if self._ring_route():
+            return ring_narrow_default_bits(self.params, self.ring_packing_pair, operand=True)
         if pair is None:
             raise FheError("Narrow(bits=None) takes its width from the packing pair given to load_packing_key; none is loaded")
         return narrow_default_bits(self.params, pair, operand=True)
@@ -957,8 +1009,10 @@ class Engine:
         coefficient j % N of GLWE j // N.  cts: a host array (count, kN+1) -> returns (n_glwe, k+1, N); or a torch device
         tensor / d_in + count: the buffer apply_lookup_table_dev or Plan.run_batch_dev wrote, packed where it lies.  With
         d_out the GLWEs are written there (asynchronous on the engine's stream) and nothing is returned; without it
-        they come back as a host array."""
+        they come back as a host array.  With only a ring packing key loaded (load_ring_packing_key) the same GLWE
+        layout comes from the ring route (csrc/ring_packing_kernels.hip.h)."""
         p = self.params
+        ring = self._ring_route()
         if cts is not None and hasattr(cts, "data_ptr"):
             if count is None:
                 count = cts.numel() // p.big_size
@@ -966,13 +1020,14 @@ class Engine:
         if d_in:
             if count is None:
                 raise FheError("pack: a device buffer needs a count")
-            dev = lambda src, dst: _check(lib().fhe_engine_pack_lwes_dev(self._h, C.c_void_p(src), count, C.c_void_p(dst)))
+            pack_dev = lib().fhe_engine_ring_pack_lwes_dev if ring else lib().fhe_engine_pack_lwes_dev
+            dev = lambda src, dst: _check(pack_dev(self._h, C.c_void_p(src), count, C.c_void_p(dst)))
             if d_out:
                 return dev(d_in, d_out)
             return self._dev_to_host(dev, d_in, (-(-count // p.N), p.k + 1, p.N))
         cts = _u64(cts).reshape(-1, p.big_size)
         out = np.zeros((-(-cts.shape[0] // p.N), p.k + 1, p.N), dtype=np.uint64)
-        _check(lib().fhe_engine_pack_lwes(self._h, _ptr(cts), cts.shape[0], _ptr(out)))
+        _check((lib().fhe_engine_ring_pack_lwes if ring else lib().fhe_engine_pack_lwes)(self._h, _ptr(cts), cts.shape[0], _ptr(out)))
         return out
 
     def packing_info(self) -> dict:
@@ -1245,6 +1300,19 @@ class ClientKey:
         _check(lib().fhe_client_gen_packing_key(self._h, C.byref(_pp(pp)), sb, _ptr(pksk), threads or min(16, os.cpu_count() or 1)))
         return pp, pksk
 
+    def gen_ring_packing_key(self, pair=None, seed=0, threads: int | None = None):
+        """Ring packing key for this client's keys (fhe_client_gen_ring_packing_key): log2(N) automorphism keys of
+        k * level GLWE ciphertexts each; returns ((base_log, level), words).  pair=None takes ring_packing_default_params."""
+        p = self.params
+        pair = tuple(pair) if pair is not None else ring_packing_default_params(p)
+        n = ring_packing_key_len(p, pair)
+        if not n:
+            raise FheError(lib().fhe_last_error().decode())
+        key = np.zeros(n, dtype=np.uint64)
+        sb = (C.c_uint8 * 32)(*seed_bytes(seed))
+        _check(lib().fhe_client_gen_ring_packing_key(self._h, C.byref(_pp(pair)), sb, _ptr(key), threads or min(16, os.cpu_count() or 1)))
+        return pair, key
+
     def decrypt_packed(self, glwes, count: int) -> np.ndarray:
         """message-and-carry value of the first `count` coefficients of packed results (Engine.pack)."""
         glwes = _u64(glwes).reshape(-1)
@@ -1292,6 +1360,81 @@ def packing_default_params(params: Params):
 def packing_key_len(params: Params, pp) -> int:
     """Words of a packing keyswitch key k N * level * (k+1) N; 0 = this (parameter set, decomposition) is refused."""
     return int(lib().fhe_packing_key_len(C.byref(params.c()), C.byref(_pp(pp))))
+
+
+def ring_packing_default_params(params: Params):
+    """(base_log, level) of the cheapest ring packing key -- fewest levels, then largest base, under the one-prime bound --
+    whose packed results still decode within the failure bound plans enforce (fhe_ring_packing_default_params)."""
+    out = _PackingParams()
+    _check(lib().fhe_ring_packing_default_params(C.byref(params.c()), C.byref(out)))
+    return (int(out.base_log), int(out.level))
+
+
+def ring_packing_key_len(params: Params, pair) -> int:
+    """Words of a ring packing key log2(N) * k * level * (k+1) N; 0 = this (parameter set, pair) is refused."""
+    return int(lib().fhe_ring_packing_key_len(C.byref(params.c()), C.byref(_pp(pair))))
+
+
+def ring_packing_noise(params: Params, pair) -> tuple:
+    """(variance of a raw block extracted from a ring-packed PBS output, in nominal units; the default PBS-input budget)."""
+    a = (C.c_double * 2)()
+    _check(lib().fhe_ring_packing_noise(C.byref(params.c()), C.byref(_pp(pair)), a))
+    return float(a[0]), float(a[1])
+
+
+def ring_narrow_noise(params: Params, pair, bits: int) -> tuple:
+    """narrow_noise for the ring route (fhe_ring_narrow_noise)."""
+    a = (C.c_double * 3)()
+    _check(lib().fhe_ring_narrow_noise(C.byref(params.c()), C.byref(_pp(pair)), bits, a))
+    return float(a[0]), float(a[1]), float(a[2])
+
+
+def ring_narrow_default_bits(params: Params, pair, operand: bool = True) -> int:
+    """narrow_default_bits for the ring route: the smallest width of 8 .. 32 bits whose list may come back as an operand
+    (out[0] <= out[1] of ring_narrow_noise).  Only the operand grade is offered."""
+    if not operand:
+        raise FheError("ring_narrow_default_bits: only the operand grade is offered; choose a client-grade width with ring_narrow_noise")
+    for bits in range(8, 33):
+        v = ring_narrow_noise(params, pair, bits)
+        if v[0] <= v[1]:
+            return bits
+    raise FheError(f"narrow: no width of 8 .. 32 bits is operand-grade under the ring packing pair {tuple(pair)}")
+
+
+def ring_pack_keyswitches(params: Params, count: int) -> int:
+    """Automorphism keyswitches of ring-packing `count` LWEs: per GLWE of c blocks, sum over d < log2 N of min(2^d, c)."""
+    return int(lib().fhe_ring_pack_keyswitches(C.byref(params.c()), count))
+
+
+def ring_pack_host(params: Params, pair, key, cts) -> np.ndarray:
+    """Ring packing on the CPU (fhe_ring_pack_host): cts (count, kN+1) -> (ceil(count / N), k+1, N).  Bit-identical to
+    Engine.pack on the ring route."""
+    key = _u64(key).reshape(-1)
+    cts = _u64(cts).reshape(-1, params.big_size)
+    if key.size != ring_packing_key_len(params, pair) or not key.size:
+        raise FheError(lib().fhe_last_error().decode() if not ring_packing_key_len(params, pair) else "ring packing key: size does not match the parameter set")
+    out = np.zeros((-(-cts.shape[0] // params.N), params.k + 1, params.N), dtype=np.uint64)
+    _check(lib().fhe_ring_pack_host(C.byref(params.c()), C.byref(_pp(pair)), _ptr(key), _ptr(cts), cts.shape[0], _ptr(out)))
+    return out
+
+
+def ring_ntt_host(polys, inverse: bool = False) -> np.ndarray:
+    """The host's negacyclic transform mod 2^32 - 2^20 + 1 (fhe_ring_ntt_host): (count, N) residues -> a new array."""
+    out = np.ascontiguousarray(polys, dtype=np.uint32).copy()
+    out = out.reshape(-1, out.shape[-1])
+    _check(lib().fhe_ring_ntt_host(out.shape[1], int(bool(inverse)), _ptr(out), out.shape[0]))
+    return out
+
+
+def ring_product_host(a, b) -> np.ndarray:
+    """sum over the terms of a[t] (*) b[t], negacyclic, for (terms, N) signed 32-bit coefficients, through the transform
+    (fhe_ring_product_host): N int64, exact while the true magnitude stays below P / 2."""
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    b = np.ascontiguousarray(b, dtype=np.int32)
+    a, b = a.reshape(-1, a.shape[-1]), b.reshape(-1, b.shape[-1])
+    out = np.zeros(a.shape[1], dtype=np.int64)
+    _check(lib().fhe_ring_product_host(a.shape[1], a.shape[0], _ptr(a), _ptr(b), _ptr(out)))
+    return out
 
 
 def packed_glwe_len(params: Params, count: int) -> int:

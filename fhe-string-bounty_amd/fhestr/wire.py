@@ -8,7 +8,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import (CompactPublicKey, FheError, Params, _check, _PackingParams, _pp, _ptr, _u64, compact_list_len, compact_pk_len, lib,
-               packing_key_len)
+               packing_key_len, ring_packing_key_len)
 
 
 class _Meta(C.Structure):
@@ -70,6 +70,8 @@ def _sigs():
             ("fhe_wire_read_compact_public_key", [PP, vp, sz, vp, szp]),
             ("fhe_wire_write_packing_key", [PP, C.POINTER(_PackingParams), vp, vp, sz, szp]),
             ("fhe_wire_read_packing_key", [PP, vp, sz, C.POINTER(_PackingParams), vp, sz, szp]),
+            ("fhe_wire_write_ring_packing_key", [PP, C.POINTER(_PackingParams), vp, vp, sz, szp]),
+            ("fhe_wire_read_ring_packing_key", [PP, vp, sz, C.POINTER(_PackingParams), vp, sz, szp]),
             ("fhe_wire_write_glwe_ciphertext", [PP, vp, vp, sz, szp]),
             ("fhe_wire_read_glwe_ciphertext", [PP, vp, sz, vp, szp]),
             ("fhe_wire_write_glwe_list", [PP, vp, C.c_uint32, vp, sz, szp]),
@@ -423,6 +425,24 @@ def read_packing_key(params: Params, data: bytes):
     pksk = np.zeros(packing_key_len(params, pp), dtype=np.uint64)
     _check(_sigs().fhe_wire_read_packing_key(C.byref(params.c()), buf, len(data), C.byref(got), _ptr(pksk), pksk.size, C.byref(used)))
     return pp, pksk
+
+
+def write_ring_packing_key(params: Params, pair, key) -> bytes:
+    """A key from ClientKey.gen_ring_packing_key in the packing key's layout (fhe_wire_write_ring_packing_key)."""
+    key = _u64(key).reshape(-1)
+    if key.size != ring_packing_key_len(params, pair) or not key.size:
+        raise FheError("ring packing key: size does not match the parameter set and decomposition")
+    return _write(lambda out, cap, n: _sigs().fhe_wire_write_ring_packing_key(C.byref(params.c()), C.byref(_pp(pair)), _ptr(key), out, cap, n))
+
+
+def read_ring_packing_key(params: Params, data: bytes):
+    """-> ((base_log, level), key words); every dimension checked against the parameter set."""
+    got, used, buf = _PackingParams(), C.c_size_t(), _in(data)
+    _check(_sigs().fhe_wire_read_ring_packing_key(C.byref(params.c()), buf, len(data), C.byref(got), None, 0, C.byref(used)))
+    pair = (int(got.base_log), int(got.level))
+    key = np.zeros(ring_packing_key_len(params, pair), dtype=np.uint64)
+    _check(_sigs().fhe_wire_read_ring_packing_key(C.byref(params.c()), buf, len(data), C.byref(got), _ptr(key), key.size, C.byref(used)))
+    return pair, key
 
 
 def write_glwe_ciphertext(params: Params, glwe) -> bytes:

@@ -664,6 +664,65 @@ int fhe_engine_pack_lwes_dev(fhe_engine *eng, const uint64_t *d_cts, uint32_t co
  * keyswitch), info[3] K steps per chunk, info[4] K steps in all. */
 int fhe_engine_packing_info(fhe_engine *eng, uint32_t info[5]);
 
+/* ---- ring packing: the same packed GLWEs through log2(N) automorphism keys ---------------------------
+ * The repacking of Chen, Dai, Kim and Song ("Efficient homomorphic conversion between (ring) LWE ciphertexts", 2021), a
+ * second route beside the packing keyswitch for the parameter sets whose matrix key is heavy or refused: the key is
+ * log2(N) * k * level GLWE ciphertexts, 39 MB on PARAM_MESSAGE_4_CARRY_4 with five levels.  The output is an ordinary
+ * GLWE under the client's GLWE key in the layout above (block j at coefficient j % N of GLWE j / N), so
+ * fhe_client_decrypt_packed, sample extraction, the narrow form and the wire forms take it unchanged; the unused
+ * coefficients of a short group hold noise around 0, not exact zeros.  All arithmetic mod 2^64:
+ *   leaf    every word w of the LWE becomes (w + N/2) >> log2 N (the division that stands in for N^-1 mod 2^64);
+ *           A_q[0] = a'[qN], A_q[i] = -a'[qN + N - i], B[0] = b', the other body coefficients 0
+ *   autoKS  level l = 1 .. log2 N, t = 2^l + 1, sigma_t(P)(X) = P(X^t) in Z[X] / (X^N + 1):
+ *           (0, .., 0, sigma_t(B)) - sum_q sum_it digit_it(sigma_t(A_q)) (*) AK[l][q][it], the keyswitch's signed digits
+ *           (level L first), (*) the negacyclic product
+ *   merge   pack(0, {ct}) = ct; e = pack(l - 1, even-indexed), o = pack(l - 1, odd-indexed), s = N / 2^l:
+ *           pack(l, cts) = (e + X^s o) + autoKS_l(e - X^s o); an absent leaf is the zero ciphertext, a node without a
+ *           leaf costs nothing.  c <= N blocks cost sum_{d < log2 N} min(2^d, c) automorphism keyswitches.
+ *   key     [log2 N][k][level, level L first][k+1][N] u64: AK[l][q][it] is a GLWE encryption under S of
+ *           S_q(X^t) << (64 - base_log * (L - it)), noise glwe_std
+ * The products are exact (balanced base-256 planes of the key, one negacyclic number-theoretic transform mod
+ * P = 2^32 - 2^20 + 1, centred lift): a pair is admitted while k * level * N * 2^(base_log - 1) * 128 < P / 2, with
+ * 1 <= base_log <= 32, level <= 16, base_log * level <= 63, N a power of two in 4 .. 32768.  Host and GPU give the same
+ * words.  Noise: a packed coefficient carries its LWE's own noise plus (N^2 / 3) V_aks, V_aks = k N level (2^(2 base_log)
+ * + 2) / 12 glwe_std^2 + (k N / 2) 2^(-2 base_log level) / 12. */
+/* Fewest levels, then largest base, under the one-prime bound, for which a packed PBS output decoded at delta / 2 stays
+ * within the failure bound of fhe_packing_default_params. */
+int fhe_ring_packing_default_params(const fhe_params_t *params, fhe_packing_params_t *out);
+size_t fhe_ring_packing_key_len(const fhe_params_t *params, const fhe_packing_params_t *pp);   /* words; 0 = refused */
+/* out[0]: variance of a raw block extracted from a ring-packed PBS output in nominal units, out[1]: the PBS-input budget
+ * (the shape of fhe_packing_unpack_noise).  fhe_ring_narrow_noise: the shape of fhe_narrow_noise. */
+int fhe_ring_packing_noise(const fhe_params_t *params, const fhe_packing_params_t *pp, double out[2]);
+int fhe_ring_narrow_noise(const fhe_params_t *params, const fhe_packing_params_t *pp, uint32_t bits, double out[3]);
+/* automorphism keyswitches of packing `count` LWEs: the cost formula, summed over the GLWEs */
+uint64_t fhe_ring_pack_keyswitches(const fhe_params_t *params, uint32_t count);
+/* ChaCha20 under `seed`, one stream per (tree level, key polynomial): the same key whatever `threads` is. */
+int fhe_client_gen_ring_packing_key(fhe_client_key *ck, const fhe_packing_params_t *pp, const uint8_t seed[32],
+                                    uint64_t *key_out, int threads);
+/* The definition on the host, with the transform as its exact product (parity; callers without a GPU). */
+int fhe_ring_pack_host(const fhe_params_t *params, const fhe_packing_params_t *pp, const uint64_t *key, const uint64_t *cts,
+                       uint32_t count, uint64_t *glwes);
+/* The host transform on its own: `count` polynomials of N residues below P, in place; forward takes natural order to
+ * bit-reversed order, inverse = 1 takes that back.  fhe_ring_product_host: sum over `terms` of a[t] (*) b[t] for
+ * polynomials of N signed coefficients, exact while the true magnitude stays below P / 2. */
+int fhe_ring_ntt_host(uint32_t N, int inverse, uint32_t *polys, uint32_t count);
+int fhe_ring_product_host(uint32_t N, uint32_t terms, const int32_t *a, const int32_t *b, int64_t *out);
+/* Upload the key and rewrite it once into transformed digit planes (csrc/ring_packing_kernels.hip.h; 4 x the key's
+ * bytes stay resident, the 64-bit form is released); replaces a ring key loaded before, leaves a matrix key alone. */
+int fhe_engine_load_ring_packing_key(fhe_engine *eng, const fhe_packing_params_t *pp, const uint64_t *key);
+/* fhe_engine_pack_lwes / _dev through the ring route, under the same contract on streams.  Scratch is bounded: the
+ * leaves take count * (k+1) * N words and at most 2 GiB (4,096 LWEs at N = 32768), a longer list is refused -- pack it
+ * in parts of whole GLWEs; a tree level's merges run in batches of at most 256 MiB of intermediates. */
+int fhe_engine_ring_pack_lwes(fhe_engine *eng, const uint64_t *cts, uint32_t count, uint64_t *glwes_host);
+int fhe_engine_ring_pack_lwes_dev(fhe_engine *eng, const uint64_t *d_cts, uint32_t count, uint64_t *d_glwes);
+/* What the last ring packing call enqueued: info[0] 1 once a call ran, info[1] tree levels, info[2] automorphism
+ * keyswitches, info[3] kernel launches, info[4] scratch bytes held. */
+int fhe_engine_ring_pack_info(fhe_engine *eng, uint64_t info[5]);
+/* The device transform on its own, host arrays in place; synchronises.  Equals fhe_ring_ntt_host word for word. */
+int fhe_engine_ring_ntt(fhe_engine *eng, uint32_t N, int inverse, uint32_t *polys, uint32_t count);
+/* With only a ring key loaded, the refresh of fhe_engine_unpack_glwes / fhe_engine_unpack_narrow is judged by
+ * fhe_ring_packing_noise / fhe_ring_narrow_noise; with a matrix packing key loaded, by that key's pair as before. */
+
 /* ---- packed GLWE ciphertexts as inputs: sample extraction at any coefficient -----------------------
  * The inverse of the packing above, extract_lwe_sample_from_glwe_ciphertext of the reference
  * (core_crypto/algorithms/glwe_sample_extraction.rs:91-147): block j of packed results is coefficient c = j % N of GLWE
@@ -982,6 +1041,12 @@ int fhe_wire_write_packing_key(const fhe_params_t *p, const fhe_packing_params_t
 /* pksk may be NULL to read the decomposition only (then size the buffer with fhe_packing_key_len and call again) */
 int fhe_wire_read_packing_key(const fhe_params_t *p, const uint8_t *in, size_t in_len, fhe_packing_params_t *pp,
                               uint64_t *pksk, size_t pksk_cap_words, size_t *consumed);
+/* The ring packing key in the same layout (data = [log2 N][k][level][k+1][N]); the reader checks the pair against
+ * fhe_ring_packing_key_len.  Parity unpinned. */
+int fhe_wire_write_ring_packing_key(const fhe_params_t *p, const fhe_packing_params_t *pp, const uint64_t *key, uint8_t *out,
+                                    size_t out_cap, size_t *written);
+int fhe_wire_read_ring_packing_key(const fhe_params_t *p, const uint8_t *in, size_t in_len, fhe_packing_params_t *pp,
+                                   uint64_t *key, size_t key_cap_words, size_t *consumed);
 int fhe_wire_write_glwe_ciphertext(const fhe_params_t *p, const uint64_t *glwe, uint8_t *out, size_t out_cap, size_t *written);
 int fhe_wire_read_glwe_ciphertext(const fhe_params_t *p, const uint8_t *in, size_t in_len, uint64_t *glwe, size_t *consumed);
 int fhe_wire_write_glwe_list(const fhe_params_t *p, const uint64_t *glwes, uint32_t n_glwes, uint8_t *out, size_t out_cap,
