@@ -1119,6 +1119,30 @@ int fhe_str_splitn_encn(fhe_engine* eng, const char* op, const uint64_t* a, uint
     const uint32_t caps[2] = {a_cap, pat ? pat_cap : 0};
     return fhe_str_op(eng, name.c_str(), operands, caps, pat ? 2 : 1, n_digits, pat ? nullptr : clear, pat ? 0 : clear_len, out, n_outputs);
 }
+// the slice family: one plan name per (operation, clear / encrypted position, clear / encrypted t, output capacity)
+int fhe_str_slice(fhe_engine* eng, const char* op, const uint64_t* a, uint32_t a_cap, const uint64_t* t, uint32_t t_cap,
+                  const uint8_t* clear, uint32_t clear_len, const uint64_t* n_digits, uint32_t n_or_n_max, uint32_t out_cap,
+                  uint64_t* out, uint32_t* n_outputs) {
+    if (!op) return fail("null pointer: op");
+    const std::string base(op);
+    const fhe::opname::Row* row = fhe::opname::find_row(base);
+    if (!row || row->family != fhe::opname::SLICE || row->split.enc_count)
+        return fail("fhe_str_slice: op must be \"take\", \"skip\", \"split_at\", \"char_at\" or \"insert\", got: " + base);
+    const bool inserts = row->how == fhe::opname::INSERT;
+    if (!inserts && (t || clear || clear_len)) return fail("fhe_str_slice: only insert takes a string to insert");
+    if (t && (clear || clear_len)) return fail("fhe_str_slice: give an encrypted string to insert or a clear one, not both");
+    if (t && t_cap == 0) return fail("fhe_str_slice: the encrypted string to insert needs a capacity of at least one character");
+    if (!t && !clear && clear_len) return fail("null clear pattern");
+    const bool is_clear = inserts && !t;
+    std::string name = base + (n_digits ? "_encn" : "") + (is_clear ? "_clear" : "") + ":" + std::to_string(n_or_n_max);
+    if (out_cap) name += ":" + std::to_string(out_cap);
+    if (out || !n_outputs) {                            // (not a query)
+        if (!a) return fail("null pointer: a");
+    }
+    const uint64_t* operands[2] = {a, t};
+    const uint32_t caps[2] = {a_cap, t ? t_cap : 0};
+    return fhe_str_op(eng, name.c_str(), operands, caps, t ? 2 : 1, n_digits, is_clear ? clear : nullptr, is_clear ? clear_len : 0, out, n_outputs);
+}
 
 int fhe_str_repeat_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, uint32_t count, uint64_t* out) {
     if (count == 0 || count > 255) return fail("repeat: count must be in 1..255");

@@ -205,6 +205,40 @@ struct OpBuilder {
         }
         return 0;
     }
+    // take / skip / split_at / char_at / insert at a clear position n, or (_encn) at an encrypted one with the bound n_max:
+    // the first parameter; the second, where the row has one, is the output capacity C (str_slice.cpp)
+    int build_slice() {
+        const bool enc = row.split.enc_count, inserts = row.how == opname::INSERT;
+        const std::string op = row.name, position = enc ? "the position's bound n_max" : "the position n";
+        if (n.clear && !inserts) return fail(op + ": _clear is a form of insert only (the clear string to insert)");
+        if (!row.takes(n.params.size()))
+            return fail(row.params == 1 ? op + " takes one parameter: " + position + " (one character comes back: there is no output capacity)"
+                                        : op + " takes one or two parameters: " + position + " and the output capacity");
+        if (enc && n.params[0] == 0) return fail(op + ": n_max must be at least 1");
+        const uint32_t out_cap = n.params.size() == 2 ? n.params[1] : a_cap + (inserts ? rhs.cap() : 0);
+        if (out_cap == 0) return fail(op + ": the output capacity must be > 0");
+        if (enc && s.T < 16) return fail(op + " needs a message * carry space of at least 16 values");
+        std::vector<uint32_t> digits;
+        if (enc) digits = s.count_inputs(n.params[0]);
+        const Position at{n.params[0], enc ? &digits : nullptr};
+        std::vector<uint32_t> outs;
+        auto string = [&](const Str& r) { for (auto& blocks : s.fit(r, out_cap).ch) append(outs, blocks); };
+        switch (row.how) {
+        case opname::TAKE: string(s.take(a, at, out_cap)); break;
+        case opname::SKIP: string(s.skip(a, at)); break;
+        case opname::SPLIT_AT: string(s.take(a, at, out_cap)); string(s.skip(a, at)); break;
+        case opname::CHAR_AT: outs = s.char_at(a, at); break;
+        default: string(s.insert(a, at, rhs, out_cap)); break;
+        }
+        s.settle(outs);
+        // a result known at build time (take:0, a position beyond the capacity) still runs as a plan: one lookup level,
+        // a constant table read on the first block of the string
+        int64_t known = 0;
+        if (c.n_pbs() == 0 && s.is_trivial(outs[0], &known))
+            outs[0] = c.pbs(a.ch[0][0], c.lut_fn([known](uint64_t) { return (uint64_t)known; }));
+        output(outs);
+        return 0;
+    }
 
     int build() {
         switch (row.family) {
@@ -224,6 +258,7 @@ struct OpBuilder {
         case opname::REPLACE: return build_replace();
         case opname::SPLIT: return build_split();
         case opname::MATCHES: return build_matches();
+        case opname::SLICE: return build_slice();
         }
         return 0;
     }

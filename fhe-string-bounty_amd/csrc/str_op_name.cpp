@@ -46,6 +46,16 @@ static const Row TABLE[] = {
     Row("split_once", SPLIT, ENC | CLR, 1, true, AS_NAMED, ONCE),       // name[_clear][:C]
     Row("rsplit_once", SPLIT, ENC | CLR, 1, true, AS_NAMED, REVERSE | ONCE),
     Row("split_ascii_whitespace", SPLIT, UNARY, 2, false, AS_NAMED, WHITESPACE),
+    Row("take", SLICE, UNARY, 2, false, TAKE),                          // name:n[:C], name_encn:n_max[:C]: default C = a_cap
+    Row("take_encn", SLICE, UNARY, 2, false, TAKE, ENC_COUNT),
+    Row("skip", SLICE, UNARY, 2, false, SKIP),
+    Row("skip_encn", SLICE, UNARY, 2, false, SKIP, ENC_COUNT),
+    Row("split_at", SLICE, UNARY, 2, false, SPLIT_AT),
+    Row("split_at_encn", SLICE, UNARY, 2, false, SPLIT_AT, ENC_COUNT),
+    Row("char_at", SLICE, UNARY, 1, false, CHAR_AT),                    // char_at:n, char_at_encn:n_max
+    Row("char_at_encn", SLICE, UNARY, 1, false, CHAR_AT, ENC_COUNT),
+    Row("insert", SLICE, ENC | CLR, 2, false, INSERT),                  // insert[_clear]:n[:C]: default C = a_cap + the capacity / length of t
+    Row("insert_encn", SLICE, ENC | CLR, 2, false, INSERT, ENC_COUNT),
     Row("matches", MATCHES, CLR, 0, true),                              // matches_clear: the pattern text /.../ of regex.h
 };
 

@@ -1,7 +1,7 @@
 // str_op_name.h -- the names of the FheString plans: the one parser and the one table.
 //
 // A plan name is  base[_reference][_clear][:p1[:p2[:p3]]]  ("eq", "find_reference_clear", "replacen_encn_clear:2:1:8",
-// "split_once:3", "matches_clear").  build_string_op (fhe_string.cpp), the layout table of string programs
+// "split_once:3", "skip_encn:32", "matches_clear").  build_string_op (fhe_string.cpp), the layout table of string programs
 // (str_program.cpp) and the C ABI's split entry points (c_api.cpp) all read names through parse() and find_row(); nothing else
 // compares a name.  Standard headers only (tests/test_program_host.py compiles this stand-alone).
 #pragma once
@@ -14,17 +14,20 @@
 namespace fhe {
 namespace opname {
 
-enum Family : uint8_t { COMPARE, ORDER, AFFIX, FIND, STRIP_BIT, UNARY_STRING, LEN, IS_EMPTY, CONCAT, REPEAT, REPLACE, SPLIT, MATCHES };
+enum Family : uint8_t { COMPARE, ORDER, AFFIX, FIND, STRIP_BIT, UNARY_STRING, LEN, IS_EMPTY, CONCAT, REPEAT, REPLACE, SPLIT, MATCHES, SLICE };
 enum Form : uint8_t { ENC = 1, CLR = 2, UNARY = 4 };         // an encrypted second operand / a clear one (name_clear) / none
 // Which member of its family a row is, where the family has several (the order family passes its name to order_bit):
-// eq / ne / eq_ignore_case, where an affix, a search, a strip or a trim works, the case, replace / replacen / replacen_encn.
-enum How : uint8_t { AS_NAMED, NEGATED, IGNORE_CASE, AT_START, AT_END, ANYWHERE, UPPER, LOWER, BOTH_ENDS, FIRST_N, COUNTED };
+// eq / ne / eq_ignore_case, where an affix, a search, a strip or a trim works, the case, replace / replacen / replacen_encn,
+// the operation of the slice family.
+enum How : uint8_t { AS_NAMED, NEGATED, IGNORE_CASE, AT_START, AT_END, ANYWHERE, UPPER, LOWER, BOTH_ENDS, FIRST_N, COUNTED,
+                     TAKE, SKIP, SPLIT_AT, CHAR_AT, INSERT };
 enum Split : uint8_t { REVERSE = 1, TERMINATOR = 2, INCLUSIVE = 4, LIMITED = 8, ONCE = 16, WHITESPACE = 32, ENC_COUNT = 64 };
 
 // Which operation of the split family: see include/fhestr.h for the semantics of each.
 struct SplitKind {
     bool reverse, terminator, inclusive, limited, once, whitespace;
-    bool enc_count;                // splitn_encn / rsplitn_encn: n is encrypted, max_parts is its public bound
+    bool enc_count;                // splitn_encn / rsplitn_encn: n is encrypted, max_parts is its public bound; the _encn
+                                   // rows of the slice family: the position is encrypted, the first parameter its bound
     constexpr SplitKind(unsigned f = 0) : reverse(f & REVERSE), terminator(f & TERMINATOR), inclusive(f & INCLUSIVE), limited(f & LIMITED),
                                           once(f & ONCE), whitespace(f & WHITESPACE), enc_count(f & ENC_COUNT) {}
 };
@@ -34,7 +37,8 @@ struct Row {
     Family family;
     uint8_t forms;                 // Form bits
     // The name takes `params` numeric parameters; bare: it also builds without any.  The last parameter of a split
-    // row, the part capacity, may be left out.  Rows with params = 0 ignore parameters (matches_clear refuses them).
+    // row, the part capacity, and the output capacity of a slice row with two parameters may be left out.  Rows with
+    // params = 0 ignore parameters (matches_clear refuses them).
     uint8_t params;
     bool bare;
     How how;
@@ -43,7 +47,8 @@ struct Row {
         : name(name), family(family), forms((uint8_t)forms), params((uint8_t)params), bare(bare), how(how), split(split) {}
     bool unary() const { return forms & UNARY; }
     bool takes(size_t n_params) const {
-        return n_params == params || (bare && n_params == 0) || (family == SPLIT && n_params + 1 == params);
+        return n_params == params || (bare && n_params == 0) || (family == SPLIT && n_params + 1 == params) ||
+               (family == SLICE && params == 2 && n_params == 1);
     }
 };
 

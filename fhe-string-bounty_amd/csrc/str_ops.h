@@ -43,6 +43,12 @@ struct Occurrences {
 struct GroupWeights { std::vector<int32_t> c, d; int64_t theta = 0, lmax = 0; double noise = 0; };   // str_match.cpp: group_match
 // (offset, j) -> sel[offset] AND nzf[j]: the occurrence selected at `offset` still runs j characters on
 using RunMemo = std::map<std::pair<uint32_t, uint32_t>, uint32_t>;
+// Where a string is cut: a clear position n, or an encrypted one -- its digits (count_inputs) and n = the public bound n_max.
+struct Position {
+    uint32_t n = 0;
+    const std::vector<uint32_t>* digits = nullptr;
+    bool enc() const { return digits != nullptr; }
+};
 
 class StrOps {
 public:
@@ -236,12 +242,23 @@ public:
     Str extract_part(const Str& s, const std::vector<uint32_t>& in, uint32_t part_cap);
     void emit_count(const std::vector<uint32_t>& unary, uint32_t max_value);   // outputs the digits of sum(unary), unary monotone
     std::vector<uint32_t> count_inputs(uint32_t n_max);                    // the digits of an encrypted count with public bound n_max, as inputs
-    std::vector<uint32_t> count_thermometer(const std::vector<uint32_t>& digits, uint32_t n_max);   // g[q - 1] = [n >= q], q = 1 .. n_max
+    // g[q - from] = [n >= q], q = from .. n_max (from = 1: the whole thermometer)
+    std::vector<uint32_t> count_thermometer(const std::vector<uint32_t>& digits, uint32_t n_max, uint32_t from = 1);
     // selected occurrences of the pattern in s, leftmost or rightmost first, and the characters they cover; sel has s.cap entries
     Occurrences select_occurrences(const Str& s, const Operand& pat, bool from_right);
     // outputs: the count digits (split_once / rsplit_once: the found bit), then P parts of part_cap characters
     // g (splitn_encn / rsplitn_encn only): the thermometer of the encrypted n, P entries
     void split(const Str& s, const SplitKind& kind, const Operand& pat, uint32_t P, uint32_t part_cap, const std::vector<uint32_t>* g = nullptr);
+
+    // ---- slicing at a position: take, skip, char_at, insert (str_slice.cpp) ----
+    // the bits of min(n, bound), least significant first: as many as `bound` has; bound < M^D for D digits
+    std::vector<uint32_t> count_bits(const std::vector<uint32_t>& digits, uint32_t bound);
+    Str take(const Str& s, const Position& at, uint32_t cap);             // s[:n]: min(cap, s.cap, n) characters
+    Str skip(const Str& s, const Position& at);                           // s[n:], left-justified
+    std::vector<uint32_t> char_at(const Str& s, const Position& at);      // the bit [n < len(s)], then the blocks of s[n:n+1]
+    Str insert(const Str& s, const Position& at, const Operand& t, uint32_t cap);    // s[:n] + t + s[n:], cut or padded to cap
+    // every output block of a slice is a lookup's result: a bare input goes through the identity
+    void settle(std::vector<uint32_t>& blocks);
 
     // ---- matches: a clear regular expression (str_regex_match.cpp) ----
     uint32_t gated_or(std::vector<uint32_t> bits, uint32_t gate);          // gate AND (OR of bits), in one lookup where that fits

@@ -83,6 +83,16 @@ int op_layout(const std::string& op, uint32_t msg_mod, const uint32_t* caps, uin
             for (uint64_t p = 0; p < P && p < (1u << 16); p++) string(full ? params[1] : a_cap);
         }
         break;
+    case opname::SLICE:
+        if (!row.takes(params.size()) || (n.clear && row.how != opname::INSERT)) break;
+        if (row.how == opname::CHAR_AT) {
+            bit();
+            string(1);
+        } else {
+            const uint64_t cap = params.size() == 2 ? params[1] : a_cap + (row.how != opname::INSERT ? 0 : n.clear ? clear_len : b_cap);
+            for (int p = 0; p < (row.how == opname::SPLIT_AT ? 2 : 1); p++) string(cap);
+        }
+        break;
     }
     return 0;
 }

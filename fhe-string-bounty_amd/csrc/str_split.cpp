@@ -59,7 +59,8 @@ void StrOps::emit_count(const std::vector<uint32_t>& unary, uint32_t max_value) 
 }
 // ---- encrypted counts ("Encrypted counts") ----
 // n arrives as D little-endian base-M digits, D the smallest with M^D > n_max (the public bound); every consumer
-// works from the thermometer g[q - 1] = [n >= q], q = 1 .. n_max, so a value above the bound acts as the bound.
+// works from the thermometer g[q - 1] = [n >= q], q = 1 .. n_max, so a value above the bound acts as the bound (from > 1:
+// only the entries q = from .. n_max).
 std::vector<uint32_t> StrOps::count_inputs(uint32_t n_max) {
     std::vector<uint32_t> digits;
     for (uint32_t d = 0; d < opname::count_digits(M, n_max); d++) digits.push_back(c.input(M - 1));
@@ -69,7 +70,7 @@ std::vector<uint32_t> StrOps::count_inputs(uint32_t n_max) {
 // every q at once: the digits are packed in pairs hi * M + lo where that fits the box and the budget.  One packed
 // unit (D <= 2): [unit >= q] is one lookup per q.  More: the sign of (unit - q's unit) per unit, the most
 // significant non-equal one wins, and the last pick answers [sign != less] directly.
-std::vector<uint32_t> StrOps::count_thermometer(const std::vector<uint32_t>& digits, uint32_t n_max) {
+std::vector<uint32_t> StrOps::count_thermometer(const std::vector<uint32_t>& digits, uint32_t n_max, uint32_t from) {
     const bool pack = (uint64_t)M * M <= (uint64_t)T && 1.0 + (double)M * M <= budget();
     const uint32_t per = pack ? 2 : 1;
     std::vector<uint32_t> units;
@@ -80,7 +81,7 @@ std::vector<uint32_t> StrOps::count_thermometer(const std::vector<uint32_t>& dig
     const uint32_t pick = c.lut_fn([](uint64_t x) { const uint64_t msb = (x / 4) & 3, lsb = x & 3; return msb == 1 ? lsb : msb; });
     const uint32_t pick_ge = c.lut_fn([](uint64_t x) { const uint64_t msb = (x / 4) & 3, lsb = x & 3; return (uint64_t)((msb == 1 ? lsb : msb) != 0); });
     std::vector<uint32_t> g;
-    for (uint32_t q = 1; q <= n_max; q++) {
+    for (uint32_t q = from; q <= n_max; q++) {
         if (units.size() == 1) {
             g.push_back(c.pbs(units[0], c.lut_fn([q](uint64_t x) { return (uint64_t)(x >= q); })));
             continue;

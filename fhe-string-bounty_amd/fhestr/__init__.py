@@ -185,7 +185,7 @@ EXPORTS = [
 ] + [f"fhe_str_{n}{s}" for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat")
      for s in ("", "_clear")] + ["fhe_str_repeat_clear", "fhe_str_split", "fhe_str_replacen", "fhe_str_replacen_clear",
                                    "fhe_str_repeat", "fhe_str_replacen_encn", "fhe_str_replacen_encn_clear", "fhe_str_splitn_encn",
-                                   "fhe_str_matches_clear", "fhe_regex_check",
+                                   "fhe_str_slice", "fhe_str_matches_clear", "fhe_regex_check",
                                    "fhe_str_program_create", "fhe_str_program_create_offline", "fhe_str_program_destroy",
                                    "fhe_str_program_set_dedupe", "fhe_str_program_input_string", "fhe_str_program_input_count",
                                    "fhe_str_program_op", "fhe_str_program_value_info", "fhe_str_program_output",
@@ -327,6 +327,7 @@ def lib() -> C.CDLL:
     sig("fhe_str_replacen_encn", vp, vp, u32, vp, u32, vp, u32, vp, u32, u32, vp)
     sig("fhe_str_replacen_encn_clear", vp, vp, u32, vp, u32, vp, u32, vp, u32, u32, vp)
     sig("fhe_str_splitn_encn", vp, C.c_char_p, vp, u32, vp, u32, vp, u32, vp, u32, u32, vp, C.POINTER(u32))
+    sig("fhe_str_slice", vp, C.c_char_p, vp, u32, vp, u32, vp, u32, vp, u32, u32, vp, C.POINTER(u32))
     for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat"):
         sig(f"fhe_str_{n}", vp, vp, u32, vp, u32, vp)
         sig(f"fhe_str_{n}_clear", vp, vp, u32, vp, u32, vp)
@@ -1881,7 +1882,8 @@ def encode_count(params: Params, n: int, n_max: int) -> np.ndarray:
 
 
 class EncryptedCount:
-    """An encrypted count for FheStringOps.repeat / replacen / splitn / rsplitn: `digits`, the ciphertexts of its
+    """An encrypted count for FheStringOps.repeat / replacen / splitn / rsplitn, or an encrypted position for take / skip /
+    split_at / char_at / insert / substring: `digits`, the ciphertexts of its
     little-endian base-msg_mod digits -- fresh encryptions of encode_count(...), or what len, find / rfind (without the
     found block) or a split's count returned, expanded (D, kN+1), a PackedString or a NarrowString -- and the public bound `n_max` that
     travels with them.  n_max=None: the largest value the digits hold, msg_mod^D - 1 (needs `params`)."""
@@ -2007,9 +2009,27 @@ def resolve_split(op, a_cap, pat, max_parts, part_cap=None) -> StrCall:
     return StrCall(name, b_cap, clear, (0,) + order + ((2,) if counted else ()))
 
 
+def resolve_slice(op, a_cap, n, t=None, out_cap=None) -> StrCall:
+    """take / skip / split_at / char_at / insert; n: a clear int or NMax(n_max); t (insert only): an encrypted string or
+    clear bytes; out_cap=None: the capacity of the string, for insert plus that / the length of t."""
+    counted = isinstance(n, NMax)
+    if (t is not None) != (op == "insert"):
+        raise FheError(f"{op}: {'takes the string to insert' if op == 'insert' else 'only insert takes a second string'}")
+    if not counted and int(n) < 0:
+        raise FheError(f"{op}: the position must be >= 0")
+    if out_cap is not None and (op == "char_at" or int(out_cap) <= 0):
+        raise FheError(f"{op}: " + ("one character comes back: there is no output capacity" if op == "char_at" else "the output capacity must be > 0"))
+    suffix, b_cap, clear, order = _patterns(op, t)
+    if order and b_cap == 0:
+        raise FheError(f"{op}: the encrypted string to insert needs a capacity of at least one character")
+    name = op + ("_encn" if counted else "") + suffix + f":{int(n)}" + ("" if out_cap is None else f":{int(out_cap)}")
+    return StrCall(name, b_cap, clear, (0,) + ((2,) if order else ()) + ((1,) if counted else ()))
+
+
 class FheStringOps:
     """FheString operator surface over one engine (eq/ne/starts_with/ends_with/contains/find/
-    to_upper/to_lower, ..., replace / replacen, the split family).  Strings are (cap*blocks, kN+1) arrays of big-key LWEs (see string_to_blocks)."""
+    to_upper/to_lower, ..., replace / replacen, the split family, take / skip / split_at / char_at / insert at a clear or an
+    encrypted position).  Strings are (cap*blocks, kN+1) arrays of big-key LWEs (see string_to_blocks)."""
 
     def __init__(self, engine: Engine, out_alloc=None):
         """out_alloc(shape) -> uint64 array the results are written into (default: np.zeros; pass fhestr.pinned_empty --
@@ -2200,8 +2220,9 @@ class FheStringOps:
         PackedString --, clear bytes, or None for unary operations.  `op` may be any plan name, parameters included
         ("split:3" -- with clear bytes "split_clear:3" is meant, and may be written).  Returns (count, n_outputs, kN+1); with
         packed=True one PackedString, output o of row r at block r * n_outputs + o.
-        count: the encrypted count of an encrypted-count plan name ("repeat:3", "splitn_encn:3", "replacen_encn:2:1:8"),
-        shared by all rows like b; its n_max must be the one in the name."""
+        count: the encrypted count of an encrypted-count plan name ("repeat:3", "splitn_encn:3", "replacen_encn:2:1:8") or the
+        encrypted position of a slice name ("skip_encn:8", "insert_encn:8" with b the string to insert), shared by all rows
+        like b; its n_max must be the one in the name."""
         big = self.engine.params.big_size
         digits = self._count_operand(count) if count is not None else None
         clear = b if isinstance(b, (bytes, bytearray)) else None
@@ -2344,6 +2365,49 @@ class FheStringOps:
         """a repeated count times.  count: a clear int (1..255), or an EncryptedCount (n_max 1..255): the result then has
         n_max * a_cap characters and holds min(n, n_max) copies -- none for n = 0."""
         return self._call(resolve_repeat, (a, count), packed)
+
+    # ---- slicing at a position: an int, or an EncryptedCount (what find / rfind / len return, or a fresh encryption) ----
+    def _slice(self, op, a, n, t=None, out_cap=None, packed=False):
+        return self._call(functools.partial(resolve_slice, op), (a, n, t), packed, out_cap=out_cap)
+
+    def take(self, a, n: "int | EncryptedCount", out_cap: int | None = None, packed=False):
+        """s[:n] on the unpadded bytes, out_cap characters (default: the capacity of a).  An encrypted n above its bound
+        n_max acts as n_max; positions beyond the hidden length clamp as Python's slices do."""
+        return self._slice("take", a, n, None, out_cap, packed)
+
+    def truncate(self, a, n, out_cap: int | None = None, packed=False):
+        """= take."""
+        return self.take(a, n, out_cap, packed)
+
+    def skip(self, a, n: "int | EncryptedCount", out_cap: int | None = None, packed=False):
+        """s[n:], left-justified, out_cap characters (default: the capacity of a)."""
+        return self._slice("skip", a, n, None, out_cap, packed)
+
+    def substring(self, a, start, length, out_cap: int | None = None, packed=False):
+        """s[start:start + length]: take(skip(a, start), length), two plans."""
+        rest = self.skip(a, start, None, packed)
+        return self.take(rest, length, out_cap, packed)
+
+    def split_at(self, a, n: "int | EncryptedCount", out_cap: int | None = None, packed=False):
+        """(s[:n], s[n:]), out_cap characters each; packed=True: each part packed on its own, like split."""
+        call, a_cap, operands, digits = self._resolved(functools.partial(resolve_slice, "split_at"), (a, n, None), out_cap=out_cap)
+        n_part = (a_cap if out_cap is None else int(out_cap)) * self.bpc
+        if packed:
+            out, keep = self._run_device(call.name, a_cap, call.b_cap, call.clear, operands + ([digits] if digits is not None else []))
+            return tuple(self._packed_out(out[p * n_part:(p + 1) * n_part], n_part, n_part // self.bpc, packed) for p in range(2))
+        out = self._run(call.name, a_cap, call.b_cap, call.clear, operands, False, digits)
+        return out[:n_part], out[n_part:]
+
+    def char_at(self, a, n: "int | EncryptedCount", packed=False):
+        """(the 0/1 block [n < len(s)], the character s[n:n+1] -- zero when the bit is 0).  packed=True: ONE packed array, the
+        bit at coefficient 0 and the character's blocks after it."""
+        out = self._slice("char_at", a, n, None, None, packed)
+        return out if packed else (out[0], out[1:])
+
+    def insert(self, a, n: "int | EncryptedCount", t, out_cap: int | None = None, packed=False):
+        """s[:n] + t + s[n:], cut at out_cap characters (default: the capacity of a plus that -- or the length -- of t).
+        t: an encrypted (zero padded) string or clear bytes."""
+        return self._slice("insert", a, n, t, out_cap, packed)
 
 
 def _register_with_engine(engine, obj):
@@ -2532,6 +2596,20 @@ class StringProgram:
     def split_once(self, a, pat, part_cap=None): return self._split("split_once", a, pat, 2, part_cap)
     def rsplit_once(self, a, pat, part_cap=None): return self._split("rsplit_once", a, pat, 2, part_cap)
     def split_ascii_whitespace(self, a, max_parts, part_cap=None): return self._split("split_ascii_whitespace", a, None, max_parts, part_cap)
+
+    def _slice(self, op, a, n, t=None, out_cap=None):
+        return self._call(functools.partial(resolve_slice, op), a, n, t, out_cap=out_cap)
+
+    def take(self, a, n, out_cap: int | None = None): return self._slice("take", a, n, None, out_cap)[0]
+    def truncate(self, a, n, out_cap: int | None = None): return self.take(a, n, out_cap)
+    def skip(self, a, n, out_cap: int | None = None): return self._slice("skip", a, n, None, out_cap)[0]
+    def split_at(self, a, n, out_cap: int | None = None): return tuple(self._slice("split_at", a, n, None, out_cap))
+    def char_at(self, a, n): return tuple(self._slice("char_at", a, n))                     # (valid, character)
+    def insert(self, a, n, t, out_cap: int | None = None): return self._slice("insert", a, n, t, out_cap)[0]
+
+    def substring(self, a, start, length, out_cap: int | None = None):
+        """s[start:start + length]: two operations of this one plan; start / length: clear ints or symbolic counts."""
+        return self.take(self.skip(a, start), length, out_cap)
 
     # ---- results ----
     def output(self, *values):

@@ -465,6 +465,28 @@ int fhe_str_replacen_encn_clear(fhe_engine *eng, const uint64_t *a, uint32_t a_c
 int fhe_str_splitn_encn(fhe_engine *eng, const char *op, const uint64_t *a, uint32_t a_cap, const uint64_t *pat,
                         uint32_t pat_cap, const uint8_t *clear, uint32_t clear_len, const uint64_t *n_digits,
                         uint32_t max_parts, uint32_t part_cap, uint64_t *out, uint32_t *n_outputs);
+/* ---- slicing at a position ----
+ * Python slicing on the unpadded bytes s of `a`, at a position n that is clear or ENCRYPTED (n_digits, as the encrypted
+ * counts above: D digits with the public bound n_max; a value above the bound acts as the bound, and n_max may exceed
+ * a_cap).  Positions beyond the hidden length clamp as Python's slices do; nothing is refused at run time.  `op` is one of:
+ *   "take"       s[:n]                       one string of C characters
+ *   "skip"       s[n:]                       one string of C characters, left-justified
+ *   "split_at"   (s[:n], s[n:])              two strings of C characters each
+ *   "char_at"    (n < len(s), s[n:n+1])      one 0/1 block, then one character (blocks LWEs, zero when the bit is 0)
+ *   "insert"     s[:n] + t + s[n:]           one string of C characters, cut there; t is encrypted (t, t_cap characters,
+ *                                            zero padded: hidden length) or clear (clear, clear_len bytes, may be empty)
+ * C = out_cap, the output capacity; 0: a_cap, for insert a_cap + t_cap resp. a_cap + clear_len.  Results are cut or zero
+ * padded to C.  char_at takes no output capacity.  n_digits == NULL: n_or_n_max is the clear position n; otherwise it is
+ * n_max (>= 1) and n_digits the D digit ciphertexts, the plan's last inputs.  t and clear are read by insert only (give one
+ * of them).  *n_outputs and out == NULL as for fhe_str_split.
+ * Plan op names: "take:<n>[:<C>]" "skip:<n>[:<C>]" "split_at:<n>[:<C>]" "char_at:<n>" "insert[_clear]:<n>[:<C>]", and with
+ * an encrypted position "take_encn:<n_max>[:<C>]" "skip_encn:<n_max>[:<C>]" "split_at_encn:<n_max>[:<C>]"
+ * "char_at_encn:<n_max>" "insert_encn[_clear]:<n_max>[:<C>]".  Refused when the plan is built: a missing position, n_max == 0,
+ * C == 0, an output capacity on char_at, "_clear" on anything but insert; the _encn names need msg_mod * carry_mod >= 16.
+ * substring(s, start, length) is take of skip; truncate is take. */
+int fhe_str_slice(fhe_engine *eng, const char *op, const uint64_t *a, uint32_t a_cap, const uint64_t *t, uint32_t t_cap,
+                  const uint8_t *clear, uint32_t clear_len, const uint64_t *n_digits, uint32_t n_or_n_max, uint32_t out_cap,
+                  uint64_t *out, uint32_t *n_outputs);
 /* ANY FheString operation in one call, by its plan name: the single-row sibling of fhe_str_op_many below, and where every
  * fhe_str_<operation> entry point of this section ends.  Those are shorthands: each one spells a plan name from its
  * arguments (the names are given with them above) and calls this.  `name` is a plan name of fhe_str_plan_create with its
@@ -531,6 +553,11 @@ int fhe_str_to_lower(fhe_engine *eng, const uint64_t *a, uint32_t a_cap, uint64_
  *   replace[_clear]:<F>:<C>, replacen[_encn][_clear]:<n>:<F>:<C>      string (C)
  *   split_once rsplit_once [_clear][:<C>]           bit `found`, 2 strings (C, default a_cap)
  *   the other split names [_clear]:<P>[:<C>]        count (n_max = P + 1), P strings (C, default a_cap)
+ *   take skip [_encn]:<n>[:<C>]                     string (C, default a_cap)
+ *   split_at[_encn]:<n>[:<C>]                       2 strings (C, default a_cap)
+ *   char_at[_encn]:<n>                              bit `valid`, string (1)
+ *   insert[_encn][_clear]:<n>[:<C>]                 string (C, default a_cap + b_cap / a_cap + clear_len)
+ * The _encn names take the position as their count operand: the index of find or a len feeds "skip_encn:<a_cap>" as it is.
  * An operand that is not what a fresh input would be -- a block that is a linear combination, carries more than nominal
  * noise or a wider range than a message -- passes through one cleaning lookup when it is bound; every other operand is
  * bound as it is, at no cost.

@@ -11,6 +11,7 @@ import oracle as O
 import fhestr
 from split_ref import ONCE, SPLIT_OPS, decode_split, split_ref        # the clear-text definitions of the split family
 from count_ref import repeat_ref, replacen_ref, splitn_ref            # ... and of the operations with an encrypted count
+from slice_ref import decode_slice, slice_ref                         # ... and of the slices at a clear or an encrypted position
 
 N_CASES = int(sys.argv[1]) if len(sys.argv) > 1 else 150
 SEED = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -39,7 +40,7 @@ def digits_to_int(d):
     return sum(int(v) * (p.msg_mod ** i) for i, v in enumerate(d))
 
 
-fails = 0
+fails = slices = 0
 def check(name, got, want, ctx):
     global fails
     if got != want:
@@ -63,7 +64,7 @@ for case in range(N_CASES):
     op = str(rng.choice(["eq", "ne", "lt", "le", "gt", "ge", "eqic", "starts", "ends", "contains", "find", "rfind",
                          "upper", "lower", "trim_start", "trim_end", "strip", "replace", "len", "is_empty",
                          "strip_prefix", "strip_suffix", "concat", "repeat", "replace_general", "split", "split_ws", "replacen",
-                         "repeat_encn", "replacen_encn", "splitn_encn", "rsplitn_encn"]))
+                         "repeat_encn", "replacen_encn", "splitn_encn", "rsplitn_encn", "slice", "slice"]))
     clear = bool(rng.random() < 0.5)
     rhs = b if clear else eb
     ctx = (op, a, b, cap, b_cap, clear)
@@ -163,6 +164,24 @@ for case in range(N_CASES):
         else:
             got = dec_str(ops.replacen(ea, eb, enc(to, max(1, len(to) + int(rng.integers(0, 2)))), n, out_cap=out_cap))
         check(op, got, want, ctx + (to, n, out_cap))
+    elif op == "slice":
+        # take / skip / split_at / char_at / insert at a clear position, or at an encrypted one with a bound below, at or above
+        # the capacity: n in 0 .. n_max + 2 (what the digits of n_max cannot hold is left out); t = b, encrypted or clear
+        name = str(rng.choice(["take", "skip", "split_at", "char_at", "insert"]))
+        slices += 1
+        n_max = int(rng.integers(1, 2 * cap + 2)) if rng.random() < 0.6 else None
+        n = int(rng.integers(0, (n_max or cap) + 3))
+        out_cap = int(rng.integers(1, cap + 4)) if name != "char_at" and rng.random() < 0.4 else None
+        at = n
+        if n_max is not None:
+            n = min(n, p.msg_mod ** fhestr.count_input_digits(P, n_max) - 1)
+            at = fhestr.EncryptedCount(ck.encrypt_many(fhestr.encode_count(P, n, n_max)), n_max)
+        args = (ea, at, rhs) if name == "insert" else (ea, at)
+        got = getattr(ops, name)(*args) if out_cap is None else getattr(ops, name)(*args, out_cap=out_cap)
+        flat = np.concatenate([np.asarray(x).reshape(-1, p.big_size) for x in got]) if isinstance(got, tuple) else got
+        cap_out = out_cap or cap + ((len(b) if clear else b_cap) if name == "insert" else 0)
+        check(op + "." + name, decode_slice(name, dec(flat), p.msg_mod, cap_out),
+              slice_ref(name, a, n, n_max, cap_out, b if name == "insert" else b""), ctx + (n, n_max, out_cap))
     elif op.endswith("_encn"):
         # an encrypted count: n in 0 .. n_max + 1 (what the digits of n_max cannot hold is left out)
         n_max = int(rng.integers(1, 6))
@@ -186,5 +205,5 @@ for case in range(N_CASES):
             flat = np.concatenate([np.asarray(res.count).reshape(-1, p.big_size)] + list(res.parts))
             check(op, decode_split("splitn", dec(flat), p.msg_mod, n_max, part_cap or cap),
                   splitn_ref(name, a, b, n, n_max, part_cap=part_cap), ctx + (n, n_max, part_cap))
-print(f"fuzz: {N_CASES} cases, {fails} mismatches")
+print(f"fuzz: {N_CASES} cases ({slices} of them slices), {fails} mismatches")
 sys.exit(1 if fails else 0)
