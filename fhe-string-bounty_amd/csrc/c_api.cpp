@@ -1144,6 +1144,52 @@ int fhe_str_slice(fhe_engine* eng, const char* op, const uint64_t* a, uint32_t a
     return fhe_str_op(eng, name.c_str(), operands, caps, t ? 2 : 1, n_digits, is_clear ? clear : nullptr, is_clear ? clear_len : 0, out, n_outputs);
 }
 
+// the names that combine results: operands of any kind, in the plan's input order, checked against the name's shape
+int fhe_str_combine(fhe_engine* eng, const char* name, const uint64_t* const* operands, const uint32_t* n_blocks, uint32_t n_operands,
+                    const uint8_t* clear, uint32_t clear_len, uint64_t* out, uint32_t* n_outputs) {
+    API_BEGIN
+    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(name);
+    if (n_operands) { CHECK_PTR(operands); CHECK_PTR(n_blocks); }
+    const std::string op(name);
+    const fhe::opname::Name n = fhe::opname::parse(op);
+    if (n.status != fhe::opname::OK || !n.combines())
+        return fail("fhe_str_combine: not a name that combines results (and or xor not select select_count count_...): " + op);
+    const bool query = !out && n_outputs;
+    if (!query) CHECK_PTR(out);
+    const uint32_t msg_mod = eng->impl->p.msg_mod, bpc = fhe::opname::blocks_per_char(msg_mod);
+    if (bpc == 0) return fail("string ops need msg_mod = 2^b with b | 8 and carry_mod >= msg_mod");
+    std::vector<uint32_t> caps;
+    if (n.is(fhe::opname::SELECT) && n.row->how == fhe::opname::OF_STRINGS)
+        for (uint32_t i = 0; i < (n.clear ? 1u : 2u) && i < n_operands; i++) {
+            if (n_blocks[i] == 0 || n_blocks[i] % bpc)
+                return fail(op + ": operand " + std::to_string(i) + " is a string: " + std::to_string(n_blocks[i]) + " blocks are no whole characters of " +
+                            std::to_string(bpc) + " blocks");
+            caps.push_back(n_blocks[i] / bpc);
+        }
+    const uint32_t a_cap = caps.empty() ? 0 : caps[0], b_cap = caps.size() > 1 ? caps[1] : 0;
+    fhe::program::OpLayout lay;
+    std::string why;
+    if (fhe::program::op_layout(op, msg_mod, caps.data(), (uint32_t)caps.size(), clear, clear_len, lay, why)) return fail(why);
+    if (lay.known) {
+        static const char* const kinds[] = {"string", "bit", "count"};
+        if (n_operands != lay.operands.size())
+            return fail(op + ": takes " + std::to_string(lay.operands.size()) + " operand(s), got " + std::to_string(n_operands));
+        for (uint32_t i = 0; i < n_operands; i++) {
+            if (!query) CHECK_PTR(operands[i]);
+            if (n_blocks[i] != lay.operands[i].blocks)
+                return fail(op + ": operand " + std::to_string(i) + " has " + std::to_string(n_blocks[i]) + " blocks, the name takes a " +
+                            kinds[lay.operands[i].kind] + " of " + std::to_string(lay.operands[i].blocks));
+        }
+    }
+    fhe_plan* plan = nullptr;               // (a name the shape refuses: the builder says why)
+    if (cached_str_plan(eng, op, a_cap, b_cap, clear, clear_len, &plan)) return 1;
+    if (!lay.known) return fail("internal: " + op + " builds and has no layout");
+    if (n_outputs) *n_outputs = plan->c->n_outputs();
+    if (query) return 0;
+    return plan->c->run_host_parts(operands, n_blocks, n_operands, out);
+    API_END
+}
+
 int fhe_str_repeat_clear(fhe_engine* eng, const uint64_t* a, uint32_t a_cap, uint32_t count, uint64_t* out) {
     if (count == 0 || count > 255) return fail("repeat: count must be in 1..255");
     const uint8_t c = (uint8_t)count;
@@ -1285,6 +1331,14 @@ int fhe_str_program_input_count(fhe_str_program* prog, uint32_t n_max, uint32_t*
     CHECK_PTR(prog); LOCK_PROGRAM(prog); CHECK_PTR(value);
     std::string why;
     return prog->prog.input_count(n_max, *value, why) ? fail(why) : 0;
+    API_END
+}
+
+int fhe_str_program_input_bit(fhe_str_program* prog, uint32_t* value) {
+    API_BEGIN
+    CHECK_PTR(prog); LOCK_PROGRAM(prog); CHECK_PTR(value);
+    std::string why;
+    return prog->prog.input_bit(*value, why) ? fail(why) : 0;
     API_END
 }
 

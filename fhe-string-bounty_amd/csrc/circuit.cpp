@@ -39,7 +39,7 @@ std::vector<uint32_t> Circuit::take_outputs(uint32_t mark) {
     return taken;
 }
 
-uint32_t Circuit::bound_input(uint64_t degree) {
+uint32_t Circuit::bound_input(uint64_t degree, bool linear_ok) {
     if (bound_next_ >= bound_.size()) {
         set_error("input binding: the operation takes more input blocks than the " + std::to_string(bound_.size()) + " bound to it");
         return 0;
@@ -48,12 +48,14 @@ uint32_t Circuit::bound_input(uint64_t degree) {
     const Node& n = nodes_[id];
     if (n.kind == Node::LIN && n.terms.empty()) return id;                       // a trivial constant
     const bool materialised = n.kind == Node::INPUT || n.kind == Node::PBS;
-    if (materialised && n.noise <= 1.0 && n.vmin >= 0 && n.vmax <= (int64_t)degree) return id;
+    if ((materialised || linear_ok) && n.noise <= 1.0 && n.vmin >= 0 && n.vmax <= (int64_t)degree) return id;
     // one cleaning lookup, x mod (degree + 1): the identity on [0, degree], message extraction on a wider range, and a
     // table whose largest entry is `degree` -- what comes out is what a fresh input would be, range included
     const uint64_t mod = degree + 1;
     return pbs(id, lut_fn([mod](uint64_t x) { return x % mod; }));
 }
+
+uint32_t Circuit::input_linear(uint64_t degree) { return binding_ ? bound_input(degree, true) : input(degree); }
 
 uint32_t Circuit::input(uint64_t degree) {
     if (binding_) return bound_input(degree);

@@ -73,6 +73,10 @@ public:
     Circuit(const fhe_params_t& params, Engine* eng);
 
     uint32_t input(uint64_t degree);                             // next input ciphertext
+    // The same for an operation that reads the block only through linear combinations of its own (the bit logic and the
+    // condition of a select): a bound node that is a linear combination of nominal noise within [0, degree] -- a negated
+    // bit -- is handed out as it is, without the cleaning lookup.  Outside a binding: input(degree).
+    uint32_t input_linear(uint64_t degree);
     // degree_override >= 0: the caller asserts the value lies in [0, degree_override] (it knows more
     // than interval arithmetic, e.g. "at most one term is non-zero")
     uint32_t lin(const std::vector<Term>& terms, int64_t cst = 0, int64_t degree_override = -1);
@@ -197,7 +201,7 @@ public:
 
 private:
     void set_error(std::string e) { if (error_.empty()) error_ = std::move(e); }   // the first error is the cause
-    uint32_t bound_input(uint64_t degree);
+    uint32_t bound_input(uint64_t degree, bool linear_ok = false);
     // form: 0 plain, 1 signed input, 2 full-box table
     struct PbsKey {
         std::vector<std::pair<uint32_t, int32_t>> terms;

@@ -11,6 +11,7 @@
 // (tfhe/docs/tutorials/ascii_fhe_string.md:84-131, tfhe/examples/regex_engine/execution.rs:63-86).
 #include <string>
 
+#include "count_ops.h"
 #include "str_ops.h"
 
 namespace fhe {
@@ -18,9 +19,10 @@ namespace fhe {
 
 // ------------------------------------------------------------------------------------------------
 // op dispatch used by the C ABI: builds the circuit for `op` and declares its outputs.  The names and their grammar are
-// defined in str_op_name.cpp.  build_string_op parses the name, runs the refusals that every family shares, creates the
-// inputs -- a, then b; the digits of an encrypted count come last, from the family's own function after its parameter
-// checks -- and OpBuilder::build switches on the family of the name's row.
+// defined in str_op_name.cpp.  The names that combine results (bit logic, select, count arithmetic) take bits and counts as
+// well as strings and are built by build_combined.  For every other name build_string_op parses the name, runs the
+// refusals that every family shares, creates the inputs -- a, then b; the digits of an encrypted count come last, from the
+// family's own function after its parameter checks -- and OpBuilder::build switches on the family of the name's row.
 namespace {
 using opname::AT_END;
 using opname::AT_START;
@@ -259,10 +261,59 @@ struct OpBuilder {
         case opname::SPLIT: return build_split();
         case opname::MATCHES: return build_matches();
         case opname::SLICE: return build_slice();
+        case opname::LOGIC: case opname::SELECT: case opname::COUNT: break;     // build_combined
         }
         return 0;
     }
 };
+
+// The names that combine results ("Combining results").  Inputs in the order of opname::combine_shape;
+// a bit is read through linear combinations only, so inside a program a negated bit is bound as it is.  A stand-alone
+// plan's outputs are settled; inside a program they stay as built: `not` is linear there and adds no lookup.
+int build_combined(Circuit& c, StrOps& s, const opname::Name& n, uint32_t a_cap, uint32_t b_cap, const uint8_t* clear, uint32_t clear_len) {
+    const opname::Row& row = *n.row;
+    opname::Combine shape;
+    std::string why;
+    if (opname::combine_shape(n, a_cap, b_cap, clear, clear_len, shape, why)) return fail(why);
+    const std::string op = std::string(row.name) + (n.clear ? "_clear" : "");
+    if (row.family == opname::COUNT && s.T < 16)
+        return fail(op + " needs a message * carry space of at least 16 values: the digit sums of a count do not fit a smaller one");
+    const bool in_program = c.binding();
+    std::vector<Str> strings;
+    std::vector<std::vector<uint32_t>> counts;
+    std::vector<uint32_t> bits;
+    uint32_t anchor = UINT32_MAX;
+    for (const opname::Piece& p : shape.operands) {
+        if (p.kind == opname::A_STRING) strings.push_back(s.input_string(p.extent));
+        else if (p.kind == opname::A_COUNT) counts.push_back(s.count_inputs(p.extent));
+        else bits.push_back(c.input_linear(1));
+        if (anchor == UINT32_MAX) anchor = p.kind == opname::A_STRING ? strings[0].ch[0][0] : p.kind == opname::A_COUNT ? counts[0][0] : bits[0];
+    }
+    std::vector<uint32_t> outs;
+    switch (row.family) {
+    case opname::LOGIC:
+        if (row.how == opname::L_NOT) outs = s.not_bits(bits);
+        else outs.push_back(s.combine_bits(bits, row.how));
+        break;
+    case opname::SELECT:
+        if (row.how == opname::OF_COUNTS) {
+            outs = s.select_digits(bits[0], counts[0], counts[1]);
+            break;
+        }
+        for (auto& blocks : s.select(bits[0], strings[0], n.clear ? s.clear_string(clear, clear_len) : strings[1], n.params[0]).ch) append(outs, blocks);
+        break;
+    default: {
+        const opname::Piece& res = shape.results[0];
+        const uint32_t n_out = res.kind == opname::A_BIT ? 1 : opname::count_digits(s.M, res.extent);
+        outs = CountOps(c, s).build(row.how, counts[0], n.params[0], n.clear ? nullptr : &counts[1], n.clear ? 0 : n.params[1], shape.scalar, n_out);
+        break;
+    }
+    }
+    if (c.failed()) return fail("circuit build error: " + c.error());
+    if (!in_program) s.settle_combined(outs, anchor);
+    for (uint32_t o : outs) c.output(o);
+    return 0;
+}
 }  // namespace
 
 int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t b_cap,
@@ -278,6 +329,13 @@ int build_string_op(Circuit& c, const std::string& op, uint32_t a_cap, uint32_t 
         s.full_box_reduce = false;         // ... and its chunks of T - 1 comparison bits
     }
     if (!s.ok) return fail("string ops need msg_mod = 2^b with b | 8 and carry_mod >= msg_mod");
+    if (n.combines()) {
+        if (n.reference) return fail("unknown string op: " + op);
+        if (n.clear && !clear && clear_len) return fail("null clear pattern");
+        if (build_combined(c, s, n, a_cap, b_cap, clear, clear_len)) return 1;
+        if (c.failed()) return fail("circuit build error: " + c.error());
+        return 0;
+    }
     if (a_cap == 0) return fail("string capacity must be > 0");
     if (n.clear && !clear && clear_len) return fail("null clear pattern");
     Str a = s.input_string(a_cap);

@@ -352,6 +352,56 @@ uint32_t StrOps::and_all(const std::vector<uint32_t>& bits) {
     if (terms.size() == 1) return terms[0].node;
     return c.pbs(c.lin(terms), lut_equals(terms.size()));
 }
+// ---- combining results ----
+uint32_t StrOps::combine_bits(const std::vector<uint32_t>& bits, opname::How how) {
+    std::vector<uint32_t> open;
+    int64_t ones = 0;
+    for (uint32_t b : bits) {
+        int64_t v = 0;
+        if (!is_trivial(b, &v)) open.push_back(b);
+        else if (how == opname::L_XOR) ones += v & 1;
+        else if ((v != 0) != (how == opname::L_AND)) return c.trivial(how == opname::L_AND ? 0 : 1);    // AND with 0, OR with 1
+    }
+    if (how != opname::L_XOR) return open.empty() ? c.trivial(how == opname::L_AND ? 1 : 0) : reduce_bits(open, how == opname::L_AND);
+    // parity: sums of up to T - 1 bits, each read by x & 1, then the parity of those
+    const uint32_t odd = c.lut_fn([](uint64_t x) { return x & 1; });
+    while (open.size() > 1) {
+        std::vector<Term> terms;
+        for (uint32_t b : open) terms.push_back({b, 1});
+        auto groups = term_groups(terms, T - 1);
+        if (groups.size() == open.size()) groups.assign(1, terms);      // no two fit one lookup: the build fails on the budget, with its message
+        std::vector<uint32_t> next;
+        for (const auto& g : groups) next.push_back(g.size() == 1 ? g[0].node : c.pbs(c.lin(g), odd));
+        open.swap(next);
+    }
+    if (open.empty()) return c.trivial(ones & 1);
+    return (ones & 1) ? not_bit(open[0]) : open[0];
+}
+Str StrOps::select(uint32_t sel, const Str& a, const Str& b, uint32_t cap) {
+    const Str fa = fit(a, cap), fb = fit(b, cap);
+    return build_str(cap, [&](uint32_t i, uint32_t k) {
+        Scope sc(c, owner_for(i, cap));
+        if (i >= a.cap) return gate_block(fb.ch[i][k], sel, false);
+        if (i >= b.cap) return gate_block(fa.ch[i][k], sel, true);
+        return select_block(fb.ch[i][k], fa.ch[i][k], sel, M - 1);
+    });
+}
+std::vector<uint32_t> StrOps::select_digits(uint32_t sel, const std::vector<uint32_t>& a, const std::vector<uint32_t>& b) {
+    std::vector<uint32_t> out;
+    for (size_t d = 0; d < std::max(a.size(), b.size()); d++)
+        out.push_back(d >= a.size() ? gate_block(b[d], sel, false) : d >= b.size() ? gate_block(a[d], sel, true) : select_block(b[d], a[d], sel, M - 1));
+    return out;
+}
+void StrOps::settle_combined(std::vector<uint32_t>& blocks, uint32_t anchor) {
+    for (uint32_t& b : blocks) {
+        int64_t known = 0;
+        const Node& n = c.node(b);
+        bool looked_up = n.kind == Node::PBS;
+        for (const Term& t : n.terms) looked_up |= n.kind == Node::LIN && c.node(t.node).kind == Node::PBS;
+        if (is_trivial(b, &known)) b = c.pbs(anchor, c.lut_fn([known](uint64_t) { return (uint64_t)known; }));
+        else if (!looked_up) b = c.pbs(b, lut_message());
+    }
+}
 // len = offset of the first null char (cap when there is none): found bit is always 1
 std::vector<uint32_t> StrOps::len(const Str& s, uint32_t n_digits) {
     std::vector<uint32_t> z;

@@ -171,6 +171,19 @@ public:
     // sel ? a : b as two gates and their sum (if_then_else without the final message_extract, integer/.../cmux.rs:194-248)
     uint32_t select_gated(uint32_t sel, uint32_t a, uint32_t b) { return c.lin({{gate_block(a, sel, true), 1}, {gate_block(b, sel, false), 1}}, 0, M - 1); }
 
+    // ---- combining results ("Combining results") ----
+    // AND / OR / XOR of any number of bits: bits known at build time drop out; what is left is summed in groups one lookup
+    // holds (two bits: one lookup); a linear bit -- a NOT -- enters the sums as it is
+    uint32_t combine_bits(const std::vector<uint32_t>& bits, opname::How how);
+    // sel ? a : b, each side cut or zero-padded to `cap` characters (fit): one lookup per block where select_block fits
+    Str select(uint32_t sel, const Str& a, const Str& b, uint32_t cap);
+    // the same on two digit vectors (little endian, the shorter one extended with zeros)
+    std::vector<uint32_t> select_digits(uint32_t sel, const std::vector<uint32_t>& a, const std::vector<uint32_t>& b);
+    // every output block of a stand-alone combining plan is a lookup's result (as settle): one that no lookup has gone into
+    // -- an input, its negation -- goes through the identity, one known at build time becomes a constant table read on
+    // `anchor`, an input of the plan
+    void settle_combined(std::vector<uint32_t>& blocks, uint32_t anchor);
+
     // ---- shapes: case, whitespace, trims, shifts, concatenation, length ----
     Str change_case(const Str& s, bool to_lower);
     std::vector<uint32_t> whitespace_bits(const Str& s, bool null_too);    // [s[i] is ASCII whitespace] (+ [s[i] == 0])

@@ -26,6 +26,28 @@ int op_layout(const std::string& op, uint32_t msg_mod, const uint32_t* caps, uin
     }
     const opname::Row& row = *n.row;
     const std::vector<uint32_t>& params = n.params;
+    if (n.combines()) {
+        // the shape is the name table's (opname::combine_shape); what it refuses, the builder refuses with the same words
+        opname::Combine shape;
+        uint32_t b_sum = 0;
+        for (uint32_t i = 1; i < n_caps; i++) b_sum += caps[i];
+        if (n.reference) out.refusal = "unknown string op: " + op;
+        if (n.reference || opname::combine_shape(n, n_caps ? caps[0] : 0, b_sum, clear, clear_len, shape, out.refusal)) {
+            out.known = false;
+            return 0;
+        }
+        auto spec = [&](const opname::Piece& p) {
+            const uint32_t blocks = p.kind == opname::A_STRING ? p.extent * bpc : p.kind == opname::A_COUNT ? opname::count_digits(msg_mod, p.extent) : 1;
+            return ResultSpec{(Kind)p.kind, blocks, p.extent};
+        };
+        out.strings_min = out.strings_max = 0;
+        for (const opname::Piece& p : shape.operands) {
+            out.operands.push_back(spec(p));
+            if (p.kind == opname::A_STRING) out.strings_min = ++out.strings_max;
+        }
+        for (const opname::Piece& p : shape.results) out.results.push_back(spec(p));
+        return 0;
+    }
     const bool full = params.size() == row.params;           // every parameter given (takes(): or none, or all but a part capacity)
     const uint64_t a_cap = n_caps ? caps[0] : 0;
     uint64_t b_cap = 0;
@@ -83,6 +105,7 @@ int op_layout(const std::string& op, uint32_t msg_mod, const uint32_t* caps, uin
             for (uint64_t p = 0; p < P && p < (1u << 16); p++) string(full ? params[1] : a_cap);
         }
         break;
+    case opname::LOGIC: case opname::SELECT: case opname::COUNT: break;      // (answered above)
     case opname::SLICE:
         if (!row.takes(params.size()) || (n.clear && row.how != opname::INSERT)) break;
         if (row.how == opname::CHAR_AT) {
@@ -149,6 +172,13 @@ int Program::input_count(uint32_t n_max, uint32_t& value, std::string& why) {
     return 0;
 }
 
+int Program::input_bit(uint32_t& value, std::string& why) {
+    if (usable(why)) return 1;
+    if (values_.size() >= INDEX_MASK) { why = "string program: too large"; return 1; }
+    value = add_value(BIT, 1, {b_.input(1)}, NO_OP);
+    return 0;
+}
+
 int Program::value(uint32_t id, const Value*& v, std::string& why) const {
     v = nullptr;
     if ((id >> INDEX_BITS) != tag_) { why = "value " + std::to_string(id) + " belongs to another program"; return 1; }
@@ -164,6 +194,18 @@ int Program::op(const std::string& name, const uint32_t* operands, uint32_t n_op
     if (usable(why)) return 1;
     if (n_operands && !operands) { why = "null pointer: operands"; return 1; }
     if (clear_len && !clear) { why = "null clear pattern"; return 1; }
+    {
+        const opname::Name parsed = opname::parse(name);
+        if (parsed.status == opname::OK && parsed.combines()) {
+            std::vector<const Value*> all;
+            for (uint32_t i = 0; i < n_operands; i++) {
+                const Value* v;
+                if (value(operands[i], v, why)) { why = name + ": operand " + std::to_string(i) + ": " + why; return 1; }
+                all.push_back(v);
+            }
+            return op_combined(name, all, clear, clear_len, results, results_cap, n_results, why);
+        }
+    }
     // operands: strings, then at most one count
     std::vector<const Value*> strings;
     const Value* count = nullptr;
@@ -215,12 +257,7 @@ int Program::op(const std::string& name, const uint32_t* operands, uint32_t n_op
         }
     }
     n_results = (uint32_t)lay.results.size();
-    if (n_results > results_cap) {
-        why = name + ": results_cap " + std::to_string(results_cap) + " is too small, the op returns " + std::to_string(n_results) + " values";
-        return 1;
-    }
-    if (n_results && !results) { why = "null pointer: results"; return 1; }
-    if (values_.size() + n_results >= INDEX_MASK) { why = "string program: too large"; return 1; }
+    if (results_fit(name, n_results, results, results_cap, why)) return 1;
 
     // the operands' nodes in the order the plan takes its inputs: string, pattern operand(s), count digits
     std::vector<uint32_t> queue;
@@ -233,10 +270,26 @@ int Program::op(const std::string& name, const uint32_t* operands, uint32_t n_op
         queue.insert(queue.end(), count->nodes.begin(), count->nodes.end());
         for (size_t d = count->nodes.size(); d < lay.count_digits; d++) queue.push_back(b_.trivial(0));
     }
+    return bind_and_build(name, lay.results, lay.known, queue, strings[0]->extent, b_cap, clear, clear_len, results, n_results, why);
+}
+
+int Program::results_fit(const std::string& name, uint32_t n, const uint32_t* results, uint32_t results_cap, std::string& why) const {
+    if (n > results_cap) {
+        why = name + ": results_cap " + std::to_string(results_cap) + " is too small, the op returns " + std::to_string(n) + " values";
+        return 1;
+    }
+    if (n && !results) { why = "null pointer: results"; return 1; }
+    if (values_.size() + n >= INDEX_MASK) { why = "string program: too large"; return 1; }
+    return 0;
+}
+
+int Program::bind_and_build(const std::string& name, const std::vector<ResultSpec>& specs, bool known, const std::vector<uint32_t>& queue,
+                            uint32_t a_cap, uint32_t b_cap, const uint8_t* clear, uint32_t clear_len, uint32_t* results, uint32_t& n_results,
+                            std::string& why) {
     const uint32_t mark = b_.n_outputs();
     b_.bind_inputs(queue);
     std::string refusal;
-    const int rc = b_.build_op(name, strings[0]->extent, b_cap, clear, clear_len, refusal);
+    const int rc = b_.build_op(name, a_cap, b_cap, clear, clear_len, refusal);
     const std::string bind_error = b_.end_binding();
     const std::vector<uint32_t> outs = b_.take_outputs(mark);
     if (rc || !bind_error.empty()) {
@@ -246,22 +299,69 @@ int Program::op(const std::string& name, const uint32_t* operands, uint32_t n_op
         return 1;
     }
     size_t total = 0;
-    for (const ResultSpec& r : lay.results) total += r.blocks;
-    if (total != outs.size() || !lay.known) {
-        why = lay.known ? "internal: " + name + " declared " + std::to_string(outs.size()) + " outputs, its layout has " + std::to_string(total)
-                        : name + ": not a name of the layout table of string programs, its outputs cannot be cut into values";
+    for (const ResultSpec& r : specs) total += r.blocks;
+    if (total != outs.size() || !known) {
+        why = known ? "internal: " + name + " declared " + std::to_string(outs.size()) + " outputs, its layout has " + std::to_string(total)
+                    : name + ": not a name of the layout table of string programs, its outputs cannot be cut into values";
         broken_ = why;
         n_results = 0;
         return 1;
     }
     size_t at = 0;
     for (uint32_t i = 0; i < n_results; i++) {
-        const ResultSpec& r = lay.results[i];
+        const ResultSpec& r = specs[i];
         results[i] = add_value(r.kind, r.extent, std::vector<uint32_t>(outs.begin() + at, outs.begin() + at + r.blocks), n_ops_);
         at += r.blocks;
     }
     n_ops_++;
     return 0;
+}
+
+// The names that combine results: bits and counts may come first; what the name takes is the name table's shape.  The
+// capacities of a select's strings come from the operands.
+int Program::op_combined(const std::string& name, const std::vector<const Value*>& operands, const uint8_t* clear, uint32_t clear_len,
+                         uint32_t* results, uint32_t results_cap, uint32_t& n_results, std::string& why) {
+    // the strings where the name may take them (a select: the first operand, and the second unless it is clear bytes)
+    std::vector<uint32_t> caps;
+    for (size_t i = 0; i < operands.size() && i < 2 && operands[i]->kind == STRING; i++) caps.push_back(operands[i]->extent);
+    const opname::Name n = opname::parse(name);
+    if (n.is(opname::SELECT) && n.row->how == opname::OF_STRINGS)
+        caps.resize(n.clear ? 1 : 2, 1);                     // (a missing string: refused below, by its kind)
+    else caps.clear();
+    OpLayout lay;
+    if (op_layout(name, b_.msg_modulus(), caps.data(), (uint32_t)caps.size(), clear, clear_len, lay, why)) return 1;
+    if (!lay.known) {                                        // refused by the name alone: the circuit stays as it is
+        why = lay.refusal;
+        return 1;
+    }
+    std::string takes;
+    for (const ResultSpec& o : lay.operands) takes += (takes.empty() ? "" : ", ") + std::string(kind_name(o.kind));
+    if (operands.size() != lay.operands.size()) {
+        why = name + ": takes " + std::to_string(lay.operands.size()) + " operand(s) (" + takes + "), got " + std::to_string(operands.size());
+        return 1;
+    }
+    for (size_t i = 0; i < operands.size(); i++) {
+        const Value& v = *operands[i];
+        const ResultSpec& o = lay.operands[i];
+        if (v.kind != o.kind) {
+            why = name + ": operand " + std::to_string(i) + " is a " + kind_name(v.kind) + ": the op takes " + takes;
+            return 1;
+        }
+        if (v.kind == COUNT && v.nodes.size() > o.blocks) {
+            why = name + ": the count operand has " + std::to_string(v.nodes.size()) + " digits, the op takes " + std::to_string(o.blocks) +
+                  " (n_max = " + std::to_string(o.extent) + ")";
+            return 1;
+        }
+    }
+    n_results = (uint32_t)lay.results.size();
+    if (results_fit(name, n_results, results, results_cap, why)) return 1;
+    std::vector<uint32_t> queue;
+    for (size_t i = 0; i < operands.size(); i++) {
+        queue.insert(queue.end(), operands[i]->nodes.begin(), operands[i]->nodes.end());
+        for (size_t d = operands[i]->nodes.size(); d < lay.operands[i].blocks; d++) queue.push_back(b_.trivial(0));
+    }
+    return bind_and_build(name, lay.results, true, queue, caps.empty() ? 0 : caps[0], caps.size() > 1 ? caps[1] : 0, clear, clear_len, results,
+                          n_results, why);
 }
 
 int Program::output(uint32_t id, std::string& why) {

@@ -35,9 +35,14 @@ struct OpLayout {
     bool from_to = false;                        // the replace forms: the operands after a are `from` and `to` ...
     uint32_t from_cap = 0;                       // ... of these many characters (0: equal capacities)
     std::vector<ResultSpec> results;             // in output order
+    // The names that combine results (bit logic, select, count arithmetic) take bits and counts as well as strings: their
+    // operands in input order, a condition bit last.  Empty for every other name: the string rule above holds.
+    std::vector<ResultSpec> operands;
+    std::string refusal;                         // a combining name that is not known: why its shape is refused, in the builder's words
 };
 
-// 0, or nonzero with the reason in `why`.  caps: the capacities of the encrypted string operands as given (a first).
+// 0, or nonzero with the reason in `why`.  caps: the capacities of the encrypted string operands as given (a first); for a
+// name that combines results those of its string operands, none for one that takes bits and counts only.
 // Refused here: a msg_mod no string operation works on.  A name the table does not know or cannot parse (known = false),
 // and one it knows but the builder refuses (a missing parameter, a malformed regular expression: no results), are left
 // to build_string_op, which says why.
@@ -75,6 +80,7 @@ public:
     int set_dedupe(bool on, std::string& why);
     int input_string(uint32_t cap, uint32_t& value, std::string& why);
     int input_count(uint32_t n_max, uint32_t& value, std::string& why);
+    int input_bit(uint32_t& value, std::string& why);
     // `n_results` is set as soon as the layout is known, also when results_cap is too small (nothing is built then)
     int op(const std::string& name, const uint32_t* operands, uint32_t n_operands, const uint8_t* clear, uint32_t clear_len,
            uint32_t* results, uint32_t results_cap, uint32_t& n_results, std::string& why);
@@ -89,6 +95,13 @@ public:
 private:
     uint32_t add_value(Kind kind, uint32_t extent, std::vector<uint32_t> nodes, uint32_t op_index);
     int usable(std::string& why) const;
+    int op_combined(const std::string& name, const std::vector<const Value*>& operands, const uint8_t* clear, uint32_t clear_len,
+                    uint32_t* results, uint32_t results_cap, uint32_t& n_results, std::string& why);
+    int results_fit(const std::string& name, uint32_t n, const uint32_t* results, uint32_t results_cap, std::string& why) const;
+    // binds `queue` to the inputs of `name`, builds it and cuts its outputs into the values of `specs`
+    int bind_and_build(const std::string& name, const std::vector<ResultSpec>& specs, bool known, const std::vector<uint32_t>& queue,
+                       uint32_t a_cap, uint32_t b_cap, const uint8_t* clear, uint32_t clear_len, uint32_t* results, uint32_t& n_results,
+                       std::string& why);
     Backend& b_;
     uint32_t tag_;                 // value ids carry it: an id of another program is recognised
     std::vector<Value> values_;

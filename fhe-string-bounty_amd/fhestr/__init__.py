@@ -185,7 +185,7 @@ EXPORTS = [
 ] + [f"fhe_str_{n}{s}" for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat")
      for s in ("", "_clear")] + ["fhe_str_repeat_clear", "fhe_str_split", "fhe_str_replacen", "fhe_str_replacen_clear",
                                    "fhe_str_repeat", "fhe_str_replacen_encn", "fhe_str_replacen_encn_clear", "fhe_str_splitn_encn",
-                                   "fhe_str_slice", "fhe_str_matches_clear", "fhe_regex_check",
+                                   "fhe_str_slice", "fhe_str_combine", "fhe_str_program_input_bit", "fhe_str_matches_clear", "fhe_regex_check",
                                    "fhe_str_program_create", "fhe_str_program_create_offline", "fhe_str_program_destroy",
                                    "fhe_str_program_set_dedupe", "fhe_str_program_input_string", "fhe_str_program_input_count",
                                    "fhe_str_program_op", "fhe_str_program_value_info", "fhe_str_program_output",
@@ -339,6 +339,8 @@ def lib() -> C.CDLL:
     sig("fhe_str_program_set_dedupe", vp, i32)
     sig("fhe_str_program_input_string", vp, u32, C.POINTER(u32))
     sig("fhe_str_program_input_count", vp, u32, C.POINTER(u32))
+    sig("fhe_str_program_input_bit", vp, C.POINTER(u32))
+    sig("fhe_str_combine", vp, C.c_char_p, vp, vp, u32, vp, u32, vp, C.POINTER(u32))
     sig("fhe_str_program_op", vp, C.c_char_p, vp, u32, vp, u32, vp, u32, C.POINTER(u32))
     sig("fhe_str_program_value_info", vp, u32, C.POINTER(u32))
     sig("fhe_str_program_output", vp, u32)
@@ -2026,10 +2028,56 @@ def resolve_slice(op, a_cap, n, t=None, out_cap=None) -> StrCall:
     return StrCall(name, b_cap, clear, (0,) + ((2,) if order else ()) + ((1,) if counted else ()))
 
 
+# ---- combining results: the plan names of the bit logic, select and the count arithmetic (include/fhestr.h) ----
+# A call is (plan name, a_cap, b_cap, clear bytes or None, which of the given operands are the plan's inputs, in its order).
+COUNT_OPS = ("add", "sub", "eq", "ne", "lt", "le", "gt", "ge")
+
+
+def resolve_bits(op, k):
+    if op not in ("and", "or", "xor", "not") or int(k) < (1 if op == "not" else 2):
+        raise FheError(f"{op}: takes at least {1 if op == 'not' else 2} bit(s)")
+    return f"{op}:{int(k)}", 0, 0, None, tuple(range(int(k)))
+
+
+def resolve_select(a, b, out_cap=None):
+    """a, b as described for the resolvers above: capacities (b may be clear bytes), or both NMax; the condition is operand 2."""
+    if isinstance(a, NMax) or isinstance(b, NMax):
+        if not (isinstance(a, NMax) and isinstance(b, NMax)):
+            raise FheError("select: both sides are strings (b may be clear bytes) or both are encrypted counts")
+        if out_cap is not None:
+            raise FheError("select: counts have no output capacity")
+        return f"select_count:{int(a)}:{int(b)}", 0, 0, None, (0, 1, 2)
+    if _is_clear(a) or not isinstance(a, (int, np.integer)) or not (_is_clear(b) or isinstance(b, (int, np.integer))):
+        raise FheError("select: a is an encrypted string, b an encrypted string or clear bytes")
+    cap = int(out_cap) if out_cap is not None else max(int(a), len(b) if _is_clear(b) else int(b), 1)
+    if cap <= 0:
+        raise FheError("select: the output capacity must be > 0")
+    if _is_clear(b):
+        return f"select_clear:{cap}", int(a), 0, bytes(b), (0, 2)
+    return f"select:{cap}", int(a), int(b), None, (0, 1, 2)
+
+
+def resolve_count(op, a, b):
+    """count_<op> on NMax(a_max) and NMax(b_max), or a clear int b (0 .. 2^32 - 1) in as few bytes as hold it."""
+    if op not in COUNT_OPS or not isinstance(a, NMax):
+        raise FheError(f"count_{op}: the first operand is an encrypted count")
+    if isinstance(b, NMax):
+        return f"count_{op}:{int(a)}:{int(b)}", 0, 0, None, (0, 1)
+    if not isinstance(b, (int, np.integer)) or not 0 <= int(b) < 2 ** 32:
+        raise FheError(f"count_{op}: the second operand is an encrypted count or an int in 0 .. 2^32 - 1")
+    return f"count_{op}_clear:{int(a)}", 0, 0, int(b).to_bytes(max(1, (int(b).bit_length() + 7) // 8), "little"), (0,)
+
+
+def count_result_bound(op, a_max, b):
+    """The public bound of count_add / count_sub; b: the other bound, or the clear int."""
+    return int(a_max) + int(b) if op == "add" else int(a_max)
+
+
 class FheStringOps:
     """FheString operator surface over one engine (eq/ne/starts_with/ends_with/contains/find/
     to_upper/to_lower, ..., replace / replacen, the split family, take / skip / split_at / char_at / insert at a clear or an
-    encrypted position).  Strings are (cap*blocks, kN+1) arrays of big-key LWEs (see string_to_blocks)."""
+    encrypted position; and what combines their results: bit_and / bit_or / bit_xor / bit_not, select, count_add /
+    count_sub / count_eq .. count_ge / count_min / count_max).  Strings are (cap*blocks, kN+1) arrays of big-key LWEs (see string_to_blocks)."""
 
     def __init__(self, engine: Engine, out_alloc=None):
         """out_alloc(shape) -> uint64 array the results are written into (default: np.zeros; pass fhestr.pinned_empty --
@@ -2409,6 +2457,98 @@ class FheStringOps:
         t: an encrypted (zero padded) string or clear bytes."""
         return self._slice("insert", a, n, t, out_cap, packed)
 
+    # ---- combining results: bits (eq, contains, found, ...), strings and EncryptedCounts (len, find, ...) ----
+    def _combine(self, call, given, packed=False):
+        """One run of a combining plan name (resolve_bits / resolve_select / resolve_count): the outputs (n_outputs, kN+1),
+        or a PackedString.  A bit is one ciphertext row."""
+        name, a_cap, b_cap, clear, order = call
+        big = self.engine.params.big_size
+        operands = [x if isinstance(x, _PACKED) else _u64(x).reshape(-1, big) for x in (given[i] for i in order)]
+        kinds = name.split(":")[0]
+        for i, x in zip(order, operands):                   # a bit is one block, however it travels (expanded, packed, narrow)
+            is_bit = kinds in ("and", "or", "xor", "not") or (kinds.startswith("select") and i == 2)
+            have = x.count if isinstance(x, _PACKED) else x.shape[0]
+            if is_bit and have != 1:
+                raise FheError(f"{name}: operand {i} is a bit, one 0/1 block, got {have} blocks")
+        if self._dev(packed, *operands):
+            d_out, keep = self._run_device(name, a_cap, b_cap, clear, operands)
+            return self._finish(d_out, d_out.shape[0], packed)
+        ptrs = (C.c_void_p * len(operands))(*[x.ctypes.data for x in operands])
+        counts = (C.c_uint32 * len(operands))(*[x.shape[0] for x in operands])
+        buf = (C.c_uint8 * max(1, len(clear)))(*clear) if clear is not None else None
+        args = (self.engine.handle, name.encode(), ptrs, counts, len(operands), buf, len(clear) if clear is not None else 0)
+        n_out = C.c_uint32(0)
+        _check(lib().fhe_str_combine(*args, None, C.byref(n_out)))         # outputs (builds and caches the plan)
+        out = self._alloc((n_out.value, big))
+        _check(lib().fhe_str_combine(*args, _ptr(out), C.byref(n_out)))
+        return out
+
+    def _bits(self, op, bits, packed=False):
+        out = self._combine(resolve_bits(op, len(bits)), list(bits), packed)
+        return out if packed or op == "not" and len(bits) > 1 else out[0]
+
+    def bit_and(self, *bits, packed=False):
+        """AND of two or more 0/1 blocks (what eq, contains, matches, is_empty or the found of find return): one block."""
+        return self._bits("and", bits, packed)
+
+    def bit_or(self, *bits, packed=False): return self._bits("or", bits, packed)
+    def bit_xor(self, *bits, packed=False): return self._bits("xor", bits, packed)
+
+    def bit_not(self, *bits, packed=False):
+        """The negation of every bit given: one block for one bit, (k, kN+1) for k."""
+        return self._bits("not", bits, packed)
+
+    def select(self, cond, a, b, out_cap: int | None = None, packed=False):
+        """cond ? a : b.  a, b: encrypted strings (expanded, PackedString or NarrowString; b may be clear bytes) -- each side is
+        cut or zero padded to out_cap characters (default: the larger capacity) --, or both EncryptedCounts: then an
+        EncryptedCount with the larger bound comes back."""
+        (ga, da), (gb, db) = self._describe(a), self._describe(b)
+        out = self._combine(resolve_select(da, db, out_cap), [ga, gb, cond], packed)
+        return EncryptedCount(out, max(da, db)) if isinstance(da, NMax) else out
+
+    def _count(self, op, a: "EncryptedCount", b: "EncryptedCount | int", packed=False):
+        if not isinstance(a, EncryptedCount):
+            raise FheError(f"count_{op}: the first operand is an EncryptedCount")
+        (ga, da), (gb, db) = self._describe(a), self._describe(b)
+        out = self._combine(resolve_count(op, da, db), [ga, gb], packed)
+        if op in ("add", "sub"):
+            return EncryptedCount(out, count_result_bound(op, da, db))
+        return out if packed else out[0]
+
+    def count_add(self, a, b, packed=False):
+        """a + b of two counts (b: an EncryptedCount or an int): an EncryptedCount with the bound a.n_max + b.n_max (+ b)."""
+        return self._count("add", a, b, packed)
+
+    def count_sub(self, a, b, packed=False):
+        """max(a - b, 0), Rust's saturating_sub: an EncryptedCount with the bound of a."""
+        return self._count("sub", a, b, packed)
+
+    def count_min(self, a, b, packed=False):
+        """min(a, b): a comparison and a select (two plans); with an int b: a - max(a - b, 0)."""
+        if isinstance(b, EncryptedCount):
+            return self.select(self._count("lt", a, b), a, b, packed=packed)
+        return self._count("sub", a, self._count("sub", a, b), packed)
+
+    def count_max(self, a, b, packed=False):
+        """max(a, b): a comparison and a select (two plans); with an int b: max(a - b, 0) + b."""
+        if isinstance(b, EncryptedCount):
+            return self.select(self._count("lt", a, b), b, a, packed=packed)
+        return self._count("add", self._count("sub", a, b), b, packed)
+
+
+def _combining_methods(cls):
+    """count_eq .. count_ge on FheStringOps and StringProgram alike: thin names over cls._count."""
+    for op in COUNT_OPS[2:]:
+        def method(self, a, b, _op=op, **kw):
+            return self._count(_op, a, b, **kw)
+        method.__name__ = f"count_{op}"
+        method.__doc__ = f"The bit [a {dict(eq='==', ne='!=', lt='<', le='<=', gt='>', ge='>=')[op]} b] of two counts; b: an encrypted count or an int."
+        setattr(cls, f"count_{op}", method)
+    return cls
+
+
+_combining_methods(FheStringOps)
+
 
 def _register_with_engine(engine, obj):
     """Engine.close closes `obj` before the engine goes: what it holds points into the engine."""
@@ -2508,6 +2648,13 @@ class StringProgram:
     def count(self, n_max: int) -> ProgramValue:
         vid = C.c_uint32()
         _check(lib().fhe_str_program_input_count(self._h, n_max, C.byref(vid)))
+        self.inputs.append(ProgramValue(self, vid.value))
+        return self.inputs[-1]
+
+    def bit(self) -> ProgramValue:
+        """A bit input: one 0/1 block."""
+        vid = C.c_uint32()
+        _check(lib().fhe_str_program_input_bit(self._h, C.byref(vid)))
         self.inputs.append(ProgramValue(self, vid.value))
         return self.inputs[-1]
 
@@ -2611,6 +2758,47 @@ class StringProgram:
         """s[start:start + length]: two operations of this one plan; start / length: clear ints or symbolic counts."""
         return self.take(self.skip(a, start), length, out_cap)
 
+    # ---- combining results, as FheStringOps: bits, strings and counts are symbolic values ----
+    @staticmethod
+    def _described(x):
+        if isinstance(x, ProgramValue):
+            return NMax(x.extent) if x.kind == "count" else x.extent if x.kind == "string" else None
+        return x
+
+    def _combine(self, call, given):
+        name, _, _, clear, order = call
+        return self.op(name, *[given[i] for i in order], clear=clear)
+
+    def bit_and(self, *bits): return self._combine(resolve_bits("and", len(bits)), bits)[0]
+    def bit_or(self, *bits): return self._combine(resolve_bits("or", len(bits)), bits)[0]
+    def bit_xor(self, *bits): return self._combine(resolve_bits("xor", len(bits)), bits)[0]
+
+    def bit_not(self, *bits):
+        """Linear inside a program: no lookup is added.  One value for one bit, a tuple for several."""
+        res = self._combine(resolve_bits("not", len(bits)), bits)
+        return res[0] if len(bits) == 1 else tuple(res)
+
+    def select(self, cond, a, b, out_cap: int | None = None):
+        """cond ? a : b on symbolic strings (b may be clear bytes) or on two symbolic counts."""
+        return self._combine(resolve_select(self._described(a), self._described(b), out_cap), [a, b, cond])[0]
+
+    def _count(self, op, a, b):
+        return self._combine(resolve_count(op, self._described(a), self._described(b)), [a, b])[0]
+
+    def count_add(self, a, b): return self._count("add", a, b)
+    def count_sub(self, a, b): return self._count("sub", a, b)
+
+    def count_min(self, a, b):
+        """A comparison and a select_count in this one plan; with an int b: a - max(a - b, 0)."""
+        if isinstance(b, ProgramValue):
+            return self.select(self._count("lt", a, b), a, b)
+        return self._count("sub", a, self._count("sub", a, b))
+
+    def count_max(self, a, b):
+        if isinstance(b, ProgramValue):
+            return self.select(self._count("lt", a, b), b, a)
+        return self._count("add", self._count("sub", a, b), b)
+
     # ---- results ----
     def output(self, *values):
         """The next outputs of the plan: symbolic values, or whole split results."""
@@ -2626,6 +2814,9 @@ class StringProgram:
         h = C.c_void_p()
         _check(lib().fhe_str_program_finish(self._h, world, C.byref(h)))
         return CompiledProgram(self, Plan(self.engine, h, self.params))
+
+
+_combining_methods(StringProgram)
 
 
 class CompiledProgram:

@@ -487,6 +487,43 @@ int fhe_str_splitn_encn(fhe_engine *eng, const char *op, const uint64_t *a, uint
 int fhe_str_slice(fhe_engine *eng, const char *op, const uint64_t *a, uint32_t a_cap, const uint64_t *t, uint32_t t_cap,
                   const uint8_t *clear, uint32_t clear_len, const uint64_t *n_digits, uint32_t n_or_n_max, uint32_t out_cap,
                   uint64_t *out, uint32_t *n_outputs);
+/* ---- combining results: bit logic, select, arithmetic on counts ----
+ * Every operation above returns a string, a 0/1 bit (eq, contains, matches, is_empty, the `found` of find) or a count (len,
+ * find / rfind, the split counts: D digits with a public bound).  The names below combine such results.  Their inputs are
+ * listed in plan order; a condition bit always comes last, where the digits of an _encn name come.
+ *   "and:<k>" "or:<k>" "xor:<k>"            k bits (k >= 2)                          one bit
+ *   "not:<k>"                               k bits (k >= 1)                          k bits, each negated
+ *   "select:<C>"                            string a, string b, bit c                string of C characters: c ? a : b, each side
+ *                                                                                    cut or zero padded to C
+ *   "select_clear:<C>"                      string a, bit c; b = the clear bytes     the same
+ *   "select_count:<a_max>:<b_max>"          digits of a, digits of b, bit c          count c ? a : b, bound max(a_max, b_max)
+ *   "count_add:<a_max>:<b_max>"             digits of a, digits of b                 count a + b, bound a_max + b_max
+ *   "count_sub:<a_max>:<b_max>"                                                      count max(a - b, 0), bound a_max (saturating_sub)
+ *   "count_eq" "count_ne" "count_lt" "count_le" "count_gt" "count_ge" ":<a_max>:<b_max>"                 one bit
+ *   "<count name>_clear:<a_max>"            digits of a; b = the clear integer: `clear` holds its 1 to 4 little-endian bytes
+ *                                           (count_add_clear: bound a_max + b)
+ * min and max are a comparison and a select_count.  Result digits are clean -- each in [0, msg_mod - 1], as many as the
+ * result's bound needs (the D of the encrypted counts above) -- so a result is the count operand of any _encn name and of
+ * the names here as it is; a result bit is 0 or 1 and may be a condition.
+ * An operand count above its declared bound: the count_ names apply the clamping of the _encn names -- the value acts as the
+ * bound, they compute on min(a, a_max) and min(b, b_max).  select_count passes the chosen digits through as they are: a
+ * value above its bound stays above it and acts as the bound in whatever takes the result.
+ * fhe_str_plan_create[_offline] build these names with a_cap / b_cap = the capacities of the strings of a select (b_cap = 0
+ * for select_clear) and 0 for every other name: a capacity the name does not use must be 0.  Refused when the plan is built,
+ * with a message: a missing parameter, k = 0 (k < 2 for and / or / xor), C = 0, a bound of 0, "_clear" on a name without
+ * that form (the bit logic, select_count), a clear integer of no bytes or of more than 4, a capacity the name does not
+ * use; the count_ names need msg_mod * carry_mod >= 16 (the digit sums of a count do not fit a smaller message-and-carry
+ * space).  Every output block of such a plan has gone through a lookup,
+ * as for the slices.  The blocks of a select or a select_count are the unchosen side plus one lookup's correction where
+ * that fits the box and the budget -- a value in [0, msg_mod - 1] that carries two nominal variances, not one, the
+ * tolerance the slices keep for their outputs; every other result block is a single lookup's output.  Inside a string
+ * program `not` stays linear and costs no lookup.
+ * fhe_str_combine runs one of these names on host buffers: operands[i] = n_blocks[i] ciphertexts, the n_operands operands in
+ * plan order (a string: capacity * blocks; a count: its D digits; a bit: 1); the block counts are checked against the name.
+ * clear / clear_len: the clear bytes of select_clear, the clear integer of a count name.  out, *n_outputs and out == NULL
+ * as for fhe_str_split; the plan is built on the first call and kept in the cache of the one-call operations. */
+int fhe_str_combine(fhe_engine *eng, const char *name, const uint64_t *const *operands, const uint32_t *n_blocks,
+                    uint32_t n_operands, const uint8_t *clear, uint32_t clear_len, uint64_t *out, uint32_t *n_outputs);
 /* ANY FheString operation in one call, by its plan name: the single-row sibling of fhe_str_op_many below, and where every
  * fhe_str_<operation> entry point of this section ends.  Those are shorthands: each one spells a plan name from its
  * arguments (the names are given with them above) and calls this.  `name` is a plan name of fhe_str_plan_create with its
@@ -557,6 +594,16 @@ int fhe_str_to_lower(fhe_engine *eng, const uint64_t *a, uint32_t a_cap, uint64_
  *   split_at[_encn]:<n>[:<C>]                       2 strings (C, default a_cap)
  *   char_at[_encn]:<n>                              bit `valid`, string (1)
  *   insert[_encn][_clear]:<n>[:<C>]                 string (C, default a_cap + b_cap / a_cap + clear_len)
+ *   and or xor :<k>                                 bit                              operands: k bits
+ *   not:<k>                                         k bits                           operands: k bits
+ *   select:<C> / select_clear:<C>                   string (C)                       operands: string, string, bit / string, bit
+ *   select_count:<a_max>:<b_max>                    count (n_max = max(a_max, b_max))     operands: count, count, bit
+ *   count_add:<a_max>:<b_max> / _clear:<a_max>      count (n_max = a_max + b_max / a_max + the integer)   operands: count, count / count
+ *   count_sub:<a_max>:<b_max> / _clear:<a_max>      count (n_max = a_max)            operands: count, count / count
+ *   count_eq ne lt le gt ge :<a_max>:<b_max> / _clear:<a_max>      bit               operands: count, count / count
+ * The names of the last seven rows ("combining results" above) take their operands in the order given, so bits and counts
+ * may come first; a wrong kind or number is refused and leaves the program usable.  A bit operand that is the linear result
+ * of a `not` is bound as it is: negation costs no lookup inside a program.
  * The _encn names take the position as their count operand: the index of find or a len feeds "skip_encn:<a_cap>" as it is.
  * An operand that is not what a fresh input would be -- a block that is a linear combination, carries more than nominal
  * noise or a wider range than a message -- passes through one cleaning lookup when it is bound; every other operand is
@@ -578,6 +625,7 @@ int fhe_str_program_destroy(fhe_str_program *prog);
 int fhe_str_program_set_dedupe(fhe_str_program *prog, int on);
 int fhe_str_program_input_string(fhe_str_program *prog, uint32_t cap, uint32_t *value);
 int fhe_str_program_input_count(fhe_str_program *prog, uint32_t n_max, uint32_t *value);
+int fhe_str_program_input_bit(fhe_str_program *prog, uint32_t *value);      /* one 0/1 block */
 int fhe_str_program_op(fhe_str_program *prog, const char *op, const uint32_t *operands, uint32_t n_operands,
                        const uint8_t *clear, uint32_t clear_len, uint32_t *results, uint32_t results_cap,
                        uint32_t *n_results);

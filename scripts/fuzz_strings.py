@@ -12,6 +12,7 @@ import fhestr
 from split_ref import ONCE, SPLIT_OPS, decode_split, split_ref        # the clear-text definitions of the split family
 from count_ref import repeat_ref, replacen_ref, splitn_ref            # ... and of the operations with an encrypted count
 from slice_ref import decode_slice, slice_ref                         # ... and of the slices at a clear or an encrypted position
+from combine_ref import COUNT_OPS, bits_ref, count_bound, count_ref, decode_bit, decode_digits, decode_string, select_ref   # ... and of what combines results
 
 N_CASES = int(sys.argv[1]) if len(sys.argv) > 1 else 150
 SEED = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -40,7 +41,7 @@ def digits_to_int(d):
     return sum(int(v) * (p.msg_mod ** i) for i, v in enumerate(d))
 
 
-fails = slices = 0
+fails = slices = combines = 0
 def check(name, got, want, ctx):
     global fails
     if got != want:
@@ -64,7 +65,7 @@ for case in range(N_CASES):
     op = str(rng.choice(["eq", "ne", "lt", "le", "gt", "ge", "eqic", "starts", "ends", "contains", "find", "rfind",
                          "upper", "lower", "trim_start", "trim_end", "strip", "replace", "len", "is_empty",
                          "strip_prefix", "strip_suffix", "concat", "repeat", "replace_general", "split", "split_ws", "replacen",
-                         "repeat_encn", "replacen_encn", "splitn_encn", "rsplitn_encn", "slice", "slice"]))
+                         "repeat_encn", "replacen_encn", "splitn_encn", "rsplitn_encn", "slice", "slice", "combine", "combine"]))
     clear = bool(rng.random() < 0.5)
     rhs = b if clear else eb
     ctx = (op, a, b, cap, b_cap, clear)
@@ -182,6 +183,37 @@ for case in range(N_CASES):
         cap_out = out_cap or cap + ((len(b) if clear else b_cap) if name == "insert" else 0)
         check(op + "." + name, decode_slice(name, dec(flat), p.msg_mod, cap_out),
               slice_ref(name, a, n, n_max, cap_out, b if name == "insert" else b""), ctx + (n, n_max, out_cap))
+    elif op == "combine":
+        # bit logic on k random bits, a select between a and b (encrypted or clear, any output capacity), or a count operation on
+        # two counts with random bounds (the second one encrypted or clear): operands above their bound included
+        combines += 1
+        kind = str(rng.choice(["bits", "select", "count", "count"]))
+        enc_bit = lambda v: ck.encrypt_many(np.array([v], dtype=np.uint64))
+        msgs = lambda ct: [int(m) for m in dec(ct)]
+        if kind == "bits":
+            name = str(rng.choice(["and", "or", "xor", "not"]))
+            bits = [int(v) for v in rng.integers(0, 2, size=int(rng.integers(1 if name == "not" else 2, 20)))]
+            got = msgs(getattr(ops, "bit_" + name)(*[enc_bit(v) for v in bits]))
+            check(op + "." + name, got if name == "not" else decode_bit(got), bits_ref(name, bits), ctx + (bits,))
+        elif kind == "select":
+            c = int(rng.integers(0, 2))
+            out_cap = int(rng.integers(1, cap + 4)) if rng.random() < 0.5 else None
+            cap_out = out_cap or max(cap, len(b) if clear else b_cap, 1)
+            got = ops.select(enc_bit(c), ea, rhs) if out_cap is None else ops.select(enc_bit(c), ea, rhs, out_cap=out_cap)
+            check(op + ".select", decode_string(msgs(got), p.msg_mod, cap_out), select_ref(c, a, b, cap_out), ctx + (c, out_cap))
+        else:
+            name = str(rng.choice(COUNT_OPS))
+            a_max, b_max = int(rng.integers(1, 70)), int(rng.integers(1, 70))
+            holds = lambda n_max: p.msg_mod ** fhestr.count_input_digits(P, n_max) - 1
+            x, y = int(rng.integers(0, min(a_max + 3, holds(a_max)) + 1)), int(rng.integers(0, min(b_max + 3, holds(b_max)) + 1))
+            count = lambda v, n_max: fhestr.EncryptedCount(ck.encrypt_many(fhestr.encode_count(P, v, n_max)), n_max)
+            got = getattr(ops, "count_" + name)(count(x, a_max), y if clear else count(y, b_max))
+            want = count_ref(name, x, a_max, y, None if clear else b_max)
+            if name in ("add", "sub"):
+                got = decode_digits(msgs(got.digits), p.msg_mod, count_bound(name, a_max, y if clear else b_max))
+            else:
+                got = decode_bit(msgs(got))
+            check(op + ".count_" + name, got, want, ctx + (x, a_max, y, b_max))
     elif op.endswith("_encn"):
         # an encrypted count: n in 0 .. n_max + 1 (what the digits of n_max cannot hold is left out)
         n_max = int(rng.integers(1, 6))
@@ -205,5 +237,5 @@ for case in range(N_CASES):
             flat = np.concatenate([np.asarray(res.count).reshape(-1, p.big_size)] + list(res.parts))
             check(op, decode_split("splitn", dec(flat), p.msg_mod, n_max, part_cap or cap),
                   splitn_ref(name, a, b, n, n_max, part_cap=part_cap), ctx + (n, n_max, part_cap))
-print(f"fuzz: {N_CASES} cases ({slices} of them slices), {fails} mismatches")
+print(f"fuzz: {N_CASES} cases ({slices} of them slices, {combines} combining results), {fails} mismatches")
 sys.exit(1 if fails else 0)
