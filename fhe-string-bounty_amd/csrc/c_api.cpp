@@ -1553,4 +1553,125 @@ int fhe_transcipher_timing(fhe_transcipher* tc, int on, double ms[3], uint32_t* 
     API_END
 }
 
+// ---- casting keys (cast.h; the device side: cast_dev.hip; parameters, key generation and the host loop: client.cpp) ----
+struct fhe_cast_key {
+    fhe_engine* eng;
+    fhe::CastKey* impl;          // owned by eng->impl->cast_keys
+};
+
+int fhe_cast_key_create(fhe_engine* eng, const fhe_cast_params_t* cp, const uint64_t* key, fhe_cast_key** out) {
+    API_BEGIN
+    CHECK_PTR(out);
+    *out = nullptr;
+    CHECK_PTR(eng); LOCK_ENGINE(eng); CHECK_PTR(cp); CHECK_PTR(key);
+    fhe::CastKey* k = nullptr;
+    if (fhe::CastKey::create(*eng->impl, *cp, key, &k)) return 1;
+    *out = new fhe_cast_key{eng, k};
+    return 0;
+    API_END
+}
+
+int fhe_cast_key_destroy(fhe_cast_key* h) {
+    API_BEGIN
+    if (!h) return 0;
+    {
+        LOCK_ENGINE(h->eng);
+        fhe::Engine& e = *h->eng->impl;
+        if (e.use() || e.sync_all_streams()) return 1;              // launches in flight still read its buffers
+        for (auto it = e.cast_keys.begin(); it != e.cast_keys.end(); ++it)
+            if (it->get() == h->impl) { e.cast_keys.erase(it); break; }
+    }
+    delete h;
+    return 0;
+    API_END
+}
+
+int fhe_cast_key_info(fhe_cast_key* h, uint32_t info[8]) {
+    API_BEGIN
+    CHECK_PTR(h); LOCK_ENGINE(h->eng); CHECK_PTR(info);
+    h->impl->info(info);
+    return 0;
+    API_END
+}
+
+int fhe_cast_key_set_fused(fhe_cast_key* h, int on) {
+    API_BEGIN
+    CHECK_PTR(h); LOCK_ENGINE(h->eng);
+    h->impl->fused = on != 0;
+    return 0;
+    API_END
+}
+
+int fhe_cast_key_set_input_noise(fhe_cast_key* h, double v_in) {
+    API_BEGIN
+    CHECK_PTR(h); LOCK_ENGINE(h->eng);
+    if (!(v_in >= 0)) return fail("cast: the declared input noise must be a variance >= 0 in the source's nominal units");
+    h->impl->v_in = v_in;
+    return 0;
+    API_END
+}
+
+int fhe_cast_key_set_group(fhe_cast_key* h, uint32_t group) {
+    API_BEGIN
+    CHECK_PTR(h); LOCK_ENGINE(h->eng);
+    return h->impl->set_group(group);
+    API_END
+}
+
+int fhe_cast_lwes(fhe_cast_key* h, const uint64_t* in, uint32_t count, int mode, uint64_t* out) {
+    API_BEGIN
+    CHECK_PTR(h); LOCK_ENGINE(h->eng);
+    if (count) { CHECK_PTR(in); CHECK_PTR(out); }
+    return h->impl->cast_host(in, 0, count, false, mode, out);
+    API_END
+}
+
+int fhe_cast_lwes_dev(fhe_cast_key* h, const uint64_t* d_in, uint32_t count, int mode, uint64_t* d_out) {
+    API_BEGIN
+    CHECK_PTR(h); LOCK_ENGINE(h->eng);
+    if (count) { CHECK_PTR(d_in); CHECK_PTR(d_out); }
+    return h->impl->cast_dev(d_in, 0, count, false, mode, d_out);
+    API_END
+}
+
+int fhe_cast_packed(fhe_cast_key* h, const uint64_t* glwes, uint32_t first, uint32_t count, int mode, uint64_t* out) {
+    API_BEGIN
+    CHECK_PTR(h); LOCK_ENGINE(h->eng);
+    if (count) { CHECK_PTR(glwes); CHECK_PTR(out); }
+    return h->impl->cast_host(glwes, first, count, true, mode, out);
+    API_END
+}
+
+int fhe_cast_packed_dev(fhe_cast_key* h, const uint64_t* d_glwes, uint32_t first, uint32_t count, int mode, uint64_t* d_out) {
+    API_BEGIN
+    CHECK_PTR(h); LOCK_ENGINE(h->eng);
+    if (count) { CHECK_PTR(d_glwes); CHECK_PTR(d_out); }
+    return h->impl->cast_dev(d_glwes, first, count, true, mode, d_out);
+    API_END
+}
+
+int fhe_cast_narrow(fhe_cast_key* h, const uint64_t* narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int mode, uint64_t* out) {
+    API_BEGIN
+    CHECK_PTR(h); LOCK_ENGINE(h->eng);
+    if (count) { CHECK_PTR(narrow); CHECK_PTR(out); }
+    return h->impl->cast_narrow_host(narrow, held, bits, first, count, mode, out);
+    API_END
+}
+
+int fhe_cast_narrow_dev(fhe_cast_key* h, const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int mode, uint64_t* d_out) {
+    API_BEGIN
+    CHECK_PTR(h); LOCK_ENGINE(h->eng);
+    if (count) { CHECK_PTR(d_narrow); CHECK_PTR(d_out); }
+    return h->impl->cast_narrow_dev(d_narrow, held, bits, first, count, mode, d_out);
+    API_END
+}
+
+int fhe_cast_debug_digits(fhe_cast_key* h, const uint64_t* src, uint32_t first, uint32_t count, int packed, int8_t* out, size_t* bytes) {
+    API_BEGIN
+    CHECK_PTR(h); LOCK_ENGINE(h->eng); CHECK_PTR(bytes);
+    if (count && out) CHECK_PTR(src);
+    return h->impl->digits_host(src, first, count, packed != 0, out, bytes);
+    API_END
+}
+
 }  // extern "C"

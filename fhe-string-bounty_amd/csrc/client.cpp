@@ -16,6 +16,7 @@
 #include <thread>
 #include <vector>
 
+#include "cast.h"
 #include "det_math.h"
 #include "engine.h"
 #include "glwe_narrow.h"
@@ -66,17 +67,20 @@ struct ClientKey {
         return (x + rounding) / d;
     }
 
-    // lwe_keyswitch_key_generation.rs:65-130
-    void gen_ksk(uint64_t* ksk) const {
-        const size_t in_dim = glwe_sk.size(), osz = (size_t)p.n + 1;
+    // lwe_keyswitch_key_generation.rs:65-130, for any pair of LWE keys: row (i, it) encrypts in_sk[i] at level `level - it`
+    // under out_sk; one generator per input key bit.  The clients' own keyswitch key and the casting keys (cast.h).
+    static void gen_lwe_ksk(const uint64_t* in_sk, size_t in_dim, const uint64_t* out_sk, size_t out_dim, uint32_t base_log, uint32_t level,
+                            double std_dev, const Seed256& seed, uint64_t stream_base, uint64_t* ksk) {
         for (size_t i = 0; i < in_dim; i++) {
-            Rng r(seed, 0x4B534B0000000000ull + i);
-            for (uint32_t it = 0; it < p.ks_level; it++) {
-                const uint32_t level = p.ks_level - it;
-                const uint64_t pt = glwe_sk[i] << (64 - p.ks_base_log * level);
-                lwe_encrypt(small_sk.data(), p.n, pt, p.lwe_std, r, ksk + (i * p.ks_level + it) * osz);
+            Rng r(seed, stream_base + i);
+            for (uint32_t it = 0; it < level; it++) {
+                const uint64_t pt = in_sk[i] << (64 - base_log * (level - it));
+                lwe_encrypt(out_sk, out_dim, pt, std_dev, r, ksk + (i * level + it) * (out_dim + 1));
             }
         }
+    }
+    void gen_ksk(uint64_t* ksk) const {
+        gen_lwe_ksk(glwe_sk.data(), glwe_sk.size(), small_sk.data(), p.n, p.ks_base_log, p.ks_level, p.lwe_std, seed, 0x4B534B0000000000ull, ksk);
     }
     // glwe_encryption.rs:17-60 with a binary key: body += e + sum_q A_q * S_q (signed shifts)
     void glwe_encrypt_assign(uint64_t* glwe, Rng& r) const {
@@ -505,6 +509,65 @@ int fhe_packing_unpack_noise(const fhe_params_t* params, const fhe_packing_param
     out[0] = out[1] = 0;
     if (fhe::packing_params_check(*params, *pp)) return 1;
     fhe::packing_unpack_noise(*params, *pp, out);
+    return 0;
+}
+
+// ---- casting keys (cast.h, cast.cpp) ------------------------------------------------------------------------------------
+static int cast_answer(const std::string& why) { return why.empty() ? 0 : fhe::fail(why); }
+
+int fhe_cast_default_params(const fhe_params_t* src, const fhe_params_t* dst, uint32_t target, fhe_cast_params_t* cp) {
+    if (!src || !dst || !cp) return fhe::fail("null pointer");
+    return cast_answer(fhe::cast_default_params(*src, *dst, target, cp));
+}
+
+size_t fhe_cast_key_len(const fhe_params_t* dst, const fhe_cast_params_t* cp) {
+    if (!dst || !cp || cast_answer(fhe::cast_params_check(*dst, *cp))) return 0;
+    return (size_t)fhe::cast_key_words(*dst, *cp);
+}
+
+int fhe_cast_rshift(const fhe_params_t* src, const fhe_params_t* dst, int32_t* shift) {
+    if (!src || !dst || !shift) return fhe::fail("null pointer");
+    *shift = 0;
+    return cast_answer(fhe::cast_rshift(*src, *dst, shift));
+}
+
+int fhe_cast_regroup_check(const fhe_params_t* src, const fhe_params_t* dst, uint32_t group, uint64_t* degree, uint64_t* space) {
+    if (!src || !dst || !degree || !space) return fhe::fail("null pointer");
+    *degree = *space = 0;
+    return cast_answer(fhe::cast_regroup_check(*src, *dst, group, degree, space));
+}
+
+int fhe_client_gen_cast_key(fhe_client_key* ck_src, fhe_client_key* ck_dst, const fhe_cast_params_t* cp, const uint8_t seed[32], uint64_t* out) {
+    if (!ck_src || !ck_dst || !cp || !seed || !out) return fhe::fail("null pointer");
+    try {
+        const auto &s = *ck_src->impl, &d = *ck_dst->impl;
+        if (cast_answer(fhe::cast_params_check(d.p, *cp))) return 1;
+        if (s.p.k != cp->src.k || s.p.N != cp->src.N) return fhe::fail("casting key: the source client key is not of the source parameter set");
+        const bool small = cp->target == FHE_CAST_TO_SMALL;
+        fhe::ClientKey::gen_lwe_ksk(s.glwe_sk.data(), s.glwe_sk.size(), small ? d.small_sk.data() : d.glwe_sk.data(), fhe::cast_out_dim(d.p, *cp), cp->base_log,
+                                    cp->level, d.p.lwe_std, fhe::seed_from_bytes(seed), 0x43534B0000000000ull, out);
+    } catch (const std::exception& e) {
+        return fhe::fail(e.what());
+    }
+    return 0;
+}
+
+int fhe_cast_host(const fhe_params_t* dst, const fhe_cast_params_t* cp, const uint64_t* key, const uint64_t* in, uint32_t count, uint64_t* out) {
+    if (!dst || !cp || !key || (count && (!in || !out))) return fhe::fail("null pointer");
+    try {
+        if (cast_answer(fhe::cast_params_check(*dst, *cp))) return 1;
+        fhe::cast_keyswitch_host(*dst, *cp, key, in, count, out);
+    } catch (const std::exception& e) {
+        return fhe::fail(e.what());
+    }
+    return 0;
+}
+
+int fhe_cast_noise(const fhe_params_t* dst, const fhe_cast_params_t* cp, double v_in, double out[3]) {
+    if (!dst || !cp || !out) return fhe::fail("null pointer");
+    out[0] = out[1] = out[2] = 0;
+    if (cast_answer(fhe::cast_params_check(*dst, *cp))) return 1;
+    fhe::cast_noise(*dst, *cp, v_in, out);
     return 0;
 }
 

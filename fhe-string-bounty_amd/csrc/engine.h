@@ -1,6 +1,6 @@
 // engine.h -- internal C++ interface of the engine (the public surface is include/fhestr.h).  Engine's members are defined in
 // engine.hip, and in blind_rotate.hip where they need a blind-rotation kernel; Packing's in packing_dev.hip, Transcipher's
-// in transcipher_dev.hip.
+// in transcipher_dev.hip, CastKey's in cast_dev.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -131,11 +131,13 @@ struct Packing {
     int load_key(const fhe_packing_params_t& pp, const uint64_t* pksk);
     int pack_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_glwes);
     int pack_host(const uint64_t* cts, uint32_t count, uint64_t* glwes);
+    int extract_dev(const char* who, uint32_t k, uint32_t N, const uint64_t* d_glwes, uint32_t first, uint32_t count, uint64_t* d_cts, uint32_t* chunks = nullptr);
     int unpack_dev(const uint64_t* d_glwes, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts);
     int unpack_host(const uint64_t* glwes, uint32_t first, uint32_t count, int refresh, uint64_t* cts);
     int narrow_dev(const uint64_t* d_glwes, uint32_t held, uint32_t bits, uint64_t* d_narrow);
     int narrow_host(const uint64_t* glwes, uint32_t held, uint32_t bits, uint64_t* narrow);
     int widen_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint64_t* d_glwes);
+    int widen_shape_dev(const char* who, uint32_t k, uint32_t N, const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint64_t* d_glwes);
     int unpack_narrow_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int refresh, uint64_t* d_cts);
     int unpack_narrow_host(const uint64_t* narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int refresh, uint64_t* cts);
 
@@ -184,6 +186,46 @@ struct Transcipher {
     int begin(const uint8_t* ivs_host, uint32_t streams);
     int next(const uint8_t* data_host, uint32_t n_bytes, int refresh, uint64_t* out_host, uint64_t* d_out);
     int run_round(uint32_t rows, uint32_t n_bytes, uint32_t m, uint64_t* d_blocks);
+    void info(uint32_t out[8]) const;
+};
+
+// Casting keys (cast.h, cast_kernels.hip.h; members in cast_dev.hip): one resident key from a source client's big key to
+// this engine's big or small key, in the matrix-core keyswitch's digit planes, with the buffers of its casts -- the
+// digit fragments, the keyswitched rows, the bodies gathered from packed GLWEs, the staging of the host forms.  An engine
+// serves many source clients: owned by its engine (Engine::cast_keys), every launch on the engine's stream.
+struct CastKey {
+    Engine* e = nullptr;
+    fhe_cast_params_t cp{};
+    int32_t shift = 0;                  // cast_rshift
+    uint32_t in_dim = 0, out_size = 0;  // source k N; out_dim + 1 words of a keyswitched row
+    DeviceBuffer<int8_t> key;           // B-fragment planes
+    DeviceBuffer<int8_t> digits;        // A fragments; same reuse rules as PipeLane::digits
+    DeviceBuffer<uint64_t> rows;        // the keyswitched rows, then the regrouped ones behind them
+    DeviceBuffer<uint64_t> bodies;      // B[j_b] of a packed batch, one word per block: what the product reads as bodies
+    DeviceBuffer<uint64_t> lwes;        // the extracted rows of a packed batch when the fused digit kernel is off
+    DeviceBuffer<uint64_t> glwes;       // a narrow list widened to the source's full GLWEs (cast_narrow_dev)
+    DeviceBuffer<uint32_t> idx;         // the follow-up table's index, once per row of the largest cast so far
+    DeviceBuffer<unsigned char> meta;   // regrouping: offsets, sources, weights, constants of lincomb_kernel
+    DeviceBuffer<uint64_t> in, out;     // staging of the host forms
+    bool fused = true;                  // packed inputs through cast_decompose_glwe_kernel
+    uint32_t group = 1;                 // source blocks per destination block (fhe_cast_key_set_group)
+    uint32_t meta_count = 0;            // the batch `meta` was written for
+    uint32_t lut = 0;                   // the follow-up table's id on the engine, once uploaded
+    bool lut_ready = false;
+    uint32_t last = 0;                  // fhe_cast_key_info[7]
+    double v_in = 1.0;                  // what the source blocks are declared to carry, in the source's nominal units (gate)
+
+    static int create(Engine& e, const fhe_cast_params_t& cp, const uint64_t* key, CastKey** out);
+    int set_group(uint32_t group);
+    int gate(const char* who) const;    // the follow-up lookup's input against the PBS-input budget (cast_noise)
+    int keyswitch_dev(const uint64_t* d_src, uint32_t first, uint32_t count, bool packed, uint64_t* d_rows);
+    int cast_dev(const uint64_t* d_src, uint32_t first, uint32_t count, bool packed, int mode, uint64_t* d_out);
+    int cast_host(const uint64_t* src, uint32_t first, uint32_t count, bool packed, int mode, uint64_t* out);
+    // blocks first .. first + count - 1 of the source's narrow list of `held` blocks: widened on the device (glwe_widen_kernel at
+    // the source's shape), then cast as packed GLWEs
+    int cast_narrow_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int mode, uint64_t* d_out);
+    int cast_narrow_host(const uint64_t* narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count, int mode, uint64_t* out);
+    int digits_host(const uint64_t* src, uint32_t first, uint32_t count, bool packed, int8_t* out, size_t* bytes);
     void info(uint32_t out[8]) const;
 };
 
@@ -250,6 +292,7 @@ struct Engine {
     Packing packing;                    // the packed-ciphertext family: pack, unpack, narrow (packing_dev.hip)
     DeviceBuffer<uint32_t> refresh_idx; // refresh_rows_dev's table indices: the identity table's id, once per row of the largest refresh so far
     std::vector<std::unique_ptr<Transcipher>> transciphers;   // fhe_transcipher_create .. fhe_transcipher_destroy, or the engine's end
+    std::vector<std::unique_ptr<CastKey>> cast_keys;          // fhe_cast_key_create .. fhe_cast_key_destroy, or the engine's end
 
     static int create(const fhe_params_t& p, int device, Engine** out);
     ~Engine();
@@ -291,6 +334,9 @@ struct Engine {
     int pbs_ks_host(const uint64_t* in_small, const uint32_t* lut_idx, uint64_t* out_small, uint32_t count);
     int lincomb_dev(const uint64_t* d_pool, const uint32_t* d_off, const uint32_t* d_src,
                     const int32_t* d_coeff, const uint64_t* d_cst, uint64_t* d_out, uint32_t jobs);
+    // the same on rows of any length (the casting keys combine keyswitched rows, small ones too)
+    int lincomb_rows_dev(const uint64_t* d_pool, const uint32_t* d_off, const uint32_t* d_src, const int32_t* d_coeff, const uint64_t* d_cst,
+                         uint64_t* d_out, uint32_t jobs, uint32_t row_words);
     // `instances` copies of a plan level at once (lincomb_batch_kernel); strides in ciphertext rows
     int lincomb_batch_dev(const uint64_t* d_pool, const uint32_t* d_off, const uint32_t* d_src, const int32_t* d_coeff,
                           const uint64_t* d_cst, uint64_t* d_out, uint32_t jobs, uint32_t instances, uint32_t src_slot, uint32_t src_inst,

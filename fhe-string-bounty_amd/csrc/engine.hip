@@ -85,6 +85,7 @@ Engine::~Engine() {
     (void)hipSetDevice(device);
     if (stream) (void)sync_all_streams();
     transciphers.clear();
+    cast_keys.clear();
     for (auto& e : ring) if (e) (void)hipEventDestroy(e);
     pipe.destroy();
     if (own_stream) (void)hipStreamDestroy(own_stream);
@@ -371,17 +372,29 @@ KsMfmaLaunch ks_mfma_plan(const KsMfmaGeom& g, uint32_t count, uint32_t base_log
     l.chunks = (g.steps + l.spc - 1) / l.spc;
     return l;
 }
-int ks_mfma_digits(Engine& e, DeviceBuffer<int8_t>& digits, const KsMfmaLaunch& l, const KsMfmaGeom& g, const uint64_t* d_lwes, uint32_t count, hipStream_t s) {
+int ks_mfma_reserve_digits(Engine& e, DeviceBuffer<int8_t>& digits, const KsMfmaLaunch& l, hipStream_t s) {
     if (digits.bytes < l.digit_bytes) {
         if (e.reserve_idle(digits, l.digit_bytes)) return 1;
         HIP_TRY(hipMemsetAsync(digits, 0, l.digit_bytes, s));
     }
+    return 0;
+}
+int ks_mfma_digits(Engine& e, DeviceBuffer<int8_t>& digits, const KsMfmaLaunch& l, const KsMfmaGeom& g, const uint64_t* d_lwes, uint32_t count, hipStream_t s) {
+    if (ks_mfma_reserve_digits(e, digits, l, s)) return 1;
     KsDecomposeArgs da{d_lwes, digits, g, count};
     hipLaunchKernelGGL(ks_decompose_kernel, dim3((2 * g.steps + 255) / 256, count), dim3(256), 0, s, da);
     return 0;
 }
 void ks_mfma_repack(const uint64_t* d_std, int8_t* planes, const KsMfmaGeom& g, hipStream_t s) {
     hipLaunchKernelGGL(ksk_repack_mfma_kernel, dim3(g.col_groups, g.steps), dim3(64), 0, s, d_std, planes, g);
+}
+void ks_mfma_product(const KsMfmaArgs& ma, const KsMfmaLaunch& l, hipStream_t s) {
+    switch (l.mt) {
+        case 1: hipLaunchKernelGGL(keyswitch_mfma_kernel<1>, l.grid(ma.g), dim3(64), 0, s, ma); break;
+        case 2: hipLaunchKernelGGL(keyswitch_mfma_kernel<2>, l.grid(ma.g), dim3(128), 0, s, ma); break;
+        case 4: hipLaunchKernelGGL(keyswitch_mfma_kernel<4>, l.grid(ma.g), dim3(256), 0, s, ma); break;
+        default: hipLaunchKernelGGL(keyswitch_mfma_kernel<8>, l.grid(ma.g), dim3(512), 0, s, ma); break;
+    }
 }
 
 int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t count, DeviceBuffer<int8_t>& digits, hipStream_t on, bool shadow) {
@@ -395,13 +408,7 @@ int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t cou
         const KsMfmaGeom g = ks_mfma_geom(in_dim, out_size, p.ks_level, p.ks_base_log);
         const KsMfmaLaunch l = ks_mfma_plan(g, count, p.ks_base_log, cu_count, cfg.ks_chunks_override);
         if (ks_mfma_digits(*this, digits, l, g, d_big, count, s)) return 1;
-        KsMfmaArgs ma{d_big, d_ksk_mfma, digits, d_sm, g, count, l.row_tiles, l.spc};
-        switch (l.mt) {
-            case 1: hipLaunchKernelGGL(keyswitch_mfma_kernel<1>, l.grid(g), dim3(64), 0, s, ma); break;
-            case 2: hipLaunchKernelGGL(keyswitch_mfma_kernel<2>, l.grid(g), dim3(128), 0, s, ma); break;
-            case 4: hipLaunchKernelGGL(keyswitch_mfma_kernel<4>, l.grid(g), dim3(256), 0, s, ma); break;
-            default: hipLaunchKernelGGL(keyswitch_mfma_kernel<8>, l.grid(g), dim3(512), 0, s, ma); break;
-        }
+        ks_mfma_product(KsMfmaArgs{d_big + in_dim, in_dim + 1, d_ksk_mfma, digits, d_sm, g, count, l.row_tiles, l.spc}, l, s);
         l.info(ks_last, FHE_KS_KERNEL_MFMA, g);
         HIP_TRY(hipGetLastError());
         return 0;
@@ -632,8 +639,13 @@ int Engine::pbs_ks_host(const uint64_t* in_small, const uint32_t* lut_idx, uint6
 
 int Engine::lincomb_dev(const uint64_t* d_pool_, const uint32_t* d_off, const uint32_t* d_src,
                         const int32_t* d_coeff, const uint64_t* d_cst, uint64_t* d_o, uint32_t jobs) {
+    return lincomb_rows_dev(d_pool_, d_off, d_src, d_coeff, d_cst, d_o, jobs, p.k * p.N + 1);
+}
+
+int Engine::lincomb_rows_dev(const uint64_t* d_pool_, const uint32_t* d_off, const uint32_t* d_src, const int32_t* d_coeff, const uint64_t* d_cst,
+                             uint64_t* d_o, uint32_t jobs, uint32_t row_words) {
     if (jobs == 0) return 0;
-    LincombArgs a{d_pool_, d_off, d_src, d_coeff, d_cst, d_o, p.k * p.N + 1, jobs};
+    LincombArgs a{d_pool_, d_off, d_src, d_coeff, d_cst, d_o, row_words, jobs};
     hipLaunchKernelGGL(lincomb_kernel, dim3(jobs), dim3(256), 0, stream, a);
     HIP_TRY(hipGetLastError());
     return 0;

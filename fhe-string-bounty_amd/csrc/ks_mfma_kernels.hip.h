@@ -18,7 +18,8 @@
 // their levels (digits of one element are produced together), the remaining slots are zero digits.
 //   key   [column group][step][plane][lane][16] int8   exactly the B fragments, 8 KB per (group, step): one coalesced
 //                                                       16-byte load per thread, staged through LDS for the waves
-//   digits[row tile][step][lane][16] int8              exactly the A fragments, written by ks_decompose_kernel
+//   digits[row tile][step][lane][16] int8              exactly the A fragments, written by ks_decompose_kernel (from packed
+//                                                       GLWEs: cast_decompose_glwe_kernel, cast_kernels.hip.h)
 // K is split over workgroups (grid.z) so that the launch fills the GPU; partial sums meet in 64-bit integer atomics
 // (wrapping addition is associative and commutative: deterministic, bit-exact).
 // This header holds the geometry, the argument structs and the product kernel (a template: instantiated where it is launched).
@@ -62,7 +63,8 @@ struct KsDecomposeArgs {
 };
 
 struct KsMfmaArgs {
-    const uint64_t* lwe_in;     // bodies are added here
+    const uint64_t* bodies;     // sample b's body is bodies[b * body_stride], added to column out_size - 1: lwe_in + in_dim with
+    uint32_t body_stride;       // stride in_dim + 1 for LWE rows; a dense array with stride 1 where no row exists (cast_kernels.hip.h)
     const int8_t* key;          // ksk_repack_mfma_kernel output
     const int8_t* digits;       // ks_decompose_kernel output
     uint64_t* lwe_out;          // [batch][out_size], zero-filled before the launch
@@ -140,7 +142,7 @@ __global__ void __launch_bounds__(64 * MT) keyswitch_mfma_kernel(KsMfmaArgs a) {
 #pragma unroll
         for (int t = 0; t < 8; t++) p += (uint64_t)(int64_t)acc[t][r] << (8 * t);
         uint64_t v = 0 - p;
-        if (blockIdx.z == 0 && col == a.g.out_size - 1) v += a.lwe_in[(size_t)b * (a.g.in_dim + 1) + a.g.in_dim];   // body (:146)
+        if (blockIdx.z == 0 && col == a.g.out_size - 1) v += a.bodies[(size_t)b * a.body_stride];   // body (:146)
         atomicAdd(reinterpret_cast<unsigned long long*>(a.lwe_out + (size_t)b * a.g.out_size + col), (unsigned long long)v);
     }
 }

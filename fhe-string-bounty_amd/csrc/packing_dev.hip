@@ -137,6 +137,19 @@ int Packing::pack_host(const uint64_t* cts, uint32_t count, uint64_t* glwes) {
 }
 
 // ---- packed inputs (glwe_extract_kernels.hip.h) -----------------------------------------------------------------------
+// The extraction launch alone, at any GLWE shape (k, N), N a power of two: the engine's own set for unpack_dev, a source
+// client's for a cast with the fused digit kernel off (CastKey::keyswitch_dev).  On the engine's stream.
+int Packing::extract_dev(const char* who, uint32_t k, uint32_t N, const uint64_t* d_glwes, uint32_t first, uint32_t count, uint64_t* d_cts, uint32_t* chunks_out) {
+    fhe_params_t shape = e->p;
+    shape.k = k; shape.N = N;
+    uint32_t chunks;
+    if (extract_chunks(shape, who, count, &chunks)) return 1;
+    hipLaunchKernelGGL(glwe_sample_extract_kernel, dim3(count * chunks), dim3(256), 0, e->stream, d_glwes, d_cts, N, k * N, first, count, chunks);
+    HIP_TRY(hipGetLastError());
+    if (chunks_out) *chunks_out = chunks;
+    return 0;
+}
+
 // Blocks first .. first + count - 1 of the packed GLWEs at d_glwes (block j = coefficient j % N of GLWE j / N, the layout
 // pack_dev writes) -> count big-key LWEs at d_cts.  Ordered on the engine's stream, nothing synchronises -- except,
 // like pack_dev, in the throughput modes, and once per engine when the first refresh uploads the identity table.
@@ -151,10 +164,8 @@ int Packing::unpack_dev(const uint64_t* d_glwes, uint32_t first, uint32_t count,
     if (refresh && refresh_gate(*this, "unpack_glwes", 0)) return 1;
     if (e->leave_pipelined_run()) return 1;                 // pipelined calls may still read or write these buffers on other streams
     uint32_t chunks;
-    if (extract_chunks(p, "unpack_glwes", count, &chunks)) return 1;
-    hipLaunchKernelGGL(glwe_sample_extract_kernel, dim3(count * chunks), dim3(256), 0, e->stream, d_glwes, d_cts, p.N, p.k * p.N, first, count, chunks);
+    if (extract_dev("unpack_glwes", p.k, p.N, d_glwes, first, count, d_cts, &chunks)) return 1;
     unpack_last[0] = 1; unpack_last[1] = count; unpack_last[2] = count * chunks; unpack_last[3] = 0;
-    HIP_TRY(hipGetLastError());
     if (!refresh) return 0;
     if (e->refresh_rows_dev(d_cts, count)) return 1;
     unpack_last[3] = 1;
@@ -172,15 +183,19 @@ int Packing::unpack_host(const uint64_t* glwes, uint32_t first, uint32_t count, 
 }
 
 // ---- narrow packed results (glwe_narrow.h, glwe_narrow_kernels.hip.h) -------------------------------------------------
-// Both layout changes, one thread per word written: glwe_narrow_kernel (`words` of the list) or glwe_widen_kernel (of the GLWEs).
-static int relayout(Packing& pk, const char* who, uint32_t kernel, const uint64_t* d_src, uint64_t* d_dst, uint32_t held, uint32_t bits, uint64_t words) {
+// Both layout changes, one thread per word written: glwe_narrow_kernel (`words` of the list) or glwe_widen_kernel (of the
+// GLWEs), at the GLWE shape (k, N): the engine's own, or a source client's for a cast (CastKey::cast_narrow_dev).
+static int relayout(Packing& pk, const char* who, uint32_t kernel, uint32_t k, uint32_t N, const uint64_t* d_src, uint64_t* d_dst, uint32_t held, uint32_t bits,
+                    uint64_t words) {
     Engine& e = *pk.e;
     if (e.leave_pipelined_run()) return 1;
     const uint64_t wgs = (words + 255) / 256;
-    uint32_t stride;
-    if (narrow_launch(pk, who, kernel, bits, words, wgs, &stride)) return 1;
+    if (wgs > 0x7FFFFFFFull) return fail(std::string(who) + ": too many blocks for one launch");
+    const uint32_t stride = (uint32_t)narrow_stream_words((size_t)(k + 1) * N, bits);
+    const uint32_t last[5] = {1, kernel, (uint32_t)words, (uint32_t)wgs, bits};
+    std::copy(last, last + 5, pk.narrow_last);
     hipLaunchKernelGGL(kernel == FHE_NARROW_KERNEL_NARROW ? glwe_narrow_kernel : glwe_widen_kernel, dim3((uint32_t)wgs), dim3(256), 0, e.stream, d_src, d_dst,
-                       e.p.N, e.p.k * e.p.N, held, bits, stride, words);
+                       N, k * N, held, bits, stride, words);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -191,16 +206,20 @@ int Packing::narrow_dev(const uint64_t* d_glwes, uint32_t held, uint32_t bits, u
     if (e->use()) return 1;
     const uint64_t words = narrow_len(e->p.N, e->p.k, held, bits);
     if (!words) return held ? fail("narrow_glwes: the width must be 8 .. 32 bits and the polynomial size a power of two") : 0;
-    return relayout(*this, "narrow_glwes", FHE_NARROW_KERNEL_NARROW, d_glwes, d_narrow, held, bits, words);
+    return relayout(*this, "narrow_glwes", FHE_NARROW_KERNEL_NARROW, e->p.k, e->p.N, d_glwes, d_narrow, held, bits, words);
 }
 
 // The inverse layout change on the device: the narrow list at d_narrow -> ceil(held / N) full GLWEs at d_glwes, what
 // unpack_dev reads.  Same contract.
 int Packing::widen_dev(const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint64_t* d_glwes) {
+    return widen_shape_dev("widen_narrow", e->p.k, e->p.N, d_narrow, held, bits, d_glwes);
+}
+
+// The same at any GLWE shape (k, N): a source client's narrow list on the destination's engine.
+int Packing::widen_shape_dev(const char* who, uint32_t k, uint32_t N, const uint64_t* d_narrow, uint32_t held, uint32_t bits, uint64_t* d_glwes) {
     if (e->use()) return 1;
-    const fhe_params_t& p = e->p;
-    if (!narrow_len(p.N, p.k, held, bits)) return held ? fail("widen_narrow: the width must be 8 .. 32 bits and the polynomial size a power of two") : 0;
-    return relayout(*this, "widen_narrow", FHE_NARROW_KERNEL_WIDEN, d_narrow, d_glwes, held, bits, (((uint64_t)held + p.N - 1) / p.N) * ((uint64_t)(p.k + 1) * p.N));
+    if (!narrow_len(N, k, held, bits)) return held ? fail(std::string(who) + ": the width must be 8 .. 32 bits and the polynomial size a power of two") : 0;
+    return relayout(*this, who, FHE_NARROW_KERNEL_WIDEN, k, N, d_narrow, d_glwes, held, bits, (((uint64_t)held + N - 1) / N) * ((uint64_t)(k + 1) * N));
 }
 
 int Packing::narrow_host(const uint64_t* glwes, uint32_t held, uint32_t bits, uint64_t* narrow) {

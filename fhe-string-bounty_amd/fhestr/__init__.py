@@ -6,6 +6,7 @@ library or a GPU is missing every call fails loudly -- there is no CPU fallback 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import functools
 import os
@@ -126,6 +127,14 @@ class _PackingParams(C.Structure):
     _fields_ = [("base_log", C.c_uint32), ("level", C.c_uint32)]
 
 
+class _CastParams(C.Structure):
+    _fields_ = [("src", _Params), ("base_log", C.c_uint32), ("level", C.c_uint32), ("target", C.c_uint32)]
+
+
+CAST_TO_BIG, CAST_TO_SMALL = 0, 1                      # fhe_cast_params_t.target
+CAST_RAW, CAST_REFRESH, CAST_KEYSWITCHED = 0, 1, 2     # the mode of a cast
+
+
 _lib = None
 
 EXPORTS = [
@@ -182,6 +191,10 @@ EXPORTS = [
     "fhe_transcipher_init_host", "fhe_transcipher_gather_host", "fhe_transcipher_apply_host", "fhe_engine_transcipher_init",
     "fhe_engine_transcipher_gather", "fhe_engine_transcipher_apply", "fhe_transcipher_create", "fhe_transcipher_destroy",
     "fhe_transcipher_begin", "fhe_transcipher_next", "fhe_transcipher_info", "fhe_transcipher_timing",
+    "fhe_cast_default_params", "fhe_cast_key_len", "fhe_cast_rshift", "fhe_client_gen_cast_key", "fhe_cast_host", "fhe_cast_noise",
+    "fhe_cast_key_create", "fhe_cast_key_destroy", "fhe_cast_key_info", "fhe_cast_key_set_fused", "fhe_cast_key_set_group", "fhe_cast_key_set_input_noise",
+    "fhe_cast_lwes", "fhe_cast_lwes_dev", "fhe_cast_packed", "fhe_cast_packed_dev", "fhe_cast_narrow", "fhe_cast_narrow_dev",
+    "fhe_cast_regroup_check", "fhe_cast_debug_digits",
 ] + [f"fhe_str_{n}{s}" for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat")
      for s in ("", "_clear")] + ["fhe_str_repeat_clear", "fhe_str_split", "fhe_str_replacen", "fhe_str_replacen_clear",
                                    "fhe_str_repeat", "fhe_str_replacen_encn", "fhe_str_replacen_encn_clear", "fhe_str_splitn_encn",
@@ -419,6 +432,28 @@ def lib() -> C.CDLL:
     sig("fhe_transcipher_next", vp, vp, u32, i32, vp, vp)
     sig("fhe_transcipher_info", vp, C.POINTER(u32))
     sig("fhe_transcipher_timing", vp, i32, C.POINTER(C.c_double), C.POINTER(u32))
+    CP = C.POINTER(_CastParams)
+    sig("fhe_cast_default_params", PP, PP, u32, CP)
+    L.fhe_cast_key_len.restype = C.c_size_t
+    L.fhe_cast_key_len.argtypes = [PP, CP]
+    sig("fhe_cast_rshift", PP, PP, C.POINTER(C.c_int32))
+    sig("fhe_client_gen_cast_key", vp, vp, CP, vp, vp)
+    sig("fhe_cast_host", PP, CP, vp, vp, u32, vp)
+    sig("fhe_cast_noise", PP, CP, C.c_double, C.POINTER(C.c_double))
+    sig("fhe_cast_key_create", vp, CP, vp, C.POINTER(vp))
+    sig("fhe_cast_key_destroy", vp)
+    sig("fhe_cast_key_info", vp, C.POINTER(u32))
+    sig("fhe_cast_key_set_fused", vp, i32)
+    sig("fhe_cast_key_set_group", vp, u32)
+    sig("fhe_cast_key_set_input_noise", vp, C.c_double)
+    sig("fhe_cast_lwes", vp, vp, u32, i32, vp)
+    sig("fhe_cast_lwes_dev", vp, vp, u32, i32, vp)
+    sig("fhe_cast_packed", vp, vp, u32, u32, i32, vp)
+    sig("fhe_cast_packed_dev", vp, vp, u32, u32, i32, vp)
+    sig("fhe_cast_narrow", vp, vp, u32, u32, u32, u32, i32, vp)
+    sig("fhe_cast_narrow_dev", vp, vp, u32, u32, u32, u32, i32, vp)
+    sig("fhe_cast_regroup_check", PP, PP, u32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
+    sig("fhe_cast_debug_digits", vp, vp, u32, u32, i32, vp, C.POINTER(C.c_size_t))
     for name in ("fhe_params_ksk_len", "fhe_params_bsk_len"):
         getattr(L, name).restype = C.c_size_t
         getattr(L, name).argtypes = [PP]
@@ -891,6 +926,22 @@ class Engine:
         of ClientKey.encrypt_stream_key, (L, kN+1) in spec order; up to max_streams strings run in lockstep."""
         return Transcipher(self, cipher, key_cts, max_streams)
 
+    def cast_key(self, cp: "CastParams", key) -> "CastKey":
+        """A source client's casting key made resident on this (the destination's) engine (fhe_cast_key_create): the
+        CastKey that FheStringOps.cast and CastKey.cast take blocks of that client through.  An engine holds any number."""
+        return CastKey(self, cp, key)
+
+    def cast_prepare(self, blocks, shift: int) -> np.ndarray:
+        """On the SOURCE client's engine, before a cast to a set with fewer bits per block (cast_rshift = shift < 0): one
+        keyswitch + PBS with the table x -> (x << -shift) % (msg_mod * carry_mod), the reference's first half of that cast
+        (key_switching_key/mod.rs:128-140).  The destination cannot tell blocks that skipped this step."""
+        if shift >= 0:
+            raise FheError(f"cast_prepare: only a cast to fewer bits (a negative shift) needs the source's server key, got {shift}")
+        M = self.params.msg_mod * self.params.carry_mod
+        lut_id, _ = self.generate_lookup_table(lambda x: (x << -shift) % M)
+        blocks = _u64(blocks).reshape(-1, self.params.big_size)
+        return self.apply_lookup_table(blocks, np.full(blocks.shape[0], lut_id, dtype=np.uint32))
+
     def transcipher_init(self, cipher, streams: int, key, ivs, ring=None) -> np.ndarray:
         """transcipher_init_host through transcipher_init_kernel."""
         ring = np.zeros(transcipher_ring_len(self.params, streams), dtype=np.uint64) if ring is None else _u64(ring).reshape(-1).copy()
@@ -1316,6 +1367,18 @@ class ClientKey:
         _check(lib().fhe_client_gen_ring_packing_key(self._h, C.byref(_pp(pair)), sb, _ptr(key), threads or min(16, os.cpu_count() or 1)))
         return pair, key
 
+    def gen_cast_key(self, dst_ck: "ClientKey", target: int = CAST_TO_SMALL, pair=None, seed=0):
+        """The key that takes THIS client's blocks to dst_ck's engine (fhe_client_gen_cast_key; shortint::KeySwitchingKey):
+        returns (CastParams, words) for Engine.cast_key on the destination's engine.  target: CAST_TO_BIG, the
+        reference's form with the default pair (1, 15), or CAST_TO_SMALL, to the destination's small key with its own
+        keyswitch pair.  pair=(base_log, level) overrides the default."""
+        cp = cast_default_params(self.params, dst_ck.params, target, pair)
+        n = cast_key_len(dst_ck.params, cp)
+        key = np.zeros(n, dtype=np.uint64)
+        sb = (C.c_uint8 * 32)(*seed_bytes(seed))
+        _check(lib().fhe_client_gen_cast_key(self._h, dst_ck._h, C.byref(cp.c()), sb, _ptr(key)))
+        return cp, key
+
     def decrypt_packed(self, glwes, count: int) -> np.ndarray:
         """message-and-carry value of the first `count` coefficients of packed results (Engine.pack)."""
         glwes = _u64(glwes).reshape(-1)
@@ -1345,6 +1408,216 @@ class ClientKey:
         s = np.zeros(p.n, dtype=np.uint64)
         _check(lib().fhe_client_secret_keys(self._h, _ptr(g), _ptr(s)))
         return g, s
+
+
+@dataclass(frozen=True)
+class CastParams:
+    """fhe_cast_params_t: the source client's parameter set, the cast key's decomposition and its target."""
+    src: Params
+    base_log: int
+    level: int
+    target: int
+
+    def c(self) -> _CastParams:
+        return _CastParams(self.src.c(), int(self.base_log), int(self.level), int(self.target))
+
+
+def cast_default_params(src: Params, dst: Params, target: int = CAST_TO_SMALL, pair=None) -> CastParams:
+    """The casting key's parameters from src to dst (fhe_cast_default_params): (1, 15) for CAST_TO_BIG, the destination's
+    own keyswitch pair for CAST_TO_SMALL, or `pair`.  Raises with the reason for a refused combination."""
+    out = _CastParams()
+    if pair is None:
+        _check(lib().fhe_cast_default_params(C.byref(src.c()), C.byref(dst.c()), int(target), C.byref(out)))
+        return CastParams(src, int(out.base_log), int(out.level), int(target))
+    cp = CastParams(src, int(pair[0]), int(pair[1]), int(target))
+    cast_key_len(dst, cp)
+    return cp
+
+
+def cast_key_len(dst: Params, cp: CastParams) -> int:
+    """u64 words of the casting key (fhe_cast_key_len); raises with the reason when the parameters are refused."""
+    n = int(lib().fhe_cast_key_len(C.byref(dst.c()), C.byref(cp.c())))
+    if not n:
+        raise FheError(lib().fhe_last_error().decode())
+    return n
+
+
+def cast_rshift(src: Params, dst: Params) -> int:
+    """log2 of dst's msg_mod * carry_mod minus log2 of src's (fhe_cast_rshift; key_switching_key/mod.rs:62-80)."""
+    out = C.c_int32()
+    _check(lib().fhe_cast_rshift(C.byref(src.c()), C.byref(dst.c()), C.byref(out)))
+    return int(out.value)
+
+
+def cast_regroup_check(src: Params, dst: Params, group: int) -> tuple:
+    """(largest lookup input, the destination's msg_mod * carry_mod) of regrouping `group` source blocks into one
+    destination block, (msg_src^group - 1) << cast_rshift (fhe_cast_regroup_check); raises with the reason when refused."""
+    degree, space = C.c_uint64(), C.c_uint64()
+    _check(lib().fhe_cast_regroup_check(C.byref(src.c()), C.byref(dst.c()), int(group), C.byref(degree), C.byref(space)))
+    return int(degree.value), int(space.value)
+
+
+def cast_out_size(dst: Params, cp: CastParams) -> int:
+    """Words of a keyswitched row: the destination's k N + 1 (CAST_TO_BIG) or n + 1 (CAST_TO_SMALL)."""
+    return (dst.n if cp.target == CAST_TO_SMALL else dst.k * dst.N) + 1
+
+
+def cast_host(dst: Params, cp: CastParams, key, cts) -> np.ndarray:
+    """The cast's keyswitch as a plain CPU loop (fhe_cast_host): (count, src kN+1) -> (count, cast_out_size).  Bit-identical
+    to CastKey.cast(..., mode=CAST_KEYSWITCHED)."""
+    cts = _u64(cts).reshape(-1, cp.src.big_size)
+    key = _u64(key).reshape(-1)
+    if key.size != cast_key_len(dst, cp):
+        raise FheError(f"cast_host: {key.size} words are not the casting key of these parameters")
+    out = np.zeros((cts.shape[0], cast_out_size(dst, cp)), dtype=np.uint64)
+    _check(lib().fhe_cast_host(C.byref(dst.c()), C.byref(cp.c()), _ptr(key), _ptr(cts), cts.shape[0], _ptr(out)))
+    return out
+
+
+def cast_noise(dst: Params, cp: CastParams, v_in: float = 1.0) -> tuple:
+    """(what the destination's next lookup sees of a keyswitched block, in its nominal units; its PBS-input budget; the
+    keyswitched block's variance with the torus as unit) for a source block of v_in source-nominal variances: fhe_cast_noise."""
+    a = (C.c_double * 3)()
+    _check(lib().fhe_cast_noise(C.byref(dst.c()), C.byref(cp.c()), float(v_in), a))
+    return float(a[0]), float(a[1]), float(a[2])
+
+
+class CastKey:
+    """One source client's casting key resident on the destination's engine (fhe_cast_key_*; Engine.cast_key).  cast and
+    cast_packed take that client's blocks -- rows, or packed GLWEs as they are stored -- to blocks of the engine's client."""
+
+    def __init__(self, engine: "Engine", cp: CastParams, key):
+        self.engine, self.cp, self.params = engine, cp, engine.params
+        key = _u64(key).reshape(-1)
+        if key.size != cast_key_len(engine.params, cp):
+            raise FheError(f"cast_key: {key.size} words are not the casting key of these parameters")
+        self._h = C.c_void_p()
+        _check(lib().fhe_cast_key_create(engine._h, C.byref(cp.c()), _ptr(key), C.byref(self._h)))
+        self.shift = cast_rshift(cp.src, engine.params)
+        self.group, self.v_in = 1, 1.0
+
+    def close(self):
+        if self._h and self.engine._h:          # the engine owns it: gone with the engine at the latest
+            lib().fhe_cast_key_destroy(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        a = (C.c_uint32 * 8)()
+        _check(lib().fhe_cast_key_info(self._h, a))
+        v = [int(x) for x in a]
+        return {"target": v[0], "base_log": v[1], "level": v[2], "in_dim": v[3], "out_dim": v[4], "shift": v[5] - 64, "fused": bool(v[6]),
+                "last": {0: None, 1: "lwes", 2: "fused", 3: "extract"}[v[7]]}
+
+    def set_fused(self, on: bool):
+        """Packed inputs through cast_decompose_glwe_kernel (default) or through extraction + ks_decompose_kernel."""
+        _check(lib().fhe_cast_key_set_fused(self._h, int(bool(on))))
+
+    def set_group(self, group: int):
+        """`group` source blocks into one destination block (fhe_cast_key_set_group); 1 switches regrouping off."""
+        _check(lib().fhe_cast_key_set_group(self._h, int(group)))
+        self.group = int(group)
+
+    def set_input_noise(self, v_in: float):
+        """Declare what the source blocks carry, in the source's nominal units (fhe_cast_key_set_input_noise): 1 for stored
+        results (the default), 0 for fresh encryptions.  The refusal of a cast that ends in a table judges by it."""
+        _check(lib().fhe_cast_key_set_input_noise(self._h, float(v_in)))
+        self.v_in = float(v_in)
+
+    def _out_shape(self, count, mode, group):
+        if mode == CAST_KEYSWITCHED:
+            return (count, cast_out_size(self.params, self.cp))
+        return (count // group, self.params.big_size)
+
+    @contextlib.contextmanager
+    def _settings(self, group, v_in):
+        """`group` and `v_in` of ONE call: the handle's settings are put back when the call has been enqueued, so a later
+        call on the same key does not inherit them.  None leaves the handle's own setting."""
+        old_group, old_v = self.group, self.v_in
+        try:
+            if group is not None and group != old_group:
+                self.set_group(group)
+            if v_in is not None and v_in != old_v:
+                self.set_input_noise(v_in)
+            yield self.group
+        finally:
+            if self.group != old_group:
+                self.set_group(old_group)
+            if self.v_in != old_v:
+                self.set_input_noise(old_v)
+
+    def cast(self, cts, mode: int = CAST_REFRESH, d_out: int | None = None, count: int | None = None, group: int | None = None,
+             v_in: float | None = None):
+        """Source blocks (count, src kN+1) -> destination blocks (fhe_cast_lwes).  mode: CAST_RAW (the reference's
+        behaviour: no table where the bits per block agree), CAST_REFRESH (the identity table then), CAST_KEYSWITCHED (the
+        keyswitched rows alone).  cts may be a torch device tensor with d_out a device pointer: asynchronous on the
+        engine's stream (fhe_cast_lwes_dev), nothing is returned.  group / v_in: regrouping and declared input noise of
+        this call alone (set_group, set_input_noise)."""
+        with self._settings(group, v_in) as g:
+            if hasattr(cts, "data_ptr"):
+                count = cts.numel() // self.cp.src.big_size if count is None else count
+                _check(lib().fhe_cast_lwes_dev(self._h, C.c_void_p(cts.data_ptr()), count, mode, C.c_void_p(d_out)))
+                return None
+            cts = _u64(cts).reshape(-1, self.cp.src.big_size)
+            out = np.zeros(self._out_shape(cts.shape[0], mode, g), dtype=np.uint64)
+            _check(lib().fhe_cast_lwes(self._h, _ptr(cts), cts.shape[0], mode, _ptr(out)))
+            return out
+
+    def cast_packed(self, glwes, count: int | None = None, first: int = 0, mode: int = CAST_REFRESH, d_out: int | None = None,
+                    group: int | None = None, v_in: float | None = None):
+        """Blocks first .. first + count - 1 of the source's packed GLWEs -> destination blocks (fhe_cast_packed): the
+        digits are taken straight from the GLWEs, the blocks are never unpacked under the old key.  A PackedString brings
+        its count; a torch device tensor with d_out runs asynchronously (fhe_cast_packed_dev).  v_in: what a packed block
+        carries, packing_unpack_noise(source set, source's packing pair)[0] for a packed lookup output."""
+        if count is None:
+            count = getattr(glwes, "count", None)
+        if count is None:
+            raise FheError("cast_packed: a block count is required")
+        with self._settings(group, v_in) as g:
+            if hasattr(glwes, "data_ptr"):
+                _check(lib().fhe_cast_packed_dev(self._h, C.c_void_p(glwes.data_ptr()), first, count, mode, C.c_void_p(d_out)))
+                return None
+            src = self.cp.src
+            glwes = _u64(glwes).reshape(-1)
+            if glwes.size < packed_glwe_len(src, first + count) or glwes.size % src.glwe_len:
+                raise FheError(f"cast_packed: {glwes.size} words do not hold packed block {first + count - 1} of the source parameter set")
+            out = np.zeros(self._out_shape(count, mode, g), dtype=np.uint64)
+            _check(lib().fhe_cast_packed(self._h, _ptr(glwes), first, count, mode, _ptr(out)))
+            return out
+
+    def cast_narrow(self, narrow, held: int | None = None, bits: int | None = None, count: int | None = None, first: int = 0,
+                    mode: int = CAST_REFRESH, d_out: int | None = None, group: int | None = None, v_in: float | None = None):
+        """Blocks first .. first + count - 1 of the source's narrow list -> destination blocks (fhe_cast_narrow): the list
+        goes up as it is stored, is widened on the GPU at the source's shape and cast as packed GLWEs.  A NarrowString
+        brings held and bits; a torch device tensor with d_out runs asynchronously (fhe_cast_narrow_dev).  v_in: what such
+        a block carries, narrow_noise(source set, source's packing pair, bits)[0] for a packed lookup output."""
+        held = getattr(narrow, "count", None) if held is None else held
+        bits = getattr(narrow, "bits", None) if bits is None else bits
+        if held is None or bits is None:
+            raise FheError("cast_narrow: the blocks the list holds and its width are required")
+        count = held - first if count is None else count
+        with self._settings(group, v_in) as g:
+            if hasattr(narrow, "data_ptr"):
+                _check(lib().fhe_cast_narrow_dev(self._h, C.c_void_p(narrow.data_ptr()), held, bits, first, count, mode, C.c_void_p(d_out)))
+                return None
+            words = _narrow_words("cast_narrow", self.cp.src, narrow, held, bits)
+            out = np.zeros(self._out_shape(count, mode, g), dtype=np.uint64)
+            _check(lib().fhe_cast_narrow(self._h, _ptr(words), held, bits, first, count, mode, _ptr(out)))
+            return out
+
+    def digits(self, src, count: int, first: int = 0, packed: bool = False) -> np.ndarray:
+        """The batch's digit fragments as the product reads them (fhe_cast_debug_digits): int8, for tests."""
+        n = C.c_size_t(0)
+        src = _u64(src).reshape(-1)
+        _check(lib().fhe_cast_debug_digits(self._h, None, first, count, int(packed), None, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.int8)
+        _check(lib().fhe_cast_debug_digits(self._h, _ptr(src), first, count, int(packed), _ptr(out), C.byref(n)))
+        return out
 
 
 def _pp(pp) -> _PackingParams:
@@ -2214,6 +2487,44 @@ class FheStringOps:
         out = self._alloc((n_out.value, self.engine.params.big_size))
         _check(lib().fhe_str_op(*args, _ptr(out), C.byref(n_out)))
         return out
+
+    def cast(self, string, cast_key: "CastKey", src_cap: int | None = None, pp=None, v_in: float | None = None):
+        """A string of the SOURCE client of cast_key -- its block array, a PackedString or a NarrowString as stored --
+        as a block array of this engine's client, which every other method takes.  A packed form goes up as it is stored
+        and is cast on the GPU (CastKey.cast_packed; a NarrowString is widened there first, CastKey.cast_narrow).  Where
+        the destination's blocks hold more message bits, consecutive source blocks are regrouped into one for this call
+        (1 -> 2 and 2 -> 4 bits); narrowing a string (to fewer message bits per block) is refused.
+        The cast ends in a lookup and is refused when the noise the blocks are DECLARED to carry puts its input above
+        the budget (cast_noise).  Block arrays are judged as lookup outputs (1 nominal variance of the source's set).  A
+        stored form carries the SOURCE's packing keyswitch on top, and the narrowing's: pass pp, the (base_log, level) the
+        source packed with, and the cast is judged at packing_unpack_noise / narrow_noise of the source's set, the figures
+        the unpack refresh judges by; a packed form without pp (or v_in) is refused.  v_in overrides either.
+        src_cap: the string's capacity in characters, checked when given."""
+        if cast_key.engine is not self.engine:
+            raise FheError("cast: the casting key is resident on another engine than this FheStringOps' one")
+        src, dst = cast_key.cp.src, self.engine.params
+        sb, db = src.msg_mod.bit_length() - 1, dst.msg_mod.bit_length() - 1
+        if db < sb:
+            raise FheError(f"cast: narrowing a string from {sb} to {db} message bits per block is not supported (out of scope: "
+                           "it needs the source's server key per block, Engine.cast_prepare)")
+        if db % sb:
+            raise FheError(f"cast: {sb} message bits per source block do not divide the destination's {db}")
+        group, src_bpc = db // sb, 8 // sb
+        stored = isinstance(string, _PACKED)
+        if not stored:
+            string = _u64(string).reshape(-1, src.big_size)
+        count = string.count if stored else string.shape[0]
+        if count % src_bpc or (src_cap is not None and count != src_cap * src_bpc):
+            raise FheError(f"cast: {count} source blocks are not a string of capacity {src_cap if src_cap is not None else count // src_bpc}")
+        if v_in is None and stored:
+            if pp is None:
+                raise FheError("cast: a packed string carries its packing keyswitch's noise: pass pp, the source's packing pair, or v_in")
+            v_in = narrow_noise(src, pp, string.bits)[0] if isinstance(string, NarrowString) else packing_unpack_noise(src, pp)[0]
+        if isinstance(string, NarrowString):
+            return cast_key.cast_narrow(string, mode=CAST_REFRESH, group=group, v_in=v_in)
+        if stored:
+            return cast_key.cast_packed(string, count, 0, CAST_REFRESH, group=group, v_in=v_in)
+        return cast_key.cast(string, CAST_REFRESH, group=group, v_in=v_in)
 
     def _cap(self, ct):
         if isinstance(ct, _PACKED):

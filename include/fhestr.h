@@ -976,6 +976,111 @@ int fhe_transcipher_info(fhe_transcipher *tc, uint32_t info[8]);
  * since begin.  ms / rounds may be NULL to switch only. */
 int fhe_transcipher_timing(fhe_transcipher *tc, int on, double ms[3], uint32_t *rounds);
 
+/* ---- casting keys: blocks move between clients and between parameter sets ---------------------------
+ * shortint::KeySwitchingKey of the reference (shortint/key_switching_key/mod.rs, parameters/key_switching.rs): an LWE
+ * keyswitch key from the SOURCE client's big LWE key (k N words of cp.src) to a key of the DESTINATION client, whose
+ * engine then serves the source's blocks.  Definition, noise and the host loop: csrc/cast.h, csrc/cast.cpp; the device
+ * side: csrc/cast_dev.hip, csrc/cast_kernels.hip.h.
+ *   FHE_CAST_TO_BIG    the reference's form: to the destination's big key, noise of the destination's lwe_std
+ *                      (new_key_switching_key); default decomposition (1, 15), the constant of
+ *                      PARAM_KEYSWITCH_1_1_KS_PBS_TO_2_2_KS_PBS.  A cast is this keyswitch and, where a table follows
+ *                      (below), one ordinary keyswitch + PBS level.
+ *   FHE_CAST_TO_SMALL  the project's own form: straight to the destination's small key, so that the cast block feeds
+ *                      the blind rotation directly: one lookup level in all.  Defaults to the destination's own
+ *                      (ks_base_log, ks_level).
+ *   key    [src k N][level, level L first][out_dim + 1] u64, out_dim = the destination's k N or n: the layout of
+ *          LweKeyswitchKey, which fhe_wire_write_keyswitch_key / fhe_wire_read_keyswitch_key carry
+ * Refused, with the reason in fhe_last_error: more than 16 levels, base_log above 7, base_log * level above 63, a key
+ * above 4 GiB, message-and-carry moduli that are not powers of two.  fhe_cast_key_len returns 0 then. */
+#define FHE_CAST_TO_BIG 0u
+#define FHE_CAST_TO_SMALL 1u
+typedef struct fhe_cast_params_t {
+    fhe_params_t src;          /* the source client's parameter set */
+    uint32_t base_log, level;  /* decomposition of the cast key */
+    uint32_t target;           /* FHE_CAST_TO_BIG / FHE_CAST_TO_SMALL */
+} fhe_cast_params_t;
+int fhe_cast_default_params(const fhe_params_t *src, const fhe_params_t *dst, uint32_t target, fhe_cast_params_t *cp);
+size_t fhe_cast_key_len(const fhe_params_t *dst, const fhe_cast_params_t *cp);   /* words; 0 = refused */
+/* cast_rshift of the reference (mod.rs:62-80): log2 of the destination's msg_mod * carry_mod minus log2 of the source's. */
+int fhe_cast_rshift(const fhe_params_t *src, const fhe_params_t *dst, int32_t *shift);
+/* The key, by the routine that generates the clients' own keyswitch keys: row (i, l) encrypts source key bit i shifted to
+ * level l under the destination's key of cp->target.  ck_src must have been created with cp->src.  out: fhe_cast_key_len
+ * words.  `seed` drives masks and noise. */
+int fhe_client_gen_cast_key(fhe_client_key *ck_src, fhe_client_key *ck_dst, const fhe_cast_params_t *cp,
+                            const uint8_t seed[32], uint64_t *out);
+/* The keyswitch in plain loops (the pin of the kernels): count rows of src k N + 1 words -> count rows of out_dim + 1. */
+int fhe_cast_host(const fhe_params_t *dst, const fhe_cast_params_t *cp, const uint64_t *key, const uint64_t *in,
+                  uint32_t count, uint64_t *out);
+/* Noise of a keyswitched block, by the keyswitch terms of fhe_noise_model at the cast key's dimensions.  v_in: the
+ * source block's variance in units of the SOURCE set's nominal (PBS output) variance.  out[0]: what the destination's
+ * next lookup sees, in units of the destination's nominal variance -- TO_BIG: the block itself; TO_SMALL: the input of
+ * equal effect, (torus variance - the destination's own keyswitch term) / V_pbs.  out[1]: the destination's default
+ * PBS-input budget.  out[2]: the keyswitched block's variance with the torus as unit. */
+int fhe_cast_noise(const fhe_params_t *dst, const fhe_cast_params_t *cp, double v_in, double out[3]);
+
+/* One cast key on the destination's engine; an engine may hold many (one per source client).  The words go up once and
+ * are rewritten into the matrix-core keyswitch's digit planes (csrc/ks_mfma_kernels.hip.h).  Owned by the engine like a
+ * fhe_transcipher: destroy it before the engine, never use it after. */
+typedef struct fhe_cast_key fhe_cast_key;
+int fhe_cast_key_create(fhe_engine *eng, const fhe_cast_params_t *cp, const uint64_t *key, fhe_cast_key **out);
+int fhe_cast_key_destroy(fhe_cast_key *h);
+/* info[0] target, [1] base_log, [2] level, [3] source k N, [4] out_dim, [5] shift + 64, [6] 1 if packed inputs take the
+ * fused digit kernel, [7] what the last cast launched: 0 nothing, 1 digits from LWEs, 2 fused digits from GLWEs,
+ * 3 extraction + digits. */
+int fhe_cast_key_info(fhe_cast_key *h, uint32_t info[8]);
+/* Packed inputs: 1 (default) cast_decompose_glwe_kernel writes the digits straight from the GLWEs; 0 the GLWEs are
+ * extracted to LWEs first (fhe_engine_unpack_glwes_dev's kernel).  Same results; for measurement and tests. */
+int fhe_cast_key_set_fused(fhe_cast_key *h, int on);
+/* Regrouping for strings cast to a set with more message bits per block: `group` consecutive source blocks, least
+ * significant first, become ONE destination block.  The keyswitched rows are combined as sum_i msg_src^i * row_i before
+ * the single table x -> x >> shift, so a destination block costs one lookup; count must then be a multiple of group
+ * and count / group blocks come out.  Refused unless msg_src^group is the destination's msg_mod and the largest lookup
+ * input, (msg_src^group - 1) << shift, stays inside the destination's message-and-carry space: 1_1 -> 2_2 and
+ * 2_2 -> 4_4 (group 2) qualify, 1_1 -> 4_4 (group 4: up to 960 against 255) does not.  group = 1 switches it off. */
+int fhe_cast_key_set_group(fhe_cast_key *h, uint32_t group);
+/* The rule above without an engine: *degree the largest lookup input, *space the destination's msg_mod * carry_mod;
+ * returns 1 with the reason when the regrouping is refused. */
+int fhe_cast_regroup_check(const fhe_params_t *src, const fhe_params_t *dst, uint32_t group, uint64_t *degree, uint64_t *space);
+/* What the source blocks are declared to carry, in the source set's nominal units, for the refusal below: 1 (default) for
+ * the outputs of a lookup, 0 for fresh encryptions; a block of a packed lookup output carries out[0] of
+ * fhe_packing_unpack_noise for the SOURCE's set and packing pair, of a narrow list out[0] of fhe_narrow_noise.  Like a
+ * plan's inputs it is a declaration. */
+int fhe_cast_key_set_input_noise(fhe_cast_key *h, double v_in);
+/* count source blocks -> count destination big-key blocks.  After the keyswitch:
+ *   TO_BIG,   shift > 0   one keyswitch + PBS with the table x -> x >> shift                  (mod.rs:107-127)
+ *   TO_BIG,   shift == 0  FHE_CAST_RAW: nothing more, the reference's behaviour; FHE_CAST_REFRESH: the identity table
+ *   TO_SMALL              always the blind rotation with that table
+ *   FHE_CAST_KEYSWITCHED  the keyswitched rows alone, out_dim + 1 words each (what fhe_cast_host gives)
+ * A cast that ends in a table is refused when fhe_cast_noise at the declared input noise puts out[0] above out[1] (the
+ * reference's own (1, 15) key from 1_1 to 2_2 is: 1,126 nominal variances against a budget of 138; its two steps stay
+ * available unguarded as FHE_CAST_KEYSWITCHED followed by fhe_ks_pbs_batch).  shift < 0, a cast to
+ * fewer bits, needs the SOURCE server key first (mod.rs:128-140): one lookup with x -> (x << -shift) % (msg * carry) on
+ * the source's engine, Engine.cast_prepare of the Python layer; blocks that skipped it cannot be told apart here.
+ * fhe_cast_lwes: host rows in and out, synchronises.  _dev: device buffers, asynchronous on the engine's stream under the
+ * contract of fhe_engine_unpack_glwes_dev. */
+#define FHE_CAST_RAW 0
+#define FHE_CAST_REFRESH 1
+#define FHE_CAST_KEYSWITCHED 2
+int fhe_cast_lwes(fhe_cast_key *h, const uint64_t *in, uint32_t count, int mode, uint64_t *out);
+int fhe_cast_lwes_dev(fhe_cast_key *h, const uint64_t *d_in, uint32_t count, int mode, uint64_t *d_out);
+/* The same for blocks first .. first + count - 1 of the source's packed GLWEs ([src k + 1][src N], block j = coefficient
+ * j % N of GLWE j / N).  The GLWE key flattened is the big LWE key, so nothing is unpacked under the old key: the digits
+ * of the sample-extracted rows are written straight from the GLWEs.  The host form takes the GLWEs from GLWE 0 on. */
+int fhe_cast_packed(fhe_cast_key *h, const uint64_t *glwes, uint32_t first, uint32_t count, int mode, uint64_t *out);
+int fhe_cast_packed_dev(fhe_cast_key *h, const uint64_t *d_glwes, uint32_t first, uint32_t count, int mode, uint64_t *d_out);
+/* The same for the source's narrow list of `held` blocks at `bits` bits (fhe_engine_narrow_glwes on the source's side):
+ * the list is widened on the device at the source's (k, N) -- the kernel of fhe_engine_widen_narrow_dev -- and cast as
+ * packed GLWEs; nothing of it is widened on the host.  The list starts at its first stream; first + count > held is refused. */
+int fhe_cast_narrow(fhe_cast_key *h, const uint64_t *narrow, uint32_t held, uint32_t bits, uint32_t first, uint32_t count,
+                    int mode, uint64_t *out);
+int fhe_cast_narrow_dev(fhe_cast_key *h, const uint64_t *d_narrow, uint32_t held, uint32_t bits, uint32_t first,
+                        uint32_t count, int mode, uint64_t *d_out);
+/* The digit fragments of a batch as the product reads them ([row tile][step][lane][16] int8, ceil(count / 32) * steps KB;
+ * *bytes receives that size, out may be NULL to query it): from LWE rows (packed = 0) or from packed GLWEs through the
+ * kernel fhe_cast_key_set_fused selects.  Host arrays; synchronises.  What tests compare byte for byte. */
+int fhe_cast_debug_digits(fhe_cast_key *h, const uint64_t *src, uint32_t first, uint32_t count, int packed, int8_t *out,
+                          size_t *bytes);
+
 /* ---- tfhe-rs wire format (serde + bincode 1.x, fixed-width little endian) ---------------------- */
 /* Byte forms of core_crypto's LweCiphertext<Vec<u64>>, LweKeyswitchKey<Vec<u64>>, standard-domain
  * LweBootstrapKey<Vec<u64>> and shortint::Ciphertext as tfhe-rs 0.5 writes them with bincode::serialize /
