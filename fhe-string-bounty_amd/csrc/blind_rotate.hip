@@ -333,6 +333,7 @@ static int rotate_multibit_combined(Engine& e, const BrVariant* v, const BlindRo
     const size_t groups = e.p.n / e.p.grouping_factor;
     if (e.d_ws.reserve((size_t)a.batch * groups * v->combined_bytes)) return 1;
     MultiBitCombineArgs ca{a, reinterpret_cast<double2*>(e.d_ws.ptr)};
+    if (e.one_span("multi-bit combine", (a.batch + v->combine_chunk - 1) / v->combine_chunk, 2)) return 1;   // grid.z = chunks of the batch: at most multibit_combine_max LWEs take this path
     void* cargs[] = {(void*)&ca};
     HIP_TRY(launch(v->combine, dim3((unsigned)groups, (unsigned)v->combine_grid_y, (a.batch + v->combine_chunk - 1) / v->combine_chunk), cargs,
                    e.p.n, e.stream));
@@ -366,6 +367,7 @@ static int rotate_multibit_two_kernel(Engine& e, const BrVariant* v, const Blind
         MultiBitCombineGenericArgs ca{a.lwe_small + (size_t)first * (p.n + 1), reinterpret_cast<const double2*>(e.d_fbsk.ptr), e.d_slot_exp,
                                       reinterpret_cast<double2*>(e.d_ws.ptr), p.n, logN, p.N / 2, ggsw_elems, sub};
         void* cargs[] = {(void*)&ca};
+        if (e.one_span("multi-bit combine", (ggsw_elems + per_wg - 1) / per_wg, 1) || e.one_span("multi-bit combine", (sub + chunk - 1) / chunk, 2)) return 1;
         HIP_TRY(launch(v->combine_generic, dim3((unsigned)groups, (ggsw_elems + per_wg - 1) / per_wg, (sub + chunk - 1) / chunk), cargs, p.n, e.stream));
         BlindRotateLargeArgs la{{a.lwe_small + (size_t)first * (p.n + 1), a.lut_idx ? a.lut_idx + first : nullptr, a.luts,
                                  reinterpret_cast<const double*>(e.d_ws.ptr), a.lwe_out + (size_t)first * big, p.n, p.pbs_base_log, sub,

@@ -35,7 +35,7 @@ int CastKey::create(Engine& e, const fhe_cast_params_t& cp, const uint64_t* word
     if (under(who, d_std.alloc(n_words * 8)) || under(who, k->key.alloc((size_t)g.col_groups * g.steps * 8 * 1024)) ||
         under(who, hipMemcpyAsync(d_std, words, n_words * 8, hipMemcpyHostToDevice, e.stream)))
         return 1;
-    ks_mfma_repack(d_std, k->key, g, e.stream);
+    ks_mfma_repack(e, d_std, k->key, g, e.stream);
     if (under(who, hipGetLastError()) || under(who, hipStreamSynchronize(e.stream))) return 1;
     *out = k.get();
     e.cast_keys.push_back(std::move(k));
@@ -69,7 +69,7 @@ int CastKey::gate(const char* who) const {
 // source's packed GLWEs from the one that holds block 0.
 int CastKey::keyswitch_dev(const uint64_t* d_src, uint32_t first, uint32_t count, bool packed, uint64_t* d_rows) {
     Engine& en = *e;
-    if (count > 65535u) return fail("cast: batch too large for one launch (max 65535 blocks)");      // grid.y of the digit kernels
+    if (count > 65535u) return fail("cast: batch too large for one launch (max 65535 blocks)");      // the documented limit (include/fhestr.h); the launches below are held to the device's maxGridSize
     const KsMfmaGeom g = geom_of(*this);
     const KsMfmaLaunch l = ks_mfma_plan(g, count, cp.base_log, en.cu_count, en.cfg.ks_chunks_override);
     hipStream_t s = en.stream;
@@ -81,6 +81,7 @@ int CastKey::keyswitch_dev(const uint64_t* d_src, uint32_t first, uint32_t count
         if (N < 2 || (N & (N - 1))) return fail("cast_packed: the source polynomial size must be a power of two");
         if (ks_mfma_reserve_digits(en, digits, l, s) || en.reserve_idle(bodies, (size_t)count * 8)) return 1;
         CastDecomposeArgs a{d_src, digits, bodies, g, N, first, count, l.row_tiles};
+        if (en.one_span("cast digits", l.row_tiles, 1)) return 1;      // grid.y = 32-row tiles: at most 2048 under the limit above
         hipLaunchKernelGGL(cast_decompose_glwe_kernel, dim3((g.steps + CAST_DECOMPOSE_WAVES - 1) / CAST_DECOMPOSE_WAVES, l.row_tiles),
                            dim3(64 * CAST_DECOMPOSE_WAVES), 0, s, a);
         d_bodies = bodies; body_stride = 1;
@@ -98,7 +99,7 @@ int CastKey::keyswitch_dev(const uint64_t* d_src, uint32_t first, uint32_t count
         d_bodies = d_lwes + in_dim; body_stride = in_dim + 1;
         last = packed ? 3 : 1;
     }
-    ks_mfma_product(KsMfmaArgs{d_bodies, body_stride, key, digits, d_rows, g, count, l.row_tiles, l.spc}, l, s);
+    if (ks_mfma_product(en, KsMfmaArgs{d_bodies, body_stride, key, digits, d_rows, g, count, l.row_tiles, l.spc}, l, s)) return 1;
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -16,6 +16,7 @@
 #include "blind_rotate.h"
 #include "device_buffer.h"
 #include "engine_settings.h"
+#include "grid_spans.h"
 
 // bumped whenever a device kernel changes; profiles/r03_counters.json records the revision its
 // rocprofv3 counters were taken on and bench.py only attaches them to a matching build
@@ -241,6 +242,15 @@ struct Engine {
     const BrVariant* variant = nullptr;       // layout used up to one LWE per CU
     const BrVariant* variant_large = nullptr; // same Fourier-key layout, used for larger batches (may equal variant)
     int cu_count = 256;
+    uint32_t max_grid[3] = {0x7FFFFFFFu, 65535u, 65535u};   // hipDeviceProp_t::maxGridSize, read in Engine::create: no launch passes a larger grid dimension
+    // The spans of a grid dimension that grows with a batch or a key size (grid_spans.h); axis 0, 1, 2 = x, y, z.
+    GridSpans spans(uint64_t count, int axis) const { return grid_spans(count, max_grid[axis]); }
+    // A dimension that a documented batch limit keeps within one launch: anything else is refused, never launched.
+    int one_span(const char* who, uint64_t count, int axis) const {
+        if (spans(count, axis).spans == 1) return 0;
+        return fail(std::string(who) + ": grid." + "xyz"[axis] + " = " + std::to_string(count) + " does not fit one launch (the device allows " +
+                    std::to_string(max_grid[axis]) + ")");
+    }
     EngineSettings cfg;                       // defaults, environment (Engine::create) and the fhe_engine_set_* setters: engine_settings.h
     int pipeline = 0;                         // ks_pbs_dev throughput modes: 1 = keyswitch of call k+1 in the shadow of the blind rotation of call k; 2 = whole calls overlapped on pipe.width lanes
     Pipeline pipe;                           // streams, events, buffers and hazard records of the throughput modes; lane 0's buffers serve every serial call

@@ -75,6 +75,7 @@ int Engine::create(const fhe_params_t& p, int device, Engine** out) {
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     e->cu_count = prop.multiProcessorCount;
+    for (int q = 0; q < 3; q++) e->max_grid[q] = prop.maxGridSize[q] > 0 ? (uint32_t)prop.maxGridSize[q] : 0u;
     HIP_TRY(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
     e->stream = e->own_stream;
     *out = e.release();
@@ -265,12 +266,23 @@ int Engine::install_keys(DeviceBuffer<uint64_t>&& ksk_std, DeviceBuffer<uint64_t
     {   // repack into byte planes once
         const uint32_t rows = p.k * p.N * p.ks_level, osz = p.n + 1;
         if (d_ksk_packed.alloc((size_t)(rows / 4) * 8 * osz * 4)) return 1;
-        hipLaunchKernelGGL(ksk_pack_kernel, dim3((osz + 255) / 256, rows / 4), dim3(256), 0, stream,
-                           d_ksk_std.ptr, d_ksk_packed.ptr, rows, osz);
-        const uint32_t tiles = (p.k * p.N + KS_IC - 1) / KS_IC;
+        // grid.y = quads of key rows: k N ks_level / 4 reaches 90112 (PARAM_MESSAGE_3_CARRY_4_COMPACT_PK_PBS_KS), so one launch
+        // per span of the device's grid.y, each on its own rows of both arrays (the kernel sees a shorter key)
+        const GridSpans quads = spans(rows / 4, 1);
+        if (!quads.spans) return fail("install_keys: the device reports no grid.y");
+        for (uint64_t i = 0; i < quads.spans; i++) {
+            const GridSpan q = quads.at(i);
+            hipLaunchKernelGGL(ksk_pack_kernel, dim3((osz + 255) / 256, q.count), dim3(256), 0, stream, d_ksk_std.ptr + q.first * 4 * osz,
+                               d_ksk_packed.ptr + q.first * 8 * osz, (uint32_t)(rows - q.first * 4), osz);
+        }
+        const uint32_t tiles = (p.k * p.N + KS_IC - 1) / KS_IC, tile_rows = (uint32_t)KS_IC * p.ks_level;
         if (d_ksk_rowsum.alloc((size_t)tiles * osz * 8)) return 1;
-        hipLaunchKernelGGL(ksk_rowsum_kernel, dim3((osz + 255) / 256, tiles), dim3(256), 0, stream,
-                           d_ksk_std.ptr, d_ksk_rowsum.ptr, rows, osz, (uint32_t)KS_IC * p.ks_level);
+        const GridSpans tsp = spans(tiles, 1);
+        for (uint64_t i = 0; i < tsp.spans; i++) {
+            const GridSpan t = tsp.at(i);
+            hipLaunchKernelGGL(ksk_rowsum_kernel, dim3((osz + 255) / 256, t.count), dim3(256), 0, stream, d_ksk_std.ptr + t.first * tile_rows * osz,
+                               d_ksk_rowsum.ptr + t.first * osz, (uint32_t)(rows - t.first * tile_rows), osz, tile_rows);
+        }
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));
     }
@@ -282,7 +294,7 @@ int Engine::install_keys(DeviceBuffer<uint64_t>&& ksk_std, DeviceBuffer<uint64_t
         const KsMfmaGeom g = ks_mfma_geom(p.k * p.N, p.n + 1, p.ks_level, p.ks_base_log);
         const size_t bytes = (size_t)g.col_groups * g.steps * 8 * 1024;
         if (d_ksk_mfma.alloc(bytes)) return 1;
-        ks_mfma_repack(d_ksk_std, d_ksk_mfma, g, stream);
+        ks_mfma_repack(*this, d_ksk_std, d_ksk_mfma, g, stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));
     }
@@ -381,26 +393,41 @@ int ks_mfma_reserve_digits(Engine& e, DeviceBuffer<int8_t>& digits, const KsMfma
 }
 int ks_mfma_digits(Engine& e, DeviceBuffer<int8_t>& digits, const KsMfmaLaunch& l, const KsMfmaGeom& g, const uint64_t* d_lwes, uint32_t count, hipStream_t s) {
     if (ks_mfma_reserve_digits(e, digits, l, s)) return 1;
-    KsDecomposeArgs da{d_lwes, digits, g, count};
-    hipLaunchKernelGGL(ks_decompose_kernel, dim3((2 * g.steps + 255) / 256, count), dim3(256), 0, s, da);
+    // grid.y = samples: one launch per span of the device's grid.y, the span's first sample in the arguments
+    const GridSpans sp = e.spans(count, 1);
+    if (!sp.spans) return fail("keyswitch digits: the device reports no grid.y");
+    for (uint64_t i = 0; i < sp.spans; i++) {
+        const GridSpan b = sp.at(i);
+        KsDecomposeArgs da{d_lwes, digits, g, count, (uint32_t)b.first};
+        hipLaunchKernelGGL(ks_decompose_kernel, dim3((2 * g.steps + 255) / 256, b.count), dim3(256), 0, s, da);
+    }
+    HIP_TRY(hipGetLastError());
     return 0;
 }
-void ks_mfma_repack(const uint64_t* d_std, int8_t* planes, const KsMfmaGeom& g, hipStream_t s) {
-    hipLaunchKernelGGL(ksk_repack_mfma_kernel, dim3(g.col_groups, g.steps), dim3(64), 0, s, d_std, planes, g);
+void ks_mfma_repack(const Engine& e, const uint64_t* d_std, int8_t* planes, const KsMfmaGeom& g, hipStream_t s) {
+    const GridSpans sp = e.spans(g.steps, 1);      // grid.y = K steps of the key: 16384 at N = 32768 with 11 levels
+    for (uint64_t i = 0; i < sp.spans; i++) {
+        const GridSpan t = sp.at(i);
+        hipLaunchKernelGGL(ksk_repack_mfma_kernel, dim3(g.col_groups, t.count), dim3(64), 0, s, d_std, planes, g, (uint32_t)t.first);
+    }
 }
-void ks_mfma_product(const KsMfmaArgs& ma, const KsMfmaLaunch& l, hipStream_t s) {
+int ks_mfma_product(const Engine& e, const KsMfmaArgs& ma, const KsMfmaLaunch& l, hipStream_t s) {
+    // grid.y = row tiles / mt, at most 2048 under the 524280-LWE limit; grid.z = K chunks, at most steps / 8
+    if (e.one_span("keyswitch product", l.gy, 1) || e.one_span("keyswitch product", l.chunks, 2)) return 1;
     switch (l.mt) {
         case 1: hipLaunchKernelGGL(keyswitch_mfma_kernel<1>, l.grid(ma.g), dim3(64), 0, s, ma); break;
         case 2: hipLaunchKernelGGL(keyswitch_mfma_kernel<2>, l.grid(ma.g), dim3(128), 0, s, ma); break;
         case 4: hipLaunchKernelGGL(keyswitch_mfma_kernel<4>, l.grid(ma.g), dim3(256), 0, s, ma); break;
         default: hipLaunchKernelGGL(keyswitch_mfma_kernel<8>, l.grid(ma.g), dim3(512), 0, s, ma); break;
     }
+    return 0;
 }
 
 int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t count, DeviceBuffer<int8_t>& digits, hipStream_t on, bool shadow) {
     if (!d_ksk_packed) return fail("keys not loaded");
     hipStream_t s = on ? on : stream;
-    // grid.y = sample tiles; HIP caps grid.y at 65535
+    // The documented batch limit (include/fhestr.h).  It was sized for the byte-plane kernel's grid.y = count / 8 under a cap
+    // of 65535; what the device allows is hipDeviceProp_t::maxGridSize (max_grid), and every launch below is held to that.
     if (count > 65535u * KSD_S) return fail("batch too large for one keyswitch launch (max 524280 LWEs)");
     const uint32_t in_dim = p.k * p.N, out_size = p.n + 1;
     HIP_TRY(hipMemsetAsync(d_sm, 0, (size_t)count * out_size * 8, s));
@@ -408,7 +435,7 @@ int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t cou
         const KsMfmaGeom g = ks_mfma_geom(in_dim, out_size, p.ks_level, p.ks_base_log);
         const KsMfmaLaunch l = ks_mfma_plan(g, count, p.ks_base_log, cu_count, cfg.ks_chunks_override);
         if (ks_mfma_digits(*this, digits, l, g, d_big, count, s)) return 1;
-        ks_mfma_product(KsMfmaArgs{d_big + in_dim, in_dim + 1, d_ksk_mfma, digits, d_sm, g, count, l.row_tiles, l.spc}, l, s);
+        if (ks_mfma_product(*this, KsMfmaArgs{d_big + in_dim, in_dim + 1, d_ksk_mfma, digits, d_sm, g, count, l.row_tiles, l.spc}, l, s)) return 1;
         l.info(ks_last, FHE_KS_KERNEL_MFMA, g);
         HIP_TRY(hipGetLastError());
         return 0;
@@ -417,14 +444,27 @@ int Engine::launch_keyswitch(const uint64_t* d_big, uint64_t* d_sm, uint32_t cou
     if (shadow) {     // small-register variant: co-resident with the blind rotation of the previous batch
         constexpr int S = 4;
         dim3 pgrid((out_size + KS_COLS - 1) / KS_COLS, (count + S - 1) / S, (in_dim + KS_IC - 1) / KS_IC);
+        if (one_span("keyswitch", pgrid.y, 1) || one_span("keyswitch", pgrid.z, 2)) return 1;   // at most one LWE per CU here
         hipLaunchKernelGGL((keyswitch_dot4_kernel<S, 8>), pgrid, dim3(KS_COLS), (size_t)KS_IC * p.ks_level * S, s, pa);
         ks_last[0] = FHE_KS_KERNEL_DOT4_SHADOW; ks_last[1] = S; ks_last[2] = pgrid.z; ks_last[3] = KS_IC; ks_last[4] = in_dim;
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    dim3 pgrid((out_size + KS_COLS - 1) / KS_COLS, (count + KSD_S - 1) / KSD_S, (in_dim + KS_IC - 1) / KS_IC);
-    hipLaunchKernelGGL((keyswitch_dot4_kernel<KSD_S, 2>), pgrid, dim3(KS_COLS), (size_t)KS_IC * p.ks_level * KSD_S, s, pa);
-    ks_last[0] = FHE_KS_KERNEL_DOT4; ks_last[1] = KSD_S; ks_last[2] = pgrid.z; ks_last[3] = KS_IC; ks_last[4] = in_dim;
+    // grid.y = tiles of KSD_S samples (65535 at the batch limit), one launch per span of the device's grid.y on its own rows of
+    // both arrays; grid.z = tiles of KS_IC mask elements (1024 at k N = 65536)
+    const uint32_t gx = (out_size + KS_COLS - 1) / KS_COLS, gz = (in_dim + KS_IC - 1) / KS_IC;
+    const GridSpans sp = spans((count + KSD_S - 1) / KSD_S, 1);
+    if (!sp.spans) return fail("keyswitch: the device reports no grid.y");
+    if (one_span("keyswitch", gz, 2)) return 1;
+    for (uint64_t i = 0; i < sp.spans; i++) {
+        const GridSpan t = sp.at(i);
+        KeyswitchPackedArgs ta = pa;
+        ta.lwe_in += t.first * KSD_S * (in_dim + 1);
+        ta.lwe_out += t.first * KSD_S * out_size;
+        ta.batch = (uint32_t)(count - t.first * KSD_S);
+        hipLaunchKernelGGL((keyswitch_dot4_kernel<KSD_S, 2>), dim3(gx, t.count, gz), dim3(KS_COLS), (size_t)KS_IC * p.ks_level * KSD_S, s, ta);
+    }
+    ks_last[0] = FHE_KS_KERNEL_DOT4; ks_last[1] = KSD_S; ks_last[2] = gz; ks_last[3] = KS_IC; ks_last[4] = in_dim;
     HIP_TRY(hipGetLastError());
     return 0;
 }

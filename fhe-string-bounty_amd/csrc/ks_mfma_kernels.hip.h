@@ -60,6 +60,7 @@ struct KsDecomposeArgs {
     int8_t* digits;             // [row tile][step][64][16], pad slots zeroed at allocation and never written
     KsMfmaGeom g;
     uint32_t batch;
+    uint32_t first;             // first sample of this launch: grid.y covers one span of the batch (grid_spans.h)
 };
 
 struct KsMfmaArgs {

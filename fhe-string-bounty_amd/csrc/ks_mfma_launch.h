@@ -20,15 +20,17 @@ struct KsMfmaLaunch {
 };
 KsMfmaLaunch ks_mfma_plan(const KsMfmaGeom& g, uint32_t count, uint32_t base_log, int cu_count, uint32_t chunks_override);
 // The batch's digit fragments on stream s.  The buffer is zeroed when it is allocated and only grows: the pad slots stay
-// zero, rows past the batch are never read.  Another stream's launch may still read the allocation being replaced.
+// zero, rows past the batch are never read.  One launch per span of the device's grid.y (grid_spans.h); reads the launches'
+// error.  Another stream's launch may still read the allocation being replaced.
 int ks_mfma_digits(Engine& e, DeviceBuffer<int8_t>& digits, const KsMfmaLaunch& l, const KsMfmaGeom& g, const uint64_t* d_lwes, uint32_t count, hipStream_t s);
 // Only the buffer of the above, for a caller that writes the fragments with a kernel of its own (cast_dev.hip).
 int ks_mfma_reserve_digits(Engine& e, DeviceBuffer<int8_t>& digits, const KsMfmaLaunch& l, hipStream_t s);
 // keyswitch_mfma_kernel<l.mt> at l.grid(a.g) on stream s: the one place the product is instantiated and launched (the
-// keyswitch and the casting keys).  Only the launch: the caller reads hipGetLastError.
-void ks_mfma_product(const KsMfmaArgs& a, const KsMfmaLaunch& l, hipStream_t s);
+// keyswitch and the casting keys).  Refuses a grid the device does not allow (Engine::one_span); otherwise only the launch:
+// the caller reads hipGetLastError.
+int ks_mfma_product(const Engine& e, const KsMfmaArgs& a, const KsMfmaLaunch& l, hipStream_t s);
 // A key's words at d_std -> its balanced base-256 digit planes in B-fragment order at planes (col_groups x steps x 8 KB), on
-// stream s.  Only the launch: the caller reads hipGetLastError and synchronises under its own name.
-void ks_mfma_repack(const uint64_t* d_std, int8_t* planes, const KsMfmaGeom& g, hipStream_t s);
+// stream s, one launch per span of the device's grid.y.  Only the launches: the caller reads hipGetLastError and synchronises under its own name.
+void ks_mfma_repack(const Engine& e, const uint64_t* d_std, int8_t* planes, const KsMfmaGeom& g, hipStream_t s);
 
 }  // namespace fhe

@@ -8,8 +8,9 @@
 namespace fhe {
 
 // Key words -> balanced base-256 digit planes in B-fragment order.  One thread per (column group, step, lane, plane-octet).
-__global__ void __launch_bounds__(64) ksk_repack_mfma_kernel(const uint64_t* __restrict__ ksk, int8_t* __restrict__ out, KsMfmaGeom g) {
-    const uint32_t cg = blockIdx.x, step = blockIdx.y, lane = threadIdx.x;
+__global__ void __launch_bounds__(64) ksk_repack_mfma_kernel(const uint64_t* __restrict__ ksk, int8_t* __restrict__ out, KsMfmaGeom g,
+                                                             uint32_t first_step) {
+    const uint32_t cg = blockIdx.x, step = first_step + blockIdx.y, lane = threadIdx.x;   // a launch covers one span of the steps (grid_spans.h)
     const uint32_t c = lane & 31, h = lane >> 5;
     const uint32_t col = cg * 32 + c;
     int8_t frag[8][16];
@@ -40,8 +41,8 @@ __global__ void __launch_bounds__(64) ksk_repack_mfma_kernel(const uint64_t* __r
 // One thread per (sample, 16-slot group): the reference's signed decomposition (level L first, iter.rs:101-127) of the
 // group's floor(16 / level) mask elements, stored as ONE 16-byte A-fragment element (pad slots written as zero digits).
 __global__ void __launch_bounds__(256) ks_decompose_kernel(KsDecomposeArgs a) {
-    const uint32_t grp = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-    if (grp >= 2 * a.g.steps) return;
+    const uint32_t grp = blockIdx.x * 256 + threadIdx.x, b = a.first + blockIdx.y;   // a launch covers one span of the batch (grid_spans.h)
+    if (grp >= 2 * a.g.steps || b >= a.batch) return;
     const uint32_t L = a.g.level, bl = a.g.base_log, rep = bl * L;
     const uint64_t mask = (1ull << bl) - 1;
     const uint64_t* src = a.lwe_in + (size_t)b * (a.g.in_dim + 1);

@@ -89,7 +89,7 @@ int Packing::load_key(const fhe_packing_params_t& new_pp, const uint64_t* pksk) 
     if (under(who, planes.alloc((size_t)g.col_groups * g.steps * 8 * 1024)) ||
         under(who, hipMemcpyAsync(d_std, pksk, words * 8, hipMemcpyHostToDevice, e->stream)))
         return 1;
-    ks_mfma_repack(d_std, planes, g, e->stream);
+    ks_mfma_repack(*e, d_std, planes, g, e->stream);
     if (under(who, hipGetLastError()) || under(who, hipStreamSynchronize(e->stream))) return 1;
     d_std.release();      // the 64-bit layout (3.2 GB at N = 8192) goes as soon as the repack is done
     key = std::move(planes);
@@ -105,7 +105,7 @@ int Packing::pack_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_glwes) 
     if (e->use()) return 1;
     if (!key) return fail("packing key not loaded");
     if (count == 0) return 0;
-    if (count > 65535u) return fail("batch too large for one packing launch (max 65535 LWEs)");   // grid.y of the digit kernel
+    if (count > 65535u) return fail("batch too large for one packing launch (max 65535 LWEs)");   // the documented limit (include/fhestr.h); the launches below are held to the device's maxGridSize
     if (e->leave_pipelined_run()) return 1;                 // pipelined calls may still write the input on another stream
     const fhe_params_t& p = e->p;
     const uint32_t in_dim = p.k * p.N, out_size = (p.k + 1) * p.N;
@@ -115,6 +115,7 @@ int Packing::pack_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_glwes) 
     const KsMfmaLaunch l = ks_mfma_plan(g, count, pp.base_log, e->cu_count, e->cfg.ks_chunks_override);
     if (ks_mfma_digits(*e, digits, l, g, d_cts, count, e->stream)) return 1;
     PackKsArgs pa{d_cts, key, digits, d_glwes, g, count, l.row_tiles, l.spc, p.N, p.k * p.N / 32};
+    if (e->one_span("packing product", l.gy, 1) || e->one_span("packing product", l.chunks, 2)) return 1;   // at most 256 row-tile groups; steps / 8 chunks
     switch (l.mt) {
         case 1: hipLaunchKernelGGL(packing_ks_mfma_kernel<1>, l.grid(g), dim3(64), 0, e->stream, pa); break;
         case 2: hipLaunchKernelGGL(packing_ks_mfma_kernel<2>, l.grid(g), dim3(128), 0, e->stream, pa); break;
@@ -326,7 +327,7 @@ int Packing::ring_pack_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_gl
     const fhe_params_t& p = e->p;
     const uint32_t N = p.N, k = p.k, k1 = k + 1, L = ring_pp.level, kL = k * L, logN = ring_log2(N);
     const size_t glwe_len = (size_t)k1 * N, slot_bytes = (size_t)count * glwe_len * 8;
-    if (count > 65535u) return fail("batch too large for one ring packing call (max 65535 LWEs)");   // grid.y of the leaf kernel
+    if (count > 65535u) return fail("batch too large for one ring packing call (max 65535 LWEs)");   // the documented limit (include/fhestr.h)
     if (slot_bytes > RING_SLOTS_CAP)
         return fail("ring packing: " + std::to_string(count) + " LWEs need " + std::to_string(slot_bytes) + " bytes of leaves, the cap is " +
                     std::to_string(RING_SLOTS_CAP) + "; pack the list in parts of whole GLWEs");
@@ -334,7 +335,7 @@ int Packing::ring_pack_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_gl
     const uint32_t full_groups = count / N, c_last = count % N;
     const size_t per_merge = (size_t)N * 8 + (size_t)kL * N * 4 + (size_t)k1 * RING_PLANES * N * 4;
     const uint64_t widest = (uint64_t)full_groups * (N / 2) + std::min(N / 2, c_last);      // level 1
-    const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({widest, RING_TMP_CAP / per_merge, 65535u}));   // grid.z of the combine kernel
+    const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({widest, RING_TMP_CAP / per_merge, 65535u, e->max_grid[2]}));   // merges per launch: grid.z of the combine kernel
     if (e->reserve_idle(ring_slots, slot_bytes) || e->reserve_idle(ring_tmp, batch * per_merge)) return 1;
     RingLevelArgs a{};
     a.slots = ring_slots;
@@ -345,8 +346,16 @@ int Packing::ring_pack_dev(const uint64_t* d_cts, uint32_t count, uint64_t* d_gl
     a.inv = ring_tw.ptr + N;
     a.N = N; a.logN = logN; a.k = k; a.L = L; a.base_log = ring_pp.base_log; a.n_inv = ring_n_inv;
     a.full_groups = full_groups; a.c_last = c_last;
-    hipLaunchKernelGGL(ring_leaf_kernel, dim3((uint32_t)((glwe_len + 255) / 256), count), dim3(256), 0, e->stream, d_cts, ring_slots.ptr, N, logN, k);
-    uint64_t launches = 1, keyswitches = 0;
+    // grid.y = LWEs: one launch per span of the device's grid.y, each on its own rows of both arrays
+    const GridSpans leaves = e->spans(count, 1);
+    if (!leaves.spans) return fail("ring packing: the device reports no grid.y");
+    if (e->one_span("ring packing", batch, 2)) return 1;
+    for (uint64_t i = 0; i < leaves.spans; i++) {
+        const GridSpan lf = leaves.at(i);
+        hipLaunchKernelGGL(ring_leaf_kernel, dim3((uint32_t)((glwe_len + 255) / 256), lf.count), dim3(256), 0, e->stream,
+                           d_cts + lf.first * ((size_t)k * N + 1), ring_slots.ptr + lf.first * glwe_len, N, logN, k);
+    }
+    uint64_t launches = leaves.spans, keyswitches = 0;
     const uint32_t threads = ring_threads(N);
     for (uint32_t level = 1; level <= logN; level++) {
         a.s = N >> level;

@@ -161,6 +161,20 @@ int fhe_lut_download(fhe_engine *eng, uint32_t lut_id, uint64_t *accumulator);
 int fhe_lut_count(const fhe_engine *eng, uint32_t *count);
 
 /* ---- the hot path -------------------------------------------------------------------------- */
+/* Batch limits of the batched entry points, in one place.  A count above its limit is refused with the message quoted,
+ * nothing is launched and the engine stays usable.  Below it, no launch passes a grid dimension above what the device
+ * reports (hipDeviceProp_t::maxGridSize, read when the engine is created; an MI355X reports 2147483647 x 65536 x 65536): a
+ * grid dimension that grows with the count or with a key size is covered in spans of that size, one launch each
+ * (csrc/grid_spans.h).
+ *   fhe_keyswitch_batch, fhe_ks_pbs_batch (_dev), fhe_pbs_ks_batch, and every level of fhe_plan_run / fhe_plan_run_batch
+ *   (jobs x instances rows of a level are ONE such batch)        524280 LWEs   "batch too large for one keyswitch launch (max 524280 LWEs)"
+ *   fhe_pbs_batch                                                2^31 - 1 workgroups of the blind rotation; no check of its own
+ *   fhe_engine_pack_lwes (_dev)                                  65535 LWEs    "batch too large for one packing launch (max 65535 LWEs)"
+ *   fhe_engine_ring_pack_lwes (_dev)                             65535 LWEs    "batch too large for one ring packing call (max 65535 LWEs)",
+ *                                                                and 2 GiB of leaves (count (k+1) N words): refused with the sizes
+ *   fhe_cast_lwes, fhe_cast_packed, fhe_cast_narrow (_dev)       65535 blocks  "cast: batch too large for one launch (max 65535 blocks)"
+ *   fhe_engine_expand_compact_list (_dev)                        count * ceil(k N / 512) < 2^31 workgroups
+ * tests/test_gpu_batch_limits.py runs each of the first, third, fourth and fifth rows at its limit and one past it. */
 /* keyswitch_lwe_ciphertext (core_crypto/algorithms/lwe_keyswitch.rs:96-170), batched. */
 int fhe_keyswitch_batch(fhe_engine *eng, const uint64_t *lwe_big_in, uint64_t *lwe_small_out,
                         uint32_t count);
