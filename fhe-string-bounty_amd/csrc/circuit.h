@@ -152,6 +152,7 @@ public:
     bool failed() const { return !error_.empty(); }
     const std::string& error() const { return error_; }
     std::string take_error() { std::string e; e.swap(error_); return e; }   // report once, then keep building
+    void refuse(std::string e) { set_error(std::move(e)); }                 // a builder's own refusal; the first error is the cause
 
     // ---- finalise + query ----
     int finalize(uint32_t world);                 // owners, exports, pool layout, gather descriptions

@@ -33,10 +33,7 @@ struct CountOps {
     StrOps& s;
     RadixOps r;
     using How = opname::How;
-    CountOps(Circuit& c, StrOps& s) : c(c), s(s), r(c) {
-        // the comparator subtracts two packed pairs: 2 (1 + M^2) variances, beyond the budget of 4-bit blocks
-        r.pair_blocks = (uint64_t)s.M * s.M <= (uint64_t)s.T && 2.0 * (1.0 + (double)s.M * s.M) <= s.budget();
-    }
+    CountOps(Circuit& c, StrOps& s) : c(c), s(s), r(c) { r.pair_blocks = r.two_pairs_fit(); }
 
     static bool is_bit(How how) { return how != opname::C_ADD && how != opname::C_SUB; }
     // the clear-text definition on clamped operands

@@ -17,7 +17,8 @@
 //   eq / ne / gt / ge / lt / le (+ scalar_*)   integer/server_key/comparator.rs:193-280: pack two blocks,
 //        true LWE subtraction whose sign lands in the padding bit, sign lookup + 1 in {0, 1, 2},
 //        pairwise reduction 4*msb + lsb, final sign -> bool lookup; equality through
-//        radix_parallel/scalar_comparison.rs:147-233
+//        radix_parallel/scalar_comparison.rs:147-233.  Block by block where two packed pairs exceed the noise budget
+//        (RadixOps::two_pairs_fit); a scalar beyond the integer's range is decided at build (scalar_comparison.rs:23-60)
 // Every lookup of one level of one operation is one batched KS+PBS launch (circuit.h).
 #include <algorithm>
 #include <string>
@@ -38,6 +39,21 @@ int build_integer_op(Circuit& c, const std::string& op, uint32_t n_blocks, uint6
     auto emit = [&](const std::vector<uint32_t>& v) { for (uint32_t b : v) c.output(b); };
     const bool is_scalar = op.compare(0, 7, "scalar_") == 0;
     const std::string base = is_scalar ? op.substr(7) : op;
+    // two encrypted operands: compare block by block where two packed pairs exceed the budget (scalar forms pack one pair)
+    if (!is_scalar) r.pair_blocks = r.two_pairs_fit();
+    // is_scalar_out_of_bounds (radix_parallel/scalar_comparison.rs:23-60): a scalar with bits beyond the integer's is
+    // above every value of it, and the answer is known here.  scalar_add / scalar_sub wrap instead.  The plan keeps
+    // its inputs; its output is a constant table read on the first of them, a lookup's result like every other output.
+    const uint32_t total_bits = n_blocks * r.bits;
+    const bool above = is_scalar && total_bits < 64 && (scalar >> total_bits) != 0;
+    if (above && base != "add" && base != "sub") {
+        const bool known = base == "ne" || base == "lt" || base == "le";
+        if (!known && base != "eq" && base != "gt" && base != "ge") return fail("unknown integer op: " + op);
+        const auto a = r.input(n_blocks);
+        c.output(c.pbs(a[0], c.lut_fn([known](uint64_t) { return (uint64_t)known; })));
+        if (c.failed()) return fail("circuit build error: " + c.error());
+        return 0;
+    }
     if (op == "cmux") {
         const uint32_t cond = c.input(1);
         const auto t = r.input(n_blocks), f = r.input(n_blocks);

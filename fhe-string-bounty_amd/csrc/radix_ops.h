@@ -5,6 +5,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "circuit.h"
@@ -42,18 +43,30 @@ struct RadixOps {
     bool late_fits(uint32_t flag, double budget) const { return 4 * M <= T && 2.0 + 4.0 * M * M * c.node(flag).noise <= budget; }
     // propagate_single_carry_parallelized_low_latency (add.rs:518-542): sums[i] in [0, 2M-1]
     // carry_out: one more block, the carry out of the last one (a sum that needs one digit more than its operands)
+    //
+    // Two scan states share one lookup input as base * later + earlier.  A state has three values, so the base is M only
+    // from M = 4 on; 1-bit blocks take base 4, which a box below 4 * 2 + 2 + 1 = 11 cannot hold: refused.  The state of
+    // the last block is never read; 1-bit blocks do not scan it (wider blocks do, as their plans always have), so two
+    // blocks need no scan and build in any box.
+    uint32_t scan_base() const { return std::max(M, 4u); }
     std::vector<uint32_t> propagate(const std::vector<uint32_t>& sums, bool carry_out = false, const Late* late = nullptr) {
-        const uint32_t n = (uint32_t)sums.size(), m = M;
+        const uint32_t n = (uint32_t)sums.size(), m = M, base = scan_base();
+        const uint32_t scanned = m >= 4 ? n : n - 1;
+        if (scanned > 1 && base != m && 2 * base + 2 >= T) {
+            c.refuse("carry propagation over " + std::to_string(n) + " blocks: msg_mod " + std::to_string(m) + " packs two scan states in base " +
+                     std::to_string(base) + ", up to " + std::to_string(2 * base + 2) + ", beyond the box msg_mod * carry_mod = " + std::to_string(T));
+            return std::vector<uint32_t>(n + (carry_out ? 1 : 0), c.trivial(0));
+        }
         // generate_init_carry_array (add.rs:724-772): 0 = None, 1 = Generated, 2 = Propagated
         const uint32_t first = c.lut_fn([m](uint64_t x) { return (uint64_t)(x >= m ? 1 : 0); });
         const uint32_t other = c.lut_fn([m](uint64_t x) { return (uint64_t)(x >= m ? 1 : (x == m - 1 ? 2 : 0)); });
         std::vector<uint32_t> st(n);
         for (uint32_t i = 0; i < n; i++) st[i] = c.pbs(sums[i], i == 0 ? first : other);
         // compute_prefix_sum_hillis_steele (add.rs:572-624) with prefix_sum_carry_propagation (add.rs:36-42)
-        const uint32_t comb = c.lut_fn([m](uint64_t x) { const uint64_t msb = (x / m) % m, lsb = x % m; return msb == 2 ? lsb : msb; });
-        for (uint32_t space = 1; space < n; space *= 2) {
+        const uint32_t comb = c.lut_fn([base](uint64_t x) { const uint64_t msb = (x / base) % base, lsb = x % base; return msb == 2 ? lsb : msb; });
+        for (uint32_t space = 1; space < scanned; space *= 2) {
             std::vector<uint32_t> next(st);
-            for (uint32_t i = space; i < n; i++) next[i] = c.pbs(c.lin({{st[i], (int32_t)M}, {st[i - space], 1}}), comb);
+            for (uint32_t i = space; i < scanned; i++) next[i] = c.pbs(c.lin({{st[i], (int32_t)base}, {st[i - space], 1}}), comb);
             st.swap(next);
         }
         // the output carry of block i-1 is the input carry of block i; add, then message_extract
@@ -123,6 +136,11 @@ struct RadixOps {
     // packed pairs hi*M + lo as LIN nodes (pack_block_chunk, scalar_comparison.rs:104-138); a trailing
     // single block stays alone.  Encrypted operand or clear digits.
     bool pair_blocks = true;       // false: every block is compared on its own (where two packed operands exceed the noise budget)
+    // the comparator subtracts two packed pairs: 2 (1 + M^2) variances, beyond the budget of 4-bit blocks
+    bool two_pairs_fit() const {
+        const double budget = c.noise_budget() > 0 ? c.noise_budget() : 1e300;
+        return (uint64_t)M * M <= (uint64_t)T && 2.0 * (1.0 + (double)M * M) <= budget;
+    }
     std::vector<uint32_t> packed(const std::vector<uint32_t>& a) {
         if (!pair_blocks) return a;
         std::vector<uint32_t> p;

@@ -312,7 +312,15 @@ int fhe_plan_gather_outputs_dev(fhe_plan *plan, const uint64_t *d_pool, uint64_t
  *   "message_extract" "carry_extract" n_blocks blocks with full carries -> their messages / carries
  *   "cmux"                            cond (0/1 block), t, f -> cond ? t : f (radix_parallel/cmux.rs:194-316)
  *   "eq" "ne" "gt" "ge" "lt" "le"     a, b -> one 0/1 block (comparator.rs:193-280, scalar_comparison.rs:147-233)
- *   "scalar_eq" ... "scalar_le"       a, clear `scalar` (at most 64 bits) */
+ *   "scalar_eq" ... "scalar_le"       a, clear `scalar` (at most 64 bits)
+ * The scalar is a 64-bit unsigned number, not a number modulo the integer's range.  scalar_add and scalar_sub wrap, so
+ * only its low n_blocks * log2(msg_mod) bits matter.  The six scalar comparisons compare with the number itself: a scalar
+ * with a bit beyond the integer's is above every value (scalar_comparison.rs:23-60, is_scalar_out_of_bounds), so eq, gt
+ * and ge answer 0 and ne, lt and le answer 1 whatever a holds; that plan still takes a's n_blocks inputs and spends one
+ * lookup on its constant.  Two encrypted operands are compared two blocks per lookup where the parameter set's noise
+ * budget holds the difference of two packed pairs, 2 (1 + msg_mod^2) variances, and block by block where it does not.
+ * Blocks of one bit (msg_mod 2) carry a three-valued scan state in base 4: add, sub and their scalar forms on three blocks
+ * and more need msg_mod * carry_mod >= 16 and are refused below it. */
 int fhe_int_plan_create(fhe_engine *eng, const char *op, uint32_t n_blocks, uint64_t scalar, uint32_t world,
                         fhe_plan **out);
 int fhe_int_plan_create_offline(const fhe_params_t *params, const char *op, uint32_t n_blocks, uint64_t scalar,

@@ -507,3 +507,30 @@ def test_refusals_of_the_existing_names_are_unchanged():
         with pytest.raises(fhestr.FheError) as err:
             prog.op(name, *operands)
         assert reason in str(err.value), (name, str(err.value))
+
+
+# ---- 1-bit blocks ---------------------------------------------------------------------------------------------------------------
+
+P13 = dict(n=745, k=1, N=2048, pbs=(23, 1), ks=(3, 5), msg_mod=2, carry_mod=8, lwe_std=6.692125069956277e-06, glwe_std=2.9403601535432533e-16)
+ONE_BIT = [("add", 20, 20, range(32), range(32)), ("sub", 40, 40, range(0, 64, 3), range(64)), ("lt", 20, 20, range(32), range(32)),
+           ("add", 5, 3, range(8), range(4)), ("sub", 7, 9, range(8), range(16))]
+
+
+@pytest.mark.parametrize("op,a_max,b_max,values_a,values_b", ONE_BIT, ids=[f"{c[0]}-{c[1]}-{c[2]}" for c in ONE_BIT])
+def test_counts_on_one_bit_blocks(op, a_max, b_max, values_a, values_b):
+    """PARAM_MESSAGE_1_CARRY_3's shape (msg_mod 2, a box of 16), offline plans on the noise-free executor (tests/clear_plan.py): a
+    count of 20 travels in five digits, the radix code with a three-valued scan state in base 4.  Every pair of the values,
+    those above the bounds included."""
+    import fhestr
+    from clear_plan import ClearBackend, run_clear
+    P = fhestr.Params(P13["n"], P13["k"], P13["N"], *P13["pbs"], *P13["ks"], P13["msg_mod"], P13["carry_mod"], P13["lwe_std"], P13["glwe_std"],
+                      "PARAM_MESSAGE_1_CARRY_3_KS_PBS")
+    plan = fhestr.Plan.string_op(None, f"count_{op}:{a_max}:{b_max}", 0, 0, None, 1, params=P)
+    noise = plan.noise_info()
+    assert noise["max_pbs_input_noise"] <= noise["budget"]
+    backend = ClearBackend(plan, P)
+    for a, b in itertools.product(values_a, values_b):
+        msgs = run_clear(backend, encode_count(2, a, a_max) + encode_count(2, b, b_max))
+        got = decode_bit(msgs) if op in COMPARISONS else decode_digits(msgs, 2, count_bound(op, a_max, b_max))
+        assert got == count_ref(op, a, a_max, b, b_max) and backend.off_centre == 0, (op, a, b, got)
+    plan.close()

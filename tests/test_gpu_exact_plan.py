@@ -218,7 +218,7 @@ def test_plan_run_every_op(p):
         _check_run(rig, "mixed", build_mixed_plan(rig.new_plan()))
 
 
-# (shape, grouping, string ops, integer ops); the multi-bit shape's noise budget refuses the radix comparisons
+# (shape, grouping, string ops, integer ops); the radix comparisons on every shape: tests/test_gpu_integer.py
 OTHER = [(N1024, 0, (), ()), (MB_G2, 2, ("eq", "lt", "find"), ("add", "cmux")), (P22, 0, ("le",), ("le", "add"))]
 
 
