@@ -10,30 +10,15 @@ import contextlib
 import ctypes as C
 import functools
 import os
-import sys
 import typing
+import weakref
 from dataclasses import dataclass
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# FHESTR_LIB: load another build of the same library (kernel A/B experiments, scripts/ab_bench.sh)
-LIB_PATH = os.environ.get("FHESTR_LIB") or os.path.join(os.path.dirname(_HERE), "libfhestr.so")
-
-
-class FheError(RuntimeError):
-    pass
-
-
-class _Params(C.Structure):
-    _fields_ = [
-        ("n", C.c_uint32), ("k", C.c_uint32), ("N", C.c_uint32),
-        ("pbs_base_log", C.c_uint32), ("pbs_level", C.c_uint32),
-        ("ks_base_log", C.c_uint32), ("ks_level", C.c_uint32),
-        ("msg_mod", C.c_uint32), ("carry_mod", C.c_uint32),
-        ("lwe_std", C.c_double), ("glwe_std", C.c_double),
-        ("grouping_factor", C.c_uint32),
-    ]
+# _abi.py is the one place that knows the C ABI: the structures, the signature table, lib() and EXPORTS
+from ._abi import (EXPORTS, LIB_PATH, FheError, _CastParams, _check, _clear, _Handle, _last_error, _nonzero,  # noqa: F401
+                   _PackingParams, _Params, _ptr, _record, _u64, lib, seed_bytes)
 
 
 @dataclass(frozen=True)
@@ -123,352 +108,9 @@ PARAM_MESSAGE_1_CARRY_1_KS_PBS = Params(684, 3, 512, 18, 1, 4, 3, 2, 2,
                                         0.00002043784477291318, 0.0000000000034525330484572114,
                                         "PARAM_MESSAGE_1_CARRY_1_KS_PBS")
 
-class _PackingParams(C.Structure):
-    _fields_ = [("base_log", C.c_uint32), ("level", C.c_uint32)]
-
-
-class _CastParams(C.Structure):
-    _fields_ = [("src", _Params), ("base_log", C.c_uint32), ("level", C.c_uint32), ("target", C.c_uint32)]
-
 
 CAST_TO_BIG, CAST_TO_SMALL = 0, 1                      # fhe_cast_params_t.target
 CAST_RAW, CAST_REFRESH, CAST_KEYSWITCHED = 0, 1, 2     # the mode of a cast
-
-
-_lib = None
-
-EXPORTS = [
-    "fhe_last_error", "fhe_kernel_revision", "fhe_engine_create", "fhe_engine_destroy", "fhe_engine_params",
-    "fhe_engine_load_keys", "fhe_engine_generate_keys", "fhe_engine_stream", "fhe_engine_synchronize", "fhe_engine_set_variant",
-    "fhe_engine_set_multibit_combine_max", "fhe_engine_set_cluster_mode", "fhe_engine_set_keep_busy", "fhe_engine_pipeline_input_event", "fhe_engine_cluster_info", "fhe_engine_keyswitch_info", "fhe_engine_cluster_fallbacks", "fhe_engine_load_seeded_keys", "fhe_engine_set_pipeline",
-    "fhe_lut_generate", "fhe_lut_upload", "fhe_lut_download", "fhe_lut_count",
-    "fhe_keyswitch_batch", "fhe_pbs_batch", "fhe_ks_pbs_batch", "fhe_ks_pbs_batch_dev", "fhe_pbs_ks_batch",
-    "fhe_lwe_lincomb_batch", "fhe_last_kernel_ms", "fhe_kernel_times",
-    "fhe_params_ksk_len", "fhe_params_bsk_len", "fhe_client_key_create", "fhe_client_key_destroy",
-    "fhe_client_encrypt", "fhe_client_decrypt", "fhe_client_gen_server_keys", "fhe_client_secret_keys",
-    "fhe_random_seed", "fhe_chacha20_block", "fhe_int_plan_create", "fhe_int_plan_create_offline",
-    "fhe_wire_write_lwe_ciphertext", "fhe_wire_read_lwe_ciphertext", "fhe_wire_write_keyswitch_key",
-    "fhe_wire_read_keyswitch_key", "fhe_wire_write_bootstrap_key", "fhe_wire_read_bootstrap_key",
-    "fhe_wire_write_shortint_ciphertext", "fhe_wire_read_shortint_ciphertext",
-    "fhe_aes128_encrypt_block", "fhe_seeded_mask_words", "fhe_seeded_decompress_keyswitch_key",
-    "fhe_seeded_decompress_bootstrap_key", "fhe_seeded_split_keyswitch_key", "fhe_seeded_split_bootstrap_key",
-    "fhe_wire_write_seeded_keyswitch_key", "fhe_wire_read_seeded_keyswitch_key", "fhe_wire_write_seeded_bootstrap_key",
-    "fhe_wire_read_seeded_bootstrap_key", "fhe_wire_write_multi_bit_bootstrap_key", "fhe_wire_read_multi_bit_bootstrap_key",
-    "fhe_wire_write_compressed_server_key", "fhe_wire_read_compressed_server_key",
-    "fhe_compact_pk_len", "fhe_compact_list_len", "fhe_client_gen_compact_public_key", "fhe_compact_pk_encrypt",
-    "fhe_compact_expand_host", "fhe_compact_conv", "fhe_engine_expand_compact_list", "fhe_engine_expand_compact_list_dev",
-    "fhe_wire_write_compact_list", "fhe_wire_read_compact_list", "fhe_wire_write_shortint_compact_list",
-    "fhe_wire_read_shortint_compact_list", "fhe_wire_write_compact_public_key", "fhe_wire_read_compact_public_key",
-    "fhe_engine_expand_seeded_lwe", "fhe_seeded_decompress_lwe_batch", "fhe_wire_write_compressed_ciphertext",
-    "fhe_wire_read_compressed_ciphertext", "fhe_wire_write_radix_ciphertext", "fhe_wire_read_radix_ciphertext",
-    "fhe_wire_write_compressed_radix_ciphertext", "fhe_wire_read_compressed_radix_ciphertext",
-    "fhe_plan_create", "fhe_plan_destroy", "fhe_plan_input", "fhe_plan_lut", "fhe_plan_lin", "fhe_plan_pbs",
-    "fhe_plan_output", "fhe_plan_finalize", "fhe_plan_info", "fhe_plan_level_info", "fhe_plan_export_level",
-    "fhe_plan_run", "fhe_plan_run_level_rank_dev", "fhe_plan_gather_outputs_dev", "fhe_str_plan_create",
-    "fhe_plan_level_rank_info", "fhe_plan_noise_info", "fhe_noise_model", "fhe_noise_model_is_calibrated", "fhe_params_supported", "fhe_plan_run_batch", "fhe_plan_run_batch_dev", "fhe_str_op", "fhe_str_op_many", "fhe_plan_set_noise_budget",
-    "fhe_host_alloc", "fhe_host_free",
-    "fhe_plan_pbs_signed", "fhe_plan_pbs_full_box", "fhe_plan_set_owner_hint",
-    "fhe_str_to_upper", "fhe_str_to_lower", "fhe_plan_create_offline", "fhe_str_plan_create_offline",
-    "fhe_str_trim_start", "fhe_str_trim_end", "fhe_str_strip", "fhe_str_replace", "fhe_str_replace_clear",
-    "fhe_plan_lut_count", "fhe_plan_export_lut", "fhe_engine_set_stream", "fhe_engine_reset_stream",
-    "fhe_str_len", "fhe_str_is_empty", "fhe_str_strip_prefix_clear", "fhe_str_strip_suffix_clear",
-    "fhe_str_strip_prefix", "fhe_str_strip_suffix", "fhe_str_replace_general", "fhe_str_replace_clear_general",
-    "fhe_packing_default_params", "fhe_packing_key_len", "fhe_packed_glwe_len", "fhe_client_gen_packing_key",
-    "fhe_client_decrypt_packed", "fhe_packing_keyswitch_host", "fhe_engine_load_packing_key", "fhe_engine_pack_lwes",
-    "fhe_engine_pack_lwes_dev", "fhe_engine_packing_info", "fhe_wire_write_packing_key", "fhe_wire_read_packing_key",
-    "fhe_ring_packing_default_params", "fhe_ring_packing_key_len", "fhe_ring_packing_noise", "fhe_ring_narrow_noise",
-    "fhe_ring_pack_keyswitches", "fhe_client_gen_ring_packing_key", "fhe_ring_pack_host", "fhe_ring_ntt_host", "fhe_ring_product_host",
-    "fhe_engine_load_ring_packing_key", "fhe_engine_ring_pack_lwes", "fhe_engine_ring_pack_lwes_dev", "fhe_engine_ring_pack_info",
-    "fhe_engine_ring_ntt", "fhe_wire_write_ring_packing_key", "fhe_wire_read_ring_packing_key",
-    "fhe_wire_write_glwe_ciphertext", "fhe_wire_read_glwe_ciphertext", "fhe_wire_write_glwe_list", "fhe_wire_read_glwe_list",
-    "fhe_glwe_sample_extract_host", "fhe_packing_unpack_noise", "fhe_engine_unpack_glwes", "fhe_engine_unpack_glwes_dev",
-    "fhe_engine_unpack_info",
-    "fhe_narrow_noise", "fhe_narrow_default_bits", "fhe_narrow_len", "fhe_glwe_narrow_host", "fhe_glwe_widen_host",
-    "fhe_narrow_sample_extract_host", "fhe_client_decrypt_narrow", "fhe_engine_narrow_glwes", "fhe_engine_narrow_glwes_dev",
-    "fhe_engine_widen_narrow_dev", "fhe_engine_unpack_narrow", "fhe_engine_unpack_narrow_dev", "fhe_engine_narrow_info", "fhe_wire_write_narrow_list",
-    "fhe_wire_read_narrow_list",
-    "fhe_stream_cipher_info", "fhe_stream_cipher_keystream", "fhe_transcipher_supported", "fhe_transcipher_table", "fhe_transcipher_ring_len",
-    "fhe_transcipher_init_host", "fhe_transcipher_gather_host", "fhe_transcipher_apply_host", "fhe_engine_transcipher_init",
-    "fhe_engine_transcipher_gather", "fhe_engine_transcipher_apply", "fhe_transcipher_create", "fhe_transcipher_destroy",
-    "fhe_transcipher_begin", "fhe_transcipher_next", "fhe_transcipher_info", "fhe_transcipher_timing",
-    "fhe_cast_default_params", "fhe_cast_key_len", "fhe_cast_rshift", "fhe_client_gen_cast_key", "fhe_cast_host", "fhe_cast_noise",
-    "fhe_cast_key_create", "fhe_cast_key_destroy", "fhe_cast_key_info", "fhe_cast_key_set_fused", "fhe_cast_key_set_group", "fhe_cast_key_set_input_noise",
-    "fhe_cast_lwes", "fhe_cast_lwes_dev", "fhe_cast_packed", "fhe_cast_packed_dev", "fhe_cast_narrow", "fhe_cast_narrow_dev",
-    "fhe_cast_regroup_check", "fhe_cast_debug_digits",
-] + [f"fhe_str_{n}{s}" for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat")
-     for s in ("", "_clear")] + ["fhe_str_repeat_clear", "fhe_str_split", "fhe_str_replacen", "fhe_str_replacen_clear",
-                                   "fhe_str_repeat", "fhe_str_replacen_encn", "fhe_str_replacen_encn_clear", "fhe_str_splitn_encn",
-                                   "fhe_str_slice", "fhe_str_combine", "fhe_str_program_input_bit", "fhe_str_matches_clear", "fhe_regex_check",
-                                   "fhe_str_program_create", "fhe_str_program_create_offline", "fhe_str_program_destroy",
-                                   "fhe_str_program_set_dedupe", "fhe_str_program_input_string", "fhe_str_program_input_count",
-                                   "fhe_str_program_op", "fhe_str_program_value_info", "fhe_str_program_output",
-                                   "fhe_str_program_finish"]
-
-
-def lib() -> C.CDLL:
-    """Load libfhestr.so; raises if it has not been built (no fallback)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise FheError(f"{LIB_PATH} is missing: run `make -C fhe-string-bounty_amd` "
-                       "(or __graft_entry__.build()); there is no CPU fallback")
-    # PyTorch-ROCm wheels bundle their own libamdhip64.so.7 / libhsa-runtime64: two HIP runtimes in
-    # one process do not see the same device (the second one finds no GPU) and cannot share streams.
-    # Importing torch first makes its copy the process-wide one; libfhestr.so (NEEDED libamdhip64.so.7)
-    # then binds to it, so torch streams / tensors and the engine live in a single runtime.
-    if "torch" not in sys.modules:
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-    L = C.CDLL(LIB_PATH)
-    vp, u32, i32 = C.c_void_p, C.c_uint32, C.c_int
-    PP = C.POINTER(_Params)
-    L.fhe_last_error.restype = C.c_char_p
-    L.fhe_last_error.argtypes = []
-    L.fhe_kernel_revision.restype = C.c_char_p
-    L.fhe_kernel_revision.argtypes = []
-    L.fhe_engine_stream.restype = vp
-    L.fhe_engine_stream.argtypes = [vp]
-
-    def sig(name, *args):
-        fn = getattr(L, name)
-        fn.restype = i32
-        fn.argtypes = list(args)
-
-    sig("fhe_engine_create", PP, i32, C.POINTER(vp))
-    sig("fhe_engine_destroy", vp)
-    sig("fhe_engine_params", vp, PP)
-    sig("fhe_engine_load_keys", vp, vp, vp)
-    sig("fhe_engine_generate_keys", vp, vp, vp, vp, vp, vp)
-    sig("fhe_random_seed", vp)
-    sig("fhe_chacha20_block", vp, C.c_uint64, C.c_uint64, vp)
-    sig("fhe_debug_det_log", vp, C.c_size_t, vp)
-    sig("fhe_debug_noise_samples", vp, C.c_uint64, C.c_double, C.c_size_t, vp)
-    sig("fhe_debug_round_torus", vp, C.c_size_t, vp, vp)
-    sig("fhe_engine_synchronize", vp)
-    sig("fhe_engine_set_variant", vp, i32)
-    sig("fhe_engine_set_multibit_combine_max", vp, u32)
-    sig("fhe_engine_set_pipeline", vp, i32)
-    sig("fhe_engine_set_cluster_mode", vp, i32, u32)
-    sig("fhe_engine_set_keep_busy", vp, C.c_int)
-    sig("fhe_engine_cluster_info", vp, C.POINTER(u32))
-    sig("fhe_engine_keyswitch_info", vp, C.POINTER(u32))
-    sig("fhe_engine_cluster_fallbacks", vp, C.POINTER(u32))
-    sig("fhe_engine_load_seeded_keys", vp, vp, vp, vp, vp, vp, vp)
-    sig("fhe_engine_expand_seeded_lwe", vp, vp, vp, u32, vp, vp)
-    sig("fhe_engine_expand_compact_list", vp, vp, u32, vp, vp)
-    sig("fhe_engine_expand_compact_list_dev", vp, vp, u32, vp)
-    sig("fhe_client_gen_compact_public_key", vp, vp, vp)
-    sig("fhe_compact_pk_encrypt", PP, vp, vp, vp, u32, vp, i32)
-    sig("fhe_compact_expand_host", u32, vp, u32, vp)
-    sig("fhe_compact_conv", vp, vp, u32, vp, i32)
-    L.fhe_compact_pk_len.restype = C.c_size_t
-    L.fhe_compact_pk_len.argtypes = [PP]
-    L.fhe_compact_list_len.restype = C.c_size_t
-    L.fhe_compact_list_len.argtypes = [PP, u32]
-    sig("fhe_lut_generate", vp, vp, C.POINTER(u32), C.POINTER(C.c_uint64))
-    sig("fhe_lut_upload", vp, vp, C.POINTER(u32))
-    sig("fhe_lut_download", vp, u32, vp)
-    sig("fhe_lut_count", vp, C.POINTER(u32))
-    sig("fhe_keyswitch_batch", vp, vp, vp, u32)
-    sig("fhe_pbs_batch", vp, vp, vp, vp, u32)
-    sig("fhe_ks_pbs_batch", vp, vp, vp, vp, u32)
-    sig("fhe_ks_pbs_batch_dev", vp, vp, vp, vp, u32)
-    sig("fhe_pbs_ks_batch", vp, vp, vp, vp, u32)
-    sig("fhe_lwe_lincomb_batch", vp, vp, u32, vp, vp, vp, vp, vp, u32)
-    sig("fhe_last_kernel_ms", vp, C.POINTER(C.c_float))
-    sig("fhe_kernel_times", vp, C.POINTER(C.c_double), C.POINTER(u32), i32)
-    sig("fhe_client_key_create", PP, vp, C.POINTER(vp))
-    sig("fhe_client_key_destroy", vp)
-    sig("fhe_client_encrypt", vp, vp, u32, vp)
-    sig("fhe_client_decrypt", vp, vp, u32, vp)
-    sig("fhe_client_gen_server_keys", vp, vp, vp, i32)
-    sig("fhe_client_secret_keys", vp, vp, vp)
-    sig("fhe_plan_create", vp, C.POINTER(vp))
-    sig("fhe_plan_destroy", vp)
-    sig("fhe_plan_create_offline", PP, C.POINTER(vp))
-    sig("fhe_str_plan_create_offline", PP, C.c_char_p, u32, u32, vp, u32, u32, C.POINTER(vp))
-    sig("fhe_plan_lut_count", vp, C.POINTER(u32))
-    sig("fhe_plan_export_lut", vp, u32, vp)
-    sig("fhe_engine_set_stream", vp, vp)
-    sig("fhe_engine_reset_stream", vp)
-    sig("fhe_plan_input", vp, C.c_uint64, C.POINTER(u32))
-    sig("fhe_plan_lut", vp, vp, C.POINTER(u32))
-    sig("fhe_plan_lin", vp, vp, vp, u32, C.c_int64, C.POINTER(u32))
-    sig("fhe_plan_pbs", vp, u32, u32, C.POINTER(u32))
-    sig("fhe_plan_output", vp, u32)
-    sig("fhe_plan_finalize", vp, u32)
-    sig("fhe_plan_info", vp, C.POINTER(u32))
-    sig("fhe_plan_level_info", vp, u32, C.POINTER(u32))
-    sig("fhe_plan_export_level", vp, u32, vp, vp, vp, vp, vp)
-    sig("fhe_plan_run", vp, vp, vp)
-    sig("fhe_plan_run_batch", vp, u32, vp, vp)
-    sig("fhe_plan_run_batch_dev", vp, u32, vp, vp)
-    sig("fhe_str_op", vp, C.c_char_p, vp, vp, u32, vp, vp, u32, vp, C.POINTER(u32))
-    sig("fhe_str_op_many", vp, C.c_char_p, vp, u32, u32, vp, u32, vp, u32, vp, C.POINTER(u32))
-    sig("fhe_plan_run_level_rank_dev", vp, vp, u32, u32)
-    sig("fhe_plan_level_rank_info", vp, u32, u32, C.POINTER(u32))
-    sig("fhe_plan_noise_info", vp, C.POINTER(C.c_double))
-    sig("fhe_noise_model", PP, C.POINTER(C.c_double))
-    sig("fhe_noise_model_is_calibrated", PP)
-    sig("fhe_params_supported", PP)
-    sig("fhe_host_alloc", C.c_size_t, C.POINTER(vp))
-    sig("fhe_host_free", vp)
-    sig("fhe_plan_set_noise_budget", vp, C.c_double)
-    sig("fhe_plan_pbs_signed", vp, u32, u32, C.POINTER(u32))
-    sig("fhe_plan_pbs_full_box", vp, u32, C.c_int, C.POINTER(u32))
-    sig("fhe_plan_set_owner_hint", vp, i32)
-    sig("fhe_plan_gather_outputs_dev", vp, vp, vp)
-    sig("fhe_str_plan_create", vp, C.c_char_p, u32, u32, vp, u32, u32, C.POINTER(vp))
-    sig("fhe_int_plan_create", vp, C.c_char_p, u32, C.c_uint64, u32, C.POINTER(vp))
-    sig("fhe_int_plan_create_offline", PP, C.c_char_p, u32, C.c_uint64, u32, C.POINTER(vp))
-    sig("fhe_str_len", vp, vp, u32, vp)
-    sig("fhe_str_is_empty", vp, vp, u32, vp)
-    sig("fhe_str_strip_prefix_clear", vp, vp, u32, vp, u32, vp)
-    sig("fhe_str_strip_suffix_clear", vp, vp, u32, vp, u32, vp)
-    sig("fhe_str_repeat_clear", vp, vp, u32, u32, vp)
-    sig("fhe_str_strip_prefix", vp, vp, u32, vp, u32, vp)
-    sig("fhe_str_strip_suffix", vp, vp, u32, vp, u32, vp)
-    sig("fhe_str_replace_general", vp, vp, u32, vp, u32, vp, u32, u32, vp)
-    sig("fhe_str_replace_clear_general", vp, vp, u32, vp, u32, vp, u32, u32, vp)
-    sig("fhe_str_replacen", vp, vp, u32, vp, u32, vp, u32, u32, u32, vp)
-    sig("fhe_str_replacen_clear", vp, vp, u32, vp, u32, vp, u32, u32, u32, vp)
-    sig("fhe_str_split", vp, C.c_char_p, vp, u32, vp, u32, vp, u32, u32, u32, vp, C.POINTER(u32))
-    sig("fhe_str_repeat", vp, vp, u32, vp, u32, vp)
-    sig("fhe_str_replacen_encn", vp, vp, u32, vp, u32, vp, u32, vp, u32, u32, vp)
-    sig("fhe_str_replacen_encn_clear", vp, vp, u32, vp, u32, vp, u32, vp, u32, u32, vp)
-    sig("fhe_str_splitn_encn", vp, C.c_char_p, vp, u32, vp, u32, vp, u32, vp, u32, u32, vp, C.POINTER(u32))
-    sig("fhe_str_slice", vp, C.c_char_p, vp, u32, vp, u32, vp, u32, vp, u32, u32, vp, C.POINTER(u32))
-    for n in ("eq", "ne", "starts_with", "ends_with", "contains", "find", "rfind", "eq_ignore_case", "lt", "le", "gt", "ge", "concat"):
-        sig(f"fhe_str_{n}", vp, vp, u32, vp, u32, vp)
-        sig(f"fhe_str_{n}_clear", vp, vp, u32, vp, u32, vp)
-    sig("fhe_str_matches_clear", vp, vp, u32, vp, u32, vp)
-    sig("fhe_regex_check", vp, u32, C.POINTER(u32), C.POINTER(u32))
-    sig("fhe_str_program_create", vp, C.POINTER(vp))
-    sig("fhe_str_program_create_offline", PP, C.POINTER(vp))
-    sig("fhe_str_program_destroy", vp)
-    sig("fhe_str_program_set_dedupe", vp, i32)
-    sig("fhe_str_program_input_string", vp, u32, C.POINTER(u32))
-    sig("fhe_str_program_input_count", vp, u32, C.POINTER(u32))
-    sig("fhe_str_program_input_bit", vp, C.POINTER(u32))
-    sig("fhe_str_combine", vp, C.c_char_p, vp, vp, u32, vp, u32, vp, C.POINTER(u32))
-    sig("fhe_str_program_op", vp, C.c_char_p, vp, u32, vp, u32, vp, u32, C.POINTER(u32))
-    sig("fhe_str_program_value_info", vp, u32, C.POINTER(u32))
-    sig("fhe_str_program_output", vp, u32)
-    sig("fhe_str_program_finish", vp, u32, C.POINTER(vp))
-    for n in ("trim_start", "trim_end", "strip"):
-        sig(f"fhe_str_{n}", vp, vp, u32, vp)
-    sig("fhe_str_replace", vp, vp, u32, vp, u32, vp)
-    sig("fhe_str_replace_clear", vp, vp, u32, vp, vp, u32, vp)
-    sig("fhe_str_to_upper", vp, vp, u32, vp)
-    sig("fhe_str_to_lower", vp, vp, u32, vp)
-    KP = C.POINTER(_PackingParams)
-    sig("fhe_packing_default_params", PP, KP)
-    L.fhe_packing_key_len.restype = C.c_size_t
-    L.fhe_packing_key_len.argtypes = [PP, KP]
-    L.fhe_packed_glwe_len.restype = C.c_size_t
-    L.fhe_packed_glwe_len.argtypes = [PP, u32]
-    sig("fhe_client_gen_packing_key", vp, KP, vp, vp, i32)
-    sig("fhe_client_decrypt_packed", vp, vp, u32, vp)
-    sig("fhe_packing_keyswitch_host", PP, KP, vp, vp, u32, vp)
-    sig("fhe_engine_load_packing_key", vp, KP, vp)
-    sig("fhe_engine_pack_lwes", vp, vp, u32, vp)
-    sig("fhe_engine_pack_lwes_dev", vp, vp, u32, vp)
-    sig("fhe_engine_packing_info", vp, C.POINTER(u32))
-    sig("fhe_ring_packing_default_params", PP, KP)
-    L.fhe_ring_packing_key_len.restype = C.c_size_t
-    L.fhe_ring_packing_key_len.argtypes = [PP, KP]
-    sig("fhe_ring_packing_noise", PP, KP, C.POINTER(C.c_double))
-    sig("fhe_ring_narrow_noise", PP, KP, u32, C.POINTER(C.c_double))
-    L.fhe_ring_pack_keyswitches.restype = C.c_uint64
-    L.fhe_ring_pack_keyswitches.argtypes = [PP, u32]
-    sig("fhe_client_gen_ring_packing_key", vp, KP, vp, vp, i32)
-    sig("fhe_ring_pack_host", PP, KP, vp, vp, u32, vp)
-    sig("fhe_ring_ntt_host", u32, i32, vp, u32)
-    sig("fhe_ring_product_host", u32, u32, vp, vp, vp)
-    sig("fhe_engine_load_ring_packing_key", vp, KP, vp)
-    sig("fhe_engine_ring_pack_lwes", vp, vp, u32, vp)
-    sig("fhe_engine_ring_pack_lwes_dev", vp, vp, u32, vp)
-    sig("fhe_engine_ring_pack_info", vp, C.POINTER(C.c_uint64))
-    sig("fhe_engine_ring_ntt", vp, u32, i32, vp, u32)
-    sig("fhe_glwe_sample_extract_host", PP, vp, u32, u32, vp)
-    sig("fhe_packing_unpack_noise", PP, KP, C.POINTER(C.c_double))
-    sig("fhe_engine_unpack_glwes", vp, vp, u32, u32, i32, vp)
-    sig("fhe_engine_unpack_glwes_dev", vp, vp, u32, u32, i32, vp)
-    sig("fhe_engine_unpack_info", vp, C.POINTER(u32))
-    sig("fhe_narrow_noise", PP, KP, u32, C.POINTER(C.c_double))
-    sig("fhe_narrow_default_bits", PP, KP, i32, C.POINTER(u32))
-    L.fhe_narrow_len.restype = C.c_size_t
-    L.fhe_narrow_len.argtypes = [PP, u32, u32]
-    sig("fhe_glwe_narrow_host", PP, vp, u32, u32, vp)
-    sig("fhe_glwe_widen_host", PP, vp, u32, u32, vp)
-    sig("fhe_narrow_sample_extract_host", PP, vp, u32, u32, u32, u32, vp)
-    sig("fhe_client_decrypt_narrow", vp, vp, u32, u32, vp)
-    sig("fhe_engine_narrow_glwes", vp, vp, u32, u32, vp)
-    sig("fhe_engine_narrow_glwes_dev", vp, vp, u32, u32, vp)
-    sig("fhe_engine_widen_narrow_dev", vp, vp, u32, u32, vp)
-    sig("fhe_engine_unpack_narrow", vp, vp, u32, u32, u32, u32, i32, vp)
-    sig("fhe_engine_unpack_narrow_dev", vp, vp, u32, u32, u32, u32, i32, vp)
-    sig("fhe_engine_narrow_info", vp, C.POINTER(u32))
-    sig("fhe_wire_write_narrow_list", PP, vp, u32, u32, vp, C.c_size_t, C.POINTER(C.c_size_t))
-    sig("fhe_wire_read_narrow_list", PP, vp, C.c_size_t, vp, C.c_size_t, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_size_t))
-    sig("fhe_stream_cipher_info", u32, C.POINTER(u32))
-    sig("fhe_stream_cipher_keystream", u32, vp, vp, C.c_uint64, vp, C.c_size_t)
-    sig("fhe_transcipher_supported", PP, u32)
-    sig("fhe_transcipher_table", PP, u32, vp, C.POINTER(u32))
-    L.fhe_transcipher_ring_len.restype = C.c_size_t
-    L.fhe_transcipher_ring_len.argtypes = [PP, u32]
-    sig("fhe_transcipher_init_host", PP, u32, u32, vp, vp, vp)
-    sig("fhe_transcipher_gather_host", PP, u32, u32, C.c_int32, u32, vp, vp, vp, vp, u32, u32, vp, vp)
-    sig("fhe_transcipher_apply_host", PP, u32, u32, C.c_int32, vp, u32, u32, vp)
-    sig("fhe_engine_transcipher_init", vp, u32, u32, vp, vp, vp)
-    sig("fhe_engine_transcipher_gather", vp, u32, u32, C.c_int32, u32, vp, vp, vp, vp, u32, u32, vp, vp)
-    sig("fhe_engine_transcipher_apply", vp, u32, u32, C.c_int32, vp, u32, u32, vp)
-    sig("fhe_transcipher_create", vp, u32, vp, u32, C.POINTER(vp))
-    sig("fhe_transcipher_destroy", vp)
-    sig("fhe_transcipher_begin", vp, vp, u32)
-    sig("fhe_transcipher_next", vp, vp, u32, i32, vp, vp)
-    sig("fhe_transcipher_info", vp, C.POINTER(u32))
-    sig("fhe_transcipher_timing", vp, i32, C.POINTER(C.c_double), C.POINTER(u32))
-    CP = C.POINTER(_CastParams)
-    sig("fhe_cast_default_params", PP, PP, u32, CP)
-    L.fhe_cast_key_len.restype = C.c_size_t
-    L.fhe_cast_key_len.argtypes = [PP, CP]
-    sig("fhe_cast_rshift", PP, PP, C.POINTER(C.c_int32))
-    sig("fhe_client_gen_cast_key", vp, vp, CP, vp, vp)
-    sig("fhe_cast_host", PP, CP, vp, vp, u32, vp)
-    sig("fhe_cast_noise", PP, CP, C.c_double, C.POINTER(C.c_double))
-    sig("fhe_cast_key_create", vp, CP, vp, C.POINTER(vp))
-    sig("fhe_cast_key_destroy", vp)
-    sig("fhe_cast_key_info", vp, C.POINTER(u32))
-    sig("fhe_cast_key_set_fused", vp, i32)
-    sig("fhe_cast_key_set_group", vp, u32)
-    sig("fhe_cast_key_set_input_noise", vp, C.c_double)
-    sig("fhe_cast_lwes", vp, vp, u32, i32, vp)
-    sig("fhe_cast_lwes_dev", vp, vp, u32, i32, vp)
-    sig("fhe_cast_packed", vp, vp, u32, u32, i32, vp)
-    sig("fhe_cast_packed_dev", vp, vp, u32, u32, i32, vp)
-    sig("fhe_cast_narrow", vp, vp, u32, u32, u32, u32, i32, vp)
-    sig("fhe_cast_narrow_dev", vp, vp, u32, u32, u32, u32, i32, vp)
-    sig("fhe_cast_regroup_check", PP, PP, u32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
-    sig("fhe_cast_debug_digits", vp, vp, u32, u32, i32, vp, C.POINTER(C.c_size_t))
-    for name in ("fhe_params_ksk_len", "fhe_params_bsk_len"):
-        getattr(L, name).restype = C.c_size_t
-        getattr(L, name).argtypes = [PP]
-    _lib = L
-    return L
-
-
-def seed_bytes(seed) -> bytes:
-    """256-bit seed (ChaCha20 key) as 32 bytes.  Tests pass small integers (little endian, zero extended);
-    production code passes random_seed()."""
-    if isinstance(seed, (bytes, bytearray)):
-        if len(seed) != 32:
-            raise FheError("a seed is 32 bytes")
-        return bytes(seed)
-    return int(seed).to_bytes(32, "little")
 
 
 def random_seed() -> bytes:
@@ -513,7 +155,6 @@ def debug_round_torus(x):
 def pinned_empty(shape, dtype=np.uint64):
     """numpy array in page-locked host memory (fhe_host_alloc): host <-> GPU copies of it run at the full PCIe rate and
     never page-fault.  Freed when the array (and every view of it) is gone."""
-    import weakref
     shape = tuple(int(d) for d in (shape if isinstance(shape, (tuple, list)) else (shape,)))
     dt = np.dtype(dtype)
     n = int(np.prod(shape)) if shape else 1
@@ -529,7 +170,7 @@ def params_supported(params: "Params"):
     """(True, "") if fhe_engine_create would accept the parameters, else (False, reason).  Needs no device."""
     if lib().fhe_params_supported(C.byref(params.c())) == 0:
         return True, ""
-    return False, lib().fhe_last_error().decode()
+    return False, _last_error()
 
 
 def noise_model_is_calibrated(params: "Params") -> bool:
@@ -539,9 +180,8 @@ def noise_model_is_calibrated(params: "Params") -> bool:
 
 def noise_model(params: "Params") -> dict:
     """Variance model of one KS -> PBS (csrc/noise_model.h): variances with the torus = 1."""
-    a = (C.c_double * 6)()
-    _check(lib().fhe_noise_model(C.byref(params.c()), a))
-    return dict(zip(("v_pbs", "v_ks", "v_ms", "half_box", "budget", "log2_pfail_at_budget"), map(float, a)))
+    a = _record(C.c_double, 6, lib().fhe_noise_model, C.byref(params.c()))
+    return dict(zip(("v_pbs", "v_ks", "v_ms", "half_box", "budget", "log2_pfail_at_budget"), a))
 
 
 def regex_check(regex) -> dict:
@@ -549,27 +189,13 @@ def regex_check(regex) -> dict:
     expanded pattern, "max_len": the longest match in characters, None when unbounded}.  Raises FheError with the reason
     (a malformed pattern: with the byte offset)."""
     regex = regex.encode() if isinstance(regex, str) else bytes(regex)
-    buf = (C.c_uint8 * max(1, len(regex)))(*regex)
     m, longest = C.c_uint32(0), C.c_uint32(0)
-    _check(lib().fhe_regex_check(buf, len(regex), C.byref(m), C.byref(longest)))
+    _check(lib().fhe_regex_check(*_clear(regex), C.byref(m), C.byref(longest)))
     return {"positions": m.value, "max_len": None if longest.value == 0xFFFFFFFF else longest.value}
 
 
 def kernel_revision() -> str:
     return lib().fhe_kernel_revision().decode()
-
-
-def _check(rc: int):
-    if rc != 0:
-        raise FheError(lib().fhe_last_error().decode() or "fhestr call failed")
-
-
-def _u64(a) -> np.ndarray:
-    return np.ascontiguousarray(a, dtype=np.uint64)
-
-
-def _ptr(a: np.ndarray):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 # ---- transciphering (include/fhestr.h, "transciphering"; csrc/stream_cipher.h, csrc/transcipher.h) ----
@@ -587,9 +213,7 @@ def _cipher_id(cipher) -> int:
 def stream_cipher_info(cipher) -> dict:
     """{"key_bits", "iv_bits", "warmup_steps"} of 'trivium' (80-bit: for its published vectors and parity with the
     reference) or 'kreyvium' (128-bit: the one that matches the 128-bit parameter sets)."""
-    a = (C.c_uint32 * 3)()
-    _check(lib().fhe_stream_cipher_info(_cipher_id(cipher), a))
-    return {"key_bits": int(a[0]), "iv_bits": int(a[1]), "warmup_steps": int(a[2])}
+    return dict(zip(("key_bits", "iv_bits", "warmup_steps"), _record(C.c_uint32, 3, lib().fhe_stream_cipher_info, _cipher_id(cipher))))
 
 
 def _cipher_bytes(cipher, what: str, b) -> np.ndarray:
@@ -624,7 +248,7 @@ def transcipher_supported(params: "Params", cipher):
     """(True, "") if the parameter set can run the cipher homomorphically, else (False, reason).  Needs no device."""
     if lib().fhe_transcipher_supported(C.byref(params.c()), _cipher_id(cipher)) == 0:
         return True, ""
-    return False, lib().fhe_last_error().decode()
+    return False, _last_error()
 
 
 def transcipher_tables(params: "Params") -> np.ndarray:
@@ -685,17 +309,32 @@ def transcipher_apply_host(params: "Params", cipher, streams: int, round: int, r
     return out
 
 
-class Engine:
+class Engine(_Handle):
     """One GPU's evaluation engine: resident keys + LUTs, batched KS/PBS (mirrors the evaluation
     half of shortint::ServerKey, tfhe/src/shortint/server_key/mod.rs)."""
+    _destroy = "fhe_engine_destroy"
 
     def __init__(self, params: Params, device: int = 0, log2_points: int = 0):
         self.params = params
         self.device = device
         self._h = C.c_void_p()
+        self._dependents = weakref.WeakSet()    # what points into this engine and is closed before it: see _adopt
+        self.packing_pair = None                # the (base_log, level) given to load_packing_key
+        self.ring_packing_pair = None           # ... and to load_ring_packing_key
         _check(lib().fhe_engine_create(C.byref(params.c()), device, C.byref(self._h)))
         if log2_points:
             _check(lib().fhe_engine_set_variant(self._h, log2_points))
+
+    def _adopt(self, obj):
+        """close() closes `obj` before the engine goes: what it holds points into the engine.  obj._close_rank orders
+        them: the string operations' cached plans (0) go before string programs and their compiled plans (1)."""
+        self._dependents.add(obj)
+
+    def _export_buffers(self, export: bool):
+        """(bsk, ksk) arrays for the standard-domain keys a loading call also hands back, (None, None) without export."""
+        if not export:
+            return None, None
+        return np.zeros(self.params.bsk_len, dtype=np.uint64), np.zeros(self.params.ksk_len, dtype=np.uint64)
 
     def load_seeded_keys(self, ksk_seed, ksk_bodies, bsk_seed, bsk_bodies, export: bool = False):
         """A tfhe-rs CompressedServerKey (shortint/server_key/compressed.rs): bodies + two 128-bit compression seeds
@@ -706,10 +345,8 @@ class Engine:
             raise FheError("seeded key: body count does not match the parameter set")
         seeds = [(C.c_uint8 * 16).from_buffer_copy(s.to_bytes(16, "little") if isinstance(s, int) else bytes(s))
                  for s in (ksk_seed, bsk_seed)]
-        bsk = np.zeros(p.bsk_len, dtype=np.uint64) if export else None
-        ksk = np.zeros(p.ksk_len, dtype=np.uint64) if export else None
-        _check(lib().fhe_engine_load_seeded_keys(self._h, seeds[0], _ptr(kb), seeds[1], _ptr(bb),
-                                                 _ptr(bsk) if export else None, _ptr(ksk) if export else None))
+        bsk, ksk = self._export_buffers(export)
+        _check(lib().fhe_engine_load_seeded_keys(self._h, seeds[0], _ptr(kb), seeds[1], _ptr(bb), _ptr(bsk), _ptr(ksk)))
         return (bsk, ksk) if export else None
 
     def expand_seeded_lwe(self, seeds, bodies, d_out: int | None = None):
@@ -780,9 +417,7 @@ class Engine:
         """What the last keyswitch launch ran (fhe_engine_keyswitch_info, include/fhestr.h): kernel ("none", "mfma", "dot4",
         "dot4_shadow"), tile (row tiles or samples per workgroup), chunks of the sum over the input dimension, steps per chunk,
         steps in all, last_chunk (steps of the last chunk), rotation_regs.  Recorded at launch: no synchronisation."""
-        a = (C.c_uint32 * 6)()
-        _check(lib().fhe_engine_keyswitch_info(self._h, a))
-        kernel, tile, chunks, per_chunk, steps, regs = (int(x) for x in a)
+        kernel, tile, chunks, per_chunk, steps, regs = _record(C.c_uint32, 6, lib().fhe_engine_keyswitch_info, self._h)
         return {"kernel": self.KS_KERNELS[kernel], "tile": tile, "chunks": chunks, "steps_per_chunk": per_chunk, "steps": steps,
                 "last_chunk": steps - (chunks - 1) * per_chunk if chunks else 0, "rotation_regs": regs}
 
@@ -798,18 +433,9 @@ class Engine:
 
     def close(self):
         if self._h:
-            for ops in list(getattr(self, "_string_ops", ())):    # their cached plans point into this engine: they go first
-                ops.close()
-            for prog in list(getattr(self, "_programs", ())):     # string programs and their compiled plans, likewise
-                prog.close()
-            lib().fhe_engine_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            for obj in sorted(self._dependents, key=lambda o: o._close_rank):
+                obj.close()
+        super().close()
 
     @property
     def handle(self):
@@ -845,11 +471,9 @@ class Engine:
         glwe_sk, small_sk = _u64(glwe_sk), _u64(small_sk)
         if glwe_sk.size != p.k * p.N or small_sk.size != p.n:
             raise FheError("secret key size mismatch")
-        bsk = np.zeros(p.bsk_len, dtype=np.uint64) if export else None
-        ksk = np.zeros(p.ksk_len, dtype=np.uint64) if export else None
+        bsk, ksk = self._export_buffers(export)
         sb = (C.c_uint8 * 32)(*seed_bytes(seed))
-        _check(lib().fhe_engine_generate_keys(self._h, _ptr(glwe_sk), _ptr(small_sk), sb,
-                                              _ptr(bsk) if export else None, _ptr(ksk) if export else None))
+        _check(lib().fhe_engine_generate_keys(self._h, _ptr(glwe_sk), _ptr(small_sk), sb, _ptr(bsk), _ptr(ksk)))
         return (bsk, ksk) if export else None
 
     # shortint/server_key/mod.rs:383-399
@@ -883,10 +507,7 @@ class Engine:
     def load_packing_key(self, pp, pksk):
         """Upload a packing keyswitch key (ClientKey.gen_packing_key) and rewrite it into the kernel's digit planes."""
         pksk = _u64(pksk).reshape(-1)
-        n = packing_key_len(self.params, pp)
-        if not n:
-            raise FheError(lib().fhe_last_error().decode())
-        if pksk.size != n:
+        if pksk.size != _nonzero(packing_key_len(self.params, pp)):
             raise FheError("packing key: size does not match the parameter set and decomposition")
         _check(lib().fhe_engine_load_packing_key(self._h, C.byref(_pp(pp)), _ptr(pksk)))
         self.packing_pair = (int(pp[0]), int(pp[1]))        # what Narrow(bits=None) takes its default width for
@@ -896,22 +517,17 @@ class Engine:
         (csrc/ring_packing_kernels.hip.h).  With no matrix packing key loaded, Engine.pack, packed=True and the refresh
         gate of unpack / unpack_narrow take the ring route; with one loaded they behave as before."""
         key = _u64(key).reshape(-1)
-        n = ring_packing_key_len(self.params, pp)
-        if not n:
-            raise FheError(lib().fhe_last_error().decode())
-        if key.size != n:
+        if key.size != _nonzero(ring_packing_key_len(self.params, pp)):
             raise FheError("ring packing key: size does not match the parameter set and decomposition")
         _check(lib().fhe_engine_load_ring_packing_key(self._h, C.byref(_pp(pp)), _ptr(key)))
         self.ring_packing_pair = (int(pp[0]), int(pp[1]))
 
     def _ring_route(self) -> bool:
-        return getattr(self, "packing_pair", None) is None and getattr(self, "ring_packing_pair", None) is not None
+        return self.packing_pair is None and self.ring_packing_pair is not None
 
     def ring_pack_info(self) -> dict:
         """What the last ring packing call enqueued (fhe_engine_ring_pack_info)."""
-        a = (C.c_uint64 * 5)()
-        _check(lib().fhe_engine_ring_pack_info(self._h, a))
-        ran, levels, keyswitches, launches, scratch = (int(x) for x in a)
+        ran, levels, keyswitches, launches, scratch = _record(C.c_uint64, 5, lib().fhe_engine_ring_pack_info, self._h)
         return {"ran": bool(ran), "levels": levels, "keyswitches": keyswitches, "launches": launches, "scratch_bytes": scratch}
 
     def ring_ntt(self, polys, inverse: bool = False) -> np.ndarray:
@@ -957,23 +573,33 @@ class Engine:
         _check(lib().fhe_engine_transcipher_apply(self._h, _cipher_id(cipher), streams, round, _ptr(_u64(ring)), n_bytes, m, _ptr(out)))
         return out
 
-    def _dev_to_host(self, dev, d_in: int, shape) -> np.ndarray:
-        """pack / unpack / narrow / unpack_narrow on a device input without d_out: dev(d_in, pointer) writes `shape` words
-        into a device tensor allocated here, which comes back as a host array once the engine's stream is idle."""
+    def _packed_route(self, host, dev, args, shape, words, d_in, d_out):
+        """The routes of pack / unpack / narrow / unpack_narrow.  host and dev are the two entry points of the call, both
+        (engine, source, *args, destination); shape: the output's, in words; words(): the host input, checked.  The
+        source is d_in (a device pointer) or the host input, the destination d_out (a device pointer) or an array that
+        is returned.  Device to device only enqueues on the engine's stream.  Where one side is on the host and the
+        other on the device, the host side is staged through a device tensor: torch's stream is not ordered with the
+        engine's, so torch is synchronised before the call and the engine after it."""
+        if d_in and d_out:
+            return _check(dev(self._h, C.c_void_p(d_in), *args, C.c_void_p(d_out)))
+        if not d_in:
+            src = words()
+            if not d_out:
+                out = np.zeros(shape, dtype=np.uint64)
+                _check(host(self._h, _ptr(src), *args, _ptr(out)))
+                return out
         import torch
-        out = torch.empty(shape, dtype=torch.int64, device=f"cuda:{self.device}")
+        if d_in:
+            out = torch.empty(shape, dtype=torch.int64, device=f"cuda:{self.device}")
+            d_out = out.data_ptr()
+        else:
+            out = None
+            staged = torch.from_numpy(src.view(np.int64)).to(f"cuda:{self.device}")
+            d_in = staged.data_ptr()
         torch.cuda.synchronize()
-        dev(d_in, out.data_ptr())
-        self.synchronize()
-        return out.cpu().numpy().view(np.uint64)
-
-    def _host_to_dev(self, dev, words: np.ndarray, d_out: int) -> None:
-        """unpack / unpack_narrow of a host array into d_out: the words go up, dev(pointer, d_out) reads them there."""
-        import torch
-        d_in = torch.from_numpy(words.view(np.int64)).to(f"cuda:{self.device}")
-        torch.cuda.synchronize()
-        dev(d_in.data_ptr(), d_out)
-        self.synchronize()                                  # d_in is released on return
+        _check(dev(self._h, C.c_void_p(d_in), *args, C.c_void_p(d_out)))
+        self.synchronize()                                  # `staged` is released on return
+        return None if out is None else out.cpu().numpy().view(np.uint64)
 
     def narrow(self, glwes=None, held: int | None = None, bits: int | None = None, d_in: int | None = None, d_out: int | None = None):
         """Packed GLWEs narrowed to `bits`-bit coefficients on the GPU (csrc/glwe_narrow_kernels.hip.h; the definition:
@@ -984,27 +610,26 @@ class Engine:
         loaded packing key's pair (narrow_default_bits)."""
         p = self.params
         if glwes is not None and hasattr(glwes, "data_ptr"):
-            keep, d_in = glwes, glwes.data_ptr()
+            d_in = glwes.data_ptr()
         if held is None:
             held = getattr(glwes, "count", None)
         if held is None:
             raise FheError("narrow: the number of blocks the GLWEs hold is required")
         if bits is None:
             bits = self._default_narrow_bits()
-        words = narrow_len(p, held, bits)
-        if held and not words:
+        n_words = narrow_len(p, held, bits)
+        if held and not n_words:
             raise FheError(f"narrow: a width of {bits} bits is refused (8 .. 32)")
-        dev = lambda src, dst: _check(lib().fhe_engine_narrow_glwes_dev(self._h, C.c_void_p(src), held, bits, C.c_void_p(dst)))
-        if d_in:
-            if d_out:
-                return dev(d_in, d_out)
-            return NarrowString(self._dev_to_host(dev, d_in, (max(words, 1),))[:words], held, held // blocks_per_char(p), bits)
-        glwes = _u64(glwes).reshape(-1)
-        if glwes.size != packed_glwe_len(p, held):
-            raise FheError(f"narrow: {glwes.size} words are not the packed GLWEs of {held} blocks of this parameter set")
-        out = np.zeros(words, dtype=np.uint64)
-        _check(lib().fhe_engine_narrow_glwes(self._h, _ptr(glwes), held, bits, _ptr(out)))
-        return NarrowString(out, held, held // blocks_per_char(p), bits)
+
+        def words():
+            w = _u64(glwes).reshape(-1)
+            if w.size != packed_glwe_len(p, held):
+                raise FheError(f"narrow: {w.size} words are not the packed GLWEs of {held} blocks of this parameter set")
+            return w
+
+        out = self._packed_route(lib().fhe_engine_narrow_glwes, lib().fhe_engine_narrow_glwes_dev, (held, bits), (max(n_words, 1),),
+                                 words, d_in, d_out)
+        return None if out is None else NarrowString(out[:n_words], held, held // blocks_per_char(p), bits)
 
     def widen(self, d_in: int, held: int, bits: int, d_out: int):
         """A narrow list on the device back to full GLWEs on the device (fhe_engine_widen_narrow_dev): d_out receives
@@ -1012,12 +637,11 @@ class Engine:
         _check(lib().fhe_engine_widen_narrow_dev(self._h, C.c_void_p(d_in), held, bits, C.c_void_p(d_out)))
 
     def _default_narrow_bits(self) -> int:
-        pair = getattr(self, "packing_pair", None)
         if self._ring_route():
             return ring_narrow_default_bits(self.params, self.ring_packing_pair, operand=True)
-        if pair is None:
+        if self.packing_pair is None:
             raise FheError("Narrow(bits=None) takes its width from the packing pair given to load_packing_key; none is loaded")
-        return narrow_default_bits(self.params, pair, operand=True)
+        return narrow_default_bits(self.params, self.packing_pair, operand=True)
 
     def unpack_narrow(self, narrow=None, held: int | None = None, bits: int | None = None, count: int | None = None, first: int = 0,
                       refresh: bool = True, d_in: int | None = None, d_out: int | None = None):
@@ -1028,34 +652,27 @@ class Engine:
         packing key's pair and `bits`."""
         p = self.params
         if narrow is not None and hasattr(narrow, "data_ptr"):
-            keep, d_in = narrow, narrow.data_ptr()
+            d_in = narrow.data_ptr()
         held = getattr(narrow, "count", None) if held is None else held
         bits = getattr(narrow, "bits", None) if bits is None else bits
         if held is None or bits is None:
             raise FheError("unpack_narrow: the blocks the list holds and its width are required")
         if count is None:
             count = held - first
-        args = (held, bits, first, count, int(bool(refresh)))
-        dev = lambda src, dst: _check(lib().fhe_engine_unpack_narrow_dev(self._h, C.c_void_p(src), *args, C.c_void_p(dst)))
-        if d_in:
-            if d_out:
-                return dev(d_in, d_out)
-            return self._dev_to_host(dev, d_in, (max(count, 0), p.big_size))
-        narrow = _u64(narrow).reshape(-1)
-        if narrow.size != narrow_len(p, held, bits):
-            raise FheError(f"unpack_narrow: {narrow.size} words are not the narrow list of {held} blocks at {bits} bits of this parameter set")
-        if d_out:
-            return self._host_to_dev(dev, narrow, d_out)
-        out = np.zeros((max(count, 0), p.big_size), dtype=np.uint64)
-        _check(lib().fhe_engine_unpack_narrow(self._h, _ptr(narrow), *args, _ptr(out)))
-        return out
+
+        def words():
+            w = _u64(narrow).reshape(-1)
+            if w.size != narrow_len(p, held, bits):
+                raise FheError(f"unpack_narrow: {w.size} words are not the narrow list of {held} blocks at {bits} bits of this parameter set")
+            return w
+
+        return self._packed_route(lib().fhe_engine_unpack_narrow, lib().fhe_engine_unpack_narrow_dev,
+                                  (held, bits, first, count, int(bool(refresh))), (max(count, 0), p.big_size), words, d_in, d_out)
 
     def narrow_info(self) -> dict:
         """What the last narrow / unpack_narrow launched (fhe_engine_narrow_info), recorded when it was enqueued: `kernel`
         is "narrow" (then `items` counts the list's words), "extract" (rows) or "widen" (GLWE words)."""
-        a = (C.c_uint32 * 5)()
-        _check(lib().fhe_engine_narrow_info(self._h, a))
-        ran, kernel, items, workgroups, bits = (int(x) for x in a)
+        ran, kernel, items, workgroups, bits = _record(C.c_uint32, 5, lib().fhe_engine_narrow_info, self._h)
         return {"ran": bool(ran), "kernel": {0: None, 1: "narrow", 2: "extract", 3: "widen"}[kernel], "items": items, "workgroups": workgroups, "bits": bits}
 
     def pack(self, cts=None, count: int | None = None, d_in: int | None = None, d_out: int | None = None):
@@ -1066,29 +683,24 @@ class Engine:
         they come back as a host array.  With only a ring packing key loaded (load_ring_packing_key) the same GLWE
         layout comes from the ring route (csrc/ring_packing_kernels.hip.h)."""
         p = self.params
-        ring = self._ring_route()
         if cts is not None and hasattr(cts, "data_ptr"):
             if count is None:
                 count = cts.numel() // p.big_size
-            keep, d_in = cts, cts.data_ptr()
+            d_in = cts.data_ptr()
         if d_in:
             if count is None:
                 raise FheError("pack: a device buffer needs a count")
-            pack_dev = lib().fhe_engine_ring_pack_lwes_dev if ring else lib().fhe_engine_pack_lwes_dev
-            dev = lambda src, dst: _check(pack_dev(self._h, C.c_void_p(src), count, C.c_void_p(dst)))
-            if d_out:
-                return dev(d_in, d_out)
-            return self._dev_to_host(dev, d_in, (-(-count // p.N), p.k + 1, p.N))
-        cts = _u64(cts).reshape(-1, p.big_size)
-        out = np.zeros((-(-cts.shape[0] // p.N), p.k + 1, p.N), dtype=np.uint64)
-        _check((lib().fhe_engine_ring_pack_lwes if ring else lib().fhe_engine_pack_lwes)(self._h, _ptr(cts), cts.shape[0], _ptr(out)))
-        return out
+        else:
+            cts = _u64(cts).reshape(-1, p.big_size)
+            count = cts.shape[0]
+        L = lib()
+        host, dev = ((L.fhe_engine_ring_pack_lwes, L.fhe_engine_ring_pack_lwes_dev) if self._ring_route() else
+                     (L.fhe_engine_pack_lwes, L.fhe_engine_pack_lwes_dev))
+        return self._packed_route(host, dev, (count,), (-(-count // p.N), p.k + 1, p.N), lambda: cts, d_in, d_out)
 
     def packing_info(self) -> dict:
         """What the last pack launch ran (fhe_engine_packing_info): row tiles per workgroup, K chunks, K steps per chunk."""
-        a = (C.c_uint32 * 5)()
-        _check(lib().fhe_engine_packing_info(self._h, a))
-        ran, tile, chunks, spc, steps = (int(x) for x in a)
+        ran, tile, chunks, spc, steps = _record(C.c_uint32, 5, lib().fhe_engine_packing_info, self._h)
         return {"ran": bool(ran), "tile": tile, "chunks": chunks, "steps_per_chunk": spc, "steps": steps,
                 "last_chunk": steps - (chunks - 1) * spc if ran else 0}
 
@@ -1104,30 +716,24 @@ class Engine:
         and returns nothing.  The GLWEs must hold block first + count - 1."""
         p = self.params
         if glwes is not None and hasattr(glwes, "data_ptr"):
-            keep, d_in = glwes, glwes.data_ptr()
+            d_in = glwes.data_ptr()
         if count is None:
             count = getattr(glwes, "count", None)
         if count is None:
             raise FheError("unpack: a block count is required")
-        dev = lambda src, dst: _check(lib().fhe_engine_unpack_glwes_dev(self._h, C.c_void_p(src), first, count, int(bool(refresh)), C.c_void_p(dst)))
-        if d_in:
-            if d_out:
-                return dev(d_in, d_out)
-            return self._dev_to_host(dev, d_in, (count, p.big_size))
-        glwes = _u64(glwes).reshape(-1)
-        if glwes.size < packed_glwe_len(p, first + count) or glwes.size % ((p.k + 1) * p.N):
-            raise FheError(f"unpack: {glwes.size} words do not hold packed block {first + count - 1} of this parameter set")
-        if d_out:
-            return self._host_to_dev(dev, glwes, d_out)
-        out = np.zeros((count, p.big_size), dtype=np.uint64)
-        _check(lib().fhe_engine_unpack_glwes(self._h, _ptr(glwes), first, count, int(bool(refresh)), _ptr(out)))
-        return out
+
+        def words():
+            w = _u64(glwes).reshape(-1)
+            if w.size < packed_glwe_len(p, first + count) or w.size % ((p.k + 1) * p.N):
+                raise FheError(f"unpack: {w.size} words do not hold packed block {first + count - 1} of this parameter set")
+            return w
+
+        return self._packed_route(lib().fhe_engine_unpack_glwes, lib().fhe_engine_unpack_glwes_dev,
+                                  (first, count, int(bool(refresh))), (count, p.big_size), words, d_in, d_out)
 
     def unpack_info(self) -> dict:
         """What the last unpack launched (fhe_engine_unpack_info), recorded when it was enqueued."""
-        a = (C.c_uint32 * 4)()
-        _check(lib().fhe_engine_unpack_info(self._h, a))
-        ran, rows, workgroups, refreshed = (int(x) for x in a)
+        ran, rows, workgroups, refreshed = _record(C.c_uint32, 4, lib().fhe_engine_unpack_info, self._h)
         return {"ran": bool(ran), "rows": rows, "workgroups": workgroups, "refreshed": bool(refreshed)}
 
     def keyswitch(self, cts) -> np.ndarray:
@@ -1198,9 +804,7 @@ class Engine:
         return out
 
     def last_kernel_ms(self):
-        ms = (C.c_float * 2)()
-        _check(lib().fhe_last_kernel_ms(self._h, ms))
-        return float(ms[0]), float(ms[1])
+        return tuple(_record(C.c_float, 2, lib().fhe_last_kernel_ms, self._h))
 
     def kernel_times(self, reset=True):
         """(keyswitch_ms_total, blind_rotate_ms_total, calls) since the last reset (HIP events)."""
@@ -1210,11 +814,12 @@ class Engine:
         return float(ms[0]), float(ms[1]), int(calls.value)
 
 
-class Transcipher:
+class Transcipher(_Handle):
     """Strings encrypted under Trivium / Kreyvium turned into encrypted strings on the GPU (fhe_transcipher_*):
     begin(ivs) runs the warm-up of one string per IV, next(data) returns the next characters of each as the block
     ciphertexts FheStringOps and StringProgram take.  Every next starts on an 8-byte keystream boundary: `offset` is
     the keystream byte the coming call starts at, which the client passes to stream_encrypt for that call's bytes."""
+    _destroy, _engine_owned = "fhe_transcipher_destroy", True
 
     def __init__(self, engine: "Engine", cipher, key_cts, max_streams: int = 1):
         self.engine, self.cipher, self.params = engine, _cipher_id(cipher), engine.params
@@ -1225,17 +830,6 @@ class Transcipher:
         self._h = C.c_void_p()
         _check(lib().fhe_transcipher_create(engine._h, self.cipher, _ptr(key_cts), max_streams, C.byref(self._h)))
         self.max_streams, self.streams = max_streams, 0
-
-    def close(self):
-        if self._h and self.engine._h:          # the engine owns it: gone with the engine at the latest
-            lib().fhe_transcipher_destroy(self._h)
-        self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def begin(self, ivs):
         """ivs: one IV (bytes) per string, at most max_streams."""
@@ -1265,9 +859,7 @@ class Transcipher:
         return out[0] if single else out
 
     def info(self) -> dict:
-        a = (C.c_uint32 * 8)()
-        _check(lib().fhe_transcipher_info(self._h, a))
-        v = [int(x) for x in a]
+        v = _record(C.c_uint32, 8, lib().fhe_transcipher_info, self._h)
         return {"cipher": v[0], "max_streams": v[1], "streams": v[2], "warmup_rounds": v[3], "data_rounds": v[4], "pbs": v[5] | (v[6] << 32), "offset": v[7]}
 
     @property
@@ -1282,8 +874,9 @@ class Transcipher:
         return {"gather_ms": ms[0], "ks_pbs_ms": ms[1], "apply_ms": ms[2], "rounds": n.value}
 
 
-class ClientKey:
+class ClientKey(_Handle):
     """Client side (CPU): mirrors shortint::ClientKey (tfhe/src/shortint/client_key/mod.rs)."""
+    _destroy = "fhe_client_key_destroy"
 
     def __init__(self, params: Params, seed):
         """seed: 32 bytes (random_seed()) or, for reproducible tests, an int."""
@@ -1291,17 +884,6 @@ class ClientKey:
         self._h = C.c_void_p()
         sb = (C.c_uint8 * 32)(*seed_bytes(seed))
         _check(lib().fhe_client_key_create(C.byref(params.c()), sb, C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            lib().fhe_client_key_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def encrypt(self, msgs) -> np.ndarray:
         msgs = _u64(np.atleast_1d(msgs))
@@ -1346,10 +928,7 @@ class ClientKey:
         pp=None takes packing_default_params.  `seed` (32 bytes or an int) drives its masks and noise."""
         p = self.params
         pp = tuple(pp) if pp is not None else packing_default_params(p)
-        n = packing_key_len(p, pp)
-        if not n:
-            raise FheError(lib().fhe_last_error().decode())
-        pksk = np.zeros(n, dtype=np.uint64)
+        pksk = np.zeros(_nonzero(packing_key_len(p, pp)), dtype=np.uint64)
         sb = (C.c_uint8 * 32)(*seed_bytes(seed))
         _check(lib().fhe_client_gen_packing_key(self._h, C.byref(_pp(pp)), sb, _ptr(pksk), threads or min(16, os.cpu_count() or 1)))
         return pp, pksk
@@ -1359,10 +938,7 @@ class ClientKey:
         k * level GLWE ciphertexts each; returns ((base_log, level), words).  pair=None takes ring_packing_default_params."""
         p = self.params
         pair = tuple(pair) if pair is not None else ring_packing_default_params(p)
-        n = ring_packing_key_len(p, pair)
-        if not n:
-            raise FheError(lib().fhe_last_error().decode())
-        key = np.zeros(n, dtype=np.uint64)
+        key = np.zeros(_nonzero(ring_packing_key_len(p, pair)), dtype=np.uint64)
         sb = (C.c_uint8 * 32)(*seed_bytes(seed))
         _check(lib().fhe_client_gen_ring_packing_key(self._h, C.byref(_pp(pair)), sb, _ptr(key), threads or min(16, os.cpu_count() or 1)))
         return pair, key
@@ -1436,10 +1012,7 @@ def cast_default_params(src: Params, dst: Params, target: int = CAST_TO_SMALL, p
 
 def cast_key_len(dst: Params, cp: CastParams) -> int:
     """u64 words of the casting key (fhe_cast_key_len); raises with the reason when the parameters are refused."""
-    n = int(lib().fhe_cast_key_len(C.byref(dst.c()), C.byref(cp.c())))
-    if not n:
-        raise FheError(lib().fhe_last_error().decode())
-    return n
+    return _nonzero(lib().fhe_cast_key_len(C.byref(dst.c()), C.byref(cp.c())))
 
 
 def cast_rshift(src: Params, dst: Params) -> int:
@@ -1477,14 +1050,13 @@ def cast_host(dst: Params, cp: CastParams, key, cts) -> np.ndarray:
 def cast_noise(dst: Params, cp: CastParams, v_in: float = 1.0) -> tuple:
     """(what the destination's next lookup sees of a keyswitched block, in its nominal units; its PBS-input budget; the
     keyswitched block's variance with the torus as unit) for a source block of v_in source-nominal variances: fhe_cast_noise."""
-    a = (C.c_double * 3)()
-    _check(lib().fhe_cast_noise(C.byref(dst.c()), C.byref(cp.c()), float(v_in), a))
-    return float(a[0]), float(a[1]), float(a[2])
+    return tuple(_record(C.c_double, 3, lib().fhe_cast_noise, C.byref(dst.c()), C.byref(cp.c()), float(v_in)))
 
 
-class CastKey:
+class CastKey(_Handle):
     """One source client's casting key resident on the destination's engine (fhe_cast_key_*; Engine.cast_key).  cast and
     cast_packed take that client's blocks -- rows, or packed GLWEs as they are stored -- to blocks of the engine's client."""
+    _destroy, _engine_owned = "fhe_cast_key_destroy", True
 
     def __init__(self, engine: "Engine", cp: CastParams, key):
         self.engine, self.cp, self.params = engine, cp, engine.params
@@ -1496,21 +1068,8 @@ class CastKey:
         self.shift = cast_rshift(cp.src, engine.params)
         self.group, self.v_in = 1, 1.0
 
-    def close(self):
-        if self._h and self.engine._h:          # the engine owns it: gone with the engine at the latest
-            lib().fhe_cast_key_destroy(self._h)
-        self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def info(self) -> dict:
-        a = (C.c_uint32 * 8)()
-        _check(lib().fhe_cast_key_info(self._h, a))
-        v = [int(x) for x in a]
+        v = _record(C.c_uint32, 8, lib().fhe_cast_key_info, self._h)
         return {"target": v[0], "base_log": v[1], "level": v[2], "in_dim": v[3], "out_dim": v[4], "shift": v[5] - 64, "fused": bool(v[6]),
                 "last": {0: None, 1: "lwes", 2: "fused", 3: "extract"}[v[7]]}
 
@@ -1653,16 +1212,12 @@ def ring_packing_key_len(params: Params, pair) -> int:
 
 def ring_packing_noise(params: Params, pair) -> tuple:
     """(variance of a raw block extracted from a ring-packed PBS output, in nominal units; the default PBS-input budget)."""
-    a = (C.c_double * 2)()
-    _check(lib().fhe_ring_packing_noise(C.byref(params.c()), C.byref(_pp(pair)), a))
-    return float(a[0]), float(a[1])
+    return tuple(_record(C.c_double, 2, lib().fhe_ring_packing_noise, C.byref(params.c()), C.byref(_pp(pair))))
 
 
 def ring_narrow_noise(params: Params, pair, bits: int) -> tuple:
     """narrow_noise for the ring route (fhe_ring_narrow_noise)."""
-    a = (C.c_double * 3)()
-    _check(lib().fhe_ring_narrow_noise(C.byref(params.c()), C.byref(_pp(pair)), bits, a))
-    return float(a[0]), float(a[1]), float(a[2])
+    return tuple(_record(C.c_double, 3, lib().fhe_ring_narrow_noise, C.byref(params.c()), C.byref(_pp(pair)), bits))
 
 
 def ring_narrow_default_bits(params: Params, pair, operand: bool = True) -> int:
@@ -1688,7 +1243,7 @@ def ring_pack_host(params: Params, pair, key, cts) -> np.ndarray:
     key = _u64(key).reshape(-1)
     cts = _u64(cts).reshape(-1, params.big_size)
     if key.size != ring_packing_key_len(params, pair) or not key.size:
-        raise FheError(lib().fhe_last_error().decode() if not ring_packing_key_len(params, pair) else "ring packing key: size does not match the parameter set")
+        raise FheError(_last_error() if not ring_packing_key_len(params, pair) else "ring packing key: size does not match the parameter set")
     out = np.zeros((-(-cts.shape[0] // params.N), params.k + 1, params.N), dtype=np.uint64)
     _check(lib().fhe_ring_pack_host(C.byref(params.c()), C.byref(_pp(pair)), _ptr(key), _ptr(cts), cts.shape[0], _ptr(out)))
     return out
@@ -1723,7 +1278,7 @@ def packing_keyswitch_host(params: Params, pp, pksk, cts) -> np.ndarray:
     cts = _u64(cts).reshape(-1, params.big_size)
     pksk = _u64(pksk).reshape(-1)
     if pksk.size != packing_key_len(params, pp) or not pksk.size:
-        raise FheError(lib().fhe_last_error().decode() if not packing_key_len(params, pp) else "packing key: size does not match the parameter set")
+        raise FheError(_last_error() if not packing_key_len(params, pp) else "packing key: size does not match the parameter set")
     out = np.zeros((-(-cts.shape[0] // params.N), params.k + 1, params.N), dtype=np.uint64)
     _check(lib().fhe_packing_keyswitch_host(C.byref(params.c()), C.byref(_pp(pp)), _ptr(pksk), _ptr(cts), cts.shape[0], _ptr(out)))
     return out
@@ -1744,9 +1299,7 @@ def glwe_sample_extract_host(params: Params, glwes, count: int, first: int = 0) 
 def packing_unpack_noise(params: Params, pp) -> tuple:
     """(variance of a raw block extracted from a packed PBS output, in nominal units; the default PBS-input budget):
     fhe_packing_unpack_noise.  Engine.unpack(refresh=True) is refused where the first exceeds the second."""
-    a = (C.c_double * 2)()
-    _check(lib().fhe_packing_unpack_noise(C.byref(params.c()), C.byref(_pp(pp)), a))
-    return float(a[0]), float(a[1])
+    return tuple(_record(C.c_double, 2, lib().fhe_packing_unpack_noise, C.byref(params.c()), C.byref(_pp(pp))))
 
 
 class PackedString(np.ndarray):
@@ -1773,9 +1326,7 @@ def narrow_len(params: Params, held: int, bits: int) -> int:
 def narrow_noise(params: Params, pp, bits: int) -> tuple:
     """(variance of a raw block extracted from a packed PBS output narrowed to `bits`, in nominal units; the default
     PBS-input budget; log2 of the probability that the client decodes such a coefficient wrongly): fhe_narrow_noise."""
-    a = (C.c_double * 3)()
-    _check(lib().fhe_narrow_noise(C.byref(params.c()), C.byref(_pp(pp)), bits, a))
-    return float(a[0]), float(a[1]), float(a[2])
+    return tuple(_record(C.c_double, 3, lib().fhe_narrow_noise, C.byref(params.c()), C.byref(_pp(pp)), bits))
 
 
 def narrow_default_bits(params: Params, pp, operand: bool = True) -> int:
@@ -1916,9 +1467,10 @@ class CompactPublicKey:
         return self.encrypt(string_to_blocks(self.params, s, cap), seed, threads)
 
 
-class Plan:
+class Plan(_Handle):
     """A levelised shortint circuit (include/fhestr.h, "plans").  Build with input/lut/lin/pbs/output
     + finalize, or get a ready-made FheString operation from Plan.string_op."""
+    _destroy = "fhe_plan_destroy"
 
     def __init__(self, engine: "Engine | None", handle=None, params: Params | None = None):
         """engine=None builds an offline plan (exportable, not runnable) from `params`."""
@@ -1935,13 +1487,11 @@ class Plan:
     def string_op(cls, engine: "Engine | None", op: str, a_cap: int, b_cap: int = 0,
                   clear: bytes | None = None, world: int = 1, params: Params | None = None) -> "Plan":
         h = C.c_void_p()
-        buf = (C.c_uint8 * max(1, len(clear or b"")))(*(clear or b""))
         if engine is not None:
-            _check(lib().fhe_str_plan_create(engine.handle, op.encode(), a_cap, b_cap, buf,
-                                             len(clear or b""), world, C.byref(h)))
+            _check(lib().fhe_str_plan_create(engine.handle, op.encode(), a_cap, b_cap, *_clear(clear or b""), world, C.byref(h)))
         else:
-            _check(lib().fhe_str_plan_create_offline(C.byref(params.c()), op.encode(), a_cap, b_cap, buf,
-                                                     len(clear or b""), world, C.byref(h)))
+            _check(lib().fhe_str_plan_create_offline(C.byref(params.c()), op.encode(), a_cap, b_cap, *_clear(clear or b""),
+                                                     world, C.byref(h)))
         return cls(engine, h, params)
 
     @classmethod
@@ -1966,17 +1516,6 @@ class Plan:
             _check(lib().fhe_plan_export_lut(self._h, i, _ptr(acc)))
             out[i] = acc
         return out
-
-    def close(self):
-        if self._h:
-            lib().fhe_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- building ----
     def input(self, degree: int | None = None) -> int:
@@ -2026,24 +1565,19 @@ class Plan:
 
     # ---- queries ----
     def info(self) -> dict:
-        a = (C.c_uint32 * 6)()
-        _check(lib().fhe_plan_info(self._h, a))
-        return dict(zip(("n_inputs", "n_outputs", "n_levels", "n_pbs", "pool_slots", "world"), map(int, a)))
+        return dict(zip(("n_inputs", "n_outputs", "n_levels", "n_pbs", "pool_slots", "world"),
+                        _record(C.c_uint32, 6, lib().fhe_plan_info, self._h)))
 
     def noise_info(self) -> dict:
-        a = (C.c_double * 4)()
-        _check(lib().fhe_plan_noise_info(self._h, a))
-        return dict(zip(("max_pbs_input_noise", "budget", "log2_pfail_worst", "gathered_lwes"), map(float, a)))
+        return dict(zip(("max_pbs_input_noise", "budget", "log2_pfail_worst", "gathered_lwes"),
+                        _record(C.c_double, 4, lib().fhe_plan_noise_info, self._h)))
 
     def level_info(self, level: int) -> dict:
-        a = (C.c_uint32 * 8)()
-        _check(lib().fhe_plan_level_info(self._h, level, a))
-        return dict(zip(("jobs", "local_base", "local_size", "e_max", "recv_base", "terms"), map(int, a)))
+        return dict(zip(("jobs", "local_base", "local_size", "e_max", "recv_base", "terms"),
+                        _record(C.c_uint32, 8, lib().fhe_plan_level_info, self._h, level)))
 
     def level_rank_info(self, level: int, rank: int) -> dict:
-        a = (C.c_uint32 * 3)()
-        _check(lib().fhe_plan_level_rank_info(self._h, level, rank, a))
-        return dict(zip(("job_lo", "job_hi", "n_export"), map(int, a)))
+        return dict(zip(("job_lo", "job_hi", "n_export"), _record(C.c_uint32, 3, lib().fhe_plan_level_rank_info, self._h, level, rank)))
 
     def export_level(self, level: int) -> dict:
         li = self.level_info(level)
@@ -2351,18 +1885,20 @@ class FheStringOps:
     to_upper/to_lower, ..., replace / replacen, the split family, take / skip / split_at / char_at / insert at a clear or an
     encrypted position; and what combines their results: bit_and / bit_or / bit_xor / bit_not, select, count_add /
     count_sub / count_eq .. count_ge / count_min / count_max).  Strings are (cap*blocks, kN+1) arrays of big-key LWEs (see string_to_blocks)."""
+    _close_rank = 0             # Engine.close: the cached plans go before string programs
 
     def __init__(self, engine: Engine, out_alloc=None):
         """out_alloc(shape) -> uint64 array the results are written into (default: np.zeros; pass fhestr.pinned_empty --
-        or a cache of such buffers -- for large strings: pageable memory moves at a fraction of the PCIe rate)."""
+        or a cache of such buffers -- for large strings: pageable memory moves at a fraction of the PCIe rate).
+        An Engine adopts the object (Engine._adopt) and closes its cached plans before it goes itself.  Anything else
+        that is passed as `engine` -- resolving a call needs its `params` only, and the CPU tests resolve over such a
+        stand-in -- does not: whoever wraps an engine closes the FheStringOps before the engine."""
         self.engine = engine
         self.bpc = blocks_per_char(engine.params)
         self._alloc = out_alloc or (lambda shape: np.zeros(shape, dtype=np.uint64))
         self._plans = {}            # plans of the packed route, destroyed before their engine (Engine.close)
-        if not hasattr(engine, "_string_ops"):
-            import weakref
-            engine._string_ops = weakref.WeakSet()
-        engine._string_ops.add(self)
+        if isinstance(engine, Engine):
+            engine._adopt(self)
 
     def close(self):
         """Destroy the cached plans of the packed route (Engine.close does it for every FheStringOps over it)."""
@@ -2479,9 +2015,7 @@ class FheStringOps:
         parts = operands[:1] + [x for x in operands[1:] if x.shape[0]]      # an empty operand (`to` of capacity 0) is no input
         ptrs = (C.c_void_p * len(parts))(*[x.ctypes.data for x in parts])
         caps = (C.c_uint32 * len(parts))(*[x.shape[0] // self.bpc for x in parts])
-        buf = (C.c_uint8 * max(1, len(clear)))(*clear) if clear is not None else None
-        args = (self.engine.handle, name.encode(), ptrs, caps, len(parts), _ptr(digits) if digits is not None else None,
-                buf, len(clear) if clear is not None else 0)
+        args = (self.engine.handle, name.encode(), ptrs, caps, len(parts), _ptr(digits), *_clear(clear))
         n_out = C.c_uint32(0)
         _check(lib().fhe_str_op(*args, None, C.byref(n_out)))               # outputs (builds and caches the plan)
         out = self._alloc((n_out.value, self.engine.params.big_size))
@@ -2601,12 +2135,10 @@ class FheStringOps:
         if self._dev(packed, enc[0] if enc else None, digits):
             # every row's outputs after one another: output o of row r is packed block r * n_outputs + o
             return self._packed_many(name, list(rows), a_cap, enc, clear, packed, digits)
-        buf = (C.c_uint8 * max(1, len(clear)))(*clear) if clear is not None else None
         shared = enc[0] if enc else None                    # the pattern operand, then the count's digits
         if digits is not None:
             shared = np.concatenate([shared, digits]) if enc else digits
-        args = (self.engine.handle, name.encode(), _ptr(rows), a_cap, n_rows, _ptr(shared) if shared is not None else None, enc[1] if enc else 0,
-                buf, len(clear) if clear is not None else 0)
+        args = (self.engine.handle, name.encode(), _ptr(rows), a_cap, n_rows, _ptr(shared), enc[1] if enc else 0, *_clear(clear))
         n_out = C.c_uint32(0)
         _check(lib().fhe_str_op_many(*args, None, C.byref(n_out)))          # outputs per row (builds and caches the plan)
         out = self._alloc((n_rows, n_out.value, big))
@@ -2786,8 +2318,7 @@ class FheStringOps:
             return self._finish(d_out, d_out.shape[0], packed)
         ptrs = (C.c_void_p * len(operands))(*[x.ctypes.data for x in operands])
         counts = (C.c_uint32 * len(operands))(*[x.shape[0] for x in operands])
-        buf = (C.c_uint8 * max(1, len(clear)))(*clear) if clear is not None else None
-        args = (self.engine.handle, name.encode(), ptrs, counts, len(operands), buf, len(clear) if clear is not None else 0)
+        args = (self.engine.handle, name.encode(), ptrs, counts, len(operands), *_clear(clear))
         n_out = C.c_uint32(0)
         _check(lib().fhe_str_combine(*args, None, C.byref(n_out)))         # outputs (builds and caches the plan)
         out = self._alloc((n_out.value, big))
@@ -2861,16 +2392,6 @@ def _combining_methods(cls):
 _combining_methods(FheStringOps)
 
 
-def _register_with_engine(engine, obj):
-    """Engine.close closes `obj` before the engine goes: what it holds points into the engine."""
-    if engine is None:
-        return
-    if not hasattr(engine, "_programs"):
-        import weakref
-        engine._programs = weakref.WeakSet()
-    engine._programs.add(obj)
-
-
 class ProgramValue:
     """A symbolic value of a StringProgram: an input, or a result of one of its operations.  kind: "string" (`cap`
     characters), "bit", or "count" (`n_max`, the public bound its digits travel with); `blocks` ciphertexts; `op`: the
@@ -2879,11 +2400,10 @@ class ProgramValue:
     KINDS = ("string", "bit", "count")
 
     def __init__(self, program, vid: int):
-        info = (C.c_uint32 * 4)()
-        _check(lib().fhe_str_program_value_info(program._h, vid, info))
+        info = _record(C.c_uint32, 4, lib().fhe_str_program_value_info, program._h, vid)
         self.id = int(vid)
-        self.kind, self.blocks, self.extent = self.KINDS[info[0]], int(info[1]), int(info[2])
-        self.op = None if info[3] == 0xFFFFFFFF else int(info[3])
+        self.kind, self.blocks, self.extent = self.KINDS[info[0]], info[1], info[2]
+        self.op = None if info[3] == 0xFFFFFFFF else info[3]
 
     @property
     def cap(self):
@@ -2917,11 +2437,13 @@ class ProgramSplit:
         return iter((self.count, self.parts))
 
 
-class StringProgram:
+class StringProgram(_Handle):
     """Several FheString operations recorded into ONE plan (include/fhestr.h, "string programs").  Declare the inputs with
     string(cap) / count(n_max), apply operations -- the methods mirror FheStringOps, operands are symbolic values or clear
     bytes patterns --, declare the results with output(...) and compile().  Independent operations share lookup levels;
     with dedupe (the default) identical sub-circuits are built once.  engine=None: an offline program from `params`."""
+    _destroy = "fhe_str_program_destroy"
+    _close_rank = 1             # Engine.close: after the string operations' cached plans
 
     def __init__(self, engine: "Engine | None", params: Params | None = None, dedupe: bool = True):
         self.engine = engine
@@ -2936,18 +2458,8 @@ class StringProgram:
         self.inputs = []            # ProgramValue, in declaration order
         self.outputs = []           # ProgramValue / ProgramSplit, in output order
         self.n_ops = 0
-        _register_with_engine(engine, self)
-
-    def close(self):
-        if self._h:
-            lib().fhe_str_program_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        if engine is not None:
+            engine._adopt(self)
 
     # ---- declarations ----
     def string(self, cap: int) -> ProgramValue:
@@ -2977,13 +2489,13 @@ class StringProgram:
             if not isinstance(x, ProgramValue):
                 raise FheError(f"{name}: operands are values of a StringProgram, got {type(x).__name__}")
         ids = (C.c_uint32 * max(1, len(operands)))(*[x.id for x in operands])
-        buf = (C.c_uint8 * max(1, len(clear or b"")))(*(clear or b""))
+        args = (self._h, name.encode(), ids, len(operands), *_clear(clear or b""))
         res = (C.c_uint32 * 64)()
         n = C.c_uint32()
-        rc = lib().fhe_str_program_op(self._h, name.encode(), ids, len(operands), buf, len(clear or b""), res, 64, C.byref(n))
+        rc = lib().fhe_str_program_op(*args, res, 64, C.byref(n))
         if rc and n.value > 64:
             res = (C.c_uint32 * n.value)()
-            rc = lib().fhe_str_program_op(self._h, name.encode(), ids, len(operands), buf, len(clear or b""), res, n.value, C.byref(n))
+            rc = lib().fhe_str_program_op(*args, res, n.value, C.byref(n))
         _check(rc)
         self.n_ops += 1
         return [ProgramValue(self, res[i]) for i in range(n.value)]
@@ -3133,6 +2645,7 @@ _combining_methods(StringProgram)
 class CompiledProgram:
     """A finished StringProgram: `plan`, an ordinary Plan (inputs = the program's inputs in declaration order, outputs in
     output order), and the call that runs it on operands given as to FheStringOps."""
+    _close_rank = 1             # Engine.close: with the string programs
 
     def __init__(self, program: StringProgram, plan: Plan):
         self.plan, self.engine, self.params = plan, program.engine, program.params
@@ -3140,7 +2653,8 @@ class CompiledProgram:
         self.n_inputs = sum(v.blocks for v in self.inputs)
         self._ops = FheStringOps(self.engine) if self.engine is not None else None
         self._info = plan.info()
-        _register_with_engine(self.engine, self)
+        if self.engine is not None:
+            self.engine._adopt(self)
 
     def close(self):
         self.plan.close()
